@@ -25,6 +25,8 @@ whatever N (`--scaling weak` multiplies spp by N instead; `--config c4` selects 
 (TorOptions.devices): the path a Nim host uses.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
+`--dump-outputs DIR` also writes, after the timed steps, what the timed path computed in its last step (the frame rank 0
+holds) as DIR/frame.npy: the inputs are fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -55,7 +57,7 @@ ACCEL_BITS = {"none": 0, "blocks": 1, "f32": 2, "blocks+f32": 3}
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5); --workload c5 --frames F: the frames are the steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -89,8 +91,17 @@ def parse_args():
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (HBM traffic of one launch)")
     ap.add_argument("--aux-steps", type=int, default=3, help="steps of each secondary leg (host canvas, accelerations)")
     ap.add_argument("--gather", choices=["lib", "torch"], default="lib", help="N > 1: framebuffer gather inside the library (RCCL) or torch.distributed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0's frame) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a larger frame: a fixed, seeded sample of its pixels)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.workload == "c5" and args.frames > 0 and args.steps is not None:
+        ap.error("--frames F times the first F frames: it sets the steps, --steps cannot")
+    if args.steps is None:
+        args.steps = 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.accel is None:
         args.accel = "blocks+f32" if args.workload == "c5" else "none"
     if args.config:
@@ -118,6 +129,26 @@ def config_name(W, H, spp, world, scaling="strong"):
     if (W, H) == (384, 216) and base_spp == 100:
         return "BASELINE configs[0] geometry on the GPU" + tail
     return "custom size (not a BASELINE config)" + tail
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: at most 64 MB in all, .npy headers included
+DUMP_SEED = 0xFACADE
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (name, array) as out_dir/<name>.npy in float64.  An array larger than its share of the budget is
+    replaced by a fixed sample of its pixels: the rows of its (-1, 3) view that numpy's default_rng(DUMP_SEED) picks, in
+    increasing order -- the same rows in every run with the same arguments, so two builds compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1) - 4096
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            px = a.reshape(-1, a.shape[-1])
+            keep = share // px[0].nbytes
+            a = px[np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def git_head():
@@ -449,6 +480,8 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
     if rank == 0 and not args.no_pmc and world == 1:
         traffic, traffic_note = live_traffic(W, H, spp, args.depth, seeding, arith, accel, anim_frame=mid[0])
     elapsed, table = timed_pass(False)
+    if args.dump_outputs and rank == 0:   # the last frame of this rank's timed range, before the video pass renders into buf again
+        dump_outputs(args.dump_outputs, {"frame": buf.cpu().numpy()})
     steps = len(timed)                                # frames per GPU inside the region (every rank has the same number +- 1)
     total_frames = sum(1 for f in range(first_timed, n_frames))
     total = H * W * spp * total_frames
@@ -573,6 +606,8 @@ def bench_single_process_multi_device(args, tor):
         tor.render(cv, cam, scene.list(), args.depth, opt)
         k_ms_steps.append(tor.last_device_kernel_ms())
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame": cv.pixels})
     timing = tor.last_render_timing()
     note = tor.last_note()
     info = tor.last_gather_info()
@@ -820,6 +855,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # now: the secondary legs below render into `frame` again
+        dump_outputs(args.dump_outputs, {"frame": (frame if tframe is None else tframe.frame).cpu().numpy()})
     # dominant kernel: integrate_kernel, per-launch HIP events on the launch stream; N > 1: every rank's mean, the job's
     # kernel phase is the slowest rank's
     k_ms, k_n = ctx.kernel_ms_mean(args.steps)
