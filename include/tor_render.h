@@ -458,6 +458,14 @@ TOR_API int tor_debug_filter32_scene(TorHittableList world, int64_t n_rays, cons
 TOR_API int tor_debug_screen2_scene(TorHittableList world, int64_t n_rays, const double* o, const double* d,
                                     const double* time, int8_t* keep, int32_t* kind_out, int8_t* pays_out, int64_t n_segs_out);
 
+/* Stage one of the strict layout's plane-screened segments in FLOAT32 against the float64 plane screen it stands for, on the
+ * HOST (csrc/tor_screen.hpp plane_seg32 / plane_word32; the layout and segment headers tor_scene_upload builds).  For every ray
+ * and every object on a segment of xkind 10 / 11 / 12 / 14: keep[ray * world.len + object] = bit 0: the float64 plane screen
+ * keeps it, bit 1: the float32 one does; -1 for the other objects.  pad_kept[ray] = the padding slots of those segments the
+ * float32 screen keeps for that ray, *n_pad_out = the number of such padding slots. */
+TOR_API int tor_debug_plane32_scene(TorHittableList world, int64_t n_rays, const double* o, const double* d, const double* time,
+                                    int8_t* keep, int32_t* pad_kept, int64_t* n_pad_out);
+
 /* The float64 layout's segments in the order the kernel walks them (tor_scene.cpp: largest first; a plane-screened segment's long
  * tail padded to a whole word of 32 slots): out[4 * s + {0, 1, 2, 3}] = {xkind, objects, slots, first slot} for the first
  * `max_segs` segments; *n_segs_out = the number of segments.  Host only. */

@@ -136,7 +136,7 @@ EXPORTED_SYMBOLS = [
     "tor_selftest_rng_host", "tor_version",
     "tor_last_render_timing", "tor_comm_unique_id", "tor_comm_init_rank", "tor_comm_destroy", "tor_render_gather_device",
     "tor_context_scene_counters", "tor_render_ptr", "tor_last_pixel_cost", "tor_last_note", "tor_last_handoff_counters",
-    "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
+    "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
 ]
 
 _lib = None
@@ -251,6 +251,7 @@ def lib():
     L.tor_selftest_slab32_host.argtypes = [C.c_int64] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_int32)] * 2
     L.tor_debug_filter32_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8)]
     L.tor_debug_screen2_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8), C.POINTER(C.c_int32), C.POINTER(C.c_int8), C.c_int64]
+    L.tor_debug_plane32_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.tor_debug_layout_segments.argtypes = [HittableList, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]
     L.tor_selftest_math_device.argtypes = [C.c_int32, dp, dp, dp, dp, C.c_int64, C.c_int32]
     L.tor_selftest_math_host.argtypes = [C.c_int32, dp, dp, dp, dp, C.c_int64]
@@ -806,6 +807,22 @@ def debug_screen2_scene(world: HittableList, o, d, time, max_segs: int = 0):
                                          keep.ctypes.data_as(C.POINTER(C.c_int8)), kind.ctypes.data_as(C.POINTER(C.c_int32)),
                                          pays.ctypes.data_as(C.POINTER(C.c_int8)) if max_segs > 0 else None, max_segs))
     return (keep, kind, pays) if max_segs > 0 else (keep, kind)
+
+
+def debug_plane32_scene(world: HittableList, o, d, time):
+    """(keep[n_rays, n_objects] int8, pad_kept[n_rays] int32, n_pad): stage one of the plane-screened segments of xkind 10 / 11 /
+    12 / 14 in float64 and in float32 on the host -- bit 0 of keep: the float64 screen keeps the object, bit 1: the float32 one;
+    -1: the object is not on such a segment.  pad_kept: padding slots the float32 screen keeps, of n_pad."""
+    dp = lambda x: np.ascontiguousarray(x, dtype=np.float64)
+    o, d, time = dp(o), dp(d), dp(time)
+    keep = np.zeros((len(time), int(world.len)), dtype=np.int8)
+    pad_kept = np.zeros(len(time), dtype=np.int32)
+    n_pad = C.c_int64(0)
+    P = C.POINTER(C.c_double)
+    _check(lib().tor_debug_plane32_scene(world, len(time), o.ctypes.data_as(P), d.ctypes.data_as(P), time.ctypes.data_as(P),
+                                         keep.ctypes.data_as(C.POINTER(C.c_int8)), pad_kept.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         C.byref(n_pad)))
+    return keep, pad_kept, int(n_pad.value)
 
 
 def selftest_math(op: int, x: np.ndarray, y: np.ndarray | None = None, where: str = "device", device: int = -1):

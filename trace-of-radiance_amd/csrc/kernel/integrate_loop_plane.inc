@@ -2,8 +2,9 @@
 // KParams.xpl -- TOR_PLANE=0 and segments the plane would not thin out take the wave-uniform loops instead: see the gate in
 // tor_kernels.hip).
 //   STAGE ONE, wave-uniform: every object through the PLANE screen (tor_screen.hpp: plane_word / plane_word_mov) -- the distance
-//     of its centre's ground projection from the ray's ground track, from {cx, cz} alone (16 bytes through the scalar data path,
-//     one ahead; 3 float64 instructions + the v_alignbit per object) for statics and movers along y at ANY height, from
+//     of its centre's ground projection from the ray's ground track, from {cx', cz'} alone (float32 offsets from the segment's
+//     origin, 8 bytes through the scalar data path, one ahead; plane_word32: 2 v_fma_f32 + 1 v_sub_f32 + the v_alignbit per object)
+//     for statics and movers along y at ANY height, from
 //     {c0x, c0z, dcx, dcz} (32 bytes, 5 + 1 instructions) for movers whose centre travels in x or z.  Keeps the spheres within R of
 //     the ground track: ~9 of random_scene's 481 per query.  Whole words (32 slots) run without the per-block bookkeeping.
 //   STAGE TWO, per lane: the bits stage one left in the segment's words (LDS, and the running word) go through the test the
@@ -25,25 +26,37 @@
             const int i_begin = i;  // first object of the segment this pass tests (wave-uniform)
             {
               const PlaneSeg ps = plane_seg(sray, pray, SEG_REACH, SEG_TRAVEL, f, h_rmax2);
-              // (generic over the record: PW = 2 float64 {cx, cz}, or 4 {c0x, c0z, dcx, dcz} for xkind 13)
+              // (generic over the record: PW = 2 float32 {cx', cz'} relative to the segment's origin -- plane_word32 -- or 4 float64
+              // {c0x, c0z, dcx, dcz} for xkind 13; the header's last four slots: the first float32 record, Ox, Oz, {E, Cm} (tor_scene.hpp)
+              // or the first float64 record)
               auto stage_one = [&](auto PWc) {
                 constexpr int PW = decltype(PWc)::value;
-                cdptr rec = as_const(p.xpl) + ((long)pl_first + PW * (long)i);
+                using Rec = std::conditional_t<PW == 2, float, double>;
+                using RecPtr = std::conditional_t<PW == 2, cfptr, cdptr>;
+                RecPtr rec = (RecPtr)(uintptr_t)(PW == 2 ? (const void*)p.xpl32 : (const void*)p.xpl) + ((long)pl_first + PW * (long)i);
+                PlaneSeg32 ps32{};
+                Rec n0, n1, n2 = 0, n3 = 0;
+                if constexpr (PW == 2) {
+                  ps32 = plane_seg32(sray, ps, h_r1, h_r2, (double)__int_as_float(__double2loint(h_r3)), (double)__int_as_float(__double2hiint(h_r3)));
+                  n0 = __int_as_float(__double2loint(h_r0)); n1 = __int_as_float(__double2hiint(h_r0));
+                } else {
+                  n0 = h_r0; n1 = h_r1; n2 = h_r2; n3 = h_r3;
+                }
                 // the first record: from the segment's header (already here) at the segment's start, from the table when a pass
                 // resumes inside the segment (wave-uniform)
-                double n0 = h_r0, n1 = h_r1, n2 = h_r2, n3 = h_r3;
                 if (i != 0) {
                   n0 = rec[0]; n1 = rec[1];
                   if constexpr (PW == 4) { n2 = rec[2]; n3 = rec[3]; }
                 }
                 auto one = [&](unsigned m, int j) {  // object j of the block at rec; requests object j + 1 (one record of slack behind the table)
-                  const double c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+                  const Rec c0 = n0, c1 = n1, c2 = n2, c3 = n3;
                   n0 = rec[PW * (j + 1) + 0]; n1 = rec[PW * (j + 1) + 1];
                   if constexpr (PW == 4) {
                     n2 = rec[PW * (j + 1) + 2]; n3 = rec[PW * (j + 1) + 3];
                     return push_bit(m, plane_word_mov(ps, c0, c1, c2, c3));
                   } else {
-                    return push_bit(m, plane_word(ps, c0, c1));
+                    (void)c2; (void)c3;
+                    return push_bit(m, plane_word32(ps32, c0, c1));
                   }
                 };
                 // Three phases, so that the whole words -- 15 of random_scene's 16 -- run in a loop whose scalar side is a counter, the
@@ -53,7 +66,7 @@
                 //   blocks of 8 up to the next word boundary of the sorted list, whole words, blocks of 8 to the segment's end.
                 int gb = seg_block0 + (int)((unsigned)i / (unsigned)kBlock);  // block index of object i in the sorted list
                 for (;;) {
-                  // (the segment's last block runs over its padding too: at 4 instructions per slot the padding -- centres at 1e300,
+                  // (the segment's last block runs over its padding too: at 4 instructions per slot the padding -- centres at 1e300 (2^100 in float32),
                   // kept by no ray that has a ground track -- is cheaper than a loop over the real objects, whose requests cannot
                   // run ahead; a ray that keeps everything keeps the padding too and stage two, or the exact test, drops it)
                   while (i < seg_count && ((gb & 3) != 0 || seg_count - i < 4 * kBlock)) {

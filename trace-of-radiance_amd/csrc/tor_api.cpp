@@ -62,12 +62,12 @@ int fail_hip(hipError_t e, const char* what) {
 hipError_t DeviceLayout::put(const HostLayout& lay, const std::vector<double>* cold_override) {
   const std::vector<double>& c = cold_override ? *cold_override : lay.cold;
   struct Part { const void* src; size_t bytes; size_t off; };
-  Part parts[10] = {{lay.stat.data(), lay.stat.size() * 8, 0}, {lay.mov.data(), lay.mov.size() * 8, 0},
+  Part parts[11] = {{lay.stat.data(), lay.stat.size() * 8, 0}, {lay.mov.data(), lay.mov.size() * 8, 0},
                    {lay.movy.data(), lay.movy.size() * 8, 0}, {lay.segs.data(), lay.segs.size() * 8, 0},
                    {c.data(), c.size() * 8, 0},               {lay.hot32.data(), lay.hot32.size() * 4, 0},
                    {lay.coop_trips.data(), lay.coop_trips.size() * 8, 0},
                    {lay.xhdr.data(), lay.xhdr.size() * 8, 0}, {lay.xrec.data(), lay.xrec.size() * 8, 0},
-                    {lay.xpl.data(), lay.xpl.size() * 8, 0}};
+                    {lay.xpl.data(), lay.xpl.size() * 8, 0}, {lay.xpl32.data(), lay.xpl32.size() * 4, 0}};
   size_t total = 0;
   for (Part& p : parts) {
     p.off = total;
@@ -89,6 +89,7 @@ hipError_t DeviceLayout::put(const HostLayout& lay, const std::vector<double>* c
   xhdr = (const double*)(b + parts[7].off);
   xrec = (const double*)(b + parts[8].off);
   xpl = (const double*)(b + parts[9].off);
+  xpl32 = (const float*)(b + parts[10].off);
   n_segs = lay.n_segs;
   n_sorted = (int)lay.n_sorted;
   n_xrec = (int)lay.xrec.size();
@@ -563,6 +564,7 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
       q.xhdr = L.xhdr;
       q.xrec = L.xrec;
       q.xpl = ctx->plane_screen != 0 ? L.xpl : nullptr;
+      q.xpl32 = ctx->plane_screen != 0 ? L.xpl32 : nullptr;
       q.plane_gate2 = ctx->plane_screen == 2 ? 0.0 : 4.0 * tor::kPlaneGate * tor::kPlaneGate;
       // stage two of the plane-screened segments reads its records per lane: from LDS when the table fits beside the per-wave
       // queues -- and, with sample streams, the camera-ray reservoirs -- at this launch's workgroups per CU (random_scene: 15.9 KB + 18.7 KB
@@ -1599,6 +1601,67 @@ int tor_debug_screen2_scene(TorHittableList world, int64_t n_rays, const double*
         kr[orig_of((size_t)block0 * tor::kPad + (size_t)i)] = verdict;
       }
       if (pays_out && s < n_segs_out) pays_out[r * n_segs_out + s] = tor::plane_pays(pray, 4.0 * tor::kPlaneGate * tor::kPlaneGate, xs[4], xs[5], xs[6]) ? 1 : 0;
+    }
+  }
+  return TOR_OK;
+}
+
+// Stage one in float32 against the float64 plane screen over a whole scene on the HOST (include/tor_render.h): the layout and the
+// segment headers tor_scene_upload builds, PlaneSeg32 from the header's slots exactly as kernel/integrate_loop_plane.inc reads them.
+int tor_debug_plane32_scene(TorHittableList world, int64_t n_rays, const double* o, const double* d, const double* time, int8_t* keep,
+                            int32_t* pad_kept, int64_t* n_pad_out) {
+  if (world.len < 0 || (world.len > 0 && !world.objects) || n_rays < 0 || !o || !d || !time || !keep || !pad_kept || !n_pad_out)
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_plane32_scene: bad argument");
+  std::vector<int64_t> ids((size_t)world.len);
+  for (int64_t i = 0; i < world.len; ++i) ids[(size_t)i] = i;
+  tor::HostLayout lay;
+  std::string err;
+  if (!tor::build_layout(world.objects, ids, lay, err, nullptr)) return fail(TOR_ERR_INVALID_ARGUMENT, err);
+  auto orig_of = [&](size_t slot) {
+    int64_t v;
+    std::memcpy(&v, &lay.cold[16 * slot + 14], 8);
+    return v;
+  };
+  *n_pad_out = 0;
+  for (int s = 0; s < lay.n_segs; ++s) {
+    const double* sg = &lay.segs[8 * (size_t)s];
+    const int xkind = (int)lay.xsegs[8 * (size_t)s];
+    if (xkind >= 10 && xkind != 13) *n_pad_out += ((int)sg[2] >> 24);
+  }
+  for (int64_t r = 0; r < n_rays; ++r) {
+    int8_t* kr = keep + r * world.len;
+    for (int64_t i = 0; i < world.len; ++i) kr[i] = -1;
+    pad_kept[r] = 0;
+    const double* oo = o + 3 * r; const double* dd = d + 3 * r;
+    const double a = dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2];  // spheres.nim:30
+    const tor::ScreenRay ray = tor::screen2_ray(oo[0], oo[1], oo[2], dd[0], dd[1], dd[2], a);
+    const tor::PlaneRay pray = tor::plane_ray(ray);
+    for (int s = 0; s < lay.n_segs; ++s) {
+      const double* sg = &lay.segs[8 * (size_t)s];
+      const double* xs = &lay.xsegs[8 * (size_t)s];
+      const double* h = &lay.xhdr[16 * (size_t)s];
+      const int xkind = (int)xs[0];
+      if (xkind < 10 || xkind == 13) continue;
+      const int count = (int)sg[2] & 0xffffff, real = count - ((int)sg[2] >> 24), block0 = (int)sg[3];
+      const double f = xkind >= 12 ? (time[r] - sg[4]) / sg[5] : 0.0;  // moving_spheres.nim:42
+      const tor::PlaneSeg ps = tor::plane_seg(ray, pray, sg[6], sg[7], f, xs[4]);
+      float first[2], ec[2];
+      std::memcpy(first, &h[12], 8);
+      std::memcpy(ec, &h[15], 8);
+      const tor::PlaneSeg32 ps32 = tor::plane_seg32(ray, ps, h[13], h[14], (double)ec[0], (double)ec[1]);
+      for (int i = 0; i < count; ++i) {
+        const float* pl32 = &lay.xpl32[(size_t)xs[3] + 2 * (size_t)i];
+        if (i == 0 && !(pl32[0] == first[0] && pl32[1] == first[1]))
+          return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_plane32_scene: the header's first record and the table disagree (layout bug)");
+        const bool k32 = tor::plane_word32(ps32, pl32[0], pl32[1]) < 0;
+        if (i >= real) {
+          pad_kept[r] += k32 ? 1 : 0;
+          continue;
+        }
+        const double* pl = &lay.xpl[(size_t)xs[3] + 2 * (size_t)i];
+        const bool k64 = tor::plane_word(ps, pl[0], pl[1]) < 0;
+        kr[orig_of((size_t)block0 * tor::kPad + (size_t)i)] = (int8_t)((k64 ? 1 : 0) | (k32 ? 2 : 0));
+      }
     }
   }
   return TOR_OK;

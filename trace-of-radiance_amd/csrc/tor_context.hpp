@@ -73,6 +73,7 @@ struct DeviceLayout {
   const float* hot32 = nullptr;
   const double* coop_trips = nullptr;  // coop_pixel_kernel: 4 float64 per trip of 64 cold slots
   const double *xhdr = nullptr, *xrec = nullptr, *xpl = nullptr;  // second form of the FMA screen and its stage one (tor_scene.hpp)
+  const float* xpl32 = nullptr;  // stage one in float32 (xkinds 10 / 11 / 12 / 14)
   int n_segs = 0;
   int n_sorted = 0;  // cold slots (padded)
   int n_xrec = 0;    // float64 in xrec

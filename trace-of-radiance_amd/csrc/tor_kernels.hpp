@@ -47,6 +47,7 @@ struct KParams {
   int xrec_lds_doubles; // > 0: stage two reads the second-form records from LDS (that many float64 of xrec copied per workgroup); 0: vector loads
   const double* xhdr;   // ARITH 2: one 128-byte header per segment (16 float64 slots; tor_scene.hpp HostLayout::xhdr), everything the object loop reads per segment
   const double* xpl;    // stage one of every xkind >= 10 (the plane screen): {cx, cz} per slot ({c0x, c0z, dcx, dcz} for xkind 13); null = the wave-uniform test for every object (TOR_PLANE=0)
+  const float* xpl32;   // ... in float32 for xkinds 10 / 11 / 12 / 14: {cx - Ox, cz - Oz} per slot at xpl's indices (tor_screen.hpp plane_seg32); set with xpl
   double plane_gate2;   // stage one runs on a segment when most of the wave's rays expect it to keep less than 1 / gate of the segment (tor_screen.hpp plane_pays; 4 gate^2); 0 = always (TOR_PLANE=2)
   const float* hot32;  // TOR_ACCEL_F32 pair records, or null
   double org[3];       // origin of the float32 coordinates

@@ -288,7 +288,7 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
   auto xs_of = [](int xkind) { return xkind == 0 ? 0 : (xkind >= 13 ? 8 : 4); };
   auto pw_of = [](int xkind) { return xkind == 0 ? 0 : (xkind == 13 ? 4 : 2); };
   // Slots per segment: padded to blocks of 8; a plane-screened segment whose tail would be three or four blocks is padded to the
-  // next WORD instead (32 slots: the tail runs as one whole word of stage one -- 131 vector + 21 scalar instructions -- where three
+  // next WORD instead (32 slots: the tail runs as one whole word of stage one -- 131 vector + 11 scalar instructions -- where three
   // blocks cost 96 + ~120, and every segment behind it starts on a word boundary: kernel/integrate_loop_plane.inc), unless
   // that would push the sorted list into one more 512-slot pass.  random_scene is not affected (481 = 15 words + 1).
   auto slots_of = [&](const Seg64& sg, bool words) {
@@ -325,6 +325,9 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
   out.movy.assign(6 * n_movy_p + 8, 0.0);
   out.xrec.assign(n_xrec + 8, 0.0);
   out.xpl.assign(n_xpl + 8, 1e300);  // padding: far from every ground track (a ray that keeps everything keeps it too: the second form drops it)
+  out.xpl32.assign(n_xpl + 16, kPlane32PadX);  // (the same, float32: tor_screen.hpp plane_seg32)
+  for (size_t k = 1; k < out.xpl32.size(); k += 2) out.xpl32[k] = kPlane32PadZ;
+  out.xpl32seg.clear();
   out.hot32.assign(n32_floats + 32, 0.0f);
   out.cold.assign(16 * out.n_sorted + 16, 0.0);
   out.segs.clear();
@@ -374,6 +377,17 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     // ... and of its stage one: first float64 of the segment's plane table in xpl, largest radius^2 (a NaN radius: fmax skipped
     // it -- and the reference can never hit that sphere), extents of the centres' ground projection
     out.xsegs.insert(out.xsegs.end(), {(double)sg.xkind, (double)x_off, sg.y, (double)pl_off, rmax2, ext_x, ext_z, 0.0});
+    // the float32 table of stage one: offsets from the middle of the centres' ground box, their largest rounding error E and size Cm
+    double e32 = 0.0, cm32 = 0.0;
+    const bool pl32 = sg.xkind >= 10 && sg.xkind != 13;
+    const double orx = pl32 && xhi >= xlo ? 0.5 * xlo + 0.5 * xhi : 0.0, orz = pl32 && zhi >= zlo ? 0.5 * zlo + 0.5 * zhi : 0.0;
+    for (size_t k = 0; k < sg.ids.size() && pl32; ++k) {
+      const TorMovingSphere s = as_mover(sg.ids[k]);  // (a static: centre0 = its centre; xkinds 10-12 / 14 never move in x or z)
+      const float fx = plane32_offset(s.center0.x, orx, e32), fz = plane32_offset(s.center0.z, orz, e32);
+      out.xpl32[pl_off + 2 * k] = fx; out.xpl32[pl_off + 2 * k + 1] = fz;
+      cm32 = std::fmax(cm32, std::fmax(std::fabs((double)fx), std::fabs((double)fz)));
+    }
+    out.xpl32seg.insert(out.xpl32seg.end(), {orx, orz, e32, cm32});
     const size_t xs = (size_t)xs_of(sg.xkind), pw = (size_t)pw_of(sg.xkind);
     for (size_t k = 0; k < cnt_p && xs != 0; ++k) {  // padding: never a candidate (second form: t'' = T - 1e300 < 0, disc'' < 0; first form: r^2 = -1), except for a wild ray, which the exact test rejects
       double* x = &out.xrec[x_off + xs * k];
@@ -471,6 +485,7 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     out.segs.insert(out.segs.end(), {(double)kind, (double)f_off, (double)cnt_p, (double)(sorted / kPad), t0, dt,
                                      (double)f32_round_up(mc0max * 1.000001), (double)f32_round_up(dcmax * 1.000001)});
     out.xsegs.insert(out.xsegs.end(), 8, 0.0);  // (the two tables stay parallel)
+    out.xpl32seg.insert(out.xpl32seg.end(), 4, 0.0);
     f_off += cnt_p / 2 * (size_t)stride;
     sorted += cnt_p;
     return true;
@@ -505,9 +520,14 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     h[4] = sg[4]; h[5] = sg[5]; h[6] = sg[6]; h[7] = sg[7];
     h[8] = xs[2]; h[9] = xs[4]; h[10] = xs[5]; h[11] = xs[6];
     const int xkind = (int)xs[0];
-    if (xkind >= 10) {
-      const size_t pw = xkind == 13 ? 4 : 2;
-      for (size_t k = 0; k < pw; ++k) h[12 + k] = out.xpl[(size_t)xs[3] + k];
+    if (xkind == 13) {
+      for (size_t k = 0; k < 4; ++k) h[12 + k] = out.xpl[(size_t)xs[3] + k];
+    } else if (xkind >= 10) {  // the float32 stage one's (tor_screen.hpp plane_seg32)
+      const double* o32 = &out.xpl32seg[4 * (size_t)s];
+      std::memcpy(&h[12], &out.xpl32[(size_t)xs[3]], 8);
+      h[13] = o32[0]; h[14] = o32[1];
+      const float ec[2] = {o32[2] < 0x1p126 ? f32_up(o32[2]) : INFINITY, o32[3] < 0x1p126 ? f32_up(o32[3]) : INFINITY};
+      std::memcpy(&h[15], ec, 8);
     }
   }
   // trip table of the one-wave-per-pixel kernel

@@ -20,11 +20,17 @@ struct HostLayout {
   std::vector<double> xsegs, xrec;
   // what the kernel reads of segs / xsegs, one 128-byte record per segment (16 float64 slots): int32 {xkind, kind, padded count |
   // padding << 24, first block, first hot record, first float64 in xrec, first float64 in xpl, the plane screen's gate (0 never, 1 always, 2 the wave votes)}, then float64 {time0, time1 -
-  // time0, reach, travel, common c0.y, largest radius^2, extent x, extent z} and the segment's first plane record (4 slots)
+  // time0, reach, travel, common c0.y, largest radius^2, extent x, extent z} and the segment's first plane record (4 slots);
+  // for xkinds 10 / 11 / 12 / 14 those 4 slots are {the first float32 record {cx', cz'}, Ox, Oz, {E, Cm} as float32 rounded up}
   std::vector<double> xhdr;
   // stage one in front of it (tor_screen.hpp: the plane screen, kinds 11 / 12 only): {cx, cz} per slot -- 16 bytes, the wave-uniform
   // loop reads nothing else -- at xpl[xsegs[3] + 2 * slot of the segment]; xsegs[4] = the largest radius^2 of the segment
   std::vector<double> xpl;
+  // stage one in float32 (tor_screen.hpp plane_seg32, xkinds 10 / 11 / 12 / 14): {cx - Ox, cz - Oz} per slot at the SAME indices
+  // as xpl (xkind 13's stretches unused), padding {kPlane32PadX, kPlane32PadZ}; per segment {Ox, Oz, E, Cm} in xpl32seg (0 for
+  // segments without the float32 table).  The header (xhdr) of such a segment carries them in place of the float64 first record.
+  std::vector<float> xpl32;
+  std::vector<double> xpl32seg;
   std::vector<float> hot32;  // TOR_ACCEL_F32 segments (kinds 5/6/7): packed pair records, see tor_kernels.hpp
   int n_segs = 0;
   size_t n_sorted = 0;  // cold slots (padded)

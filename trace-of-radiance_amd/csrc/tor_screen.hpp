@@ -276,7 +276,7 @@ TOR_HD PlaneRay plane_ray(const ScreenRay& r) {
 TOR_HD PlaneSeg plane_seg(const ScreenRay& r, const PlaneRay& pr, double reach, double travel, double f, double rmax2) {
   PlaneSeg s;
   const double B = r.s1 + reach + travel * __builtin_fabs(f);
-#if defined(TOR_SCREEN_MUTATE)   // (level 2 of the mutation check: only stage one's margins)
+#if defined(TOR_SCREEN_MUTATE) && TOR_SCREEN_MUTATE <= 2   // (level 2 of the mutation check: only stage one's margins)
   const double M = 0.0;
   const double thr = rmax2 * pr.w2;
 #else
@@ -304,6 +304,98 @@ TOR_HD int plane_word_mov(const PlaneSeg& s, double c0x, double c0z, double dcx,
   const double q = fma_(v, v, s.negthr);
   return (int)(unsigned)(double_to_bits(q) >> 32);
 }
+// ---------------------------------------------------------------------------------------------------------------------
+// STAGE ONE IN FLOAT32 (xkinds 10, 11, 12, 14: the {cx, cz} table).  The float64 chain above costs 3 float64 fma + the
+// v_alignbit = 7 issue slots per object; the same test in float32 costs 2 v_fma_f32 + 1 v_sub_f32 (|v| - T, the abs a free
+// modifier) + the v_alignbit = 4.  The record is 8 bytes {cx - Ox, cz - Oz} (xpl32, rounded to nearest): the centre relative to a
+// per-segment origin O (the middle of the centres' ground box), so that the float32 offsets stay small against the scene.
+//     v = fma32(nx, cx', fma32(nz, cz', c0))        keep  <=>  |v| < T          (the sign bit of |v| - T, as plane_word's)
+// Stage one only has to keep a SUPERSET of what the float64 plane screen keeps: everything behind it (stage two, the exact test)
+// is unchanged, and the float64 screen's own proof only needs its band to contain every object the second form's proof needs.
+// Why it is a superset.  Let n be the float64 normal (plane_seg), S = n . (c_xz - o_xz) exactly, and v64 the float64 chain.
+//   The float64 screen keeps iff v64^2 < thr (fma(v, v, -thr) rounds without crossing 0).  Its four roundings are each <= u N1 B
+//   (u = 2^-53, N1 = |nx| + |nz|, every partial sum <= N1 (|o|_1 + reach) <= N1 B), so it keeps only if
+//   |S| < sqrt(thr) + 4 u N1 B.  Since thr >= 2^-45 B^2 w2 and N1 <= sqrt(2) w, 4 u N1 B < 2^-27 sqrt(thr):  |S| < sqrt(thr)(1 + 2^-27).
+//   The float32 chain, with n32 = (float)n (relative 2^-24 per component), o' = o - O (float64), Co = |o'x| + |o'z|, Cm >= every
+//   stored |c'| (host), E >= |c' - (c - O)| for every stored coordinate (host, exact differences), c0 = -(n32 . o') in float64
+//   rounded to float32:
+//     the exact n32 . (c'_32) + c0_32 differs from S by at most
+//       2^-24 N1 (Cm + Co + E)          n -> n32 against |c - o| <= Cm + E + Co per component
+//     + N1 (1 + 2^-24) E                the stored centres' rounding
+//     + 2^-24 N1 Co (1 + 2^-23) + 4 u N1 Co     c0: float64 chain and its rounding to float32
+//   and the two float32 fma round by 2^-24 each of a value <= N1 (1 + 2^-24)(Cm + E) + |c0|:  2^-23 N1 (Cm + Co + E) (1 + 2^-22).
+//   In all |v32 - S| <= N1 E (1 + 2^-24) + 2^-22 N1 (Cm + Co + E) (1 + 2^-20); subnormal results (conversions and fma below
+//   2^-126) add at most 2^-150 each, times a factor <= Cm + Co + E where n is involved: < 2^-140 (1 + Cm + Co + E).
+//   So with
+//     T >= (1 + 2^-20) (sqrt(thr) + N1 E) + (2^-21 N1 + 2^-140) (Cm + Co + E) + 2^-140
+//   the float64 screen's keep implies |v32| < T.  T is summed in float64 (all terms positive; the factor (1 + 2^-40) covers the
+//   sums, the products and the square root), then converted to float32 ROUNDED UP.  The comparison is |v32| - T < 0 in float32: a
+//   negative exact difference never rounds to +0.
+// The band widens by ~N1 E + 2^-21 N1 (Cm + Co): on random_scene (offsets ~11, E ~ 2^-21) ~1e-5 against R = 0.2 -- invisible.
+// Keep everything (n = 0, c0 = 0, T = +inf: |0| - inf = -inf) when the float64 screen does, or when Cm, Co or E is above 2^60 or
+// not finite, or T is not finite in float32.  The host clamps every stored offset to [-2^100, 2^100] (finite), so 0 x c' is 0;
+// a segment with a non-finite or NaN offset gets E = +inf and keeps everything.  Padding slots hold {2^100, 0x1.3c6ef3p99}: no
+// ray with a ground track keeps them (|v| ~ 2^100 against T < 2^62 unless n is perpendicular to the padding point to within
+// 2^-38), a keep-everything ray keeps them, and stage two drops them as it drops the float64 padding.
+// xkind 13 (movers in x / z) keeps the float64 chain plane_word_mov.
+// (TOR_SCREEN_MUTATE == 3: the mutation check of this proof -- T = sqrt(thr) rounded to nearest, every margin above dropped; the
+// superset test of tests/test_plane32.py must then FAIL.  Never defined in a product build.)
+constexpr float kPlane32PadX = 0x1p100f, kPlane32PadZ = 0x1.3c6ef3p99f;
+constexpr double kPlane32Clamp = 0x1p100;
+struct PlaneSeg32 {  // per ray and segment
+  float nx, nz;      // (float) of the float64 normal; 0 when everything is kept
+  float c0;          // -(n32 . (o_xz - O)), float64 rounded to float32
+  float T;           // the threshold on |v|; +inf: everything is kept
+};
+TOR_HD float f32_up(double x) {  // the smallest float32 >= x (x >= 0 and below the float32 range)
+  float f = (float)x;
+  if ((double)f < x) f = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) + 1u);
+  return f;
+}
+// ps: the float64 plane screen of the same ray and segment; (orx, orz): the segment's origin O; e32, cm: E and Cm (host)
+TOR_HD PlaneSeg32 plane_seg32(const ScreenRay& r, const PlaneSeg& ps, double orx, double orz, double e32, double cm) {
+  PlaneSeg32 s;
+  const double ox = r.ox - orx, oz = r.oz - orz;
+  const double co = __builtin_fabs(ox) + __builtin_fabs(oz);
+  const double n1 = __builtin_fabs(ps.nx) + __builtin_fabs(ps.nz);
+  const double thr = -ps.negthr;
+  const float nx = (float)ps.nx, nz = (float)ps.nz;
+  const double c0 = -fma_((double)nx, ox, (double)nz * oz);
+#if defined(TOR_SCREEN_MUTATE) && TOR_SCREEN_MUTATE == 3
+  (void)n1;
+  const double T = __builtin_sqrt(thr);
+  const float tf = (float)T;
+#else
+  const double T = (fma_(0x1p-20, __builtin_sqrt(thr) + n1 * e32, __builtin_sqrt(thr) + n1 * e32) +
+                    fma_(n1, 0x1p-21, 0x1p-140) * ((cm + co) + e32) + 0x1p-140) * (1.0 + 0x1p-40);
+  const float tf = T < 0x1p126 ? f32_up(T) : __builtin_inff();
+#endif
+  const bool all = !(ps.negthr > -__builtin_inf()) || !(cm <= 0x1p60 && co <= 0x1p60 && e32 <= 0x1p60) || !(tf < __builtin_inff());
+  s.nx = all ? 0.0f : nx;
+  s.nz = all ? 0.0f : nz;
+  s.c0 = all ? 0.0f : (float)c0;
+  s.T = all ? __builtin_inff() : tf;
+  return s;
+}
+// the returned word's SIGN BIT is the decision (set = keep); (cx, cz): the stored offsets from the segment's origin
+TOR_HD int plane_word32(const PlaneSeg32& s, float cx, float cz) {
+  const float v = __builtin_fmaf(s.nx, cx, __builtin_fmaf(s.nz, cz, s.c0));
+  const float q = __builtin_fabsf(v) - s.T;
+  return (int)__builtin_bit_cast(uint32_t, q);
+}
+// The host's side of a segment's float32 table (tor_scene.cpp build_layout): the stored offset of one coordinate c from the
+// origin coordinate o, and a bound of its error against the exact c - o (err_io: the running maximum; +inf for a non-finite
+// offset).  d + t = c - o exactly (two-sum), d - (double)f is exact (f is d rounded to float32: Sterbenz), the sum rounds once.
+TOR_HD float plane32_offset(double c, double o, double& err_io) {
+  const double d = c - o;
+  const double bb = d - c, t = (c - (d - bb)) + (-o - bb);
+  const double dc = __builtin_fmin(__builtin_fmax(d, -kPlane32Clamp), kPlane32Clamp);
+  const float f = (float)dc;
+  const double e = __builtin_fabs((d - (double)f) + t) * (1.0 + 0x1p-50);
+  err_io = !(e < __builtin_inf()) ? __builtin_inf() : __builtin_fmax(err_io, e);
+  return f;
+}
+
 // Does stage one PAY on this segment for this ray?  It leaves the objects in a band of half-width R around the ground track to a
 // per-lane stage that costs ~8 times a wave-uniform test per object, so it only pays when the band is thin against the segment:
 // a wall of spheres seen edge-on (every centre on the ray's own ground track) would send everything through both stages.  The
