@@ -283,6 +283,40 @@ TOR_API int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nro
                               int64_t max_depth, const TorOptions* opt, double* d_pixels,
                               void* hip_stream);
 
+/* ---- progressive rendering (TOR_SEED_SAMPLE only): passes of samples into exact sums, resolve, noise -------------------
+ * In TOR_SEED_SAMPLE mode a sample's stream depends only on (row, col, sample index) and every sample is rounded to a
+ * multiple of 2^-36 before it is added, so every partial sum is exact: samples [0, k) and then [k, n) added into one buffer
+ * give the same bits as one n-sample render, and tor_resolve_device turns them into the same canvas as tor_render_device
+ * with samples_per_pixel = n.  Buffers written by separate contexts or GPUs (disjoint sample ranges) add exactly too.
+ *
+ * tor_render_accumulate_device: ADDS samples [first_sample, first_sample + n_samples) of this shard's rows to d_sums, a
+ * DEVICE buffer of tor_shard_rows()*ncols*3 float64 (same row layout as tor_render_device) holding raw quantised LINEAR
+ * sums.  It never clears the buffer: the caller zeroes it once.  d_moments (nullable, same size) additionally receives
+ * the per-channel sums of quantize36(q * q) -- the input of tor_accum_noise_device (a launch without it runs the same
+ * kernels as tor_render_device).  Row shards (shard_index / shard_count / row_tile) and every accel value work as in
+ * tor_render_device.  Asynchronous on hip_stream, with the same one-stream-per-context rule; tor_last_kernel_ms and the
+ * stats calls report this launch.  TOR_ERR_INVALID_ARGUMENT for TOR_SEED_PIXEL (a pixel is one sequential chain of
+ * samples on one generator; resuming it would need per-pixel RNG state), first_sample < 0, n_samples < 1 and
+ * first_sample + n_samples > 2^17 (131072): per-sample radiance is at most 1 per channel, so up to 2^17 samples the sums
+ * stay multiples of 2^-36 below 2^17 -- integers up to 2^53 in units of 2^-36, exact in float64.  max_depth <= 0 and an
+ * empty scene add zeros: d_sums / d_moments are left untouched.
+ *
+ * tor_resolve_device: d_pixels[i] = pow(d_sums[i] / total_samples, 1 / gamma_correction) for n_values float64 (exactly
+ * Canvas.draw's operations, canvas.nim:47-54); d_sums is left as it is (d_pixels == d_sums resolves in place).
+ * 1 <= total_samples <= 2^17.  Asynchronous on hip_stream.
+ *
+ * tor_accum_noise_device: from sums S, moments M of total_samples = N >= 2 samples, each channel's standard error of the
+ * mean sqrt(max(0, (M - S*S/N) / (N - 1)) / N) in linear (pre-gamma) units; d_err (nullable, npix float64) receives the
+ * per-pixel maximum over the three channels, out[0] / out[1] the frame's mean / maximum of it, reduced in a fixed order
+ * (repeated calls return the same bits).  Blocking: returns when out is filled. */
+TOR_API int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                                         int32_t first_sample, int32_t n_samples, int64_t max_depth,
+                                         const TorOptions* opt, double* d_sums, double* d_moments, void* hip_stream);
+TOR_API int tor_resolve_device(TorContext* ctx, const double* d_sums, int64_t n_values, int64_t total_samples,
+                               float gamma_correction, double* d_pixels, void* hip_stream);
+TOR_API int tor_accum_noise_device(TorContext* ctx, const double* d_sums, const double* d_moments, int64_t npix,
+                                   int64_t total_samples, double* d_err, double out[2], void* hip_stream);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

@@ -137,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "tor_last_render_timing", "tor_comm_unique_id", "tor_comm_init_rank", "tor_comm_destroy", "tor_render_gather_device",
     "tor_context_scene_counters", "tor_render_ptr", "tor_last_pixel_cost", "tor_last_note", "tor_last_handoff_counters",
     "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
+    "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
 ]
 
 _lib = None
@@ -272,8 +273,17 @@ def lib():
     L.tor_comm_abort.argtypes = [C.c_void_p]
     L.tor_comm_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.tor_context_handoff_stalled.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    if not ab or hasattr(L, "tor_render_accumulate_device"):  # (an A/B build older than progressive rendering lacks these three)
+        _bind_progressive(L, dp)
     _lib = L
     return L
+
+
+def _bind_progressive(L, dp) -> None:
+    L.tor_render_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                               C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tor_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+    L.tor_accum_noise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, dp, C.c_void_p]
 
 
 def _check(rc: int) -> None:
@@ -581,6 +591,29 @@ class Context:
         _check(lib().tor_render_device(self._h, C.byref(cam), nrows, ncols, spp, gamma, int(max_depth),
                                        C.byref(options), C.c_void_p(d_pixels_ptr), C.c_void_p(stream_ptr)))
 
+    def accumulate_device(self, cam: Camera, nrows: int, ncols: int, first_sample: int, n_samples: int, max_depth: int,
+                          options: Options, d_sums_ptr: int, d_moments_ptr: int = 0, stream_ptr: int = 0):
+        """Adds samples [first_sample, first_sample + n_samples) of this shard's rows to the raw sums at d_sums_ptr (and their second
+        moments at d_moments_ptr, 0 = none); never clears them.  TOR_SEED_SAMPLE only.  Asynchronous on the given hipStream_t."""
+        _check(lib().tor_render_accumulate_device(self._h, C.byref(cam), nrows, ncols, first_sample, n_samples, int(max_depth),
+                                                  C.byref(options), C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr),
+                                                  C.c_void_p(stream_ptr)))
+
+    def resolve_device(self, d_sums_ptr: int, n_values: int, total_samples: int, gamma: float, d_pixels_ptr: int,
+                       stream_ptr: int = 0):
+        """pixels = pow(sums / total_samples, 1 / gamma), the sums left as they are.  Asynchronous on the given hipStream_t."""
+        _check(lib().tor_resolve_device(self._h, C.c_void_p(d_sums_ptr), n_values, total_samples, gamma,
+                                        C.c_void_p(d_pixels_ptr), C.c_void_p(stream_ptr)))
+
+    def accum_noise_device(self, d_sums_ptr: int, d_moments_ptr: int, npix: int, total_samples: int, d_err_ptr: int = 0,
+                           stream_ptr: int = 0):
+        """(mean, max) over the pixels of the largest per-channel standard error of the mean; d_err_ptr (0 = none) receives it per
+        pixel.  Blocking."""
+        out = (C.c_double * 2)()
+        _check(lib().tor_accum_noise_device(self._h, C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr), npix, total_samples,
+                                            C.c_void_p(d_err_ptr), out, C.c_void_p(stream_ptr)))
+        return float(out[0]), float(out[1])
+
     def quantize_rgb8_device(self, d_pixels_ptr: int, n_values: int, d_rgb8_ptr: int, stream_ptr: int = 0):
         _check(lib().tor_quantize_rgb8_device(self._h, C.c_void_p(d_pixels_ptr), n_values,
                                               C.c_void_p(d_rgb8_ptr), C.c_void_p(stream_ptr)))
@@ -682,6 +715,95 @@ class Context:
         st = Stats()
         _check(lib().tor_last_stats(self._h, C.byref(st)))
         return st
+
+
+class Progressive:
+    """Progressive, resumable rendering of one (camera, size, depth, options) in TOR_SEED_SAMPLE mode: owns the device sums (and,
+    with moments=True, the second moments) of this shard's rows.  Passes of samples add up exactly, so after any sequence of
+    add() calls totalling n samples, image() is the canvas a one-shot n-spp render_device gives, bit for bit.
+
+        pg = Progressive(ctx, cam, 1080, 1920, 50, make_options(seeding=SEED_SAMPLE), moments=True)
+        pg.add(16); preview = pg.image(); pg.render_until(max_se=1e-3, max_samples=4096)
+
+    The context must have the scene uploaded; all device work runs on torch's current stream of the buffers' device."""
+
+    def __init__(self, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None = None,
+                 moments: bool = False, device=None):
+        import torch
+        self.ctx, self.nrows, self.ncols, self.max_depth = ctx, int(nrows), int(ncols), int(max_depth)
+        self.cam = Camera.from_buffer_copy(cam)
+        self.options = Options.from_buffer_copy(options if options is not None else make_options(seeding=SEED_SAMPLE))
+        if self.options.seeding != SEED_SAMPLE:
+            raise TorError(ERR_INVALID_ARGUMENT, "Progressive: needs TOR_SEED_SAMPLE (TOR_SEED_PIXEL pixels are sequential chains "
+                                                 "on one generator and cannot be resumed)")
+        self.rows = len(shard_rows(self.nrows, max(int(self.options.row_tile), 1), int(self.options.shard_index),
+                                   max(int(self.options.shard_count), 1)))
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        self.sums = torch.zeros((self.rows, self.ncols, 3), dtype=torch.float64, device=dev)
+        self.moments = torch.zeros_like(self.sums) if moments else None
+        self.samples = 0
+
+    def _stream(self) -> int:
+        import torch
+        return torch.cuda.current_stream(self.sums.device).cuda_stream
+
+    def add(self, n: int) -> "Progressive":
+        """Render the next n samples per pixel into the sums (asynchronous on the current stream)."""
+        self.ctx.accumulate_device(self.cam, self.nrows, self.ncols, self.samples, int(n), self.max_depth, self.options,
+                                   self.sums.data_ptr(), self.moments.data_ptr() if self.moments is not None else 0, self._stream())
+        self.samples += int(n)
+        return self
+
+    def image(self, gamma: float = 2.2):
+        """The gamma-corrected canvas of the samples so far: a new device float64 tensor (rows of this shard, ncols, 3)."""
+        import torch
+        out = torch.empty_like(self.sums)
+        self.ctx.resolve_device(self.sums.data_ptr(), self.sums.numel(), self.samples, gamma, out.data_ptr(), self._stream())
+        return out
+
+    def to_canvas(self, canvas: Canvas) -> Canvas:
+        """Fill a host Canvas (whole frame, unsharded options) with image(canvas.gamma_correction), so export_ppm works."""
+        if (canvas.nrows, canvas.ncols) != (self.rows, self.ncols):
+            raise TorError(ERR_INVALID_ARGUMENT, "Progressive.to_canvas: the canvas must have this render's rows and columns")
+        canvas.pixels[...] = self.image(canvas.gamma_correction).cpu().numpy()
+        canvas.samples_per_pixel = self.samples
+        return canvas
+
+    def noise(self):
+        """(mean, max) over the pixels of the largest per-channel standard error of the mean, linear units.  Blocking."""
+        if self.moments is None:
+            raise TorError(ERR_INVALID_ARGUMENT, "Progressive.noise: created without moments=True")
+        return self.ctx.accum_noise_device(self.sums.data_ptr(), self.moments.data_ptr(), self.rows * self.ncols, self.samples, 0,
+                                           self._stream())
+
+    def render_until(self, max_se: float, max_samples: int, pass_samples: int = 16) -> int:
+        """Add passes of pass_samples until the largest per-pixel standard error is <= max_se or max_samples are reached
+        (the last pass is shortened to land on max_samples).  Returns the sample count."""
+        while self.samples < max_samples:
+            self.add(min(int(pass_samples), int(max_samples) - self.samples))
+            if self.moments is not None and self.samples >= 2 and self.noise()[1] <= max_se:
+                break
+        return self.samples
+
+    def state(self) -> dict:
+        """Checkpoint: the sums, the moments (or None) and the sample count as host numpy arrays / int."""
+        return {"samples": self.samples, "sums": self.sums.cpu().numpy(),
+                "moments": self.moments.cpu().numpy() if self.moments is not None else None}
+
+    @classmethod
+    def from_state(cls, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None,
+                   state: dict, device=None) -> "Progressive":
+        """Resume a checkpoint (state()) on this context -- any process, any GPU with the same scene uploaded."""
+        import torch
+        pg = cls(ctx, cam, nrows, ncols, max_depth, options, moments=state.get("moments") is not None, device=device)
+        sums = np.ascontiguousarray(state["sums"], dtype=np.float64)
+        if sums.shape != tuple(pg.sums.shape):
+            raise TorError(ERR_INVALID_ARGUMENT, f"Progressive.from_state: sums of shape {sums.shape}, expected {tuple(pg.sums.shape)}")
+        pg.sums.copy_(torch.from_numpy(sums))
+        if pg.moments is not None:
+            pg.moments.copy_(torch.from_numpy(np.ascontiguousarray(state["moments"], dtype=np.float64)))
+        pg.samples = int(state["samples"])
+        return pg
 
 
 def mp4_mux_file(src_annexb_path: str, dst_mp4_path: str, width: int, height: int, fps: int = 30) -> int:

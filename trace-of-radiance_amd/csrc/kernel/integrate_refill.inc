@@ -92,7 +92,7 @@
             const unsigned within = lrow - tile * (unsigned)p.row_tile;
             const unsigned grow = (tile * (unsigned)p.shard_count + (unsigned)p.shard_index) * (unsigned)p.row_tile + within;
             Rng g;
-            seed3(g, (uint64_t)grow, (uint64_t)gcol, (uint64_t)gs);
+            seed3(g, (uint64_t)grow, (uint64_t)gcol, (uint64_t)((unsigned)p.first_sample + gs));  // (progressive passes: the frame's sample index)
             // render.nim:64-66
             const double fs = ((double)(int)gcol + uniform01(g)) / w_div;
             const double ft = ((double)(int)grow + uniform01(g)) / h_div;
@@ -225,7 +225,7 @@
       }
     }
     if (!active && have_item) {
-      if (SEEDING != 0) seed3(rng, (uint64_t)row, (uint64_t)col, (uint64_t)s);
+      if (SEEDING != 0) seed3(rng, (uint64_t)row, (uint64_t)col, (uint64_t)((unsigned)p.first_sample + (unsigned)s));  // (progressive passes: the frame's sample index)
       have_item = false;  // the pending sample is consumed by starting its path
       // render.nim:64-66
       const double u = ((double)col + uniform01(rng)) / w_div;

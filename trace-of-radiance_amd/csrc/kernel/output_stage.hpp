@@ -1,10 +1,80 @@
-// kernel/output_stage.hpp -- the small kernels around the integrator: finalize (canvas.nim:47-54), quantize (io/ppm.nim:15-16),
+// kernel/output_stage.hpp -- the small kernels around the integrator: finalize (canvas.nim:47-54), resolve / accum_noise (progressive rendering), quantize (io/ppm.nim:15-16),
 // encode_ipcm (animation output stage), gather_rows (multi-GPU assembly), selftest, spin_until.  Textually included by tor_kernels.hip.
 // canvas.nim:47-54
 __global__ __launch_bounds__(256) void finalize_kernel(double* pixels, long long n_values, double scale,
                                                         double gamma) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_values) pixels[i] = pow_pos(scale * pixels[i], gamma);
+}
+
+// Progressive rendering (tor_resolve_device): finalize_kernel's operations on sums that stay where they are, so a resolved
+// progressive frame is the one-shot frame bit for bit and more passes can follow.  pixels == sums is allowed.
+__global__ __launch_bounds__(256) void resolve_kernel(const double* sums, double* pixels, long long n_values, double scale,
+                                                       double gamma) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_values) pixels[i] = pow_pos(scale * sums[i], gamma);
+}
+
+// Progressive rendering (tor_accum_noise_device): per pixel, the largest over the channels of the standard error of the mean,
+// sqrt(max(0, (M - S*S/n) / (n - 1)) / n), linear units; err nullable.  Block b sums / maxes pixels b*256 + t + k*gridDim*256
+// in a fixed order and a fixed tree: partials[2b] = sum, partials[2b + 1] = max.
+__global__ __launch_bounds__(256) void accum_noise_kernel(const double* sums, const double* moments, long long npix, double n,
+                                                           double* err, double* partials) {
+  __shared__ double s_sum[256], s_max[256];
+  double acc = 0.0, mx = 0.0;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < npix; i += stride) {
+    double e = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double S = sums[i * 3 + c], M = moments[i * 3 + c];
+      double var = (M - S * S / n) / (n - 1.0);
+      var = var > 0.0 ? var : 0.0;
+      const double se = __builtin_sqrt(var / n);
+      e = se > e ? se : e;
+    }
+    if (err) err[i] = e;
+    acc += e;
+    mx = e > mx ? e : mx;
+  }
+  s_sum[threadIdx.x] = acc;
+  s_max[threadIdx.x] = mx;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+      s_max[threadIdx.x] = s_max[threadIdx.x + w] > s_max[threadIdx.x] ? s_max[threadIdx.x + w] : s_max[threadIdx.x];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partials[2 * blockIdx.x] = s_sum[0];
+    partials[2 * blockIdx.x + 1] = s_max[0];
+  }
+}
+
+// ... and the partials of its n_blocks blocks, again in a fixed order: out2 = {sum, max}
+__global__ __launch_bounds__(256) void accum_noise_finish_kernel(const double* partials, int n_blocks, double* out2) {
+  __shared__ double s_sum[256], s_max[256];
+  double acc = 0.0, mx = 0.0;
+  for (int b = threadIdx.x; b < n_blocks; b += 256) {
+    acc += partials[2 * b];
+    mx = partials[2 * b + 1] > mx ? partials[2 * b + 1] : mx;
+  }
+  s_sum[threadIdx.x] = acc;
+  s_max[threadIdx.x] = mx;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+      s_max[threadIdx.x] = s_max[threadIdx.x + w] > s_max[threadIdx.x] ? s_max[threadIdx.x + w] : s_max[threadIdx.x];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out2[0] = s_sum[0];
+    out2[1] = s_max[0];
+  }
 }
 
 // io/ppm.nim:15-16 ; safe_math.nim:10-14

@@ -294,7 +294,7 @@ extern "C" {
 
 const char* tor_last_error(void) { return g_last_error.c_str(); }
 
-const char* tor_version(void) { return "tor_mi355x 0.4 (gfx950)"; }
+const char* tor_version(void) { return "tor_mi355x 0.5 (gfx950)"; }
 
 int32_t tor_knob_count(void) { return tor::kKnobCount; }
 
@@ -393,6 +393,7 @@ int tor_context_destroy(TorContext* ctx) {
   ctx->slice.release();
   ctx->gather.release();
   ctx->frame.release();
+  ctx->noise.release();
   ctx->staging.release();
   for (hipEvent_t ev : ctx->chunk_events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : ctx->ev_call) if (ev) (void)hipEventDestroy(ev);
@@ -474,19 +475,27 @@ int32_t tor_shard_rows(int32_t nrows, int32_t row_tile, int32_t shard_index, int
   return n;
 }
 
-int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
-                      int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
-                      double* d_pixels, void* hip_stream) {
-  if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: NULL argument");
-  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: no scene uploaded");
+// tor_render_device, and -- acc != null -- one pass of tor_render_accumulate_device: samples [acc->first_sample, + spp) added to the
+// raw quantised sums in d_pixels (and, with acc->moments, their second moments), no clearing, no finalize
+static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                              int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
+                              double* d_pixels, void* hip_stream, const tor::AccumLaunch* acc) {
+  const std::string who = acc ? "tor_render_accumulate_device" : "tor_render_device";
+  if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
+  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": no scene uploaded");
   // The reference divides by (ncols-1) and (nrows-1) (render.nim:64-65) and by spp
   // (canvas.nim:49); degenerate sizes are rejected instead of producing inf/NaN canvases.
   if (nrows < 2 || ncols < 2 || spp < 1)
-    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: need nrows >= 2, ncols >= 2, samples_per_pixel >= 1");
+    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": need nrows >= 2, ncols >= 2, samples_per_pixel >= 1");
   if (max_depth > 0x7fffffff) max_depth = 0x7fffffff;
   TorOptions o;
-  if (!valid_options(opt, o, false)) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: bad TorOptions: " + tor::options_why());
-  if (o.device_count > 1) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: one context renders on one device (device lists: tor_render_opt)");
+  if (!valid_options(opt, o, false)) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": bad TorOptions: " + tor::options_why());
+  if (o.device_count > 1) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": one context renders on one device (device lists: tor_render_opt)");
+  if (acc && o.seeding != TOR_SEED_SAMPLE)
+    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
+                                                "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
+  // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them
+  const int kseed = (acc && acc->moments) ? 3 : o.seeding;
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipSetDevice(ctx->device));
 
@@ -508,8 +517,8 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
   if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != hip_stream) {
     const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
     if (q == hipErrorNotReady)
-      return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_device: the previous launch of this context is still running on a different stream -- "
-                                            "launches of one context that may overlap must use ONE stream (or use one context per stream)");
+      return fail(TOR_ERR_INVALID_ARGUMENT, who + ": the previous launch of this context is still running on a different stream -- "
+                                                  "launches of one context that may overlap must use ONE stream (or use one context per stream)");
     if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
   }
   ctx->last_stream = hip_stream;
@@ -517,11 +526,12 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
   unsigned long long* const slot_counters = (unsigned long long*)ctx->counters.ptr + (size_t)slot * TorContext::kSlotWords;
   HIP_TRY(hipMemsetAsync(slot_counters, 0, TorContext::kSlotWords * sizeof(unsigned long long), stream));
   if (max_depth <= 0 || ctx->n_objects < 0) {
+    if (acc) return TOR_OK;  // every sample is black: the pass adds zeros, the sums (and moments) stay as they are
     // render.nim:25: the bounce loop does not run -> every sample is black -> pow(0, g) = 0
     HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
     return TOR_OK;
   }
-  if (o.seeding == TOR_SEED_SAMPLE) HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
+  if (o.seeding == TOR_SEED_SAMPLE && !acc) HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
 
   tor::KParams p{};
   // Small SEED_PIXEL frames: one wave per pixel (coop_pixel_kernel) -- the lane-per-pixel kernel would be bound by
@@ -574,7 +584,7 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
       q.xrec_lds_doubles = 0;
       if (q.xpl != nullptr && ctx->screen && accel == 0) {
         const size_t wgs = (size_t)std::max(1, ctx->max_blocks_per_cu[o.seeding][0]);
-        const size_t need = (size_t)L.n_xrec * 8 + (size_t)tor::integrate_fixed_lds_bytes(0, 0, o.seeding);
+        const size_t need = (size_t)L.n_xrec * 8 + (size_t)tor::integrate_fixed_lds_bytes(0, 0, kseed);
         if (need <= (size_t)(160 * 1024) / wgs - 1024 && need <= (size_t)64 * 1024) q.xrec_lds_doubles = L.n_xrec;
       }
       q.n_segs = L.n_segs;
@@ -639,7 +649,7 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
       int& wg = stage_wg;
       wg = 0;
       auto fits = [&](size_t bytes, int wgs) {
-        return bytes <= hard_cap && bytes + (size_t)tor::integrate_fixed_lds_bytes(1, q.shot32 != nullptr ? 1 : 0) <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
+        return bytes <= hard_cap && bytes + (size_t)tor::integrate_fixed_lds_bytes(1, q.shot32 != nullptr ? 1 : 0, kseed) <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
       };
       // Workgroups per CU come first: on the 1601-object animation frames 3 workgroups/CU reading the records through L2
       // render 2339 Msamples/s, 2 workgroups/CU with the records in LDS 1914.  So the launch keeps its full workgroup count
@@ -680,7 +690,7 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
     if (cap < 1) cap = 4;
     if (stage_wg > 0 && stage_wg < cap) cap = stage_wg;
     waves_per_simd = ctx->waves_override > 0 ? ctx->waves_override : ((cap >= 2 && cap <= 4) ? cap : 4);
-    int bpc_eff = tor::integrate_blocks_per_cu(p, o.seeding, o.arith, waves_per_simd);
+    int bpc_eff = tor::integrate_blocks_per_cu(p, kseed, o.arith, waves_per_simd);
     if (bpc_eff > cap) bpc_eff = cap;
     resident_waves = (long long)ctx->num_cus * bpc_eff * (tor::kThreads / 64);
     configured = true;
@@ -751,6 +761,8 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
   p.work_counter = slot_counters;
   p.stats = ctx->collect_stats ? slot_counters + 1 : nullptr;
   p.out = d_pixels;
+  p.first_sample = acc ? acc->first_sample : 0;
+  p.mom = acc ? acc->moments : nullptr;
 
   long long waves;
   p.n_pixels = (unsigned)npix;
@@ -919,7 +931,7 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
       const long long wave_blocks = (long long)ctx->num_cus * tor::coop_blocks_per_cu(wk, o.arith);
       HIP_TRY(tor::launch_coop(wk, o.arith, (int)wave_blocks, ctx->stream2));
       HIP_TRY(hipEventRecord(ctx->ev_join[slot], ctx->stream2));
-      HIP_TRY(tor::launch_integrate(p, o.seeding, o.arith, waves_per_simd, blocks, stream));
+      HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
       HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_join[slot], 0));
       HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
       ctx->launches += 1;
@@ -942,22 +954,78 @@ int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int3
     if (ev) HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
     else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(tor::launch_integrate(p, o.seeding, o.arith, waves_per_simd, blocks, stream));
+    HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
     HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     HIP_TRY(hipEventRecord(ev, stream));
   } else {
     HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(tor::launch_integrate(p, o.seeding, o.arith, waves_per_simd, blocks, stream));
+    HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
     HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
   }
   ctx->launches += 1;
   ctx->last_slot = slot;
   ctx->timing_valid = true;
   ctx->last_samples = (int64_t)npix * spp;
+  if (acc) return TOR_OK;  // raw sums: tor_resolve_device finalizes
   // canvas.nim:47-54
   const double scale = 1.0 / (double)spp;
   const double gamma = 1.0 / (double)gamma_correction;
   HIP_TRY(tor::launch_finalize(d_pixels, n_values, scale, gamma, stream));
+  return TOR_OK;
+}
+
+int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                      int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
+                      double* d_pixels, void* hip_stream) {
+  return render_device_impl(ctx, cam, nrows, ncols, spp, gamma_correction, max_depth, opt, d_pixels, hip_stream, nullptr);
+}
+
+// ---- progressive rendering (TOR_SEED_SAMPLE): passes of samples into raw sums, resolve, noise -------------------------
+// Exactness bound: a sample's quantised radiance q is a multiple of 2^-36 in [0, 1] per channel (the sky is at most 1 --
+// render.nim:41-45 -- and every bounce multiplies by an albedo of at most 1: scenes.nim's materials, the same assumption the
+// one-shot TOR_SEED_SAMPLE mode rests on).  A sum of N such values is k * 2^-36 with k <= N * 2^36; float64 holds every
+// integer k <= 2^53 exactly, so every partial sum -- in any order, any split -- is exact for N <= 2^17.  The moments
+// quantize36(q * q) lie in [0, 1] too: same bound.
+static const int64_t kMaxAccumSamples = (int64_t)1 << 17;
+
+int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols, int32_t first_sample,
+                                 int32_t n_samples, int64_t max_depth, const TorOptions* opt, double* d_sums, double* d_moments,
+                                 void* hip_stream) {
+  if (first_sample < 0 || n_samples < 1 || (int64_t)first_sample + n_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_accumulate_device: need first_sample >= 0, n_samples >= 1 and first_sample + n_samples "
+                                          "<= 2^17 (131072): beyond that the 2^-36-granular float64 sums are no longer exact");
+  if (!ctx || !cam || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_accumulate_device: NULL argument");
+  const tor::AccumLaunch acc{first_sample, d_moments};
+  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+}
+
+int tor_resolve_device(TorContext* ctx, const double* d_sums, int64_t n_values, int64_t total_samples, float gamma_correction,
+                       double* d_pixels, void* hip_stream) {
+  if (n_values < 0 || total_samples < 1 || total_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_resolve_device: need n_values >= 0 and 1 <= total_samples <= 2^17");
+  if (!ctx || !d_sums || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_resolve_device: NULL argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  // canvas.nim:47-54 with finalize_kernel's operands: a resolved progressive frame is the one-shot frame bit for bit
+  HIP_TRY(tor::launch_resolve(d_sums, d_pixels, n_values, 1.0 / (double)total_samples, 1.0 / (double)gamma_correction, (hipStream_t)hip_stream));
+  return TOR_OK;
+}
+
+int tor_accum_noise_device(TorContext* ctx, const double* d_sums, const double* d_moments, int64_t npix, int64_t total_samples,
+                           double* d_err, double out[2], void* hip_stream) {
+  if (npix < 1 || total_samples < 2 || total_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_accum_noise_device: need npix >= 1 and 2 <= total_samples <= 2^17 (the variance needs two samples)");
+  if (!ctx || !d_sums || !d_moments || !out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_accum_noise_device: NULL argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(ctx->noise.ensure(((size_t)tor::kNoiseMaxBlocks + 1) * 2 * sizeof(double)));
+  double* partials = (double*)ctx->noise.ptr;
+  double* dout = partials + 2 * tor::kNoiseMaxBlocks;
+  HIP_TRY(tor::launch_accum_noise(d_sums, d_moments, npix, (double)total_samples, d_err, partials, dout, stream));
+  double h[2] = {0.0, 0.0};
+  HIP_TRY(hipMemcpyAsync(h, dout, sizeof(h), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  out[0] = h[0] / (double)npix;
+  out[1] = h[1];
   return TOR_OK;
 }
 

@@ -147,6 +147,7 @@ struct TorContext {
   tor::DeviceBuffer slice;     // tor_render_frame_h264's device slice buffer
   tor::DeviceBuffer gather;    // root of a multi-device render / RCCL gather: the ranks' shards, rank-major
   tor::DeviceBuffer frame;     // ... de-interleaved frame (multi-device tor_render_opt)
+  tor::DeviceBuffer noise;     // tor_accum_noise_device's per-block partials and result
   tor::PinnedBuffer staging;   // D2H target
   std::vector<hipEvent_t> chunk_events;
   hipEvent_t ev_call[2] = {};    // tor_render_opt: around the launches of one call (tor_last_render_timing out[1])
@@ -198,6 +199,12 @@ struct TorContext {
 };
 
 namespace tor {
+
+// one pass of tor_render_accumulate_device (tor_api.cpp render_device_impl): its first sample index, the moments buffer (nullable)
+struct AccumLaunch {
+  int first_sample;
+  double* moments;
+};
 
 // Options with defaults applied; false when malformed.  `for_drop_in`: NULL options take tor_render()'s
 // environment defaults (TOR_DEFAULT_ACCEL, TOR_DEVICES, TOR_GATHER).

@@ -20,6 +20,9 @@
 //                        depend on the schedule.
 //       SEEDING 2 (probe)          : SEEDING 1 streams, 2 spp; only counts closest-hit queries per
 //                        tile (input of the SEED_PIXEL tile schedule); never touches the canvas.
+//       SEEDING 3 (progressive + moments): SEEDING 1 that also sums quantize36(q * q) per pixel and
+//                        channel (KParams.mom; tor_render_accumulate_device with a moments buffer).
+//     Sample streams are seeded with KParams.first_sample + the launch's sample index (progressive passes).
 //
 //     Objects are wave-uniform inside the hot loop, so their records come through the scalar data
 //     path (s_load into SGPRs, constant-bus operand of the VALU op): no VGPRs, no LDS bandwidth,
@@ -45,6 +48,7 @@
 //   tile_order_kernel  counting sort of the SEED_PIXEL tiles by probed cost (LPT schedule) + the split point
 //   gather_rows_kernel multi-GPU assembly: rank-major row shards -> frame in image order
 //   finalize_kernel    canvas.nim:47-54 (draw): pow(sum * 1/spp, 1/gamma)
+//   resolve_kernel     the same, out of place (progressive sums survive); accum_noise_kernel: per-pixel standard error
 //   quantize_kernel    io/ppm.nim:15-16
 //
 // float64 throughout, no FMA contraction (-ffp-contract=off): the only fused operations are the explicit fma() of the
@@ -149,10 +153,14 @@ constexpr int coop_bytes(int blocks) { return (blocks ? 2 : 1) * kCoopList * 4 +
 // Camera-ray reservoir (TOR_SEED_SAMPLE, float64 brute force: kernel/integrate_refill.inc): 64 started samples per wave --
 // generator state after the camera ray (4 x u64), lens offsets, film coordinates, time (5 x f64), pixel as a byte offset from
 // the batch's first pixel (+ that pixel, 16-byte padded)
-constexpr bool reservoir_variant(int seeding, int f32, int blocks) { return seeding == 1 && f32 == 0 && blocks == 0; }
+constexpr bool sample_variant(int seeding) { return seeding == 1 || seeding == 3; }  // per-sample streams, quantised deposit
+constexpr bool moment_variant(int seeding) { return seeding == 3; }
+constexpr bool reservoir_variant(int seeding, int f32, int blocks) { return sample_variant(seeding) && f32 == 0 && blocks == 0; }
 constexpr int kResBytes = 9 * 64 * 8 + 64 + 16;
-constexpr int wave_lds_bytes(int blocks, int coop = 0, int res = 0) {
-  return queue_cap(blocks) * 64 * 4 + kAccSlots * 3 * 8 + kAccSlots * 4 + kProfSlots * 8 + (coop ? coop_bytes(blocks) + 64 : 0) + (res ? kResBytes : 0);
+// (moment variants: the second-moment cache [kAccSlots][3] f64 at the END of the wave's carve-out, so every other offset stays)
+constexpr int wave_lds_bytes(int blocks, int coop = 0, int res = 0, int mom = 0) {
+  return queue_cap(blocks) * 64 * 4 + kAccSlots * 3 * 8 + kAccSlots * 4 + kProfSlots * 8 + (coop ? coop_bytes(blocks) + 64 : 0) + (res ? kResBytes : 0) +
+         (mom ? kAccSlots * 3 * 8 : 0);
 }
 // Which kernel variants resolve cooperatively: TOR_ACCEL_BLOCKS | TOR_ACCEL_F32.  (The code also runs the variants
 // without boxes -- `blocks == 0 || f32 != 0` passes every parity test -- but there the candidates are few (1.25-1.43
@@ -233,8 +241,10 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   constexpr int kQCap = kAccInLds ? 4 : kQLayout;      // ... and the ones this variant uses
   constexpr int kAccPad = coop_variant(F32, BLOCKS) ? 64 : 0;
   constexpr bool kRes = reservoir_variant(SEEDING, F32, BLOCKS);
-  constexpr int kWaveLdsBytes = wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes);
+  constexpr bool kMom = moment_variant(SEEDING);
+  constexpr int kWaveLdsBytes = wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes, kMom);
   unsigned char* wave_lds = smem_raw + wave * kWaveLdsBytes;
+  double* mom_lds = reinterpret_cast<double*>(wave_lds + wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes));  // [kAccSlots][3] (kMom variants)
   unsigned* q = reinterpret_cast<unsigned*>(wave_lds) + lane;  // q[k * 64]: k-th entry of this lane
   double* acc_lds = reinterpret_cast<double*>(wave_lds + kQLayout * 64 * 4);          // [kAccSlots][3]
   int* tag_lds = reinterpret_cast<int*>(wave_lds + kQLayout * 64 * 4 + kAccSlots * 24);  // [kAccSlots]
@@ -296,10 +306,11 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
     __syncthreads();
   }
 
-  if (SEEDING == 1) {
+  if (sample_variant(SEEDING)) {
     if (lane < kAccSlots) {
       tag_lds[lane] = -1;
       acc_lds[lane * 3 + 0] = 0.0; acc_lds[lane * 3 + 1] = 0.0; acc_lds[lane * 3 + 2] = 0.0;
+      if (kMom) { mom_lds[lane * 3 + 0] = 0.0; mom_lds[lane * 3 + 1] = 0.0; mom_lds[lane * 3 + 2] = 0.0; }
     }
   }
 
@@ -674,7 +685,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
     }
 
     TOR_SEC(kSecShade)
-    if (SEEDING == 1) {
+    if (sample_variant(SEEDING)) {
 #include "kernel/integrate_deposit.inc"
     }
     TOR_SEC(kSecDeposit)
@@ -694,12 +705,13 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
     }
   }
 
-  if (SEEDING == 1) {
+  if (sample_variant(SEEDING)) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (lane < kAccSlots * 3) {
       const int slot = lane / 3, ch = lane - slot * 3;
       const int tag = tag_lds[slot];
       if (tag >= 0) unsafeAtomicAdd(p.out + (size_t)tag * 3 + ch, acc_lds[slot * 3 + ch]);
+      if (kMom && tag >= 0) unsafeAtomicAdd(p.mom + (size_t)tag * 3 + ch, mom_lds[slot * 3 + ch]);
     }
   }
   if (stats_on) {
@@ -740,7 +752,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
 // ---------------------------------------------------------------------------------------
 // host-side launchers (called from tor_api.cpp)
 // ---------------------------------------------------------------------------------------
-// variant table: [seeding 0|1|2 (2: the cost probe)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
+// variant table: [seeding 0|1|2|3 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
 // [blocks 0|1|2 (2: two-level layouts, cooperative variants only)].  The block-expansion code (an unrolled 8-object stage per lane)
 // is what makes the 168-register variants spill; launches without TOR_ACCEL_BLOCKS use kernels compiled without it (no scratch
 // traffic at all).  (Round 5: the 20 TOR_ARITH_FUSED instantiations -- `arith 1`, not the reference's rounding -- are gone.)
@@ -751,8 +763,10 @@ static IntegrateFn integrate_variant(int seeding, int arith, int w, int f32, int
   TOR_V4(0, 0, 2) TOR_V4(1, 0, 2)
   TOR_V4(0, 0, 3) TOR_V4(1, 0, 3)
   TOR_V4(2, 0, 3)   // cost probe of the SEED_PIXEL tile schedule
+  TOR_V4(3, 0, 2) TOR_V4(3, 0, 3)  // progressive launches that also sum the second moments (tor_render_accumulate_device)
   // arith 2: the reference's arithmetic behind the conservative FMA screen (brute-force layouts only)
   TOR_V(0, 2, 2, 0, 0) TOR_V(0, 2, 3, 0, 0) TOR_V(1, 2, 2, 0, 0) TOR_V(1, 2, 3, 0, 0) TOR_V(2, 2, 3, 0, 0)
+  TOR_V(3, 2, 2, 0, 0) TOR_V(3, 2, 3, 0, 0)
   // (round 5: a 128-register build <1, 2, 4, 0, 0> for a 4th workgroup per CU now runs 2.4 x SLOWER -- 1097 against 2613 Msamples/s
   // at configs[1]: stage two's per-lane state spills inside the loops; not built)
   // (a 128-register build of <1, 2, W, 0, 0> for a 4th workgroup per CU was measured in round 4: 1951 against 1961 Msamples/s at
@@ -770,7 +784,8 @@ static int clamp_w(int waves_per_simd) {
 static int wants_f32(const KParams& p) { return (p.hot32 != nullptr || p.shot32 != nullptr) ? 1 : 0; }
 static int wants_blocks(const KParams& p) { return p.bnd != nullptr ? ((p.two_level != 0 && wants_f32(p) != 0) ? 2 : 1) : 0; }
 static size_t dynamic_lds(const KParams& p, int seeding) {
-  return (size_t)wave_lds_bytes(wants_blocks(p), coop_variant(wants_f32(p), wants_blocks(p)), reservoir_variant(seeding, wants_f32(p), wants_blocks(p))) * (kThreads / 64) + (size_t)p.shot_lds_doubles * 8 + (size_t)p.shot32_lds_floats * 4 +
+  return (size_t)wave_lds_bytes(wants_blocks(p), coop_variant(wants_f32(p), wants_blocks(p)), reservoir_variant(seeding, wants_f32(p), wants_blocks(p)),
+                                moment_variant(seeding)) * (kThreads / 64) + (size_t)p.shot_lds_doubles * 8 + (size_t)p.shot32_lds_floats * 4 +
          (size_t)p.bnd32_lds_floats * 4 +
          // (the second-form table of stage two: only the ARITH 2 variants -- brute-force layouts behind the screen -- stage it)
          ((p.screen != 0 && wants_f32(p) == 0 && wants_blocks(p) == 0) ? (size_t)p.xrec_lds_doubles * 8 : (size_t)0);
@@ -849,13 +864,31 @@ hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stre
 }
 
 int integrate_fixed_lds_bytes(int blocks, int f32, int seeding) {
-  return wave_lds_bytes(blocks, coop_variant(f32, blocks), reservoir_variant(seeding, f32, blocks)) * (kThreads / 64);
+  return wave_lds_bytes(blocks, coop_variant(f32, blocks), reservoir_variant(seeding, f32, blocks), moment_variant(seeding)) * (kThreads / 64);
 }
 
 hipError_t launch_finalize(double* pixels, long long n_values, double scale, double gamma, hipStream_t stream) {
   if (n_values <= 0) return hipSuccess;
   unsigned blocks = (unsigned)((n_values + 255) / 256);
   hipLaunchKernelGGL(finalize_kernel, dim3(blocks), dim3(256), 0, stream, pixels, n_values, scale, gamma);
+  return hipGetLastError();
+}
+
+hipError_t launch_resolve(const double* sums, double* pixels, long long n_values, double scale, double gamma, hipStream_t stream) {
+  if (n_values <= 0) return hipSuccess;
+  unsigned blocks = (unsigned)((n_values + 255) / 256);
+  hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(256), 0, stream, sums, pixels, n_values, scale, gamma);
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_noise(const double* sums, const double* moments, long long npix, double n, double* err, double* partials,
+                              double* out2, hipStream_t stream) {
+  if (npix <= 0) return hipErrorInvalidValue;
+  // the grid depends on npix alone: the same pixels meet in the same partial sums in the same order on every call
+  const long long want = (npix + 255) / 256;
+  const unsigned blocks = (unsigned)(want < kNoiseMaxBlocks ? want : kNoiseMaxBlocks);
+  hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(256), 0, stream, sums, moments, npix, n, err, partials);
+  hipLaunchKernelGGL(accum_noise_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partials, (int)blocks, out2);
   return hipGetLastError();
 }
 

@@ -107,6 +107,10 @@ struct KParams {
   unsigned mig_flags;           // bit 0: acquire (not relaxed) polling; bit 1: adaptive push threshold; bits 8-15: longest back-off of a waiting server in naps of ~3.4 us; bits 16-31: at most this many waiting servers (0 = no limit)
   int screen;                   // strict launches of brute-force layouts: 1 = conservative FMA screen in the object loop (kernel variant ARITH 2; same canvas), 0 = the reference's unfused discriminant for every object
   int n_boxes;                  // block boxes of a single-level culling layout (padded to kPad), the servers' first trip
+  // progressive rendering (tor_render_accumulate_device; SEED_SAMPLE only): this launch traces samples [first_sample, first_sample + spp)
+  // of every pixel -- sample s of the launch is seeded with first_sample + s -- and adds them to out without clearing it
+  int first_sample;
+  double* mom;  // SEEDING 3 (sample streams + second moments): per pixel and channel, the sum of quantize36(q * q) over the samples; else null
 };
 
 // Control words of the hand-off, one 128-byte line per access pattern (thousands of waiting servers poll their flags and,
@@ -141,7 +145,7 @@ int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_
 size_t coop_lds_bytes(int coop_slots);
 int coop_blocks_per_cu(const KParams& p, int arith);  // 0: the objects do not fit LDS
 hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream);
-int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir)
+int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir) (+ the moment cache, seeding 3)
 hipError_t launch_probe(const KParams& p, int blocks, hipStream_t stream);
 // schedule of the chain hand-off, computed on the device from the probe's total (tile_order_kernel): l_avg = probed queries x
 // lavg_scale = bounce iterations an average lane runs in this frame; dedicated server workgroups = srv_frac x blocks when a
@@ -160,6 +164,13 @@ bool integrate_variant_serves_chains(const KParams& p, int seeding);  // the lau
 constexpr int kTilePixelsHost = 64;  // == kTilePixels in tor_kernels.hip
 constexpr size_t kTileSortScratchBytes = 4096 * (8 + 4 + 4) + 16;  // launch_tile_order's histogram / offsets behind the per-tile arrays (kCostBins = 4096)
 hipError_t launch_finalize(double* pixels, long long n_values, double scale, double gamma, hipStream_t stream);
+// progressive rendering: pixels[i] = pow_pos(scale * sums[i], gamma), out of place (pixels == sums allowed)
+hipError_t launch_resolve(const double* sums, double* pixels, long long n_values, double scale, double gamma, hipStream_t stream);
+// per-pixel standard error of the mean from sums / moments of n samples (err nullable), and the frame's {sum, max} of it reduced
+// in a fixed order into out2 (device, 2 float64); partials: kNoiseMaxBlocks x 2 float64 of device scratch
+constexpr int kNoiseMaxBlocks = 1024;
+hipError_t launch_accum_noise(const double* sums, const double* moments, long long npix, double n, double* err, double* partials,
+                              double* out2, hipStream_t stream);
 hipError_t launch_quantize(const double* pixels, long long n_values, uint8_t* out, hipStream_t stream);
 hipError_t launch_encode_ipcm(const double* pixels, int nrows, int ncols, uint8_t* out, uint8_t* plane_y,
                               uint8_t* plane_cb, uint8_t* plane_cr, hipStream_t stream);
