@@ -317,6 +317,39 @@ TOR_API int tor_resolve_device(TorContext* ctx, const double* d_sums, int64_t n_
 TOR_API int tor_accum_noise_device(TorContext* ctx, const double* d_sums, const double* d_moments, int64_t npix,
                                    int64_t total_samples, double* d_err, double out[2], void* hip_stream);
 
+/* ---- adaptive sampling (TOR_SEED_SAMPLE only): samples where the noise is ------------------------------------------------
+ * An adaptive render is a sequence of passes over a shrinking ACTIVE LIST of pixels.  Every listed pixel holds exactly N samples
+ * [0, N) before a pass and receives the same range [N, N + k); a select then tests each listed pixel at N + k samples, records
+ * counts[p] = N + k and keeps the unconverged ones, in input order, for the next pass.  So each pixel's samples are a prefix
+ * [0, counts[p]), and -- every deposit being exact (progressive block above) -- pixel p of an adaptive render is pixel p of a
+ * uniform counts[p]-spp render, bit for bit, whatever the schedule.
+ *
+ * tor_render_accumulate_list_device: tor_render_accumulate_device over the n_list pixels of d_list only (DEVICE int32,
+ * shard-local indices in d_sums' layout, strictly ascending, unique -- ascending keeps neighbouring pixels in one wave).  Sums
+ * AND moments are required.  n_list == 0 is a no-op.  An entry outside the shard deposits nothing.  The same rejections as
+ * tor_render_accumulate_device (TOR_SEED_PIXEL, sample ranges, the 2^17 bound), and n_list < 0 or above the shard's pixel
+ * count.  Asynchronous on hip_stream.
+ *
+ * tor_adaptive_select_device: the convergence test at total_samples = n (2 <= n <= 2^17) of every listed pixel.  Per channel
+ * c, mean_c = S_c / n and se_c = sqrt(max(0, (M_c - S_c*S_c/n) / (n - 1)) / n) -- tor_accum_noise_device's standard error --
+ * each operation one IEEE float64 rounding, nothing fused; the pixel has converged iff se_c <= abs_tol + rel_tol * mean_c for
+ * all three channels.  d_counts[p] = n for every listed p (npix int32, the sample map), the unconverged pixels to d_list_out in
+ * input order (an ordered compaction: d_list_out must not alias d_list_in), their number to *n_out.  Every entry must be a pixel
+ * of d_sums.  abs_tol, rel_tol >= 0, not NaN.  n_in == 0 gives *n_out = 0.  Blocking: returns when *n_out is known.
+ *
+ * tor_resolve_counts_device: d_pixels[i] = pow(d_sums[i] / counts[i / 3], 1 / gamma_correction) for npix pixels, computed as
+ * (1.0 / counts) * sum -- tor_resolve_device's operations with total_samples = counts[i / 3], so the same bits.  Every count
+ * must lie in [1, 2^17].  d_pixels == d_sums resolves in place.  Asynchronous on hip_stream. */
+TOR_API int tor_render_accumulate_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                                              const int32_t* d_list, int32_t n_list, int32_t first_sample, int32_t n_samples,
+                                              int64_t max_depth, const TorOptions* opt, double* d_sums, double* d_moments,
+                                              void* hip_stream);
+TOR_API int tor_adaptive_select_device(TorContext* ctx, const double* d_sums, const double* d_moments, const int32_t* d_list_in,
+                                       int32_t n_in, int64_t total_samples, double abs_tol, double rel_tol, int32_t* d_list_out,
+                                       int32_t* d_counts, int32_t* n_out, void* hip_stream);
+TOR_API int tor_resolve_counts_device(TorContext* ctx, const double* d_sums, const int32_t* d_counts, int64_t npix,
+                                      float gamma_correction, double* d_pixels, void* hip_stream);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

@@ -138,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "tor_context_scene_counters", "tor_render_ptr", "tor_last_pixel_cost", "tor_last_note", "tor_last_handoff_counters",
     "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
     "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
+    "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device",
 ]
 
 _lib = None
@@ -275,6 +276,8 @@ def lib():
     L.tor_context_handoff_stalled.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     if not ab or hasattr(L, "tor_render_accumulate_device"):  # (an A/B build older than progressive rendering lacks these three)
         _bind_progressive(L, dp)
+    if not ab or hasattr(L, "tor_render_accumulate_list_device"):  # (... and one older than adaptive sampling these three)
+        _bind_adaptive(L)
     _lib = L
     return L
 
@@ -284,6 +287,14 @@ def _bind_progressive(L, dp) -> None:
                                                C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p]
     L.tor_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
     L.tor_accum_noise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, dp, C.c_void_p]
+
+
+def _bind_adaptive(L) -> None:
+    L.tor_render_accumulate_list_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tor_adaptive_select_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    L.tor_resolve_counts_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
 
 
 def _check(rc: int) -> None:
@@ -614,6 +625,29 @@ class Context:
                                             C.c_void_p(d_err_ptr), out, C.c_void_p(stream_ptr)))
         return float(out[0]), float(out[1])
 
+    def accumulate_list_device(self, cam: Camera, nrows: int, ncols: int, d_list_ptr: int, n_list: int, first_sample: int,
+                               n_samples: int, max_depth: int, options: Options, d_sums_ptr: int, d_moments_ptr: int, stream_ptr: int = 0):
+        """accumulate_device over the n_list pixels of the device int32 list at d_list_ptr (shard-local, strictly ascending, unique);
+        sums and moments both required.  Asynchronous on the given hipStream_t."""
+        _check(lib().tor_render_accumulate_list_device(self._h, C.byref(cam), nrows, ncols, C.c_void_p(d_list_ptr), int(n_list),
+                                                       int(first_sample), int(n_samples), int(max_depth), C.byref(options),
+                                                       C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr), C.c_void_p(stream_ptr)))
+
+    def adaptive_select_device(self, d_sums_ptr: int, d_moments_ptr: int, d_list_in_ptr: int, n_in: int, total_samples: int,
+                               abs_tol: float, rel_tol: float, d_list_out_ptr: int, d_counts_ptr: int, stream_ptr: int = 0) -> int:
+        """Convergence test at total_samples of every listed pixel: counts[p] = total_samples, the unconverged pixels to the output
+        list in input order.  Returns their number.  Blocking."""
+        n = C.c_int32(0)
+        _check(lib().tor_adaptive_select_device(self._h, C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr), C.c_void_p(d_list_in_ptr),
+                                                int(n_in), int(total_samples), float(abs_tol), float(rel_tol), C.c_void_p(d_list_out_ptr),
+                                                C.c_void_p(d_counts_ptr), C.byref(n), C.c_void_p(stream_ptr)))
+        return int(n.value)
+
+    def resolve_counts_device(self, d_sums_ptr: int, d_counts_ptr: int, npix: int, gamma: float, d_pixels_ptr: int, stream_ptr: int = 0):
+        """pixels = pow(sums / counts[pixel], 1 / gamma), each pixel resolved at its own sample count.  Asynchronous."""
+        _check(lib().tor_resolve_counts_device(self._h, C.c_void_p(d_sums_ptr), C.c_void_p(d_counts_ptr), int(npix), gamma,
+                                               C.c_void_p(d_pixels_ptr), C.c_void_p(stream_ptr)))
+
     def quantize_rgb8_device(self, d_pixels_ptr: int, n_values: int, d_rgb8_ptr: int, stream_ptr: int = 0):
         _check(lib().tor_quantize_rgb8_device(self._h, C.c_void_p(d_pixels_ptr), n_values,
                                               C.c_void_p(d_rgb8_ptr), C.c_void_p(stream_ptr)))
@@ -804,6 +838,173 @@ class Progressive:
             pg.moments.copy_(torch.from_numpy(np.ascontiguousarray(state["moments"], dtype=np.float64)))
         pg.samples = int(state["samples"])
         return pg
+
+
+MAX_ACCUM_SAMPLES = 1 << 17  # exactness bound of the progressive sums (tor_render.h)
+
+
+def adaptive_select_host(sums, moments, pixels, n: int, abs_tol: float, rel_tol: float) -> np.ndarray:
+    """tor_adaptive_select_device restated in numpy float64 (same operations, one rounding each): the entries of `pixels` (indices
+    into sums / moments viewed as (npix, 3)) that have NOT converged at n samples, in input order."""
+    S = np.asarray(sums, dtype=np.float64).reshape(-1, 3)
+    M = np.asarray(moments, dtype=np.float64).reshape(-1, 3)
+    pix = np.asarray(pixels, dtype=np.int64)
+    S, M, n = S[pix], M[pix], np.float64(n)
+    mean = S / n
+    var = (M - S * S / n) / (n - np.float64(1.0))
+    var = np.where(var > 0.0, var, 0.0)
+    se = np.sqrt(var / n)
+    converged = np.all(se <= np.float64(abs_tol) + np.float64(rel_tol) * mean, axis=1)
+    return pix[~converged].astype(np.int32)
+
+
+class Adaptive:
+    """Adaptive sampling of one (camera, size, depth, options) in TOR_SEED_SAMPLE mode: passes of pass_samples over the ACTIVE LIST
+    of pixels that have not converged yet.  All pixels start on the list; once N >= min_samples a select after each pass drops every
+    pixel whose per-channel standard error is <= abs_tol + rel_tol * mean (tor_render.h).  Each pixel's samples are the prefix
+    [0, counts[p]), so pixel p of image() is pixel p of a uniform counts[p]-spp render, bit for bit.
+
+        ad = Adaptive(ctx, cam, 1080, 1920, 50, make_options(seeding=SEED_SAMPLE), rel_tol=0.05)
+        ad.run(); frame = ad.image(); spp_map = ad.counts()
+
+    The context must have the scene uploaded; all device work runs on torch's current stream of the buffers' device."""
+
+    def __init__(self, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None = None,
+                 abs_tol: float = 0.0, rel_tol: float = 0.05, min_samples: int = 16, pass_samples: int = 16, max_samples: int = 4096,
+                 device=None):
+        self.ctx, self.nrows, self.ncols, self.max_depth = ctx, int(nrows), int(ncols), int(max_depth)
+        self.cam = Camera.from_buffer_copy(cam)
+        self.options = Options.from_buffer_copy(options if options is not None else make_options(seeding=SEED_SAMPLE))
+        if self.options.seeding != SEED_SAMPLE:
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: needs TOR_SEED_SAMPLE (TOR_SEED_PIXEL pixels are sequential chains "
+                                                 "on one generator and cannot be resumed)")
+        self.abs_tol, self.rel_tol = float(abs_tol), float(rel_tol)
+        if not (self.abs_tol >= 0.0 and self.rel_tol >= 0.0):
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: abs_tol and rel_tol must be >= 0 (and not NaN)")
+        self.min_samples, self.pass_samples, self.max_samples = int(min_samples), int(pass_samples), int(max_samples)
+        if self.min_samples < 2 or self.pass_samples < 1 or not 1 <= self.max_samples <= MAX_ACCUM_SAMPLES:
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: need min_samples >= 2 (the variance needs two samples), pass_samples >= 1 "
+                                                 "and 1 <= max_samples <= 2^17")
+        self.rows = self._shard_rows(self.nrows, self.options)
+        self.npix = self.rows * self.ncols
+        self._alloc(device)
+
+    @staticmethod
+    def _shard_rows(nrows: int, options: Options) -> int:
+        return len(shard_rows(int(nrows), max(int(options.row_tile), 1), int(options.shard_index), max(int(options.shard_count), 1)))
+
+    def _alloc(self, device) -> None:
+        import torch
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        self.sums = torch.zeros((self.rows, self.ncols, 3), dtype=torch.float64, device=dev)
+        self.moments = torch.zeros_like(self.sums)
+        self._counts = torch.zeros((self.rows, self.ncols), dtype=torch.int32, device=dev)
+        self._list = torch.arange(self.npix, dtype=torch.int32, device=dev)  # the active list is _list[:active]
+        self._spare = torch.empty_like(self._list)
+        self.active = self.npix
+        self.samples = 0
+
+    @staticmethod
+    def validate_list(pixels, npix: int) -> np.ndarray:
+        """A host-supplied active list as int32: strictly ascending (hence unique) shard-local pixel indices in [0, npix)."""
+        a = np.asarray(pixels)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: a pixel list is a 1-D array of integers")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= npix):
+            raise TorError(ERR_INVALID_ARGUMENT, f"Adaptive: pixel list entries must lie in [0, {npix})")
+        if a.size > 1 and not np.all(np.diff(a) > 0):
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: a pixel list must be strictly ascending (no duplicates)")
+        return a.astype(np.int32)
+
+    def _stream(self) -> int:
+        import torch
+        return torch.cuda.current_stream(self.sums.device).cuda_stream
+
+    def step(self) -> "Adaptive":
+        """One pass of pass_samples (shortened to land on max_samples) over the active list, then -- once N >= min_samples -- the
+        select that drops the converged pixels.  A no-op when the list is empty or max_samples is reached."""
+        k = min(self.pass_samples, self.max_samples - self.samples)
+        if self.active == 0 or k <= 0:
+            return self
+        st = self._stream()
+        self.ctx.accumulate_list_device(self.cam, self.nrows, self.ncols, self._list.data_ptr(), self.active, self.samples, k,
+                                        self.max_depth, self.options, self.sums.data_ptr(), self.moments.data_ptr(), st)
+        self.samples += k
+        if self.samples >= self.min_samples:
+            n = self.ctx.adaptive_select_device(self.sums.data_ptr(), self.moments.data_ptr(), self._list.data_ptr(), self.active,
+                                                self.samples, self.abs_tol, self.rel_tol, self._spare.data_ptr(),
+                                                self._counts.data_ptr(), st)
+            self._list, self._spare = self._spare, self._list
+            self.active = n
+        else:  # (no select yet: every listed pixel simply has N samples)
+            self._counts.view(-1).index_fill_(0, self._list[: self.active].long(), self.samples)
+        return self
+
+    def run(self) -> int:
+        """step() until the list is empty or max_samples is reached; the survivors then hold max_samples.  Returns N."""
+        while self.active > 0 and self.samples < self.max_samples:
+            self.step()
+        return self.samples
+
+    def counts(self):
+        """The sample map: a device int32 tensor (rows of this shard, ncols)."""
+        return self._counts.clone()
+
+    def active_list(self):
+        """The active list (device int32, ascending)."""
+        return self._list[: self.active].clone()
+
+    def total_samples(self) -> int:
+        """Samples spent over the frame (the sum of counts())."""
+        import torch
+        return int(self._counts.sum(dtype=torch.int64).item())
+
+    def image(self, gamma: float = 2.2):
+        """Each pixel resolved at its own count: a new device float64 tensor (rows of this shard, ncols, 3)."""
+        import torch
+        if self.samples == 0:
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.image: no pass has run yet")
+        out = torch.empty_like(self.sums)
+        self.ctx.resolve_counts_device(self.sums.data_ptr(), self._counts.data_ptr(), self.npix, gamma, out.data_ptr(), self._stream())
+        return out
+
+    def to_canvas(self, canvas: Canvas) -> Canvas:
+        """Fill a host Canvas (whole frame, unsharded options) with image(canvas.gamma_correction), so export_ppm works.  Its
+        samples_per_pixel is N, the largest count."""
+        if (canvas.nrows, canvas.ncols) != (self.rows, self.ncols):
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.to_canvas: the canvas must have this render's rows and columns")
+        canvas.pixels[...] = self.image(canvas.gamma_correction).cpu().numpy()
+        canvas.samples_per_pixel = self.samples
+        return canvas
+
+    def state(self) -> dict:
+        """Checkpoint: N, the sums, moments, counts and the active list as host numpy arrays / int."""
+        return {"samples": self.samples, "sums": self.sums.cpu().numpy(), "moments": self.moments.cpu().numpy(),
+                "counts": self._counts.cpu().numpy(), "list": self._list[: self.active].cpu().numpy()}
+
+    @classmethod
+    def from_state(cls, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None, state: dict,
+                   device=None, **policy) -> "Adaptive":
+        """Resume a checkpoint (state()) on this context -- any process, any GPU with the same scene uploaded.  policy: the
+        constructor's abs_tol, rel_tol, min_samples, pass_samples, max_samples."""
+        import torch
+        opts = options if options is not None else make_options(seeding=SEED_SAMPLE)
+        npix = cls._shard_rows(nrows, opts) * int(ncols)
+        lst = cls.validate_list(state["list"], npix)  # before any device work
+        ad = cls(ctx, cam, nrows, ncols, max_depth, options, device=device, **policy)
+        arrays = {"sums": (ad.sums, np.float64), "moments": (ad.moments, np.float64), "counts": (ad._counts, np.int32)}
+        for key, (dst, dt) in arrays.items():
+            a = np.ascontiguousarray(state[key], dtype=dt)
+            if a.shape != tuple(dst.shape):
+                raise TorError(ERR_INVALID_ARGUMENT, f"Adaptive.from_state: {key} of shape {a.shape}, expected {tuple(dst.shape)}")
+            dst.copy_(torch.from_numpy(a))
+        ad.samples = int(state["samples"])
+        if lst.size and not np.all(np.asarray(state["counts"]).reshape(-1)[lst] == ad.samples):
+            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.from_state: every listed pixel must hold exactly N samples")
+        ad._list[: lst.size].copy_(torch.from_numpy(lst))
+        ad.active = int(lst.size)
+        return ad
 
 
 def mp4_mux_file(src_annexb_path: str, dst_mp4_path: str, width: int, height: int, fps: int = 30) -> int:

@@ -2,6 +2,7 @@
 // get the next work item -- a wave-uniform range pulled from the global counter (SEED_PIXEL: tiles in chain-length order;
 // SEED_SAMPLE / probe: guided chunks) dealt out by ballot + prefix count -- and start its camera ray (render.nim:59-66).  The float64
 // brute force with sample streams (kRes) starts its camera rays 64 at a time into a per-wave LDS reservoir instead and pops from it.
+// SEEDING 4 (kList) walks a pixel list: the work index is list slot x spp + sample, and both seeding sites look the slot's pixel up.
 // Reads / writes the lane state declared in integrate_kernel (active, have_item, o, d, time, rng, row, col, s, pix, acc, ...).
     // ================= (A) refill lanes that have no live path =========================
     // (the cooperative variants -- both exact accelerations, 168 registers and none to spare -- keep the integer division: the
@@ -33,7 +34,12 @@
             rng.s0 = res_rng[e]; rng.s1 = res_rng[64 + e]; rng.s2 = res_rng[128 + e]; rng.s3 = res_rng[192 + e];
             const double rdx = res_f[e], rdy = res_f[64 + e], fs = res_f[128 + e], ft = res_f[192 + e];
             time = res_f[256 + e];
-            pix = (int)(res_pl0[0] + (unsigned)res_dp[e]);
+            if constexpr (kList) {  // (the reservoir keeps the list slot; the pixel is looked up again here -- same LDS layout as SEEDING 1 / 3)
+              const unsigned lp = (unsigned)p.pixel_list[res_pl0[0] + (unsigned)res_dp[e]];
+              pix = lp < p.n_pixels ? (int)lp : -1;  // an entry outside the shard deposits nothing (tag -1: never flushed)
+            } else {
+              pix = (int)(res_pl0[0] + (unsigned)res_dp[e]);
+            }
             const Camera cam = load_camera(p.cam_dev);
             const V3 offset = cam.u * rdx + cam.v * rdy;  // cameras.nim:49-55
             o = cam.origin + offset;
@@ -83,7 +89,11 @@
             const unsigned n = avail < 64u ? avail : 64u;
             const unsigned t = cs + (unsigned)lane;
             const unsigned dp = udiv_by(t, p.inv_spp);
-            const unsigned pl = cpl + dp;
+            unsigned pl = cpl + dp;
+            if constexpr (kList) {  // list slot -> pixel (lanes past the batch read nothing: their slot may lie past the list)
+              const unsigned lp = (unsigned)lane < n ? (unsigned)p.pixel_list[pl] : 0u;
+              pl = lp < p.n_pixels ? lp : 0u;
+            }
             const unsigned gs = t - dp * (unsigned)p.spp;
             const unsigned lrow = udiv_by(pl, p.inv_ncols);
             const unsigned gcol = pl - lrow * (unsigned)p.ncols;
@@ -197,6 +207,12 @@
             pl = cur_pl + dp;
             s = (int)(t - dp * (unsigned)p.spp);
           }
+          bool off_shard = false;  // kList: a list entry outside the shard
+          if constexpr (kList) {
+            const unsigned lp = (unsigned)p.pixel_list[pl];
+            off_shard = lp >= p.n_pixels;
+            pl = off_shard ? 0u : lp;
+          }
           // (round 5: the per-lane divisions by ncols, spp and row_tile are multiplications by their float64 reciprocals --
           // tor_device.hpp udiv_by, exact for every 32-bit dividend; a 32-bit division by a run-time divisor is ~22 vector
           // instructions and this section runs on nearly every bounce iteration)
@@ -207,6 +223,9 @@
           const unsigned within = lrow - tile * (unsigned)p.row_tile;
           row = (int)((tile * (unsigned)p.shard_count + (unsigned)p.shard_index) * (unsigned)p.row_tile + within);
           pix = (int)pl;
+          if constexpr (kList) {
+            if (off_shard) pix = -1;  // deposits nothing (tag -1: never flushed)
+          }
           have_item = true;
           if (SEEDING == 0) {
             seed2(rng, (uint64_t)(int64_t)row, (uint64_t)(int64_t)col);  // render.nim:59-60

@@ -1,4 +1,4 @@
-// kernel/output_stage.hpp -- the small kernels around the integrator: finalize (canvas.nim:47-54), resolve / accum_noise (progressive rendering), quantize (io/ppm.nim:15-16),
+// kernel/output_stage.hpp -- the small kernels around the integrator: finalize (canvas.nim:47-54), resolve / accum_noise (progressive rendering), adaptive select / resolve_counts (adaptive sampling), quantize (io/ppm.nim:15-16),
 // encode_ipcm (animation output stage), gather_rows (multi-GPU assembly), selftest, spin_until.  Textually included by tor_kernels.hip.
 // canvas.nim:47-54
 __global__ __launch_bounds__(256) void finalize_kernel(double* pixels, long long n_values, double scale,
@@ -75,6 +75,108 @@ __global__ __launch_bounds__(256) void accum_noise_finish_kernel(const double* p
     out2[0] = s_sum[0];
     out2[1] = s_max[0];
   }
+}
+
+// ---- adaptive sampling (tor_adaptive_select_device, tor_resolve_counts_device) ------------------------------------------------
+// Convergence of a pixel with sums S, moments M of n samples: per channel, mean = S / n, se = sqrt(max(0, (M - S*S/n) / (n-1)) / n)
+// (accum_noise_kernel's operations), converged iff se <= abs_tol + rel_tol * mean in all three channels.  Every operation is one IEEE
+// float64 rounding, nothing fused, so a host restatement in float64 reproduces the keep set bit for bit.
+__device__ __forceinline__ bool adaptive_still_active(const double* sums, const double* moments, unsigned pix, double n, double abs_tol,
+                                                      double rel_tol) {
+#pragma clang fp contract(off)
+  bool converged = true;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double S = sums[(size_t)pix * 3 + c], M = moments[(size_t)pix * 3 + c];
+    const double mean = S / n;
+    double var = (M - S * S / n) / (n - 1.0);
+    var = var > 0.0 ? var : 0.0;
+    const double se = __builtin_sqrt(var / n);
+    converged = converged && se <= abs_tol + rel_tol * mean;
+  }
+  return !converged;
+}
+
+// Ordered compaction of the list, in tiles of kSelTile entries per 256-thread block: entry i of block b is b * kSelTile + k * 256 + t.
+constexpr int kSelTile = 1024;
+
+// pass 1: counts[pix] = n for every listed pixel, keep[i] = not converged, block_count[b] = the block's survivors (wave ballots)
+__global__ __launch_bounds__(256) void adaptive_count_kernel(const double* sums, const double* moments, const int32_t* list_in, long long n_in,
+                                                              double n, double abs_tol, double rel_tol, int32_t* counts, uint8_t* keep,
+                                                              unsigned* block_count) {
+  __shared__ unsigned s_cnt[4];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  unsigned mine = 0;
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    const long long i = (long long)blockIdx.x * kSelTile + k * 256 + threadIdx.x;
+    bool act = false;
+    if (i < n_in) {
+      const unsigned pix = (unsigned)list_in[i];
+      counts[pix] = (int32_t)n;
+      act = adaptive_still_active(sums, moments, pix, n, abs_tol, rel_tol);
+      keep[i] = act ? 1 : 0;
+    }
+    mine += (unsigned)__builtin_popcountll(ballot64(act));
+  }
+  if (lane == 0) s_cnt[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// pass 2 (one block): block_count -> exclusive offsets in place, the total to *n_out
+__global__ __launch_bounds__(1024) void adaptive_scan_kernel(unsigned* block_count, int n_blocks, int32_t* n_out) {
+  __shared__ unsigned s[1024];
+  const int t = (int)threadIdx.x;
+  const int per = (n_blocks + 1023) / 1024;  // thread t owns blocks [t * per, (t + 1) * per)
+  const int b0 = t * per;
+  const int b1 = (b0 + per < n_blocks) ? b0 + per : n_blocks;
+  unsigned sum = 0;
+  for (int b = b0; b < b1; ++b) sum += block_count[b];
+  s[t] = sum;
+  __syncthreads();
+  for (int w = 1; w < 1024; w <<= 1) {  // inclusive Hillis-Steele scan of the 1024 thread totals
+    const unsigned v = t >= w ? s[t - w] : 0u;
+    __syncthreads();
+    s[t] += v;
+    __syncthreads();
+  }
+  unsigned run = s[t] - sum;
+  for (int b = b0; b < b1; ++b) {
+    const unsigned c = block_count[b];
+    block_count[b] = run;
+    run += c;
+  }
+  if (t == 1023) *n_out = (int32_t)s[1023];
+}
+
+// pass 3: the survivors to list_out at their block's offset + their rank inside the block, in input order
+__global__ __launch_bounds__(256) void adaptive_scatter_kernel(const int32_t* list_in, long long n_in, const uint8_t* keep,
+                                                                const unsigned* block_offset, int32_t* list_out) {
+  __shared__ unsigned s_cnt[kSelTile / 256][4];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  unsigned long long masks[kSelTile / 256];
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    const long long i = (long long)blockIdx.x * kSelTile + k * 256 + threadIdx.x;
+    masks[k] = ballot64(i < n_in && keep[i] != 0);
+    if (lane == 0) s_cnt[k][wave] = (unsigned)__builtin_popcountll(masks[k]);
+  }
+  __syncthreads();
+  unsigned run = block_offset[blockIdx.x];
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    const long long i = (long long)blockIdx.x * kSelTile + k * 256 + threadIdx.x;
+    unsigned before = run;
+    for (int w = 0; w < wave; ++w) before += s_cnt[k][w];
+    if ((masks[k] >> lane) & 1ull) list_out[before + lane_prefix(masks[k])] = list_in[i];
+    run += s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3];
+  }
+}
+
+// resolve_kernel with each pixel's own sample count: (1.0 / (double)c) is the host's scale of tor_resolve_device at total_samples = c,
+// so a pixel's value is that call's, bit for bit.  pixels == sums is allowed.
+__global__ __launch_bounds__(256) void resolve_counts_kernel(const double* sums, const int32_t* counts, double* pixels, long long n_values,
+                                                              double gamma) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_values) pixels[i] = pow_pos((1.0 / (double)counts[i / 3]) * sums[i], gamma);
 }
 
 // io/ppm.nim:15-16 ; safe_math.nim:10-14

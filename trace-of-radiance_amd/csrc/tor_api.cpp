@@ -294,7 +294,7 @@ extern "C" {
 
 const char* tor_last_error(void) { return g_last_error.c_str(); }
 
-const char* tor_version(void) { return "tor_mi355x 0.5 (gfx950)"; }
+const char* tor_version(void) { return "tor_mi355x 0.6 (gfx950)"; }
 
 int32_t tor_knob_count(void) { return tor::kKnobCount; }
 
@@ -394,6 +394,7 @@ int tor_context_destroy(TorContext* ctx) {
   ctx->gather.release();
   ctx->frame.release();
   ctx->noise.release();
+  ctx->adapt.release();
   ctx->staging.release();
   for (hipEvent_t ev : ctx->chunk_events) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : ctx->ev_call) if (ev) (void)hipEventDestroy(ev);
@@ -480,7 +481,8 @@ int32_t tor_shard_rows(int32_t nrows, int32_t row_tile, int32_t shard_index, int
 static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                               int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
                               double* d_pixels, void* hip_stream, const tor::AccumLaunch* acc) {
-  const std::string who = acc ? "tor_render_accumulate_device" : "tor_render_device";
+  const bool listed = acc && acc->list;
+  const std::string who = listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device");
   if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
   if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": no scene uploaded");
   // The reference divides by (ncols-1) and (nrows-1) (render.nim:64-65) and by spp
@@ -494,18 +496,20 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   if (acc && o.seeding != TOR_SEED_SAMPLE)
     return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
                                                 "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
-  // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them
-  const int kseed = (acc && acc->moments) ? 3 : o.seeding;
+  // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them, over a pixel list (4)
+  // for adaptive ones
+  const int kseed = listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding);
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipSetDevice(ctx->device));
 
   const int32_t local_rows = tor_shard_rows(nrows, o.row_tile, o.shard_index, o.shard_count, nullptr);
   const long long npix = (long long)local_rows * ncols;
   const long long n_values = npix * 3;
+  const long long work_pix = listed ? (long long)acc->n_list : npix;  // pixels this launch traces
   ctx->timing_valid = false;
   ctx->last_samples = 0;
   ctx->last_migrate = false;
-  if (npix == 0) return TOR_OK;
+  if (work_pix == 0) return TOR_OK;
 
   // a ring slot (events, camera, bounds, counters, tile schedule) is reused every kRing launches: its previous
   // launch must be done
@@ -763,6 +767,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   p.out = d_pixels;
   p.first_sample = acc ? acc->first_sample : 0;
   p.mom = acc ? acc->moments : nullptr;
+  p.pixel_list = listed ? acc->list : nullptr;
 
   long long waves;
   p.n_pixels = (unsigned)npix;
@@ -775,7 +780,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
     p.chunk = tor::kTilePixelsHost;
     waves = n_tiles;
   } else {
-    p.total_work = (unsigned long long)npix * (unsigned long long)spp;
+    p.total_work = (unsigned long long)work_pix * (unsigned long long)spp;
     long long c = (long long)(p.total_work / (unsigned long long)(resident_waves * 16));
     // largest chunk of the guided schedule: up to 1024 samples, or one whole pixel when a pixel has more (<= 4096)
     const long long cap_c = (spp > 1024) ? (spp < 4096 ? spp : 4096) : 1024;
@@ -965,7 +970,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   ctx->launches += 1;
   ctx->last_slot = slot;
   ctx->timing_valid = true;
-  ctx->last_samples = (int64_t)npix * spp;
+  ctx->last_samples = (int64_t)work_pix * spp;
   if (acc) return TOR_OK;  // raw sums: tor_resolve_device finalizes
   // canvas.nim:47-54
   const double scale = 1.0 / (double)spp;
@@ -1026,6 +1031,65 @@ int tor_accum_noise_device(TorContext* ctx, const double* d_sums, const double* 
   HIP_TRY(hipStreamSynchronize(stream));
   out[0] = h[0] / (double)npix;
   out[1] = h[1];
+  return TOR_OK;
+}
+
+// ---- adaptive sampling (TOR_SEED_SAMPLE): passes over a shrinking list of pixels, convergence select, per-pixel resolve ---------
+int tor_render_accumulate_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols, const int32_t* d_list,
+                                      int32_t n_list, int32_t first_sample, int32_t n_samples, int64_t max_depth, const TorOptions* opt,
+                                      double* d_sums, double* d_moments, void* hip_stream) {
+  const char* who = "tor_render_accumulate_list_device";
+  if (first_sample < 0 || n_samples < 1 || (int64_t)first_sample + n_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": need first_sample >= 0, n_samples >= 1 and first_sample + n_samples "
+                                          "<= 2^17 (131072): beyond that the 2^-36-granular float64 sums are no longer exact");
+  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": n_list < 0");
+  {  // (checked before the context is touched: the list may not be longer than the shard)
+    TorOptions o;
+    if (nrows >= 2 && ncols >= 2 && valid_options(opt, o, false)) {
+      const long long npix = (long long)tor_shard_rows(nrows, o.row_tile, o.shard_index, o.shard_count, nullptr) * ncols;
+      if ((long long)n_list > npix)
+        return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": n_list = " + std::to_string(n_list) + " is above the shard's " +
+                                              std::to_string(npix) + " pixels");
+    }
+  }
+  if (!ctx || !cam || !d_list || !d_sums || !d_moments) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument (sums and moments are both required)");
+  const tor::AccumLaunch acc{first_sample, d_moments, d_list, n_list};
+  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+}
+
+int tor_adaptive_select_device(TorContext* ctx, const double* d_sums, const double* d_moments, const int32_t* d_list_in, int32_t n_in,
+                               int64_t total_samples, double abs_tol, double rel_tol, int32_t* d_list_out, int32_t* d_counts, int32_t* n_out,
+                               void* hip_stream) {
+  const char* who = "tor_adaptive_select_device";
+  if (n_in < 0) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": n_in < 0");
+  if (total_samples < 2 || total_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": need 2 <= total_samples <= 2^17 (the variance needs two samples)");
+  if (!(abs_tol >= 0.0) || !(rel_tol >= 0.0))  // (false for NaN too)
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": tolerances must be >= 0 and not NaN");
+  if (!ctx || !d_sums || !d_moments || !d_list_in || !d_list_out || !d_counts || !n_out)
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument");
+  if (d_list_out == d_list_in) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": d_list_out must not alias d_list_in");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  // [0, 16): the survivor count; then the compaction's scratch
+  HIP_TRY(ctx->adapt.ensure(16 + tor::adaptive_select_scratch_bytes(n_in)));
+  int32_t* dn = (int32_t*)ctx->adapt.ptr;
+  HIP_TRY(tor::launch_adaptive_select(d_sums, d_moments, d_list_in, n_in, (double)total_samples, abs_tol, rel_tol, d_list_out, d_counts,
+                                      (char*)ctx->adapt.ptr + 16, dn, stream));
+  int32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, dn, sizeof(h), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  *n_out = h;
+  return TOR_OK;
+}
+
+int tor_resolve_counts_device(TorContext* ctx, const double* d_sums, const int32_t* d_counts, int64_t npix, float gamma_correction,
+                              double* d_pixels, void* hip_stream) {
+  if (npix < 0) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_resolve_counts_device: npix < 0");
+  if (!ctx || !d_sums || !d_counts || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_resolve_counts_device: NULL argument");
+  HIP_TRY(hipSetDevice(ctx->device));
+  // resolve_kernel's operands with scale = 1.0 / (double)counts[pixel], computed on the device exactly as the host computes it
+  HIP_TRY(tor::launch_resolve_counts(d_sums, d_counts, d_pixels, npix * 3, 1.0 / (double)gamma_correction, (hipStream_t)hip_stream));
   return TOR_OK;
 }
 

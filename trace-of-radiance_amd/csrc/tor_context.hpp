@@ -148,6 +148,7 @@ struct TorContext {
   tor::DeviceBuffer gather;    // root of a multi-device render / RCCL gather: the ranks' shards, rank-major
   tor::DeviceBuffer frame;     // ... de-interleaved frame (multi-device tor_render_opt)
   tor::DeviceBuffer noise;     // tor_accum_noise_device's per-block partials and result
+  tor::DeviceBuffer adapt;     // tor_adaptive_select_device's survivor count and compaction scratch
   tor::PinnedBuffer staging;   // D2H target
   std::vector<hipEvent_t> chunk_events;
   hipEvent_t ev_call[2] = {};    // tor_render_opt: around the launches of one call (tor_last_render_timing out[1])
@@ -200,10 +201,13 @@ struct TorContext {
 
 namespace tor {
 
-// one pass of tor_render_accumulate_device (tor_api.cpp render_device_impl): its first sample index, the moments buffer (nullable)
+// one pass of tor_render_accumulate_device (tor_api.cpp render_device_impl): its first sample index, the moments buffer (nullable),
+// and -- tor_render_accumulate_list_device -- the pixel list
 struct AccumLaunch {
   int first_sample;
   double* moments;
+  const int32_t* list = nullptr;  // tor_render_accumulate_list_device: the pixel list (kernel variant SEEDING 4) ...
+  int32_t n_list = 0;             // ... and its length
 };
 
 // Options with defaults applied; false when malformed.  `for_drop_in`: NULL options take tor_render()'s

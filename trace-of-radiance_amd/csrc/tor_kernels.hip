@@ -22,6 +22,8 @@
 //                        tile (input of the SEED_PIXEL tile schedule); never touches the canvas.
 //       SEEDING 3 (progressive + moments): SEEDING 1 that also sums quantize36(q * q) per pixel and
 //                        channel (KParams.mom; tor_render_accumulate_device with a moments buffer).
+//       SEEDING 4 (adaptive: SEEDING 3 over a pixel list): work item = list slot-sample; the slot's pixel is
+//                        KParams.pixel_list[slot] (tor_render_accumulate_list_device).
 //     Sample streams are seeded with KParams.first_sample + the launch's sample index (progressive passes).
 //
 //     Objects are wave-uniform inside the hot loop, so their records come through the scalar data
@@ -49,6 +51,7 @@
 //   gather_rows_kernel multi-GPU assembly: rank-major row shards -> frame in image order
 //   finalize_kernel    canvas.nim:47-54 (draw): pow(sum * 1/spp, 1/gamma)
 //   resolve_kernel     the same, out of place (progressive sums survive); accum_noise_kernel: per-pixel standard error
+//   adaptive_*_kernel  adaptive sampling: convergence test + ordered compaction of the pixel list; resolve_counts_kernel
 //   quantize_kernel    io/ppm.nim:15-16
 //
 // float64 throughout, no FMA contraction (-ffp-contract=off): the only fused operations are the explicit fma() of the
@@ -153,8 +156,9 @@ constexpr int coop_bytes(int blocks) { return (blocks ? 2 : 1) * kCoopList * 4 +
 // Camera-ray reservoir (TOR_SEED_SAMPLE, float64 brute force: kernel/integrate_refill.inc): 64 started samples per wave --
 // generator state after the camera ray (4 x u64), lens offsets, film coordinates, time (5 x f64), pixel as a byte offset from
 // the batch's first pixel (+ that pixel, 16-byte padded)
-constexpr bool sample_variant(int seeding) { return seeding == 1 || seeding == 3; }  // per-sample streams, quantised deposit
-constexpr bool moment_variant(int seeding) { return seeding == 3; }
+constexpr bool sample_variant(int seeding) { return seeding == 1 || seeding == 3 || seeding == 4; }  // per-sample streams, quantised deposit
+constexpr bool moment_variant(int seeding) { return seeding == 3 || seeding == 4; }
+constexpr bool list_variant(int seeding) { return seeding == 4; }  // work over KParams.pixel_list (adaptive sampling)
 constexpr bool reservoir_variant(int seeding, int f32, int blocks) { return sample_variant(seeding) && f32 == 0 && blocks == 0; }
 constexpr int kResBytes = 9 * 64 * 8 + 64 + 16;
 // (moment variants: the second-moment cache [kAccSlots][3] f64 at the END of the wave's carve-out, so every other offset stays)
@@ -242,6 +246,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   constexpr int kAccPad = coop_variant(F32, BLOCKS) ? 64 : 0;
   constexpr bool kRes = reservoir_variant(SEEDING, F32, BLOCKS);
   constexpr bool kMom = moment_variant(SEEDING);
+  constexpr bool kList = list_variant(SEEDING);
   constexpr int kWaveLdsBytes = wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes, kMom);
   unsigned char* wave_lds = smem_raw + wave * kWaveLdsBytes;
   double* mom_lds = reinterpret_cast<double*>(wave_lds + wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes));  // [kAccSlots][3] (kMom variants)
@@ -752,7 +757,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
 // ---------------------------------------------------------------------------------------
 // host-side launchers (called from tor_api.cpp)
 // ---------------------------------------------------------------------------------------
-// variant table: [seeding 0|1|2|3 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
+// variant table: [seeding 0|1|2|3|4 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only; 4: 3 over a pixel list)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
 // [blocks 0|1|2 (2: two-level layouts, cooperative variants only)].  The block-expansion code (an unrolled 8-object stage per lane)
 // is what makes the 168-register variants spill; launches without TOR_ACCEL_BLOCKS use kernels compiled without it (no scratch
 // traffic at all).  (Round 5: the 20 TOR_ARITH_FUSED instantiations -- `arith 1`, not the reference's rounding -- are gone.)
@@ -764,9 +769,11 @@ static IntegrateFn integrate_variant(int seeding, int arith, int w, int f32, int
   TOR_V4(0, 0, 3) TOR_V4(1, 0, 3)
   TOR_V4(2, 0, 3)   // cost probe of the SEED_PIXEL tile schedule
   TOR_V4(3, 0, 2) TOR_V4(3, 0, 3)  // progressive launches that also sum the second moments (tor_render_accumulate_device)
+  TOR_V4(4, 0, 2) TOR_V4(4, 0, 3)  // ... over a pixel list (adaptive sampling: tor_render_accumulate_list_device)
   // arith 2: the reference's arithmetic behind the conservative FMA screen (brute-force layouts only)
   TOR_V(0, 2, 2, 0, 0) TOR_V(0, 2, 3, 0, 0) TOR_V(1, 2, 2, 0, 0) TOR_V(1, 2, 3, 0, 0) TOR_V(2, 2, 3, 0, 0)
   TOR_V(3, 2, 2, 0, 0) TOR_V(3, 2, 3, 0, 0)
+  TOR_V(4, 2, 2, 0, 0) TOR_V(4, 2, 3, 0, 0)
   // (round 5: a 128-register build <1, 2, 4, 0, 0> for a 4th workgroup per CU now runs 2.4 x SLOWER -- 1097 against 2613 Msamples/s
   // at configs[1]: stage two's per-lane state spills inside the loops; not built)
   // (a 128-register build of <1, 2, W, 0, 0> for a 4th workgroup per CU was measured in round 4: 1951 against 1961 Msamples/s at
@@ -889,6 +896,33 @@ hipError_t launch_accum_noise(const double* sums, const double* moments, long lo
   const unsigned blocks = (unsigned)(want < kNoiseMaxBlocks ? want : kNoiseMaxBlocks);
   hipLaunchKernelGGL(accum_noise_kernel, dim3(blocks), dim3(256), 0, stream, sums, moments, npix, n, err, partials);
   hipLaunchKernelGGL(accum_noise_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partials, (int)blocks, out2);
+  return hipGetLastError();
+}
+
+// scratch of the compaction: one keep byte per list entry, then one offset per block (16-byte aligned)
+size_t adaptive_select_scratch_bytes(long long n_in) {
+  const long long n_blocks = (n_in + kSelTile - 1) / kSelTile;
+  return ((size_t)n_in + 15) / 16 * 16 + (size_t)(n_blocks > 0 ? n_blocks : 1) * 4;
+}
+
+hipError_t launch_adaptive_select(const double* sums, const double* moments, const int32_t* list_in, long long n_in, double n, double abs_tol,
+                                  double rel_tol, int32_t* list_out, int32_t* counts, void* scratch, int32_t* n_out_dev, hipStream_t stream) {
+  if (n_in <= 0) return hipMemsetAsync(n_out_dev, 0, sizeof(int32_t), stream);
+  const long long n_blocks = (n_in + kSelTile - 1) / kSelTile;
+  uint8_t* keep = (uint8_t*)scratch;
+  unsigned* block_count = (unsigned*)((char*)scratch + ((size_t)n_in + 15) / 16 * 16);
+  hipLaunchKernelGGL(adaptive_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, sums, moments, list_in, n_in, n, abs_tol, rel_tol,
+                     counts, keep, block_count);
+  hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, (int)n_blocks, n_out_dev);
+  hipLaunchKernelGGL(adaptive_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, list_in, n_in, (const uint8_t*)keep,
+                     (const unsigned*)block_count, list_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_resolve_counts(const double* sums, const int32_t* counts, double* pixels, long long n_values, double gamma, hipStream_t stream) {
+  if (n_values <= 0) return hipSuccess;
+  unsigned blocks = (unsigned)((n_values + 255) / 256);
+  hipLaunchKernelGGL(resolve_counts_kernel, dim3(blocks), dim3(256), 0, stream, sums, counts, pixels, n_values, gamma);
   return hipGetLastError();
 }
 

@@ -111,6 +111,9 @@ struct KParams {
   // of every pixel -- sample s of the launch is seeded with first_sample + s -- and adds them to out without clearing it
   int first_sample;
   double* mom;  // SEEDING 3 (sample streams + second moments): per pixel and channel, the sum of quantize36(q * q) over the samples; else null
+  // adaptive sampling (tor_render_accumulate_list_device; SEEDING 4 = SEEDING 3 over a pixel list): work index = list slot x spp + sample,
+  // the slot's pixel is pixel_list[slot] (shard-local, in out's layout); an entry >= n_pixels deposits nothing; else null
+  const int32_t* pixel_list;
 };
 
 // Control words of the hand-off, one 128-byte line per access pattern (thousands of waiting servers poll their flags and,
@@ -171,6 +174,14 @@ hipError_t launch_resolve(const double* sums, double* pixels, long long n_values
 constexpr int kNoiseMaxBlocks = 1024;
 hipError_t launch_accum_noise(const double* sums, const double* moments, long long npix, double n, double* err, double* partials,
                               double* out2, hipStream_t stream);
+// adaptive sampling: the convergence test of every listed pixel at n samples; counts[pix] = n for every listed pixel and the
+// unconverged ones to list_out in input order (an ordered stream compaction: count, single-block scan, scatter); *n_out_dev the survivors.
+// scratch: adaptive_select_scratch_bytes(n_in) bytes of device memory
+size_t adaptive_select_scratch_bytes(long long n_in);
+hipError_t launch_adaptive_select(const double* sums, const double* moments, const int32_t* list_in, long long n_in, double n, double abs_tol,
+                                  double rel_tol, int32_t* list_out, int32_t* counts, void* scratch, int32_t* n_out_dev, hipStream_t stream);
+// per-pixel resolve: pixels[i] = pow_pos((1.0 / counts[i / 3]) * sums[i], gamma) -- resolve_kernel with scale 1 / counts (pixels == sums allowed)
+hipError_t launch_resolve_counts(const double* sums, const int32_t* counts, double* pixels, long long n_values, double gamma, hipStream_t stream);
 hipError_t launch_quantize(const double* pixels, long long n_values, uint8_t* out, hipStream_t stream);
 hipError_t launch_encode_ipcm(const double* pixels, int nrows, int ncols, uint8_t* out, uint8_t* plane_y,
                               uint8_t* plane_cb, uint8_t* plane_cr, hipStream_t stream);
