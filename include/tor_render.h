@@ -510,6 +510,13 @@ TOR_API int tor_debug_accel_layout(TorHittableList world, double t_lo, double t_
                                    int64_t slot_cap, double* block_boxes, double* super_boxes, int64_t box_cap,
                                    int32_t* two_level_out);
 
+/* The integrate_kernel variant that the context's last render launch chose (tor_render_device, tor_render_accumulate_device,
+ * tor_render_accumulate_list_device, ...): out = {seeding, arith, w, f32, blocks} -- seeding 0 | 1 | 3 (sample streams + second
+ * moments) | 4 (... over a pixel list); arith 0, or 2 behind the FMA screen; w = 2 (256 VGPRs) or 3 (168 VGPRs); f32 0 | 1; blocks
+ * 0 | 1 | 2 (two-level layout).  All -1 until the context has launched one; a launch that traces nothing (an empty list) or runs
+ * the wave-per-pixel kernel leaves it as it was.  Host only, no synchronisation. */
+TOR_API int tor_debug_last_variant(TorContext* ctx, int32_t out[5]);
+
 /* TOR_ACCEL_F32 over a whole scene on the HOST: builds the layout tor_scene_upload builds and walks its float32
  * segments for each ray (origin o, direction d, time) exactly as the kernel does.
  * keep[ray * world.len + object] = 1 kept, 0 dropped, 2 object stays on the float64 loop. */

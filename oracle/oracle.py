@@ -76,6 +76,9 @@ def lib(variant: str | None = None):
     L.oracle_render.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, C.c_float, dp, dp, C.c_int64,
                                 C.c_int32, C.POINTER(OracleOptions), C.POINTER(OracleStats)]
     L.oracle_render.restype = C.c_int
+    L.oracle_accumulate.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, C.c_int64, C.c_int32,
+                                    C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.c_int32]
+    L.oracle_accumulate.restype = C.c_int
     L.oracle_random_scene.argtypes = [C.c_uint64, dp, C.c_int64, u64p]
     L.oracle_random_scene.restype = C.c_int64
     L.oracle_rng_seed1.argtypes = [C.c_uint64, u64p]
@@ -171,6 +174,35 @@ def render(nrows, ncols, spp, cam, objs, max_depth=50, gamma=2.2, seeding=SEED_P
                                     C.byref(st) if st is not None else None)
     assert rc == 0
     return RenderResult(pixels, st)
+
+
+def accumulate(nrows, ncols, first, n, cam, objs, max_depth=50, rows=None, pixels=None, variant=None):
+    """The raw sums tor_render_accumulate_device adds for samples [first, first + n) (TOR_SEED_SAMPLE, MATH_PORTABLE, strict
+    arithmetic): (sums, moments), both (nrows, ncols, 3) float64 -- per pixel the sum of q = quantize36(radiance) and of
+    quantize36(q * q).  Pixels: `pixels`, flat image indices row * ncols + col (row 0 = bottom), or the rows [rows[0], rows[1]),
+    or the whole image; the others stay 0."""
+    sums = np.zeros((nrows, ncols, 3), dtype=np.float64)
+    moments = np.zeros_like(sums)
+    objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 16)
+    cam = np.ascontiguousarray(cam, dtype=np.float64)
+    r0, r1 = rows if rows is not None else (0, nrows)
+    if pixels is not None:
+        pix = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1)
+        pp, npx = pix.ctypes.data_as(C.POINTER(C.c_int32)), len(pix)
+    else:
+        pp, npx = None, 0
+    rc = lib(variant).oracle_accumulate(_dp(sums), _dp(moments), nrows, ncols, int(first), int(n), _dp(cam), _dp(objs), objs.shape[0],
+                                        int(max_depth), pp, npx, int(r0), int(r1))
+    assert rc == 0, "oracle_accumulate: bad arguments"
+    return sums, moments
+
+
+def port_pow(x: np.ndarray, y: float, variant=None) -> np.ndarray:
+    """The portable pow of MATH_PORTABLE (canvas.nim:47-54's gamma), element-wise."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    lib(variant).oracle_port_pow(_dp(x), float(y), _dp(out), x.size)
+    return out
 
 
 def quantize_ppm(pixels: np.ndarray) -> np.ndarray:

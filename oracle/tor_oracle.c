@@ -749,6 +749,15 @@ static void stats_add(OracleStats* dst, const OracleStats* src) {
   for (size_t i = 0; i < sizeof(OracleStats) / 8; ++i) d[i] += s[i];
 }
 
+/* One sample of pixel (row, col) from the generator's current state: render.nim:62-66 (the body of the sample loop). */
+static V3 pixel_sample(const Cam* cam, int32_t nrows, int32_t ncols, int32_t row, int32_t col, const Obj* objs, int64_t n_objects,
+                       int32_t max_depth, const OracleOptions* o, Rng* g, OracleStats* st) {
+  double u = ((double)col + uniform01(g, st)) / (double)(ncols - 1);
+  double v = ((double)row + uniform01(g, st)) / (double)(nrows - 1);
+  Ray r = camera_ray(cam, u, v, g, st);
+  return radiance(r, objs, n_objects, max_depth, g, o->math, o->arith, st);
+}
+
 /* render.nim:49-68 + canvas.nim:47-54 (draw).  pixels: nrows*ncols*3 doubles, row 0 = bottom. */
 EXPORT int oracle_render(double* pixels, int32_t nrows, int32_t ncols, int32_t spp, float gamma_correction,
                          const double cam24[24], const double* objs16, int64_t n_objects,
@@ -782,10 +791,7 @@ EXPORT int oracle_render(double* pixels, int32_t nrows, int32_t ncols, int32_t s
         V3 pixel = v3(0, 0, 0);
         for (int32_t s = 0; s < spp; ++s) {
           if (o.seeding == 1) oracle_seed3(&g, (uint64_t)row, (uint64_t)col, (uint64_t)s);
-          double u = ((double)col + uniform01(&g, st)) / (double)(ncols - 1);
-          double v = ((double)row + uniform01(&g, st)) / (double)(nrows - 1);
-          Ray r = camera_ray(&cam, u, v, &g, st);
-          V3 c = radiance(r, objs, n_objects, max_depth, &g, o.math, o.arith, st);
+          V3 c = pixel_sample(&cam, nrows, ncols, row, col, objs, n_objects, max_depth, &o, &g, st);
           if (o.accum == 1) { c.x = quantize36(c.x); c.y = quantize36(c.y); c.z = quantize36(c.z); }
           pixel = vadd(pixel, c);
         }
@@ -807,6 +813,48 @@ EXPORT int oracle_render(double* pixels, int32_t nrows, int32_t ncols, int32_t s
     if (st) {
 #pragma omp critical
       stats_add(stats_out, &local);
+    }
+  }
+  return 0;
+}
+
+/* The raw sums of a TOR_SEED_SAMPLE sample range (what tor_render_accumulate_device adds; MATH_PORTABLE, strict arithmetic): for
+ * samples s in [first_sample, first_sample + n_samples) of every requested pixel, q = quantize36(radiance) per channel, and
+ * sums[pixel] = sum of q, moments[pixel] = sum of quantize36(q * q) (moments nullable).  Both are exact in any order (multiples of
+ * 2^-36 below 2^17).  Pixels: the n_pixels flat image indices row * ncols + col of `pixels` (row 0 = bottom), or -- pixels NULL --
+ * every pixel of rows [row_begin, row_end).  Unrequested pixels are left untouched; requested ones are overwritten. */
+EXPORT int oracle_accumulate(double* sums, double* moments, int32_t nrows, int32_t ncols, int32_t first_sample, int32_t n_samples,
+                             const double cam24[24], const double* objs16, int64_t n_objects, int32_t max_depth, const int32_t* pixels,
+                             int64_t n_pixels, int32_t row_begin, int32_t row_end) {
+  if (nrows < 2 || ncols < 2 || first_sample < 0 || n_samples < 0 || !sums) return -1;
+  if (!pixels) {
+    if (row_begin < 0 || row_end > nrows || row_begin > row_end) return -1;
+    n_pixels = (int64_t)(row_end - row_begin) * ncols;
+  }
+  for (int64_t k = 0; pixels && k < n_pixels; ++k)
+    if (pixels[k] < 0 || (int64_t)pixels[k] >= (int64_t)nrows * ncols) return -1;
+  OracleOptions o; memset(&o, 0, sizeof o);
+  o.seeding = 1; o.math = 1; o.arith = 0; o.accum = 1;
+  Cam cam; memcpy(&cam, cam24, sizeof cam);
+  const Obj* objs = (const Obj*)objs16;
+#pragma omp parallel for schedule(dynamic, 4)
+  for (int64_t k = 0; k < n_pixels; ++k) {
+    const int64_t flat = pixels ? (int64_t)pixels[k] : (int64_t)row_begin * ncols + k;
+    const int32_t row = (int32_t)(flat / ncols), col = (int32_t)(flat % ncols);
+    V3 s = v3(0, 0, 0), m = v3(0, 0, 0);
+    for (int32_t i = 0; i < n_samples; ++i) {
+      Rng g;
+      oracle_seed3(&g, (uint64_t)row, (uint64_t)col, (uint64_t)first_sample + (uint64_t)i);
+      V3 c = pixel_sample(&cam, nrows, ncols, row, col, objs, n_objects, max_depth, &o, &g, NULL);
+      c.x = quantize36(c.x); c.y = quantize36(c.y); c.z = quantize36(c.z);
+      s = vadd(s, c);
+      m = vadd(m, v3(quantize36(c.x * c.x), quantize36(c.y * c.y), quantize36(c.z * c.z)));
+    }
+    double* ps = sums + flat * 3;
+    ps[0] = s.x; ps[1] = s.y; ps[2] = s.z;
+    if (moments) {
+      double* pm = moments + flat * 3;
+      pm[0] = m.x; pm[1] = m.y; pm[2] = m.z;
     }
   }
   return 0;

@@ -181,7 +181,7 @@ def test_moments_noise_estimate(tor, torch, ctx):
     mean, mx = ctx.accum_noise_device(sums.data_ptr(), mom.data_ptr(), h * w, n, err.data_ptr(), _stream(torch))
     want = _numpy_se(S, M, n).reshape(-1)
     np.testing.assert_allclose(err.cpu().numpy(), want, rtol=1e-12, atol=0)
-    assert mx == pytest.approx(float(want.max()), rel=1e-12) and mx > 0.0
+    assert mx == float(want.max()) and mx > 0.0  # a max does not depend on the order: exact
     assert mean == pytest.approx(float(want.mean()), rel=1e-12) and 0.0 < mean < mx
     for _ in range(3):  # a fixed reduction order: the same bits every time
         again = ctx.accum_noise_device(sums.data_ptr(), mom.data_ptr(), h * w, n, 0, _stream(torch))

@@ -138,7 +138,7 @@ EXPORTED_SYMBOLS = [
     "tor_context_scene_counters", "tor_render_ptr", "tor_last_pixel_cost", "tor_last_note", "tor_last_handoff_counters",
     "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
     "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
-    "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device",
+    "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
 ]
 
 _lib = None
@@ -278,6 +278,8 @@ def lib():
         _bind_progressive(L, dp)
     if not ab or hasattr(L, "tor_render_accumulate_list_device"):  # (... and one older than adaptive sampling these three)
         _bind_adaptive(L)
+    if not ab or hasattr(L, "tor_debug_last_variant"):  # (... and one older than this debug entry)
+        L.tor_debug_last_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -744,6 +746,13 @@ class Context:
         if n < 0:
             _check(n)
         return buf[:n]
+
+    def last_variant(self) -> tuple:
+        """(seeding, arith, w, f32, blocks) of the integrate_kernel variant of the context's last render launch, all -1 before the
+        first (tor_debug_last_variant)."""
+        out = (C.c_int32 * 5)()
+        _check(lib().tor_debug_last_variant(self._h, out))
+        return tuple(int(v) for v in out)
 
     def last_stats(self) -> Stats:
         st = Stats()

@@ -32,9 +32,15 @@
           unsafeAtomicAdd(&acc_lds[slot * 3 + 1], qy);
           unsafeAtomicAdd(&acc_lds[slot * 3 + 2], qz);
           if (kMom) {  // q <= 1 (DESIGN 2): q * q <= 1, rounded to 2^-36 like q itself -- exact sums under the same bound
+#if defined(TOR_ACCUM_MUTATE) && TOR_ACCUM_MUTATE == 1  // (mutation check of the oracle tests: the square of the unquantised radiance)
+            unsafeAtomicAdd(&mom_lds[slot * 3 + 0], quantize36(radiance.x * radiance.x));
+            unsafeAtomicAdd(&mom_lds[slot * 3 + 1], quantize36(radiance.y * radiance.y));
+            unsafeAtomicAdd(&mom_lds[slot * 3 + 2], quantize36(radiance.z * radiance.z));
+#else
             unsafeAtomicAdd(&mom_lds[slot * 3 + 0], quantize36(qx * qx));
             unsafeAtomicAdd(&mom_lds[slot * 3 + 1], quantize36(qy * qy));
             unsafeAtomicAdd(&mom_lds[slot * 3 + 2], quantize36(qz * qz));
+#endif
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -15,6 +15,14 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double* sums, double
   if (i < n_values) pixels[i] = pow_pos(scale * sums[i], gamma);
 }
 
+// var / n of the standard error.  (TOR_ACCUM_MUTATE == 2: the mutation check of the oracle tests -- var * (1.0 / n), one rounding more,
+// which differs from var / n in the last bit for most n that are not powers of two.)
+#if defined(TOR_ACCUM_MUTATE) && TOR_ACCUM_MUTATE == 2
+#define TOR_ACCUM_VAR_OVER_N(var, n) ((var) * (1.0 / (n)))
+#else
+#define TOR_ACCUM_VAR_OVER_N(var, n) ((var) / (n))
+#endif
+
 // Progressive rendering (tor_accum_noise_device): per pixel, the largest over the channels of the standard error of the mean,
 // sqrt(max(0, (M - S*S/n) / (n - 1)) / n), linear units; err nullable.  Block b sums / maxes pixels b*256 + t + k*gridDim*256
 // in a fixed order and a fixed tree: partials[2b] = sum, partials[2b + 1] = max.
@@ -30,7 +38,7 @@ __global__ __launch_bounds__(256) void accum_noise_kernel(const double* sums, co
       const double S = sums[i * 3 + c], M = moments[i * 3 + c];
       double var = (M - S * S / n) / (n - 1.0);
       var = var > 0.0 ? var : 0.0;
-      const double se = __builtin_sqrt(var / n);
+      const double se = __builtin_sqrt(TOR_ACCUM_VAR_OVER_N(var, n));
       e = se > e ? se : e;
     }
     if (err) err[i] = e;
@@ -91,7 +99,7 @@ __device__ __forceinline__ bool adaptive_still_active(const double* sums, const 
     const double mean = S / n;
     double var = (M - S * S / n) / (n - 1.0);
     var = var > 0.0 ? var : 0.0;
-    const double se = __builtin_sqrt(var / n);
+    const double se = __builtin_sqrt(TOR_ACCUM_VAR_OVER_N(var, n));
     converged = converged && se <= abs_tol + rel_tol * mean;
   }
   return !converged;

@@ -418,6 +418,12 @@ int tor_context_set_stats(TorContext* ctx, int32_t enable) {
   return TOR_OK;
 }
 
+int tor_debug_last_variant(TorContext* ctx, int32_t out[5]) {
+  if (!ctx || !out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_last_variant: NULL argument");
+  for (int k = 0; k < 5; ++k) out[k] = ctx->last_variant[k];
+  return TOR_OK;
+}
+
 int tor_context_scene_counters(TorContext* ctx, int64_t out[3]) {
   if (!ctx || !out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_context_scene_counters: NULL argument");
   out[0] = ctx->n_uploads;
@@ -474,6 +480,14 @@ int32_t tor_shard_rows(int32_t nrows, int32_t row_tile, int32_t shard_index, int
       ++n;
     }
   return n;
+}
+
+// tor::launch_integrate, recording the kernel variant it launched (tor_debug_last_variant)
+static hipError_t launch_integrate_recorded(TorContext* ctx, const tor::KParams& p, int seeding, int arith, int waves_per_simd, int blocks,
+                                            hipStream_t stream) {
+  const hipError_t e = tor::launch_integrate(p, seeding, arith, waves_per_simd, blocks, stream);
+  if (e == hipSuccess) tor::integrate_variant_key(p, seeding, arith, waves_per_simd, ctx->last_variant);
+  return e;
 }
 
 // tor_render_device, and -- acc != null -- one pass of tor_render_accumulate_device: samples [acc->first_sample, + spp) added to the
@@ -936,7 +950,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       const long long wave_blocks = (long long)ctx->num_cus * tor::coop_blocks_per_cu(wk, o.arith);
       HIP_TRY(tor::launch_coop(wk, o.arith, (int)wave_blocks, ctx->stream2));
       HIP_TRY(hipEventRecord(ctx->ev_join[slot], ctx->stream2));
-      HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
+      HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
       HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_join[slot], 0));
       HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
       ctx->launches += 1;
@@ -959,12 +973,12 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
     if (ev) HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
     else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
+    HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
     HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
     HIP_TRY(hipEventRecord(ev, stream));
   } else {
     HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(tor::launch_integrate(p, kseed, o.arith, waves_per_simd, blocks, stream));
+    HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
     HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
   }
   ctx->launches += 1;

@@ -197,6 +197,7 @@ struct TorContext {
   double mig_stall_s = 60.0;
   int64_t n_stalled_frames = 0;  // frames the host-canvas entry points rendered again because the hand-off stalled
   bool last_migrate = false;  // the last launch carried the hand-off (its kMigStalled word means something)
+  int32_t last_variant[5] = {-1, -1, -1, -1, -1};  // {seeding, arith, w, f32, blocks} of the last integrate_kernel launch (tor_debug_last_variant)
 };
 
 namespace tor {

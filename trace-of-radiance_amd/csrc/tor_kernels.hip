@@ -840,6 +840,10 @@ hipError_t launch_integrate(const KParams& p, int seeding, int arith, int waves_
   return hipGetLastError();
 }
 
+void integrate_variant_key(const KParams& p, int seeding, int arith, int waves_per_simd, int32_t out[5]) {
+  out[0] = seeding; out[1] = arith_variant(p, arith); out[2] = clamp_w(waves_per_simd); out[3] = wants_f32(p); out[4] = wants_blocks(p);
+}
+
 int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_per_simd) {
   IntegrateFn fn = integrate_variant(seeding, arith_variant(p, arith), clamp_w(waves_per_simd), wants_f32(p), wants_blocks(p));
   int n = 0;

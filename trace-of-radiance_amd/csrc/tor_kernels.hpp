@@ -163,6 +163,7 @@ struct MigSchedule {
 hipError_t launch_tile_order(const unsigned* pixel_cost, unsigned n_pixels, unsigned* key, unsigned* work, unsigned* order, int n_tiles,
                              float split_frac, unsigned long long* split_out, unsigned long long* lane_counter,
                              float hot_chain, unsigned long long* sched, const MigSchedule& mig, hipStream_t stream);
+void integrate_variant_key(const KParams& p, int seeding, int arith, int waves_per_simd, int32_t out[5]);  // {seeding, arith, w, f32, blocks} launch_integrate picks
 bool integrate_variant_serves_chains(const KParams& p, int seeding);  // the launch's kernel variant carries the server code
 constexpr int kTilePixelsHost = 64;  // == kTilePixels in tor_kernels.hip
 constexpr size_t kTileSortScratchBytes = 4096 * (8 + 4 + 4) + 16;  // launch_tile_order's histogram / offsets behind the per-tile arrays (kCostBins = 4096)
