@@ -12,7 +12,7 @@ counter-based per-sample streams (TOR_SEED_SAMPLE) and the reference's rounding 
 Two timed regions are reported on one GPU, each over the same K steps:
   value         -- the harness contract's region: scene and camera resident in HBM before the clock starts, the
                    frame stays on the device (tor_render_device).
-  host_canvas   -- SURVEY 8(d)'s region, what a Nim caller of render() pays
+  host_canvas   -- (--full) SURVEY 8(d)'s region, what a Nim caller of render() pays
                    (trace_of_radiance.nim:60-64): tor_render_opt on a HOST canvas = scene + camera H2D (the
                    scene is cached after the first call), kernels, D2H into canvas.pixels.
 N > 1 (one process per GPU): image rows are dealt to the ranks round-robin (render.nim:55's `parallelFor row`
@@ -25,6 +25,11 @@ whatever N (`--scaling weak` multiplies spp by N instead; `--config c4` selects 
 (TorOptions.devices): the path a Nim host uses.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
+A plain run measures only the headline figure: it sets up, warms up, times the K steps and prints the line.  `--full` adds
+everything else the line can carry, each leg in runs or launches of its own after the timed steps: the CPU baseline, the
+workload counters of an extra launch, the live rocprofv3 counters, the host-canvas region, the exact-acceleration and
+pixel-seeding legs, the N = 1 value of an N-GPU run and the video pass of `--workload c5 --frames F` (the `--no-*` options
+drop single legs of a `--full` run).
 `--dump-outputs DIR` also writes, after the timed steps, what the timed path computed in its last step (the frame rank 0
 holds) as DIR/frame.npy: the inputs are fixed by the arguments, so two builds can be compared output for output.
 """
@@ -76,6 +81,9 @@ def parse_args():
                          "accelerations (default for --workload c5: blocks+f32, what tor_render() runs by default and the sensible mode for 1601 spheres)")
     ap.add_argument("--row-tile", type=int, default=1,
                     help="rows per shard tile; 1 = row-cyclic: every rank gets nrows/N rows (+-1) of statistically equal cost")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs (CPU baseline, workload and rocprofv3 counters, host-canvas region, accelerations, "
+                         "pixel seeding, the N = 1 value of an N-GPU run, the c5 video pass); a plain run measures the headline figure only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--workload", choices=["frame", "c5"], default="frame",
@@ -83,7 +91,7 @@ def parse_args():
                          "bouncing-spheres scene, 256 spp per frame, frames dealt round-robin to the GPUs (no collective)")
     ap.add_argument("--frames", type=int, default=0,
                     help="--workload c5: render the first F frames of the animation IN ORDER (240 = all of BASELINE configs[4]); steps = the frames "
-                         "this rank renders; per-frame table in the line; a second pass times the device video stage inside the region")
+                         "this rank renders; per-frame table in the line; with --full a second pass times the device video stage inside the region")
     ap.add_argument("--verify", action="store_true", help="N > 1: rank 0 also renders the whole frame alone and requires the gathered frame to be identical")
     ap.add_argument("--no-accel-leg", action="store_true", help="skip the secondary exact-acceleration measurements")
     ap.add_argument("--no-host-leg", action="store_true", help="skip the host-canvas (SURVEY 8d) region")
@@ -108,6 +116,14 @@ def parse_args():
         args.width, args.height, args.spp = {"c1": (384, 216, 100), "c2": (1920, 1080, 100), "c3": (1920, 1080, 1000),
                                              "c4": (3840, 2160, 4096)}[args.config]
     return args
+
+
+PLAIN_NOTE = "not measured (a plain run; --full measures it)"
+
+
+def skipped(args, option):
+    """What the line says of a secondary leg this run did not measure."""
+    return f"skipped ({option})" if args.full else PLAIN_NOTE
 
 
 def frame_spp(args, world):
@@ -476,8 +492,8 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
     # moves 24 MB / 165 MB: the same command gave the small numbers before the run and with --frames 3) -- the driver's clearing of the
     # freed scene buffers shares the L2 with the profiled kernel; the SQ counters were right either way
     mid = timed[len(timed) // 2]
-    traffic, traffic_note = None, "skipped (--no-pmc)" if args.no_pmc else "N > 1: not read"
-    if rank == 0 and not args.no_pmc and world == 1:
+    traffic, traffic_note = None, skipped(args, "--no-pmc") if (args.no_pmc or not args.full) else "N > 1: not read"
+    if rank == 0 and args.full and not args.no_pmc and world == 1:
         traffic, traffic_note = live_traffic(W, H, spp, args.depth, seeding, arith, accel, anim_frame=mid[0])
     elapsed, table = timed_pass(False)
     if args.dump_outputs and rank == 0:   # the last frame of this rank's timed range, before the video pass renders into buf again
@@ -487,7 +503,7 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
     total = H * W * spp * total_frames
     k_ms = sum(r[2] for r in table) / max(len(table), 1)
     video = None
-    if args.frames > 0:
+    if args.frames > 0 and args.full:
         v_elapsed, v_table = timed_pass(True)
         video = {"value": round(total / v_elapsed / 1e6, 2), "unit": "Msamples/s", "frames_per_s": round(total_frames / v_elapsed, 3),
                  "ms_per_step": round(v_elapsed / max(steps, 1) * 1e3, 3),
@@ -497,7 +513,10 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
                            "slice into pinned host memory, per frame (what trace_of_radiance_animation.nim:181-196 pays per frame)",
                  "vs_value": round(elapsed / v_elapsed, 4)}
     result = None
-    if rank == 0:
+    roof = None if args.full else {"bound": "valu_fp64", "kernel": "tor::integrate_kernel", "kernel_ms": round(k_ms, 3),
+                                   "launches_averaged": len(table), "traffic": None, "traffic_detail": traffic_note,
+                                   "note": "workload counters and the fractions of a roof: " + PLAIN_NOTE}
+    if rank == 0 and args.full:
         # workload counters and the reference-formulation operation count on the middle frame of this rank (one extra, untimed launch)
         ctx.upload(mid[2].list())
         ctx.set_stats(True)
@@ -532,6 +551,7 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
                 "note": "frac prices the throughput in the reference's units (every ray x all " + str(n_obj) + " objects in unfused float64, SURVEY 8d) and exceeds 1 with "
                         "the exact accelerations by design; executed_live (counters of one frame's launch, read in this run) holds the fractions of a roof: "
                         "frac_fp64_issue and valu_issue_util (the accelerated kernel issues packed float32 for its filters, so its float64 issue share is small)"}
+    if rank == 0:
         result = {
             "metric": "Msamples/s (pixels x spp / s) on the animated bouncing-spheres scene", "value": round(total / elapsed / 1e6, 2),
             "unit": "Msamples/s", "n_gpus": args.gpus, "steps": steps, "warmup": args.warmup,
@@ -555,8 +575,8 @@ def bench_animation(args, tor, torch, dist, world, rank, local_rank):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if args.no_cpu_baseline:
-            result["cpu_baseline"] = {"value": None, "note": "skipped (--no-cpu-baseline)"}
+        if args.no_cpu_baseline or not args.full:
+            result["cpu_baseline"] = {"value": None, "note": skipped(args, "--no-cpu-baseline")}
         else:
             from oracle import oracle as O
             mid_f = timed[len(timed) // 2][0]
@@ -589,7 +609,7 @@ def bench_single_process_multi_device(args, tor):
     devices = [k % n_dev for k in range(N)]
     n_distinct = len(set(devices))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(W, H, args.spp, args.depth, args.cpu_seconds)   # the host cores are idle: no device work yet
     scene = tor.random_scene(0xFACADE)
     cam = tor.camera(aspect_ratio=W / H) if (W * 9 != H * 16) else tor.camera()
@@ -613,19 +633,23 @@ def bench_single_process_multi_device(args, tor):
     info = tor.last_gather_info()
     value = H * W * spp * args.steps / elapsed / 1e6
     # ---- the N = 1 value of this very invocation (same frame, device 0 alone, same host-canvas region) ----
-    aux = max(1, min(args.aux_steps, args.steps))
-    one = tor.new_canvas(H, W, spp, 2.2)
-    opt1 = tor.make_options(seeding=seeding, arith=arith, accel=accel, device=devices[0])
-    tor.render(one, cam, scene.list(), args.depth, opt1)
-    t1 = time.perf_counter()
-    for _ in range(aux):
+    n1, verified = {"value": None, "note": PLAIN_NOTE}, None
+    if args.full or args.verify:
+        aux = max(1, min(args.aux_steps, args.steps))
+        one = tor.new_canvas(H, W, spp, 2.2)
+        opt1 = tor.make_options(seeding=seeding, arith=arith, accel=accel, device=devices[0])
         tor.render(one, cam, scene.list(), args.depth, opt1)
-    dt1 = time.perf_counter() - t1
-    n1_value = H * W * spp * aux / dt1 / 1e6
-    import numpy as np
-    verified = bool(np.array_equal(one.pixels, cv.pixels))
-    if args.verify and not verified:
-        raise SystemExit("multi-device canvas differs from the single-device canvas")
+        t1 = time.perf_counter()
+        for _ in range(aux):
+            tor.render(one, cam, scene.list(), args.depth, opt1)
+        dt1 = time.perf_counter() - t1
+        n1_value = H * W * spp * aux / dt1 / 1e6
+        n1 = {"value": round(n1_value, 2), "unit": "Msamples/s", "steps": aux, "ms_per_step": round(dt1 / aux * 1e3, 3),
+              "speedup": round(value / n1_value, 3), "region": "the same frame and region on devices[0] alone"}
+        import numpy as np
+        verified = bool(np.array_equal(one.pixels, cv.pixels))
+        if args.verify and not verified:
+            raise SystemExit("multi-device canvas differs from the single-device canvas")
     # ---- kernel-level roofline: every device's integrate_kernel launch (HIP events on its own stream), averaged over the steps;
     #      the job's kernel phase ends with the slowest device ----
     per_dev = [sum(st[k] for st in k_ms_steps) / len(k_ms_steps) for k in range(N)] if k_ms_steps and all(len(st) == N for st in k_ms_steps) else []
@@ -648,8 +672,8 @@ def bench_single_process_multi_device(args, tor):
                      "frac_of_nofma_peak": round(tflops / (PEAK_FP64_NOFMA_TFLOPS * n_distinct), 4),
                      "kernel_ms_per_device": [round(m, 3) for m in per_dev], "kernel_ms": round(k_max, 3), "launches_averaged": len(k_ms_steps),
                      "flops_per_sample": round(fps, 1)})
-    traffic, traffic_note = None, "skipped (--no-pmc)" if args.no_pmc else None
-    if not args.no_pmc:
+    traffic, traffic_note = None, skipped(args, "--no-pmc")
+    if args.full and not args.no_pmc:
         traffic, traffic_note = live_traffic(W, H, spp, args.depth, seeding, arith, accel, shard=(0, N, args.row_tile))
     roof["traffic"] = traffic["bytes"] if traffic else None
     roof["traffic_detail"] = traffic if traffic else traffic_note
@@ -675,11 +699,10 @@ def bench_single_process_multi_device(args, tor):
                    "timed_region": "SURVEY 8(d): host canvas in/out (scene cached after the first call)"},
         "gather": {"leg": info["leg"], "rccl_ranks": info["rccl_ranks"], "devices": info["devices"], "distinct_gpus": n_distinct, "note": note},
         "gather_leg": info["leg"], "rccl_ranks": info["rccl_ranks"],
-        "single_gpu_same_run": {"value": round(n1_value, 2), "unit": "Msamples/s", "steps": aux, "ms_per_step": round(dt1 / aux * 1e3, 3),
-                                "speedup": round(value / n1_value, 3), "region": "the same frame and region on devices[0] alone"},
+        "single_gpu_same_run": n1,
         "last_call_ms": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in timing.items()},
         "canvas_identical_to_single_device": verified, "roofline": roof,
-        "cpu_baseline": cpu if cpu is not None else {"value": None, "note": "skipped (--no-cpu-baseline)"}}))
+        "cpu_baseline": cpu if cpu is not None else {"value": None, "note": skipped(args, "--no-cpu-baseline")}}))
 
 
 _REAL_STDOUT = None
@@ -868,7 +891,7 @@ def main():
         k_ms_ranks = [float(x) for x in allk.cpu()]
     # the N = 1 value of this very invocation: rank 0 renders the whole frame alone (the other ranks wait at the barrier below)
     n1 = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             aux1 = max(1, min(args.aux_steps, args.steps))
             full1 = torch.empty((H, W, 3), dtype=torch.float64, device="cuda")
@@ -911,7 +934,7 @@ def main():
         # ---- workload counters of this very configuration, measured now (one extra, untimed launch) ----
         live = None
         flops_per_sample = FLOPS_PER_SAMPLE_SURVEY
-        if not args.no_stats:
+        if args.full and not args.no_stats:
             ctx.set_stats(True)
             one = torch.empty((len(my_rows), W, 3), dtype=torch.float64, device="cuda")
             ctx.render_device(cam, H, W, spp, 2.2, args.depth, opt, one.data_ptr(), stream)
@@ -940,8 +963,8 @@ def main():
             k_rate = total_samples / (max(k_ms_ranks) * 1e-3) / world
         tflops = k_rate * flops_per_sample / 1e12
         hbm_bytes = len(my_rows) * W * 24.0 * (2 if seeding == tor.SEED_SAMPLE else 1) + 64e3  # canvas write (+ clear in SAMPLE mode) + scene
-        traffic, traffic_note = None, "skipped (--no-pmc)" if args.no_pmc else None
-        if world == 1 and not args.no_pmc:
+        traffic, traffic_note = None, skipped(args, "--no-pmc")
+        if world == 1 and args.full and not args.no_pmc:
             traffic, traffic_note = live_traffic(W, H, spp, args.depth, seeding, arith, accel)
         roof = {
             "bound": "valu_fp64", "kernel": "tor::integrate_kernel",
@@ -958,7 +981,7 @@ def main():
             # the EXECUTED-instruction view, measured in this run (the SQ / GRBM passes of live_traffic): the fraction of a roof that
             # `frac` -- the reference formulation's operation count over the kernel time, > 1 since the screens -- no longer is
             "executed_live": executed_from_counters(traffic, local_samples) if world == 1 else None,
-            "from_profile": from_profile(W, H, spp, args.seeding, args.arith, args.accel) if world == 1 else None,
+            "from_profile": from_profile(W, H, spp, args.seeding, args.arith, args.accel) if (world == 1 and args.full) else None,
             "hbm": {"bound": "hbm", "achieved": round(hbm_bytes / (k_ms * 1e-3) / 1e9, 4), "peak": PEAK_HBM_GBPS,
                     "unit": "GB/s", "frac": round(hbm_bytes / (k_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 8),
                     "algorithmic_bytes_per_launch": hbm_bytes},
@@ -1017,7 +1040,7 @@ def main():
                 n1["speedup"] = round(value / n1["value"], 3)
                 result["single_gpu_same_run"] = n1
     aux = max(1, min(args.aux_steps, args.steps))
-    if rank == 0 and world == 1 and not args.no_host_leg:
+    if rank == 0 and world == 1 and args.full and not args.no_host_leg:
         # ---- SURVEY 8(d)'s region: what a Nim caller of render() pays (trace_of_radiance.nim:60-64) ----
         import numpy as np
         cv = tor.new_canvas(H, W, spp, 2.2)
@@ -1040,7 +1063,7 @@ def main():
             "first_call_ms": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in first.items()},
             "steady_call_ms": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in last.items()},
         }
-    if rank == 0 and world == 1 and args.accel == "none" and not args.no_accel_leg:
+    if rank == 0 and world == 1 and args.accel == "none" and args.full and not args.no_accel_leg:
         # secondary legs (never the metric's value): the same frame with the exact accelerations -- bit-identical
         # canvas (tests/test_gpu_parity.py::test_block_culling_never_changes_a_pixel), checked here again
         ref_frame = frame.clone()
@@ -1144,7 +1167,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.no_pmc:
+    if rank == 0 and world > 1 and args.full and not args.no_pmc:
         # HBM traffic of ONE launch of this run's kernel -- rank 0's shard -- now that the job is over and GPU 0 is free
         traffic, traffic_note = live_traffic(W, H, spp, args.depth, seeding, arith, accel, shard=(0, world, args.row_tile))
         result["roofline"]["traffic"] = traffic["bytes"] if traffic else None
@@ -1154,8 +1177,8 @@ def main():
         result["roofline"]["frac_executed"] = result["roofline"]["executed_live"]["frac_fp64_issue"] if result["roofline"]["executed_live"] else None
     if rank == 0:
         # (N > 1: after the process group is gone -- the other ranks have left, the host cores are free again)
-        result["cpu_baseline"] = (cpu_baseline(W, H, args.spp, args.depth, args.cpu_seconds) if not args.no_cpu_baseline
-                                  else {"value": None, "note": "skipped (--no-cpu-baseline)"})
+        result["cpu_baseline"] = (cpu_baseline(W, H, args.spp, args.depth, args.cpu_seconds) if (args.full and not args.no_cpu_baseline)
+                                  else {"value": None, "note": skipped(args, "--no-cpu-baseline")})
         emit_line(json.dumps(result))
 
 

@@ -481,7 +481,7 @@ def test_bench_multi_rank_path_on_one_gpu(tor):
     env = dict(os.environ, TOR_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1",
-                        "--warmup", "1", "--spp", "4", "--width", "640", "--height", "360", "--verify"],
+                        "--warmup", "1", "--spp", "4", "--width", "640", "--height", "360", "--verify", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -489,7 +489,7 @@ def test_bench_multi_rank_path_on_one_gpu(tor):
     assert d["n_gpus"] == 2 and d["gathered_frame_identical_to_single_process"] is True
     # strong scaling is the default: the frame -- and its spp -- do not depend on N
     assert d["scaling"] == "strong" and "640x360, 4 spp" in d["config"]["workload"] and d["value"] > 0
-    # round 4: the N > 1 line is self-contained -- CPU baseline (timed once the ranks are gone), kernel-level roofline
+    # round 4: with --full the N > 1 line is self-contained -- CPU baseline (timed once the ranks are gone), kernel-level roofline
     # (slowest rank's HIP-event kernel time, live PMC traffic of one shard's launch), the gather's rank count, the N = 1 value of the same run
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["c1"]["ppm_equals_reference_png"] is True
     assert d["roofline"]["kernel_ms"] > 0 and len(d["roofline"]["kernel_ms_per_rank"]) == 2 and d["roofline"]["frac"] > 0

@@ -6,11 +6,11 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py > $O/r6_bench_c3.json 2> $O/r6_bench_c3.err
-python bench.py --config c2 --cpu-seconds 6 > $O/r6_bench_c2.json 2> $O/r6_bench_c2.err
-python bench.py --gpus 2 --steps 3 --warmup 1 --verify --cpu-seconds 6 > $O/r6_bench_2dev.json 2> $O/r6_bench_2dev.err
-# (configs[4] in full -- 240 frames, ~3 min -- is its own call: python bench.py --workload c5 --frames 240 > profiles/r6_bench_c5_240.json)
-TOR_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --verify --cpu-seconds 6 > $O/r6_bench_torchrun2.json 2> $O/r6_bench_torchrun2.err
+python bench.py --full > $O/r6_bench_c3.json 2> $O/r6_bench_c3.err
+python bench.py --full --config c2 --cpu-seconds 6 > $O/r6_bench_c2.json 2> $O/r6_bench_c2.err
+python bench.py --full --gpus 2 --steps 3 --warmup 1 --verify --cpu-seconds 6 > $O/r6_bench_2dev.json 2> $O/r6_bench_2dev.err
+# (configs[4] in full -- 240 frames, ~3 min -- is its own run: python bench.py --workload c5 --frames 240 --full > profiles/r6_bench_c5_240.json)
+TOR_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --verify --cpu-seconds 6 > $O/r6_bench_torchrun2.json 2> $O/r6_bench_torchrun2.err
 COMMON="--no-accel-leg --no-pmc --no-host-leg --no-stats"
 prof() { # tag, bench args
   local t=$1; shift
