@@ -350,6 +350,40 @@ TOR_API int tor_adaptive_select_device(TorContext* ctx, const double* d_sums, co
 TOR_API int tor_resolve_counts_device(TorContext* ctx, const double* d_sums, const int32_t* d_counts, int64_t npix,
                                       float gamma_correction, double* d_pixels, void* hip_stream);
 
+/* ---- closest-hit queries: `hit()` of the uploaded list for the caller's rays ---------------------------------------------
+ * Every Hittable provides hit(r, t_min, t_max, rec) (physics/core.nim:38-42); these entries answer batches of rays with the uploaded
+ * list's (hittables_lists.nim:48-55 over spheres.nim:28-49 / moving_spheres.nim:39-67), bit for bit: for each ray the record of
+ * world.hit(r, t_min, t_max, rec) on the caller's list in list order.
+ *   t        the first root (-half_b - sqrt(disc)) / a if it lies in (t_min, t_max), else the second root if that one does; over the
+ *            list: the smallest accepted root, ties to the lowest index (the sequential closest_so_far loop, reduced)
+ *   p        origin + direction * t (rays.nim:24-25); normal = outward = (p - center(time)) * (1.0 / radius) (vec3s.nim:93-94), negated
+ *            when front_face = 0; front_face = dot(direction, outward) < 0 (core.nim:47-49); moving centres as moving_spheres.nim:39-44
+ *   object   the winner's index in the uploaded list (the reference's rec.material); a miss: object = -1, every other field 0
+ * Float64 throughout, unfused, correctly rounded `/` and sqrt.  Zero directions, NaN times, t_max = +inf, movers with time0 == time1,
+ * negative radii and an empty list all go through the reference's arithmetic and give its answer.
+ *
+ * tor_hit_device: n_rays DEVICE rays (TorRay) -> d_hits (n_rays TorHit, DEVICE).  d_t_range (nullable, DEVICE): 2 float64 per ray
+ * {t_min, t_max}; NULL = render.nim's (0.001, +inf).  Asynchronous on hip_stream, with the one-stream-per-context rule of the render
+ * entries.  [time_lo, time_hi] is the ray-time range the block bounds are built for (cached per scene and range) -- a speed hint only:
+ * a ray whose time lies outside it (or is NaN) is answered by the brute-force walk.  The blocks also need t_min >= 0 (their slab test
+ * clips at 0) and an origin within the reach of the boxes' margin: far from the scene the reference's own discriminant rounds by ~eps
+ * |origin - centre|^2 and accepts rays that pass outside a sphere by more than its box's inflation (reach = sqrt(r_min * 1e-6 /
+ * (64 eps)) minus the objects' extent: ~5300 units for spheres of radius 0.2).  Rays that miss any of these conditions are answered by
+ * the brute-force walk, so every result is exact whatever the hint.  mode: TOR_HIT_AUTO (blocks when the scene has a culling layout
+ * and the range has finite bounds, else brute force; tor_last_note() says which ran: "hit: blocks" | "hit: brute force (...)"),
+ * TOR_HIT_BRUTE, TOR_HIT_BLOCKS (falls back to brute force as AUTO does).  TOR_ERR_INVALID_ARGUMENT for n_rays < 0, a context without a scene, a non-finite or inverted time range and a
+ * mode outside 0..2.  n_rays == 0 is a no-op.
+ * tor_hit_host: the same on host arrays, blocking (copy in, query, copy out) -- what a Nim host's {.importc.} shim calls.  It first
+ * waits for the context's last render launch and last query, on whatever stream they run (it does not refuse another stream). */
+typedef struct TorRay { TorVec3 origin, direction; double time; } TorRay;  /* Ray -- primitives/rays.nim (56 B) */
+/* HitRecord -- physics/core.nim:30-36; the material is replaced by the object's index in the uploaded list (64 B) */
+typedef struct TorHit { TorVec3 p, normal; double t; int32_t object; int32_t front_face; } TorHit;
+enum { TOR_HIT_AUTO = 0, TOR_HIT_BRUTE = 1, TOR_HIT_BLOCKS = 2 };
+TOR_API int tor_hit_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, double time_lo,
+                           double time_hi, int32_t mode, TorHit* d_hits, void* hip_stream);
+TOR_API int tor_hit_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo, double time_hi,
+                         int32_t mode, TorHit* hits);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

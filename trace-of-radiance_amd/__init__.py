@@ -122,6 +122,17 @@ class Stats(C.Structure):
                 ("block_tests", C.c_uint64), ("exact_tests", C.c_uint64)]
 
 
+class Ray(C.Structure):
+    """TorRay -- primitives/rays.nim (origin, direction, time; 56 B)."""
+    _fields_ = [("origin", Vec3), ("direction", Vec3), ("time", C.c_double)]
+
+
+class Hit(C.Structure):
+    """TorHit -- HitRecord, physics/core.nim:30-36, with the object's index in the uploaded list in place of the material (64 B)."""
+    _fields_ = [("p", Vec3), ("normal", Vec3), ("t", C.c_double), ("object", C.c_int32), ("front_face", C.c_int32)]
+
+
+assert C.sizeof(Ray) == 56 and C.sizeof(Hit) == 64 and Hit.object.offset == 56 and Hit.front_face.offset == 60
 assert C.sizeof(Vec3) == 24 and C.sizeof(Material) == 40 and C.sizeof(Sphere) == 72
 assert C.sizeof(MovingSphere) == 112 and C.sizeof(HittableVariant) == 120
 assert C.sizeof(HittableList) == 16 and C.sizeof(Camera) == 192 and C.sizeof(CanvasStruct) == 24
@@ -139,7 +150,10 @@ EXPORTED_SYMBOLS = [
     "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
     "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
     "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
+    "tor_hit_device", "tor_hit_host",
 ]
+HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
+HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 
 _lib = None
 
@@ -280,8 +294,16 @@ def lib():
         _bind_adaptive(L)
     if not ab or hasattr(L, "tor_debug_last_variant"):  # (... and one older than this debug entry)
         L.tor_debug_last_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    if hasattr(L, "tor_hit_device"):  # (... and one older than the closest-hit queries)
+        _bind_hit(L)
     _lib = L
     return L
+
+
+def _bind_hit(L) -> None:
+    L.tor_hit_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p,
+                                 C.c_void_p]
+    L.tor_hit_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -580,6 +602,9 @@ class Context:
         self._h = C.c_void_p()
         self.last_incomplete = False   # set by last_kernel_ms(): the last launch's hand-off stalled, its frame is not whole
         _check(lib().tor_context_create(device, C.byref(self._h)))
+        # the context's device ordinal (-1: the current device, as the library resolves it) -- hit() checks tensors against it
+        torch = sys.modules.get("torch")
+        self._device = device if device >= 0 else (torch.cuda.current_device() if torch is not None else None)
 
     def close(self):
         if self._h:
@@ -758,6 +783,67 @@ class Context:
         st = Stats()
         _check(lib().tor_last_stats(self._h, C.byref(st)))
         return st
+
+    def hit(self, rays, t_range=None, time_range=None, mode="auto") -> "HitResult":
+        """Closest hits of a batch of rays against the uploaded scene: world.hit(r, t_min, t_max, rec) of the reference
+        (hittables_lists.nim:48-55), bit for bit, per ray (tor_hit_device / tor_hit_host).
+
+        rays: (n, 7) float64 {origin xyz, direction xyz, time} -- a torch CUDA tensor (zero-copy, asynchronous on torch's current
+        stream) or anything numpy takes (copied, blocking).  t_range: None (render.nim's (0.001, +inf)) or (n, 2) {t_min, t_max} of
+        the same kind; t_min >= 0 lets a ray use the block culling.  time_range: (lo, hi) the block bounds are built for (a speed hint:
+        rays outside it are still exact); None = the finite min / max of the rays' times.  mode: "auto" | "brute" | "blocks"."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
+                raise ValueError("Context.hit: rays must be an (n, 7) float64 CUDA tensor")
+            dev = getattr(self, "_device", None)
+            if dev is not None and rays.device.index != dev:
+                raise ValueError(f"Context.hit: the rays are on {rays.device}, the context on cuda:{dev}")
+            rays = rays.contiguous()
+            n = int(rays.shape[0])
+            if t_range is not None:
+                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
+                        or t_range.device != rays.device:
+                    raise ValueError("Context.hit: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
+                t_range = t_range.contiguous()
+            if time_range is None:
+                times = rays[:, 6]
+                times = times[torch.isfinite(times)]
+                time_range = (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
+            raw = torch.empty((n, 8), dtype=torch.float64, device=rays.device)
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check(lib().tor_hit_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0),
+                                        float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream)))
+            return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range))
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.hit: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        if t_range is not None:
+            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
+            if t_range.shape != (n, 2):
+                raise ValueError("Context.hit: t_range must have shape (n, 2)")
+        if time_range is None:
+            times = rays[:, 6][np.isfinite(rays[:, 6])]
+            time_range = (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
+        raw = np.zeros((n, 8), dtype=np.float64)
+        _check(lib().tor_hit_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
+                                  C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
+                                  float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.ctypes.data if n else 0)))
+        return HitResult(raw, raw.view(np.int32), last_note())
+
+
+class HitResult:
+    """Closest hits of Context.hit, one TorHit per ray (include/tor_render.h): t, p (n, 3), normal (n, 3), object (int32, -1 = miss)
+    and front_face (int32) are views of `raw` ((n, 8) float64, the records as the library wrote them) -- torch tensors or numpy
+    arrays, as the rays were.  `mode` is what ran: "blocks" or "brute force (...)" (tor_last_note)."""
+
+    def __init__(self, raw, words, note: str, keep=None):
+        self.raw, self._keep = raw, keep   # (keep: the rays' contiguous copy stays alive while the query may run)
+        self.p, self.normal, self.t = raw[:, 0:3], raw[:, 3:6], raw[:, 6]
+        self.object, self.front_face = words[:, 14], words[:, 15]
+        self.mode = note[len("hit: "):] if note.startswith("hit: ") else note
 
 
 class Progressive:

@@ -91,6 +91,24 @@ struct DeviceAccel {
 
 struct RcclComm;  // tor_multi.cpp
 
+// State of the closest-hit queries of a context (tor_hit_device / tor_hit_host, tor_query.hip).  Separate from the render path's:
+// a query never touches the bounds ring, the counters or the per-launch ring slots.  Freed by its destructor (tor_context_destroy).
+struct HitQueryState {
+  DeviceBuffer bnd;                 // block boxes (compute_block_bounds) of the cached (scene, time range)
+  std::vector<double> bnd_host;     // their host copy: source of the asynchronous upload, kept until the next rebuild
+  int64_t bnd_scene = -1;           // scene generation (n_uploads - n_cache_hits) the cache was built for, -1 = none
+  uint64_t bnd_lo = 0, bnd_hi = 0;  // bit patterns of its time range
+  bool bnd_ok = false;              // compute_block_bounds succeeded for that key
+  double org[3] = {0.0, 0.0, 0.0};  // where the boxes' margin holds (tor_query.hip hit_reach): origins within sqrt(reach2) of org,
+  double reach2 = -1.0;             // directions with |d|^2 >= a_min
+  double a_min = 0.0;
+  DeviceBuffer io;                  // tor_hit_host: rays, t ranges and hit records on the device
+  hipEvent_t ev_done = nullptr;     // recorded after the last query launch
+  bool launched = false;
+  void* stream = nullptr;           // stream of the last query launch
+  ~HitQueryState();
+};
+
 }  // namespace tor
 
 struct TorContext {
@@ -198,6 +216,7 @@ struct TorContext {
   int64_t n_stalled_frames = 0;  // frames the host-canvas entry points rendered again because the hand-off stalled
   bool last_migrate = false;  // the last launch carried the hand-off (its kMigStalled word means something)
   int32_t last_variant[5] = {-1, -1, -1, -1, -1};  // {seeding, arith, w, f32, blocks} of the last integrate_kernel launch (tor_debug_last_variant)
+  tor::HitQueryState hitq;  // closest-hit queries (tor_query.hip)
 };
 
 namespace tor {
