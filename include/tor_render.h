@@ -384,6 +384,46 @@ TOR_API int tor_hit_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays
 TOR_API int tor_hit_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo, double time_hi,
                          int32_t mode, TorHit* hits);
 
+/* ---- radiance queries: render.nim's radiance() and the camera's rays for rays and RNG states the caller supplies ------------------
+ * tor_radiance_device: color[i] = radiance(rays[i], world, max_depth, rng[i]) (render.nim:21-47) on the uploaded list, bit for bit, and
+ * rng[i] is left where the reference leaves its `var Rng` after the call.  Every bounce is world.hit(r, 0.001, +inf, rec)
+ * (render.nim:28) as tor_hit_device answers it, then the material's scatter (materials.nim:21-96) with the reference's draws in the
+ * reference's order: Lambertian keeps the ray's time; Metal and Dielectric give the scattered ray time 0 (rays.nim:19's default); an
+ * absorbed Metal ray is black; a miss is the sky 0.5 * y + 1.0 (sic, render.nim:42) of the unit direction times the attenuation; a
+ * path still bouncing after max_depth hits is black.  The colour is the unquantised float64 in the reference's operation order:
+ * unfused, `Vec3 / s` as `* (1.0 / s)`, correctly rounded `/` and sqrt, the portable sin/cos and pow of the GPU integrator.
+ * max_depth == 0 gives black and draws nothing; an empty scene gives the sky and draws nothing.  d_rays (n_rays TorRay), d_rng
+ * (n_rays TorRng, read and written) and d_color (n_rays * 3 float64) are DEVICE arrays; the states may be any the caller holds
+ * (seed1 / seed2 / seed3 of support/rng.nim, or what tor_camera_rays_device left).  mode and [time_lo, time_hi] work as in
+ * tor_hit_device, and tor_last_note() says what ran ("radiance: blocks" | "radiance: brute force (...)"); as scattered Metal and
+ * Dielectric rays carry time 0, the library widens the range to include 0 before it builds or looks up the cached block bounds.
+ * Asynchronous on hip_stream, one stream per context as for the hit queries; a query leaves every render state alone.
+ * TOR_ERR_INVALID_ARGUMENT for what tor_hit_device refuses and for max_depth < 0; n_rays == 0 is a no-op.
+ * tor_radiance_host: the same on host arrays, blocking (copy in, query, copy out; rng updated in place) -- for a Nim shim, which
+ * casts its Rng (whose fields are private) to a TorRng.
+ *
+ * tor_camera_rays_device: the library's camera rays (render.nim:63-65 + cameras.nim:47-57) for listed pixels: per pixel (row, col)
+ * and sample, u = (col + U) / (ncols - 1), v = (row + U) / (nrows - 1), cam.ray(u, v, rng), from the stream below; writes the ray
+ * and the state after the camera's draws -- ready for tor_radiance_device.
+ *   d_pixels  DEVICE int32 flat pixel indices row * ncols + col (row 0 = bottom), n_pixels of them; NULL = every pixel, row-major
+ *             (n_pixels must then be nrows * ncols).  Entries outside [0, nrows * ncols) are skipped: their rays and states are not
+ *             written.
+ *   TOR_SEED_SAMPLE  seed3(row, col, s) for s in [first_sample, first_sample + n_samples) (the per-sample streams of
+ *                    tor_render_accumulate_device); d_rng is output only; entry e, sample s at index e * n_samples + (s - first_sample)
+ *                    of d_rng and d_rays.
+ *   TOR_SEED_PIXEL   n_samples == 1 (first_sample is ignored); d_rng is read and written per listed pixel: the caller seeds
+ *                    seed2(row, col) once and passes the states tor_radiance_device left -- the reference's one stream per pixel.
+ * Asynchronous on hip_stream; it reads no scene and no other state of the context.  TOR_ERR_INVALID_ARGUMENT for nrows or ncols
+ * below 2, n_pixels < 0, first_sample < 0, n_samples < 1, first_sample + n_samples above 2^31 - 1, another seeding, NULL pointers. */
+typedef struct TorRng { uint64_t s0, s1, s2, s3; } TorRng;  /* Rng -- support/rng.nim:18-19, xoshiro256+ (32 B) */
+TOR_API int tor_radiance_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, TorRng* d_rng, int32_t max_depth,
+                                double time_lo, double time_hi, int32_t mode, double* d_color, void* hip_stream);
+TOR_API int tor_radiance_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, TorRng* rng, int32_t max_depth, double time_lo,
+                              double time_hi, int32_t mode, double* color);
+TOR_API int tor_camera_rays_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols, const int32_t* d_pixels,
+                                   int64_t n_pixels, int32_t first_sample, int32_t n_samples, int32_t seeding, TorRng* d_rng,
+                                   TorRay* d_rays, void* hip_stream);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

@@ -132,6 +132,12 @@ class Hit(C.Structure):
     _fields_ = [("p", Vec3), ("normal", Vec3), ("t", C.c_double), ("object", C.c_int32), ("front_face", C.c_int32)]
 
 
+class Rng(C.Structure):
+    """TorRng -- Rng, support/rng.nim:18-19: the four xoshiro256+ words (32 B)."""
+    _fields_ = [("s0", C.c_uint64), ("s1", C.c_uint64), ("s2", C.c_uint64), ("s3", C.c_uint64)]
+
+
+assert C.sizeof(Rng) == 32
 assert C.sizeof(Ray) == 56 and C.sizeof(Hit) == 64 and Hit.object.offset == 56 and Hit.front_face.offset == 60
 assert C.sizeof(Vec3) == 24 and C.sizeof(Material) == 40 and C.sizeof(Sphere) == 72
 assert C.sizeof(MovingSphere) == 112 and C.sizeof(HittableVariant) == 120
@@ -150,7 +156,7 @@ EXPORTED_SYMBOLS = [
     "tor_selftest_screen2_host", "tor_debug_screen2_scene", "tor_debug_layout_segments", "tor_debug_plane32_scene", "tor_knob_count", "tor_knob_info", "tor_last_gather_info", "tor_last_device_kernel_ms", "tor_comm_abort", "tor_comm_count", "tor_context_handoff_stalled",
     "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
     "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
-    "tor_hit_device", "tor_hit_host",
+    "tor_hit_device", "tor_hit_host", "tor_radiance_device", "tor_radiance_host", "tor_camera_rays_device",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
@@ -296,6 +302,8 @@ def lib():
         L.tor_debug_last_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     if hasattr(L, "tor_hit_device"):  # (... and one older than the closest-hit queries)
         _bind_hit(L)
+    if hasattr(L, "tor_radiance_device"):  # (... and one older than the radiance queries)
+        _bind_radiance(L)
     _lib = L
     return L
 
@@ -304,6 +312,15 @@ def _bind_hit(L) -> None:
     L.tor_hit_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p,
                                  C.c_void_p]
     L.tor_hit_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+
+
+def _bind_radiance(L) -> None:
+    L.tor_radiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                      C.c_void_p, C.c_void_p]
+    L.tor_radiance_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                    C.c_void_p]
+    L.tor_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -329,6 +346,51 @@ def _check(rc: int) -> None:
 # --------------------------------------------------------------------------------------
 # Reference-interface mirrors
 # --------------------------------------------------------------------------------------
+# ---- host mirrors of support/rng.nim's seeding (splitmix64, rng.nim:22-53), vectorised: (n, 4) uint64 TorRng states ----------
+_GOLDEN, _MIX = np.uint64(0x9e3779b97f4a7c15), np.uint64(0xbf58476d1ce4e5b9)
+
+
+def _u64(x) -> np.ndarray:
+    """x as a flat uint64 array: the two's-complement bits of negative integers, as the C ABI's uint64_t sees them."""
+    a = np.asarray(x)
+    if a.dtype.kind == "u":
+        return a.astype(np.uint64).reshape(-1)
+    if a.dtype.kind == "i":
+        return a.astype(np.int64).view(np.uint64).reshape(-1)
+    return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in a.reshape(-1)], dtype=np.uint64)
+
+
+def _splitmix64(state: np.ndarray):
+    """rng.nim:31-36: (next state, output)."""
+    with np.errstate(over="ignore"):
+        state = state + _GOLDEN
+        r = (state ^ (state >> np.uint64(30))) * _MIX
+        r = (r ^ (r >> np.uint64(27))) * _MIX
+    return state, r ^ (r >> np.uint64(31))
+
+
+def rng_seed1(x) -> np.ndarray:
+    """rng.nim:38-44 seed(x) for every x: (n, 4) uint64."""
+    sm = _u64(x)
+    out = np.empty((sm.shape[0], 4), dtype=np.uint64)
+    for k in range(4):
+        sm, out[:, k] = _splitmix64(sm)
+    return out
+
+
+def rng_seed2(x, y) -> np.ndarray:
+    """rng.nim:46-53 seed(x, y) = seed((x shl 32) xor y) -- render.nim:60's per-pixel stream seed(row, col)."""
+    x, y = np.broadcast_arrays(_u64(x), _u64(y))
+    return rng_seed1((x << np.uint64(32)) ^ y)
+
+
+def rng_seed3(row, col, sample) -> np.ndarray:
+    """TOR_SEED_SAMPLE's per-sample stream: h = splitmix64 output of the state (row shl 32) xor col, then seed(h xor sample)."""
+    row, col, sample = np.broadcast_arrays(_u64(row), _u64(col), _u64(sample))
+    _, h = _splitmix64((row << np.uint64(32)) ^ col)
+    return rng_seed1(h ^ sample)
+
+
 def vec3(x, y, z) -> Vec3:
     return Vec3(float(x), float(y), float(z))
 
@@ -832,6 +894,94 @@ class Context:
                                   C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
                                   float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.ctypes.data if n else 0)))
         return HitResult(raw, raw.view(np.int32), last_note())
+
+
+    def radiance(self, rays, rng, max_depth=50, time_range=None, mode="auto"):
+        """radiance(ray, world, max_depth, rng) of the reference (render.nim:21-47), bit for bit, per ray, on the uploaded scene
+        (tor_radiance_device / tor_radiance_host).  Returns (color (n, 3) float64, rng (n, 4): the states after the path's last draw,
+        mode: what ran, "blocks" or "brute force (...)").
+
+        rays: (n, 7) float64 {origin xyz, direction xyz, time}; rng: (n, 4) xoshiro256+ states (rng_seed1/2/3, or camera_rays').
+        Torch CUDA tensors (rng as int64 holding the u64 bits) are passed zero-copy, asynchronous on torch's current stream, and a
+        contiguous rng tensor is updated in place; anything numpy takes is copied (blocking) and the states come back as uint64.
+        time_range: (lo, hi) the block bounds are built for (a speed hint; the library adds 0); None = the rays' finite times.
+        mode: "auto" | "brute" | "blocks"."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
+                raise ValueError("Context.radiance: rays must be an (n, 7) float64 CUDA tensor")
+            dev = getattr(self, "_device", None)
+            if dev is not None and rays.device.index != dev:
+                raise ValueError(f"Context.radiance: the rays are on {rays.device}, the context on cuda:{dev}")
+            n = int(rays.shape[0])
+            if not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (n, 4) \
+                    or rng.device != rays.device:
+                raise ValueError("Context.radiance: with tensor rays, rng must be an (n, 4) int64 tensor on the rays' device")
+            rays, rng = rays.contiguous(), rng.contiguous()
+            if time_range is None:
+                times = rays[:, 6]
+                times = times[torch.isfinite(times)]
+                time_range = (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
+            color = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check(lib().tor_radiance_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), int(max_depth),
+                                             float(time_range[0]), float(time_range[1]), m, C.c_void_p(color.data_ptr()),
+                                             C.c_void_p(stream)))
+            return color, rng, _mode_of(last_note(), "radiance: ")
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.radiance: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        st = np.asarray(rng)
+        if st.shape != (n, 4) or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+            raise ValueError("Context.radiance: rng must be an (n, 4) array of 64-bit integers")
+        st = np.ascontiguousarray(st).view(np.uint64).copy()
+        if time_range is None:
+            times = rays[:, 6][np.isfinite(rays[:, 6])]
+            time_range = (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
+        color = np.zeros((n, 3), dtype=np.float64)
+        _check(lib().tor_radiance_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(st.ctypes.data if n else 0),
+                                       int(max_depth), float(time_range[0]), float(time_range[1]), m,
+                                       C.c_void_p(color.ctypes.data if n else 0)))
+        return color, st, _mode_of(last_note(), "radiance: ")
+
+    def camera_rays(self, cam: Camera, nrows: int, ncols: int, first_sample: int = 0, n_samples: int = 1, seeding=SEED_SAMPLE,
+                    pixels=None, rng=None):
+        """The library's camera rays (render.nim:63-65 + cameras.nim:47-57, tor_camera_rays_device) for every pixel or a list of
+        flat pixel indices row * ncols + col (row 0 = bottom): returns (rays (m, 7) float64, rng (m, 4) int64), CUDA tensors on the
+        context's device, asynchronous on torch's current stream -- the rays and the states after the camera's draws, ready for
+        radiance().  SEED_SAMPLE: seed3(row, col, s) for s in [first_sample, first_sample + n_samples), entry e and sample s at
+        e * n_samples + (s - first_sample).  SEED_PIXEL: n_samples = 1 and rng (n_pixels, 4) the states to draw from (rng_seed2,
+        or what radiance() left), updated in place when it is a contiguous int64 CUDA tensor."""
+        import torch
+        dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+        if pixels is not None:
+            pixels = torch.as_tensor(pixels).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            n_pix = int(pixels.numel())
+        else:
+            n_pix = int(nrows) * int(ncols)
+        m = n_pix * int(n_samples)
+        if int(seeding) == SEED_PIXEL:
+            if rng is None:
+                raise ValueError("Context.camera_rays: SEED_PIXEL needs the per-pixel states (rng)")
+            if not isinstance(rng, torch.Tensor):
+                rng = torch.from_numpy(np.ascontiguousarray(np.asarray(rng)).view(np.int64))
+            rng = rng.to(device=dev).contiguous()
+            if rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (m, 4):
+                raise ValueError("Context.camera_rays: rng must be (n_pixels, 4) 64-bit integers")
+        else:
+            rng = torch.empty((m, 4), dtype=torch.int64, device=dev)
+        rays = torch.empty((m, 7), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().tor_camera_rays_device(self._h, C.byref(cam), int(nrows), int(ncols),
+                                            C.c_void_p(pixels.data_ptr() if pixels is not None else 0), n_pix, int(first_sample),
+                                            int(n_samples), int(seeding), C.c_void_p(rng.data_ptr()), C.c_void_p(rays.data_ptr()),
+                                            C.c_void_p(stream)))
+        return rays, rng
+
+def _mode_of(note: str, prefix: str) -> str:
+    return note[len(prefix):] if note.startswith(prefix) else note
 
 
 class HitResult:

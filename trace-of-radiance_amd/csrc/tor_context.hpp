@@ -102,7 +102,8 @@ struct HitQueryState {
   double org[3] = {0.0, 0.0, 0.0};  // where the boxes' margin holds (tor_query.hip hit_reach): origins within sqrt(reach2) of org,
   double reach2 = -1.0;             // directions with |d|^2 >= a_min
   double a_min = 0.0;
-  DeviceBuffer io;                  // tor_hit_host: rays, t ranges and hit records on the device
+  DeviceBuffer io;                  // tor_hit_host: rays, t ranges and hit records on the device (tor_radiance_host: rays, states, colours)
+  DeviceBuffer head;                // tor_radiance_device: the persistent waves' work counter (tor_radiance.hip)
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch
@@ -216,7 +217,7 @@ struct TorContext {
   int64_t n_stalled_frames = 0;  // frames the host-canvas entry points rendered again because the hand-off stalled
   bool last_migrate = false;  // the last launch carried the hand-off (its kMigStalled word means something)
   int32_t last_variant[5] = {-1, -1, -1, -1, -1};  // {seeding, arith, w, f32, blocks} of the last integrate_kernel launch (tor_debug_last_variant)
-  tor::HitQueryState hitq;  // closest-hit queries (tor_query.hip)
+  tor::HitQueryState hitq;  // closest-hit and radiance queries (tor_query.hip, tor_radiance.hip)
 };
 
 namespace tor {

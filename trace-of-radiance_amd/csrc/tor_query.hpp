@@ -1,0 +1,239 @@
+// tor_query.hpp -- the closest-hit query's exact test, slab test and block / super-box descent (the head of tor_query.hip says why
+// they are exact), shared by the hit kernels (tor_query.hip) and the radiance kernels (tor_radiance.hip), and the host setup of
+// their launches (stream rule, layouts, cached block bounds).  The descent itself is tor_query_descent.inc.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tor_context.hpp"
+
+namespace tor {
+namespace {
+
+typedef const double __attribute__((address_space(4))) * qcdptr;  // scalar view: wave-uniform records come through s_load
+typedef const double __attribute__((address_space(1))) * qgdptr;  // global: per-lane records
+
+constexpr int kHitThreads = 256;
+
+struct QParams {
+  const double* rays;     // 7 float64 per ray (TorRay)
+  const double* t_range;  // 2 float64 per ray {t_min, t_max}, or null: render.nim's (0.001, +inf)
+  double* hits;           // 8 float64 words per ray (TorHit)
+  long long n_rays;
+  const double* cold;     // cold records (tor_kernels.hpp), 16 float64 per slot
+  int n_uniform;          // slots [0, n_uniform) go through the wave-uniform loop: the whole flat layout, or the always-layout
+  // blocks only:
+  int spatial_base;       // block b owns cold slots spatial_base + 8 b .. + 8
+  int n_spatial;          // spatial slots (8 per block)
+  const double* bnd;      // 8 float64 per box record {lo xyz, hi xyz, -, -} (compute_block_bounds)
+  int n_boxes;            // block boxes; box b stands for blocks [b fanout, (b + 1) fanout)
+  int fanout;
+  int two_level;          // the top-level loop tests the super boxes (records super0 + s, s < n_super) instead of the block boxes
+  int super0, n_super;
+  double time_lo, time_hi;  // the ray-time range the boxes hold for
+  double org[3];            // centre of the spatial objects' bounding box ...
+  double reach2;            // ... and the squared distance from it within which an origin may use the boxes (< 0: none may)
+  double a_min;             // smallest |d|^2 that may use the boxes
+};
+
+struct QRay {
+  double ox, oy, oz, dx, dy, dz, time, t_min, t_max, a;
+};
+
+struct QBest {
+  double t;
+  int orig;  // original index of the winner (ties: the lowest)
+  int slot;  // its cold slot, -1 = no hit
+};
+
+// centre of the object in cold record c at the ray's time: moving_spheres.nim:39-44 (center0 + (time - time0) / (time1 - time0) *
+// (center1 - center0); the record carries center1 - center0 and time1 - time0), or the sphere's centre
+template <typename P>
+__device__ __forceinline__ void centre_at(P c, double time, double& cx, double& cy, double& cz) {
+  cx = c[0]; cy = c[1]; cz = c[2];
+  if ((int)__double_as_longlong(c[13]) & 1) {
+    const double f = (time - c[7]) / c[8];
+    cx = cx + c[3] * f; cy = cy + c[4] * f; cz = cz + c[5] * f;
+  }
+}
+
+// spheres.nim:29-48 / moving_spheres.nim:47-66 for the object in cold record c, in the reference's operation order, reduced to the
+// order-independent update of the closest hit
+template <typename P>
+__device__ __forceinline__ void exact_test(P c, int slot, const QRay& r, QBest& b) {
+  const double r2 = c[15];
+  if (r2 == -1.0) return;  // padding slot (a real record holds radius * radius: >= 0 or NaN)
+  double cx, cy, cz;
+  centre_at(c, r.time, cx, cy, cz);
+  const double ocx = r.ox - cx, ocy = r.oy - cy, ocz = r.oz - cz;
+  const double hb = ocx * r.dx + ocy * r.dy + ocz * r.dz;
+  const double cc = (ocx * ocx + ocy * ocy + ocz * ocz) - r2;
+  const double disc = hb * hb - r.a * cc;
+  if (disc > 0.0) {
+    const double root = __builtin_sqrt(disc);
+    double sol = (-hb - root) / r.a;
+    bool ok = (r.t_min < sol) && (sol < r.t_max);
+    if (!ok) {
+      sol = (-hb + root) / r.a;
+      ok = (r.t_min < sol) && (sol < r.t_max);
+    }
+    if (ok) {
+      const int orig = (int)__double_as_longlong(c[14]);
+      if (sol < b.t || (sol == b.t && orig < b.orig)) {
+        b.t = sol;
+        b.orig = orig;
+        b.slot = slot;
+      }
+    }
+  }
+}
+
+// float64 slab test of box record bx, clipped at t = 0: the integrator's test (integrate_loop_boxes64.inc); conservative for the
+// inflated boxes of compute_block_bounds
+template <typename P>
+__device__ __forceinline__ bool slab(P bx, const QRay& r, double ix, double iy, double iz) {
+  const double tx0 = (bx[0] - r.ox) * ix, tx1 = (bx[3] - r.ox) * ix;
+  const double ty0 = (bx[1] - r.oy) * iy, ty1 = (bx[4] - r.oy) * iy;
+  const double tz0 = (bx[2] - r.oz) * iz, tz1 = (bx[5] - r.oz) * iz;
+  const double t_in = __builtin_fmax(__builtin_fmax(__builtin_fmin(tx0, tx1), __builtin_fmin(ty0, ty1)),
+                                     __builtin_fmax(__builtin_fmin(tz0, tz1), 0.0));
+  const double t_out = __builtin_fmin(__builtin_fmin(__builtin_fmax(tx0, tx1), __builtin_fmax(ty0, ty1)), __builtin_fmax(tz0, tz1));
+  return t_in <= t_out;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+
+// Where the boxes of `bnd` (compute_block_bounds for acc) hold for the reference's rounding (the head of tor_query.hip): a hit the reference
+// accepts on a spatial object of radius r from an origin at distance |oc| lies at most 6 eps (|oc|^2 + r^2) / r outside the sphere, and
+// every box is inflated by at least 1e-6.  With 16 eps (|oc|^2 + r_max^2) / r_min <= 1e-6 / 4, over 10x margin, the hit lies inside
+// its box.  |oc| <= |o - org| + half the diagonal of the boxes' union, so origins within `reach` of org qualify.  a_min keeps the
+// test's products clear of the subnormal range (an underflowed product's error is absolute, not relative): a * r_min^2 >= 2^-1000.
+void hit_reach(const tor::HostAccel& acc, const std::vector<double>& bnd, tor::HitQueryState& hq) {
+  hq.reach2 = -1.0;
+  hq.a_min = INFINITY;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t b = 0; b < acc.n_boxes; ++b) {
+    const double* c = &bnd[8 * b];
+    if (c[0] != c[0]) continue;  // NaN: empty box
+    for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], c[k]); hi[k] = std::fmax(hi[k], c[3 + k]); }
+  }
+  double r_min = INFINITY, r_max = 0.0;
+  for (const tor::HostAccel::Obj& o : acc.spatial)
+    if (o.valid) { r_min = std::fmin(r_min, o.abs_r); r_max = std::fmax(r_max, o.abs_r); }
+  if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) || !(r_min > 0.0) || !std::isfinite(r_max)) return;
+  const double eps = 0x1p-53;
+  double half_diag = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    hq.org[k] = 0.5 * lo[k] + 0.5 * hi[k];
+    half_diag += (hi[k] - lo[k]) * (hi[k] - lo[k]);
+  }
+  half_diag = 0.5 * std::sqrt(half_diag) * (1.0 + 1e-9);
+  const double oc2 = 0.25e-6 * r_min / (16.0 * eps) - r_max * r_max;  // the largest |oc|^2 the margin covers
+  if (!(oc2 > 0.0) || !std::isfinite(oc2)) return;
+  const double reach = std::sqrt(oc2) * (1.0 - 1e-9) - half_diag;
+  if (!(reach > 0.0)) return;
+  hq.reach2 = reach * reach * (1.0 - 1e-9);  // (the kernel's |o - org|^2 carries a few roundings)
+  hq.a_min = 0x1p-1000 / (r_min * r_min);
+}
+
+// The host side of a query launch on `stream` (the caller has checked its arguments): the one-stream-per-context rule, the layouts
+// and the block bounds cached per (scene, time range), and the scene part of p -- the culling layout's (blocks = true) when mode is
+// not TOR_HIT_BRUTE and the scene has one with finite bounds and a usable margin, else the flat layout's (`why` says why, if mode
+// asked for the blocks).  Used by the hit queries (tor_query.hip) and the radiance queries (tor_radiance.hip).
+int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi, int32_t mode, hipStream_t stream, QParams& p,
+                bool& blocks, std::string& why) {
+  using tor::fail;
+  using tor::fail_hip;
+  const std::string w = who;
+  tor::HitQueryState& hq = ctx->hitq;
+  // one stream per context while launches are in flight (tor_render.h): neither the context's last render launch nor its last query
+  // may still be running on another stream
+  if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != (void*)stream) {
+    const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
+    if (q == hipErrorNotReady)
+      return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the context's last render launch is still running on a different stream -- launches "
+                                                "of one context that may overlap must use ONE stream (or use one context per stream)");
+    if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
+  }
+  if (hq.launched && hq.stream != (void*)stream) {
+    const hipError_t q = hipEventQuery(hq.ev_done);
+    if (q == hipErrorNotReady)
+      return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the context's last query is still running on a different stream -- launches of one "
+                                                "context that may overlap must use ONE stream (or use one context per stream)");
+    if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
+  }
+  if (!hq.ev_done) HIP_TRY(hipEventCreateWithFlags(&hq.ev_done, hipEventDisableTiming));
+
+  blocks = false;
+  why.clear();
+  if (mode != TOR_HIT_BRUTE) {
+    const int rc = tor::ensure_layouts(ctx, TOR_ACCEL_BLOCKS);
+    if (rc != TOR_OK) return rc;
+    const tor::HostAccel& acc = ctx->accel[0];
+    if (!acc.available) {
+      why = "the scene has no culling layout";
+    } else {
+      // block bounds cached per (scene, time range); the render path's bounds ring is not touched
+      const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
+      uint64_t lo_bits, hi_bits;
+      std::memcpy(&lo_bits, &time_lo, 8);
+      std::memcpy(&hi_bits, &time_hi, 8);
+      if (hq.bnd_scene != gen || hq.bnd_lo != lo_bits || hq.bnd_hi != hi_bits) {
+        hq.bnd_scene = -1;
+        if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
+        hq.bnd_ok = tor::compute_block_bounds(acc, time_lo, time_hi, hq.bnd_host);
+        if (hq.bnd_ok) {
+          hit_reach(acc, hq.bnd_host, hq);
+          const size_t bytes = hq.bnd_host.size() * 8;
+          HIP_TRY(hq.bnd.ensure(bytes));
+          HIP_TRY(hipMemcpyAsync(hq.bnd.ptr, hq.bnd_host.data(), bytes, hipMemcpyHostToDevice, stream));
+        }
+        hq.bnd_scene = gen;
+        hq.bnd_lo = lo_bits;
+        hq.bnd_hi = hi_bits;
+      }
+      if (!hq.bnd_ok) why = "no finite block bounds for the time range";
+      else if (!(hq.reach2 > 0.0)) why = "the block boxes' margin holds for no ray origin (radii too small)";
+      else blocks = true;
+    }
+  }
+  if (!blocks) {
+    const int rc = tor::ensure_layouts(ctx, 0);
+    if (rc != TOR_OK) return rc;
+  }
+
+  if (blocks) {
+    const tor::HostAccel& acc = ctx->accel[0];
+    const size_t n_bnd_p = tor::accel_boxes_padded(acc);
+    p.cold = ctx->d_accel[0].always.cold;
+    p.n_uniform = (int)acc.spatial_base;
+    p.spatial_base = (int)acc.spatial_base;
+    p.n_spatial = (int)(acc.n_blocks * tor::kPad);
+    p.bnd = (const double*)hq.bnd.ptr;
+    p.n_boxes = (int)acc.n_boxes;
+    p.fanout = acc.fanout > 0 ? acc.fanout : 1;
+    p.two_level = acc.two_level ? 1 : 0;
+    p.super0 = (int)(n_bnd_p + 1);
+    p.n_super = (int)(n_bnd_p / tor::kPad);
+    p.time_lo = time_lo;
+    p.time_hi = time_hi;
+    for (int k = 0; k < 3; ++k) p.org[k] = hq.org[k];
+    p.reach2 = hq.reach2;
+    p.a_min = hq.a_min;
+  } else {
+    p.cold = ctx->flat[0].cold;
+    p.n_uniform = ctx->flat[0].n_sorted;
+  }
+  return TOR_OK;
+}
+
+}  // namespace
+}  // namespace tor
