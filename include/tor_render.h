@@ -424,6 +424,62 @@ TOR_API int tor_camera_rays_device(TorContext* ctx, const TorCamera* cam, int32_
                                    int64_t n_pixels, int32_t first_sample, int32_t n_samples, int32_t seeding, TorRng* d_rng,
                                    TorRay* d_rays, void* hip_stream);
 
+/* ---- path steps: one iteration of radiance()'s loop, the scatter alone, the sky and the list of the rays that go on ---------------
+ * For hosts that write their own integrator (own sky or environment map, emissive objects picked by `object`, feature buffers of
+ * any bounce, Russian roulette) and keep the reference's physics and draws.  Arrays are indexed by the RAY, not by the position in
+ * the list: a host keeps full-size arrays and a shrinking list and never moves a ray.  d_list (DEVICE int32, n_list entries; NULL:
+ * every ray, n_list must be n_rays) names the rays a call works on; entries outside [0, n_rays) are skipped (nothing read, nothing
+ * written); entries must be unique (duplicates are the caller's race); rays that are not listed are untouched in every array.
+ * n_list == 0 and n_rays == 0 are no-ops.
+ *
+ * tor_bounce_device: per listed ray i one iteration of render.nim:26-38 -- world.hit(rays[i], 0.001, +inf, rec), then
+ * rec.material.scatter(rays[i], rec, rng[i], attenuation, scattered) (materials.nim:21-96) -- bit for bit:
+ *   d_hits[i]         what tor_hit_device writes for rays[i] with d_t_range = NULL (a miss: object = -1, the rest 0)
+ *   miss              status TOR_BOUNCE_MISS, attenuation 0, ray and state untouched, nothing drawn
+ *   hit               the winner's material scatters with the reference's draws in the reference's order (float64 unfused, the
+ *                     portable sin/cos and pow5 of tor_radiance_device); d_rays[i] becomes `scattered`: origin rec.p, Lambertian
+ *                     keeps r_in.time, Metal and Dielectric write time 0 (rays.nim:19) -- written for an absorbed Metal ray too, as
+ *                     materials.nim:41 writes it before the test; d_rng[i] is the state after the scatter's last draw
+ *   d_attenuation[i]  3 float64: the albedo (Lambertian, scattered Metal), (1, 1, 1) (Dielectric), 0 (absorbed: the reference
+ *                     leaves it unset); status TOR_BOUNCE_SCATTERED | TOR_BOUNCE_ABSORBED
+ * Driven as render.nim drives it (att = 1; per step att *= attenuation; a miss ends with tor_sky_device's colour * att, an
+ * absorbed ray with black; max_depth steps, then black) the steps give tor_radiance_device's colours and states, bit for bit.
+ * mode and [time_lo, time_hi] work as in tor_hit_device (a speed hint only); the library widens the range to include 0 as
+ * tor_radiance_device does, so a chain of steps called with one range uses ONE cached set of block bounds.  tor_last_note():
+ * "bounce: blocks" | "bounce: brute force (...)".  An empty scene gives all misses and draws nothing.  Asynchronous on hip_stream,
+ * one stream per context as for the other queries; a step leaves every render state alone.  TOR_ERR_INVALID_ARGUMENT (nothing
+ * written) for what tor_hit_device refuses, n_list < 0, a NULL list with n_list != n_rays, NULL arrays.
+ *
+ * tor_scatter_device: the second half alone, from the caller's records: the material of d_hits[i].object, and p, normal,
+ * front_face as given (a host may have perturbed the normal, or taken the record from geometry of its own); t is not read.  An
+ * object outside [0, n_objects) counts as a miss.  tor_bounce_device equals tor_hit_device followed by tor_scatter_device, bit for
+ * bit.  tor_last_note(): "scatter".
+ * tor_bounce_host / tor_scatter_host: the same on host arrays, blocking (every array copied in, the step, the outputs copied
+ * out) -- what a Nim shim's {.importc.} calls; they wait for the context's last render launch and last query as tor_hit_host does.
+ *
+ * tor_sky_device: d_color[i] (3 float64) = render.nim:41-44 without the attenuation for each listed ray:
+ * (1 - t) * white + t * (0.5, 0.7, 1.0) with t = 0.5 * unit_vector(direction).y + 1.0 (sic).  Asynchronous.  It reads no scene
+ * and no other state of the context (as tor_camera_rays_device), so the one-stream rule does not apply to it.  Note: "sky".
+ *
+ * tor_bounce_select_device: ordered compaction -- the entries of d_list_in (NULL: 0 .. n_in - 1, n_in must be n_rays) that lie in
+ * [0, n_rays) and whose d_status is TOR_BOUNCE_SCATTERED, in input order, to d_list_out (room for n_in entries, not d_list_in
+ * itself); *n_out (HOST) = how many.  Blocking on hip_stream, as tor_adaptive_select_device; its scratch is the context's, so the
+ * one-stream rule of the other queries holds for it.  n_rays and n_in at most 2^31 - 1.  Note: "bounce select". */
+enum { TOR_BOUNCE_MISS = 0, TOR_BOUNCE_SCATTERED = 1, TOR_BOUNCE_ABSORBED = 2 };
+TOR_API int tor_bounce_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
+                              double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_attenuation,
+                              int32_t* d_status, void* hip_stream);
+TOR_API int tor_bounce_host(TorContext* ctx, int64_t n_rays, TorRay* rays, TorRng* rng, const int32_t* list, int64_t n_list,
+                            double time_lo, double time_hi, int32_t mode, TorHit* hits, double* attenuation, int32_t* status);
+TOR_API int tor_scatter_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, const TorHit* d_hits, TorRng* d_rng,
+                               const int32_t* d_list, int64_t n_list, double* d_attenuation, int32_t* d_status, void* hip_stream);
+TOR_API int tor_scatter_host(TorContext* ctx, int64_t n_rays, TorRay* rays, const TorHit* hits, TorRng* rng, const int32_t* list,
+                             int64_t n_list, double* attenuation, int32_t* status);
+TOR_API int tor_sky_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const int32_t* d_list, int64_t n_list,
+                           double* d_color, void* hip_stream);
+TOR_API int tor_bounce_select_device(TorContext* ctx, int64_t n_rays, const int32_t* d_status, const int32_t* d_list_in, int64_t n_in,
+                                     int32_t* d_list_out, int64_t* n_out, void* hip_stream);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

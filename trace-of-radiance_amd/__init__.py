@@ -157,9 +157,11 @@ EXPORTED_SYMBOLS = [
     "tor_render_accumulate_device", "tor_resolve_device", "tor_accum_noise_device",
     "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
     "tor_hit_device", "tor_hit_host", "tor_radiance_device", "tor_radiance_host", "tor_camera_rays_device",
+    "tor_bounce_device", "tor_bounce_host", "tor_scatter_device", "tor_scatter_host", "tor_sky_device", "tor_bounce_select_device",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
+BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
 
 _lib = None
 
@@ -304,6 +306,8 @@ def lib():
         _bind_hit(L)
     if hasattr(L, "tor_radiance_device"):  # (... and one older than the radiance queries)
         _bind_radiance(L)
+    if hasattr(L, "tor_bounce_device"):  # (... and one older than the path steps)
+        _bind_bounce(L)
     _lib = L
     return L
 
@@ -321,6 +325,16 @@ def _bind_radiance(L) -> None:
                                     C.c_void_p]
     L.tor_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _bind_bounce(L) -> None:
+    v, i64 = C.c_void_p, C.c_int64
+    L.tor_bounce_device.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v, v, v]
+    L.tor_bounce_host.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v, v]
+    L.tor_scatter_device.argtypes = [v, i64, v, v, v, v, i64, v, v, v]
+    L.tor_scatter_host.argtypes = [v, i64, v, v, v, v, i64, v, v]
+    L.tor_sky_device.argtypes = [v, i64, v, v, i64, v, v]
+    L.tor_bounce_select_device.argtypes = [v, i64, v, v, i64, v, C.POINTER(C.c_int64), v]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -980,6 +994,239 @@ class Context:
                                             C.c_void_p(stream)))
         return rays, rng
 
+    # ---- path steps (tor_bounce_device and friends): the pieces of radiance()'s loop for hosts that write their own integrator ----
+
+    def _step_tensors(self, who, rays, rng):
+        """Torch operands of a step: (rays, rng, device, stream), contiguous (a contiguous tensor is the caller's own: updated in place)."""
+        import torch
+        if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
+            raise ValueError(f"Context.{who}: rays must be an (n, 7) float64 CUDA tensor")
+        dev = getattr(self, "_device", None)
+        if dev is not None and rays.device.index != dev:
+            raise ValueError(f"Context.{who}: the rays are on {rays.device}, the context on cuda:{dev}")
+        n = int(rays.shape[0])
+        if rng is not None:
+            if not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (n, 4) \
+                    or rng.device != rays.device:
+                raise ValueError(f"Context.{who}: with tensor rays, rng must be an (n, 4) int64 tensor on the rays' device")
+            rng = rng.contiguous()
+        return rays.contiguous(), rng, rays.device, torch.cuda.current_stream(rays.device).cuda_stream
+
+    @staticmethod
+    def _step_index(index, n, device=None):
+        """The list of a step: (contiguous int32 tensor / array or None, n_list, its address -- 0 for None: every ray)."""
+        if index is None:
+            return None, n, C.c_void_p(0)
+        if device is not None:
+            import torch
+            index = torch.as_tensor(index).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+            return index, int(index.numel()), C.c_void_p(index.data_ptr() or 16)   # (an empty list is a list: never dereferenced)
+        index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
+        return index, int(index.size), C.c_void_p(index.ctypes.data or 16)
+
+    @staticmethod
+    def _time_range_of(rays, time_range):
+        if time_range is not None:
+            return float(time_range[0]), float(time_range[1])
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            times = rays[:, 6]
+            times = times[torch.isfinite(times)]
+            return (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
+        times = rays[:, 6][np.isfinite(rays[:, 6])]
+        return (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
+
+    @staticmethod
+    def _step_states(who, rng, n):
+        st = np.asarray(rng)
+        if st.shape != (n, 4) or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+            raise ValueError(f"Context.{who}: rng must be an (n, 4) array of 64-bit integers")
+        return np.ascontiguousarray(st).view(np.uint64).copy()
+
+    def bounce(self, rays, rng, index=None, time_range=None, mode="auto", out=None) -> "BounceResult":
+        """One iteration of radiance()'s loop (render.nim:26-38) for the listed rays, bit for bit (tor_bounce_device /
+        tor_bounce_host): world.hit(ray, 0.001, +inf, rec), then rec.material.scatter(ray, rec, rng, attenuation, scattered).
+
+        rays (n, 7) float64 and rng (n, 4) 64-bit states: torch CUDA tensors are passed zero-copy, asynchronous on torch's current
+        stream, and contiguous ones are updated in place (a hit ray becomes `scattered`, its state the one after the scatter's last
+        draw); anything numpy takes is copied (blocking).  index: the rays to step (int32, unique; entries outside [0, n) are
+        skipped), None = all.  Arrays are indexed by the ray, so a host keeps full-size arrays and a shrinking index.  Returns a
+        BounceResult: HitResult's fields, attenuation (n, 3), status (n,) int32 (BOUNCE_MISS / BOUNCE_SCATTERED / BOUNCE_ABSORBED),
+        rays and rng (the updated arrays) and the mode that ran.  out: a BounceResult of an earlier step on as many rays, whose
+        arrays are written again (rays that are not listed keep what they hold); otherwise new ones (object -1, the rest 0)."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            rays, rng, dev, stream = self._step_tensors("bounce", rays, rng)
+            n = int(rays.shape[0])
+            index, n_list, p_list = self._step_index(index, n, dev)
+            tr = self._time_range_of(rays, time_range)
+            if out is not None and isinstance(out.raw, torch.Tensor) and int(out.raw.shape[0]) == n and out.raw.device == dev:
+                raw, att, status = out.raw, out.attenuation, out.status
+            else:
+                raw = torch.zeros((n, 8), dtype=torch.float64, device=dev)
+                raw.view(torch.int32)[:, 14] = -1
+                att = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+                status = torch.zeros((n,), dtype=torch.int32, device=dev)
+            _check(lib().tor_bounce_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), p_list, n_list,
+                                           tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(att.data_ptr()),
+                                           C.c_void_p(status.data_ptr()), C.c_void_p(stream)))
+            note = last_note() if n and n_list else "bounce: nothing to do"
+            return BounceResult(raw, raw.view(torch.int32), note, att, status, rays, rng, keep=index)
+        rays = np.array(rays, dtype=np.float64, order="C")
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.bounce: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        st = self._step_states("bounce", rng, n)
+        index, n_list, p_list = self._step_index(index, n)
+        tr = self._time_range_of(rays, time_range)
+        if out is not None and isinstance(out.raw, np.ndarray) and out.raw.shape[0] == n:
+            raw, att, status = out.raw, out.attenuation, out.status
+        else:
+            raw = np.zeros((n, 8), dtype=np.float64)
+            raw.view(np.int32)[:, 14] = -1
+            att, status = np.zeros((n, 3), dtype=np.float64), np.zeros((n,), dtype=np.int32)
+        _check(lib().tor_bounce_host(self._h, n, C.c_void_p(rays.ctypes.data), C.c_void_p(st.ctypes.data), p_list, n_list,
+                                     tr[0], tr[1], m, C.c_void_p(raw.ctypes.data), C.c_void_p(att.ctypes.data),
+                                     C.c_void_p(status.ctypes.data)))
+        note = last_note() if n and n_list else "bounce: nothing to do"
+        return BounceResult(raw, raw.view(np.int32), note, att, status, rays, st)
+
+    def scatter(self, rays, hits, rng, index=None, out=None) -> "BounceResult":
+        """rec.material.scatter(r_in, rec, rng, attenuation, scattered) (materials.nim:21-96) for the caller's hit records, bit for
+        bit (tor_scatter_device / tor_scatter_host): the second half of bounce().  hits: a HitResult / BounceResult or its (n, 8)
+        raw records -- the material of `object`, and p, normal, front_face as given (a host may have perturbed the normal); an
+        object outside the scene counts as a miss.  rays, rng, index, out and the result as for bounce() (the result's hit
+        fields are the caller's records); bounce() equals hit() followed by scatter()."""
+        raw = hits.raw if hasattr(hits, "raw") else hits
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            rays, rng, dev, stream = self._step_tensors("scatter", rays, rng)
+            n = int(rays.shape[0])
+            if not isinstance(raw, torch.Tensor) or raw.dtype != torch.float64 or tuple(raw.shape) != (n, 8) or raw.device != dev:
+                raise ValueError("Context.scatter: with tensor rays, hits must be (n, 8) float64 records on the rays' device")
+            raw = raw.contiguous()
+            index, n_list, p_list = self._step_index(index, n, dev)
+            if out is not None and isinstance(out.status, torch.Tensor) and int(out.status.shape[0]) == n and out.status.device == dev:
+                att, status = out.attenuation, out.status
+            else:
+                att = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+                status = torch.zeros((n,), dtype=torch.int32, device=dev)
+            _check(lib().tor_scatter_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(raw.data_ptr()), C.c_void_p(rng.data_ptr()),
+                                            p_list, n_list, C.c_void_p(att.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)))
+            return BounceResult(raw, raw.view(torch.int32), "scatter", att, status, rays, rng, keep=index)
+        rays = np.array(rays, dtype=np.float64, order="C")
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.scatter: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        if raw.shape != (n, 8):
+            raise ValueError("Context.scatter: hits must be (n, 8) records")
+        st = self._step_states("scatter", rng, n)
+        index, n_list, p_list = self._step_index(index, n)
+        if out is not None and isinstance(out.status, np.ndarray) and out.status.shape[0] == n:
+            att, status = out.attenuation, out.status
+        else:
+            att, status = np.zeros((n, 3), dtype=np.float64), np.zeros((n,), dtype=np.int32)
+        _check(lib().tor_scatter_host(self._h, n, C.c_void_p(rays.ctypes.data), C.c_void_p(raw.ctypes.data), C.c_void_p(st.ctypes.data),
+                                      p_list, n_list, C.c_void_p(att.ctypes.data), C.c_void_p(status.ctypes.data)))
+        return BounceResult(raw, raw.view(np.int32), "scatter", att, status, rays, st)
+
+    def sky(self, rays, index=None, out=None):
+        """The reference's sky (render.nim:41-44) without the attenuation for the listed rays (tor_sky_device): (n, 3) float64,
+        (1 - t) * white + t * (0.5, 0.7, 1.0) with t = 0.5 * unit(direction).y + 1.0 (sic); rays that are not listed keep what
+        `out` holds (a new array: 0).  CUDA tensors zero-copy on torch's current stream; numpy goes through the device and back."""
+        import torch
+        as_numpy = not type(rays).__module__.startswith("torch")
+        if as_numpy:
+            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)).to(dev)
+            out = None if out is None else torch.from_numpy(np.ascontiguousarray(out, dtype=np.float64)).to(dev)
+        rays, _, dev, stream = self._step_tensors("sky", rays, None)
+        n = int(rays.shape[0])
+        index, n_list, p_list = self._step_index(index, n, dev)
+        if out is None:
+            out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (n, 3) or out.device != dev or not out.is_contiguous():
+            raise ValueError("Context.sky: out must be a contiguous (n, 3) float64 tensor on the rays' device")
+        _check(lib().tor_sky_device(self._h, n, C.c_void_p(rays.data_ptr()), p_list, n_list, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out.cpu().numpy() if as_numpy else out
+
+    def bounce_select(self, status, index=None):
+        """The entries of `index` (None: every ray) whose status is BOUNCE_SCATTERED, in input order: the next step's list
+        (tor_bounce_select_device, an ordered compaction on the device; blocking).  status: (n,) int32 CUDA tensor; returns an int32
+        CUDA tensor."""
+        import torch
+        if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.dim() != 1 or not status.is_cuda \
+                or not status.is_contiguous():
+            raise ValueError("Context.bounce_select: status must be a contiguous (n,) int32 CUDA tensor")
+        n = int(status.shape[0])
+        index, n_in, p_list = self._step_index(index, n, status.device)
+        lst = torch.empty((max(n_in, 1),), dtype=torch.int32, device=status.device)
+        n_out = C.c_int64(0)
+        _check(lib().tor_bounce_select_device(self._h, n, C.c_void_p(status.data_ptr()), p_list, n_in, C.c_void_p(lst.data_ptr()),
+                                              C.byref(n_out), C.c_void_p(torch.cuda.current_stream(status.device).cuda_stream)))
+        return lst[:int(n_out.value)]
+
+    def trace(self, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None):
+        """A wavefront path tracer on top of bounce(): radiance()'s loop (render.nim:21-47) one step per launch, open where the
+        reference is closed.  att = 1; per step: bounce the live rays; a miss ends with sky * att; with `emission` every hit adds
+        att * emission[object] (before the attenuation is updated); att *= attenuation for the rays that scattered, which stay
+        live, in order; rays still live after max_depth steps are black.  Returns (color (n, 3), rng (n, 4) after the path's last
+        draw, the mode that ran).  With sky, emission and on_bounce all None this is Context.radiance: colours and states, bit
+        for bit.
+
+        sky: None (Context.sky, the reference's gradient) or sky(rays, index) -> (len(index), 3) colours of the listed rays.
+        emission: (n_objects, 3) float64.  on_bounce(step, index, result): called after every step with the list that was
+        stepped (int32 tensor) and its BounceResult (result.rays are the scattered rays) -- the hook for feature buffers.
+        rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the device and come
+        back as numpy.  One time range for all steps: time_range, or the rays' finite times (the library adds 0)."""
+        import torch
+        as_numpy = not type(rays).__module__.startswith("torch")
+        if as_numpy:
+            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)).to(dev)
+            rng = torch.from_numpy(self._step_states("trace", rng, int(rays.shape[0])).view(np.int64)).to(dev)
+        rays, rng, dev, _ = self._step_tensors("trace", rays, rng)
+        n = int(rays.shape[0])
+        tr = self._time_range_of(rays, time_range)
+        work = rays.clone()
+        color = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        att = torch.ones((n, 3), dtype=torch.float64, device=dev)
+        if emission is not None:
+            emission = torch.as_tensor(emission, dtype=torch.float64).to(dev).reshape(-1, 3)
+        skybuf = torch.zeros((n, 3), dtype=torch.float64, device=dev) if sky is None else None
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        res, ran = None, None
+        for step in range(int(max_depth)):
+            if live.numel() == 0:
+                break
+            res = self.bounce(work, rng, live, tr, mode, out=res)
+            ran = ran or res.mode
+            idx = live.long()
+            st = res.status[idx]
+            if sky is None:   # the sky of every stepped ray, kept where it missed: no list of the misses, so no host synchronisation
+                self.sky(work, live, out=skybuf)
+                color[idx] = torch.where((st == BOUNCE_MISS)[:, None], skybuf[idx] * att[idx], color[idx])   # render.nim:45
+            else:
+                miss = idx[st == BOUNCE_MISS]
+                if miss.numel():
+                    color[miss] = torch.as_tensor(sky(work, miss.int()), dtype=torch.float64).to(dev).reshape(-1, 3) * att[miss]
+            if emission is not None:
+                hit = idx[st != BOUNCE_MISS]
+                color[hit] = color[hit] + att[hit] * emission[res.object[hit].long()]
+            if on_bounce is not None:
+                on_bounce(step, live, res)
+            live = self.bounce_select(res.status, live)
+            scat = live.long()
+            att[scat] = att[scat] * res.attenuation[scat]                 # render.nim:35
+        if ran is None:
+            ran = "nothing to do"
+        if as_numpy:
+            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
+        return color, rng, ran
+
+
 def _mode_of(note: str, prefix: str) -> str:
     return note[len(prefix):] if note.startswith(prefix) else note
 
@@ -994,6 +1241,17 @@ class HitResult:
         self.p, self.normal, self.t = raw[:, 0:3], raw[:, 3:6], raw[:, 6]
         self.object, self.front_face = words[:, 14], words[:, 15]
         self.mode = note[len("hit: "):] if note.startswith("hit: ") else note
+
+
+class BounceResult(HitResult):
+    """One path step of Context.bounce / Context.scatter: HitResult's fields (the records of the step's closest hits, or the caller's),
+    attenuation (n, 3) float64, status (n,) int32 (BOUNCE_MISS / BOUNCE_SCATTERED / BOUNCE_ABSORBED), rays (n, 7) and rng (n, 4) as the
+    step left them, and `mode`: "blocks" | "brute force (...)" for a bounce, "scatter" for a scatter."""
+
+    def __init__(self, raw, words, note: str, attenuation, status, rays, rng, keep=None):
+        super().__init__(raw, words, note, keep=keep)
+        self.attenuation, self.status, self.rays, self.rng = attenuation, status, rays, rng
+        self.mode = _mode_of(note, "bounce: ")
 
 
 class Progressive:

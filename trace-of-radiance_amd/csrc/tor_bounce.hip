@@ -1,0 +1,540 @@
+// tor_bounce.hip -- path steps for host integrators (tor_bounce_device / tor_scatter_device / tor_sky_device /
+// tor_bounce_select_device and the blocking _host twins, include/tor_render.h): ONE iteration of radiance()'s loop
+// (render.nim:26-38) -- world.hit(ray, 0.001, +inf, rec), then rec.material.scatter(ray, rec, rng, attenuation, scattered)
+// (materials.nim:21-96) -- per listed ray, the scatter alone for hit records the caller supplies, the sky gradient of
+// render.nim:41-44, and the ordered compaction of the rays that scattered, on gfx950.
+//
+// Exactness.  The closest hit is the hit query's (tor_query.hpp, tor_query_descent.inc: the head of tor_query.hip says why the
+// descent gives the sequential closest_so_far loop's record), and the record is built with hit_kernel's operations, so d_hits is
+// what tor_hit_device writes.  The scatter is tor_shade_scatter.inc, the text radiance_kernel (tor_radiance.hip) includes: the same
+// cold records, helpers, draws and operation order, float64 unfused.  Driven the reference's way -- att = 1; per step att *=
+// attenuation, a miss ends with sky * att, an absorbed ray with black, max_depth steps -- the steps are radiance_kernel's
+// iterations one launch at a time: colours and states equal tor_radiance_device's bit for bit.
+//
+// One ray per lane: every lane does exactly one bounce, so there is no refill queue.  Arrays are indexed by the ray, not by the
+// position in the list; the lanes of entries outside [0, n_rays) and past the end of the list take part in the descent with
+// t_max = 0 (its uniform loops use scalar loads) and touch no memory.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tor_context.hpp"
+#include "tor_device.hpp"
+#include "tor_query.hpp"
+#include "tor_scene.hpp"
+#include "tor_shade.hpp"
+
+static_assert(sizeof(TorRay) == 56 && sizeof(TorHit) == 64 && sizeof(TorRng) == 32, "TorRay / TorHit / TorRng as the kernels index them");
+static_assert(offsetof(TorHit, object) == 56 && offsetof(TorHit, front_face) == 60, "TorHit: object in the low, front_face in the high word of word 7");
+static_assert(sizeof(TorRng) == sizeof(tor::Rng), "TorRng mirrors tor::Rng");
+
+namespace tor {
+namespace {
+
+constexpr int kStepThreads = 256;
+constexpr int kSelTile = 1024;  // entries per 256-thread block of the compaction
+
+struct BParams {
+  QParams q;                 // bounce_kernel: the scene and its boxes (rays, t_range, hits, n_rays unused)
+  double* rays;              // 7 float64 per ray (TorRay): r_in, overwritten by `scattered` on a hit
+  unsigned long long* rng;   // 4 u64 per ray (TorRng), read and written on a hit
+  const int* list;           // the rays to step, or null: entry e is ray e
+  long long n_list, n_rays;
+  double* hits;              // 8 float64 words per ray (TorHit): written by bounce_kernel, read by scatter_kernel
+  double* att;               // 3 float64 per ray: the attenuation
+  int* status;               // TOR_BOUNCE_*
+  const double* obj_cold;    // scatter_kernel: the cold records by ORIGINAL index, 16 float64 per object
+  long long n_objects;
+};
+
+// the ray of list entry `e`, or -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
+__device__ __forceinline__ long long listed_ray(const BParams& P, long long e) {
+  if (e >= P.n_list) return -1;
+  const long long i = P.list ? (long long)P.list[e] : e;
+  return (i >= 0 && i < P.n_rays) ? i : -1;
+}
+
+__device__ __forceinline__ void write_miss(const BParams& P, long long i) {
+  double* a = P.att + 3 * i;
+  a[0] = 0.0; a[1] = 0.0; a[2] = 0.0;
+  P.status[i] = TOR_BOUNCE_MISS;
+}
+
+// `scattered`, the state after the scatter's last draw, the attenuation (0 for an absorbed ray: the reference leaves it unset) and
+// the status of ray i
+__device__ __forceinline__ void write_scatter(const BParams& P, long long i, const QRay& r, const Rng& g, V3 att, bool ended) {
+  double* q = P.rays + 7 * i;
+  q[0] = r.ox; q[1] = r.oy; q[2] = r.oz;
+  q[3] = r.dx; q[4] = r.dy; q[5] = r.dz;
+  q[6] = r.time;
+  unsigned long long* s = P.rng + 4 * i;
+  s[0] = g.s0; s[1] = g.s1; s[2] = g.s2; s[3] = g.s3;
+  double* a = P.att + 3 * i;
+  a[0] = ended ? 0.0 : att.x; a[1] = ended ? 0.0 : att.y; a[2] = ended ? 0.0 : att.z;
+  P.status[i] = ended ? TOR_BOUNCE_ABSORBED : TOR_BOUNCE_SCATTERED;
+}
+
+template <bool BLOCKS>
+__global__ __launch_bounds__(kStepThreads) void bounce_kernel(const BParams P) {
+  const QParams& p = P.q;
+  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  const bool live = i >= 0;
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) {
+    const double* q = P.rays + 7 * i;
+    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+    r.time = q[6];
+    r.t_min = 0.001;  // render.nim:28
+    r.t_max = __builtin_inf();
+  }
+  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
+  QBest b{r.t_max, INT_MAX, -1};
+#include "tor_query_descent.inc"
+  if (!live) return;
+  double* h = P.hits + 8 * i;
+  if (b.slot < 0) {  // miss: the record tor_hit_device writes; ray and state untouched, nothing drawn
+    for (int k = 0; k < 7; ++k) h[k] = 0.0;
+    h[7] = __longlong_as_double((long long)0xffffffffull);
+    write_miss(P, i);
+    return;
+  }
+  // the record, with hit_kernel's operations (tor_query.hip)
+  const double* c = p.cold + 16 * (size_t)b.slot;
+  double cx, cy, cz;
+  centre_at(c, r.time, cx, cy, cz);                                 // moving_spheres.nim:39-44
+  const V3 o = v3(r.ox, r.oy, r.oz), d = v3(r.dx, r.dy, r.dz);
+  const V3 hp = o + d * b.t;                                       // rays.nim:24-25
+  const V3 outward = (hp - v3(cx, cy, cz)) * c[6];                 // spheres.nim:43 (c[6] = 1.0 / radius)
+  const bool front = dot(d, outward) < 0.0;                        // core.nim:47-49
+  const V3 n = front ? outward : -outward;
+  h[0] = hp.x; h[1] = hp.y; h[2] = hp.z;
+  h[3] = n.x; h[4] = n.y; h[5] = n.z;
+  h[6] = b.t;
+  h[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)b.orig));
+  // the scatter
+  const unsigned long long* s = P.rng + 4 * i;
+  Rng g{s[0], s[1], s[2], s[3]};
+  const V3 ud = unit_vector(d);  // materials.nim:40,68
+  V3 att = v3(1.0, 1.0, 1.0);
+  bool ended = false;
+  {
+#include "tor_shade_scatter.inc"
+  }
+  write_scatter(P, i, r, g, att, ended);
+}
+
+// rec.material.scatter for the caller's record: material of hits[i].object, and p, normal, front_face as given
+__global__ __launch_bounds__(kStepThreads) void scatter_kernel(const BParams P) {
+  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  if (i < 0) return;
+  const double* h = P.hits + 8 * i;
+  const unsigned long long w7 = (unsigned long long)__double_as_longlong(h[7]);
+  const long long object = (long long)(int)(unsigned)(w7 & 0xffffffffull);
+  if (object < 0 || object >= P.n_objects) {  // no such object: a miss
+    write_miss(P, i);
+    return;
+  }
+  const bool front = (unsigned)(w7 >> 32) != 0u;
+  const double* c = P.obj_cold + 16 * (size_t)object;
+  const double* q = P.rays + 7 * i;
+  QRay r{};
+  r.time = q[6];
+  const V3 d = v3(q[3], q[4], q[5]);
+  const V3 hp = v3(h[0], h[1], h[2]);
+  const V3 n = v3(h[3], h[4], h[5]);
+  const unsigned long long* s = P.rng + 4 * i;
+  Rng g{s[0], s[1], s[2], s[3]};
+  const V3 ud = unit_vector(d);
+  V3 att = v3(1.0, 1.0, 1.0);
+  bool ended = false;
+  {
+#include "tor_shade_scatter.inc"
+  }
+  write_scatter(P, i, r, g, att, ended);
+}
+
+// render.nim:41-44 without the attenuation (sky()'s product with (1, 1, 1) is exact)
+__global__ __launch_bounds__(kStepThreads) void sky_kernel(const BParams P) {
+  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  if (i < 0) return;
+  const double* q = P.rays + 7 * i;
+  const V3 col = sky(v3(q[3], q[4], q[5]), v3(1.0, 1.0, 1.0));
+  double* a = P.att + 3 * i;
+  a[0] = col.x; a[1] = col.y; a[2] = col.z;
+}
+
+// ---- ordered compaction of the scattered rays, in tiles of kSelTile entries per block: entry b * kSelTile + k * 256 + t ----
+
+__device__ __forceinline__ bool select_keeps(const int* status, const int* list_in, long long n_in, long long n_rays, long long e, int& ray) {
+  if (e >= n_in) return false;
+  const long long i = list_in ? (long long)list_in[e] : e;
+  if (i < 0 || i >= n_rays) return false;
+  ray = (int)i;
+  return status[i] == TOR_BOUNCE_SCATTERED;
+}
+
+// pass 1: block_count[b] = the block's survivors (wave ballots)
+__global__ __launch_bounds__(256) void select_count_kernel(const int* status, const int* list_in, long long n_in, long long n_rays,
+                                                            unsigned* block_count) {
+  __shared__ unsigned s_cnt[4];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  unsigned mine = 0;
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    int ray = 0;
+    const bool keep = select_keeps(status, list_in, n_in, n_rays, (long long)blockIdx.x * kSelTile + k * 256 + threadIdx.x, ray);
+    mine += (unsigned)__popcll(__ballot(keep));
+  }
+  if (lane == 0) s_cnt[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// pass 2 (one block): block_count -> exclusive offsets in place, the total to *n_out
+__global__ __launch_bounds__(1024) void select_scan_kernel(unsigned* block_count, int n_blocks, long long* n_out) {
+  __shared__ unsigned s[1024];
+  const int t = (int)threadIdx.x;
+  const int per = (n_blocks + 1023) / 1024;  // thread t owns blocks [t * per, (t + 1) * per)
+  const int b0 = t * per < n_blocks ? t * per : n_blocks;
+  const int b1 = (b0 + per < n_blocks) ? b0 + per : n_blocks;
+  unsigned sum = 0;
+  for (int b = b0; b < b1; ++b) sum += block_count[b];
+  s[t] = sum;
+  __syncthreads();
+  for (int w = 1; w < 1024; w <<= 1) {  // inclusive Hillis-Steele scan of the 1024 thread totals
+    const unsigned v = t >= w ? s[t - w] : 0u;
+    __syncthreads();
+    s[t] += v;
+    __syncthreads();
+  }
+  unsigned run = s[t] - sum;
+  for (int b = b0; b < b1; ++b) {
+    const unsigned c = block_count[b];
+    block_count[b] = run;
+    run += c;
+  }
+  if (t == 1023) *n_out = (long long)s[1023];
+}
+
+// pass 3: the survivors to list_out at their block's offset + their rank inside the block, in input order
+__global__ __launch_bounds__(256) void select_scatter_kernel(const int* status, const int* list_in, long long n_in, long long n_rays,
+                                                              const unsigned* block_offset, int* list_out) {
+  __shared__ unsigned s_cnt[kSelTile / 256][4];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  unsigned long long masks[kSelTile / 256];
+  int rays[kSelTile / 256];
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    rays[k] = 0;
+    masks[k] = __ballot(select_keeps(status, list_in, n_in, n_rays, (long long)blockIdx.x * kSelTile + k * 256 + threadIdx.x, rays[k]));
+    if (lane == 0) s_cnt[k][wave] = (unsigned)__popcll(masks[k]);
+  }
+  __syncthreads();
+  unsigned run = block_offset[blockIdx.x];
+  for (int k = 0; k < kSelTile / 256; ++k) {
+    unsigned before = run;
+    for (int w = 0; w < wave; ++w) before += s_cnt[k][w];
+    // (before + rank < the number of survivors <= n_in: list_out holds n_in entries)
+    if ((masks[k] >> lane) & 1ull) list_out[before + (unsigned)__popcll(masks[k] & ((1ull << lane) - 1ull))] = rays[k];
+    run += s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3];
+  }
+}
+
+}  // namespace
+}  // namespace tor
+
+namespace {
+
+constexpr int64_t kMaxItems = (int64_t)0x7fffffff * 256;  // at most 2^31 - 1 workgroups of 256 lanes
+
+// the checks every step shares; none needs a device or reads *ctx
+int list_args(const std::string& w, TorContext* ctx, int64_t n_rays, const void* list, int64_t n_list) {
+  using tor::fail;
+  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
+  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
+  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
+  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
+  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
+  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
+  return TOR_OK;
+}
+
+int bounce_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* rng, const void* list, int64_t n_list,
+                double time_lo, double time_hi, int32_t mode, const void* hits, const void* att, const void* status) {
+  using tor::fail;
+  const std::string w = who;
+  const int rc = list_args(w, ctx, n_rays, list, n_list);
+  if (rc != TOR_OK) return rc;
+  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
+  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
+  if (n_rays > 0 && n_list > 0 && (!rays || !rng || !hits || !att || !status))
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, rng, hits, attenuation or status");
+  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": no scene uploaded");
+  return TOR_OK;
+}
+
+int scatter_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* hits, const void* rng, const void* list,
+                 int64_t n_list, const void* att, const void* status) {
+  using tor::fail;
+  const std::string w = who;
+  const int rc = list_args(w, ctx, n_rays, list, n_list);
+  if (rc != TOR_OK) return rc;
+  if (n_rays > 0 && n_list > 0 && (!rays || !hits || !rng || !att || !status))
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, hits, rng, attenuation or status");
+  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": no scene uploaded");
+  return TOR_OK;
+}
+
+unsigned step_grid(int64_t n_list) { return (unsigned)((n_list + tor::kStepThreads - 1) / tor::kStepThreads); }
+
+int query_done(TorContext* ctx, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  HIP_TRY(hipEventRecord(hq.ev_done, stream));
+  hq.launched = true;
+  hq.stream = (void*)stream;
+  return TOR_OK;
+}
+
+// the launches; the arguments are checked, n_rays > 0 and n_list > 0
+int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays, void* d_rng, const int32_t* d_list, int64_t n_list,
+                  double time_lo, double time_hi, int32_t mode, void* d_hits, double* d_att, int32_t* d_status, hipStream_t stream) {
+  // scattered Metal and Dielectric rays carry time 0: the boxes are built for a range that holds it, as radiance_launch builds
+  // them, so a chain of steps called with one range looks up ONE cached set of block bounds
+  const double lo = time_lo < 0.0 ? time_lo : 0.0, hi = time_hi > 0.0 ? time_hi : 0.0;
+  tor::BParams P{};
+  bool blocks = false;
+  std::string why;
+  const int rc = tor::query_setup(who, ctx, lo, hi, mode, stream, P.q, blocks, why);
+  if (rc != TOR_OK) return rc;
+  P.rays = (double*)d_rays;
+  P.rng = (unsigned long long*)d_rng;
+  P.list = d_list;
+  P.n_list = (long long)n_list;
+  P.n_rays = (long long)n_rays;
+  P.hits = (double*)d_hits;
+  P.att = d_att;
+  P.status = d_status;
+  if (blocks) hipLaunchKernelGGL(tor::bounce_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  else hipLaunchKernelGGL(tor::bounce_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  HIP_TRY(hipGetLastError());
+  const int rd = query_done(ctx, stream);
+  if (rd != TOR_OK) return rd;
+  tor::set_last_note(blocks ? std::string("bounce: blocks")
+                            : std::string("bounce: brute force") + (why.empty() ? std::string() : " (" + why + ")"));
+  return TOR_OK;
+}
+
+// the cold records by ORIGINAL index (scatter_kernel looks the material up by TorHit.object), cached per scene
+int ensure_obj_cold(TorContext* ctx, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
+  if (hq.obj_scene == gen) return TOR_OK;
+  hq.obj_scene = -1;
+  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
+  const int64_t n = ctx->n_objects;
+  std::vector<int64_t> ids((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
+  tor::HostLayout lay;
+  std::string err;
+  if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, lay, err, nullptr))
+    return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_scatter_device: " + err);
+  hq.obj_cold_host.assign((size_t)(n > 0 ? n : 1) * 16, 0.0);
+  for (size_t k = 0; k < lay.n_sorted && n > 0; ++k) {
+    const double* c = &lay.cold[16 * k];
+    if (c[15] == -1.0) continue;  // padding slot
+    int64_t orig;
+    std::memcpy(&orig, &c[14], 8);
+    if (orig >= 0 && orig < n) std::memcpy(&hq.obj_cold_host[16 * (size_t)orig], c, 16 * sizeof(double));
+  }
+  const size_t bytes = hq.obj_cold_host.size() * sizeof(double);
+  HIP_TRY(hq.obj_cold.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(hq.obj_cold.ptr, hq.obj_cold_host.data(), bytes, hipMemcpyHostToDevice, stream));
+  hq.obj_scene = gen;
+  return TOR_OK;
+}
+
+int scatter_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays, const void* d_hits, void* d_rng, const int32_t* d_list,
+                   int64_t n_list, double* d_att, int32_t* d_status, hipStream_t stream) {
+  tor::BParams P{};
+  int rc = tor::query_stream_rule(who, ctx, stream);  // (no layout and no box: the scatter reads the by-object records alone)
+  if (rc != TOR_OK) return rc;
+  rc = ensure_obj_cold(ctx, stream);
+  if (rc != TOR_OK) return rc;
+  P.rays = (double*)d_rays;
+  P.rng = (unsigned long long*)d_rng;
+  P.list = d_list;
+  P.n_list = (long long)n_list;
+  P.n_rays = (long long)n_rays;
+  P.hits = (double*)d_hits;  // (read only)
+  P.att = d_att;
+  P.status = d_status;
+  P.obj_cold = (const double*)ctx->hitq.obj_cold.ptr;
+  P.n_objects = (long long)ctx->n_objects;
+  hipLaunchKernelGGL(tor::scatter_kernel, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  HIP_TRY(hipGetLastError());
+  rc = query_done(ctx, stream);
+  if (rc != TOR_OK) return rc;
+  tor::set_last_note("scatter");
+  return TOR_OK;
+}
+
+// the blocking twins stage every per-ray array of the call in hitq.io, in this order (each padded to 64 bytes)
+struct Staging {
+  size_t off[6], bytes[6], total;
+  Staging(int64_t n_rays, int64_t n_list, bool with_list) {
+    const size_t n = (size_t)n_rays;
+    const size_t want[6] = {n * sizeof(TorRay), n * sizeof(TorRng), with_list ? (size_t)n_list * 4 : 0, n * sizeof(TorHit), n * 24, n * 4};
+    total = 0;
+    for (int k = 0; k < 6; ++k) {
+      off[k] = total;
+      bytes[k] = want[k];
+      total += (want[k] + 63) / 64 * 64;
+    }
+  }
+};
+
+int host_wait(TorContext* ctx) {
+  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
+  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+  if (ctx->hitq.launched) HIP_TRY(hipEventSynchronize(ctx->hitq.ev_done));
+  return TOR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tor_bounce_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
+                      double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_attenuation, int32_t* d_status,
+                      void* hip_stream) {
+  const int rc = bounce_args("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
+                             d_attenuation, d_status);
+  if (rc != TOR_OK) return rc;
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return bounce_launch("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_attenuation,
+                       d_status, (hipStream_t)hip_stream);
+}
+
+int tor_scatter_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, const TorHit* d_hits, TorRng* d_rng, const int32_t* d_list,
+                       int64_t n_list, double* d_attenuation, int32_t* d_status, void* hip_stream) {
+  const int rc = scatter_args("tor_scatter_device", ctx, n_rays, d_rays, d_hits, d_rng, d_list, n_list, d_attenuation, d_status);
+  if (rc != TOR_OK) return rc;
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return scatter_launch("tor_scatter_device", ctx, n_rays, d_rays, d_hits, d_rng, d_list, n_list, d_attenuation, d_status,
+                        (hipStream_t)hip_stream);
+}
+
+int tor_bounce_host(TorContext* ctx, int64_t n_rays, TorRay* rays, TorRng* rng, const int32_t* list, int64_t n_list, double time_lo,
+                    double time_hi, int32_t mode, TorHit* hits, double* attenuation, int32_t* status) {
+  int rc = bounce_args("tor_bounce_host", ctx, n_rays, rays, rng, list, n_list, time_lo, time_hi, mode, hits, attenuation, status);
+  if (rc != TOR_OK) return rc;
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = host_wait(ctx);
+  if (rc != TOR_OK) return rc;
+  // every array in (rays that are not listed keep what the caller holds), the step on the default stream, every output back
+  const Staging st(n_rays, n_list, list != nullptr);
+  HIP_TRY(ctx->hitq.io.ensure(st.total));
+  char* base = (char*)ctx->hitq.io.ptr;
+  void* const host[6] = {rays, rng, (void*)list, hits, attenuation, status};
+  for (int k = 0; k < 6; ++k)
+    if (st.bytes[k]) HIP_TRY(hipMemcpy(base + st.off[k], host[k], st.bytes[k], hipMemcpyHostToDevice));
+  rc = bounce_launch("tor_bounce_host", ctx, n_rays, base + st.off[0], base + st.off[1], list ? (const int32_t*)(base + st.off[2]) : nullptr,
+                     n_list, time_lo, time_hi, mode, base + st.off[3], (double*)(base + st.off[4]), (int32_t*)(base + st.off[5]), nullptr);
+  if (rc != TOR_OK) return rc;
+  for (int k = 0; k < 6; ++k)
+    if (k != 2) HIP_TRY(hipMemcpy(host[k], base + st.off[k], st.bytes[k], hipMemcpyDeviceToHost));
+  return TOR_OK;
+}
+
+int tor_scatter_host(TorContext* ctx, int64_t n_rays, TorRay* rays, const TorHit* hits, TorRng* rng, const int32_t* list, int64_t n_list,
+                     double* attenuation, int32_t* status) {
+  int rc = scatter_args("tor_scatter_host", ctx, n_rays, rays, hits, rng, list, n_list, attenuation, status);
+  if (rc != TOR_OK) return rc;
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = host_wait(ctx);
+  if (rc != TOR_OK) return rc;
+  const Staging st(n_rays, n_list, list != nullptr);
+  HIP_TRY(ctx->hitq.io.ensure(st.total));
+  char* base = (char*)ctx->hitq.io.ptr;
+  void* const host[6] = {rays, rng, (void*)list, (void*)hits, attenuation, status};
+  for (int k = 0; k < 6; ++k)
+    if (st.bytes[k]) HIP_TRY(hipMemcpy(base + st.off[k], host[k], st.bytes[k], hipMemcpyHostToDevice));
+  rc = scatter_launch("tor_scatter_host", ctx, n_rays, base + st.off[0], base + st.off[3], base + st.off[1],
+                      list ? (const int32_t*)(base + st.off[2]) : nullptr, n_list, (double*)(base + st.off[4]), (int32_t*)(base + st.off[5]),
+                      nullptr);
+  if (rc != TOR_OK) return rc;
+  for (int k = 0; k < 6; ++k)
+    if (k != 2 && k != 3) HIP_TRY(hipMemcpy(host[k], base + st.off[k], st.bytes[k], hipMemcpyDeviceToHost));
+  return TOR_OK;
+}
+
+int tor_sky_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const int32_t* d_list, int64_t n_list, double* d_color,
+                   void* hip_stream) {
+  const int rc = list_args("tor_sky_device", ctx, n_rays, d_list, n_list);
+  if (rc != TOR_OK) return rc;
+  if (n_rays > 0 && n_list > 0 && (!d_rays || !d_color)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_sky_device: NULL rays or color");
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  tor::BParams P{};
+  P.rays = (double*)d_rays;  // (read only)
+  P.list = d_list;
+  P.n_list = (long long)n_list;
+  P.n_rays = (long long)n_rays;
+  P.att = d_color;
+  hipLaunchKernelGGL(tor::sky_kernel, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, (hipStream_t)hip_stream, P);
+  HIP_TRY(hipGetLastError());
+  tor::set_last_note("sky");
+  return TOR_OK;
+}
+
+int tor_bounce_select_device(TorContext* ctx, int64_t n_rays, const int32_t* d_status, const int32_t* d_list_in, int64_t n_in,
+                             int32_t* d_list_out, int64_t* n_out, void* hip_stream) {
+  using tor::fail;
+  const std::string w = "tor_bounce_select_device";
+  if (!ctx || !n_out) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx or n_out is NULL");
+  if (n_rays < 0 || n_rays > (int64_t)INT32_MAX) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": need 0 <= n_rays <= 2^31 - 1 (the list holds int32 indices)");
+  if (n_in < 0 || n_in > (int64_t)INT32_MAX) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": need 0 <= n_in <= 2^31 - 1");
+  if (!d_list_in && n_in != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_in must be n_rays");
+  if (n_in > 0 && n_rays > 0 && (!d_status || !d_list_out)) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL status or list_out");
+  if (d_list_out && d_list_out == d_list_in) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": d_list_out must not alias d_list_in");
+  if (n_in == 0 || n_rays == 0) {
+    *n_out = 0;
+    return TOR_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  {  // its scratch belongs to the context: the one-stream rule of the other queries (the call itself ends synchronised)
+    const int rc = tor::query_stream_rule("tor_bounce_select_device", ctx, stream);
+    if (rc != TOR_OK) return rc;
+  }
+  // [0, 16): the survivor count; then one offset per block
+  const int64_t n_blocks = (n_in + tor::kSelTile - 1) / tor::kSelTile;
+  HIP_TRY(ctx->hitq.sel.ensure(16 + (size_t)n_blocks * 4));
+  long long* dn = (long long*)ctx->hitq.sel.ptr;
+  unsigned* block_count = (unsigned*)((char*)ctx->hitq.sel.ptr + 16);
+  hipLaunchKernelGGL(tor::select_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_status, d_list_in, (long long)n_in,
+                     (long long)n_rays, block_count);
+  hipLaunchKernelGGL(tor::select_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, (int)n_blocks, dn);
+  hipLaunchKernelGGL(tor::select_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_status, d_list_in, (long long)n_in,
+                     (long long)n_rays, (const unsigned*)block_count, d_list_out);
+  HIP_TRY(hipGetLastError());
+  long long h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, dn, sizeof(h), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  *n_out = (int64_t)h;
+  tor::set_last_note("bounce select");
+  return TOR_OK;
+}
+
+}  // extern "C"

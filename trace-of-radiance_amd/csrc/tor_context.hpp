@@ -91,7 +91,8 @@ struct DeviceAccel {
 
 struct RcclComm;  // tor_multi.cpp
 
-// State of the closest-hit queries of a context (tor_hit_device / tor_hit_host, tor_query.hip).  Separate from the render path's:
+// State of the queries of a context (closest hits: tor_query.hip, radiance: tor_radiance.hip, path steps: tor_bounce.hip).
+// Separate from the render path's:
 // a query never touches the bounds ring, the counters or the per-launch ring slots.  Freed by its destructor (tor_context_destroy).
 struct HitQueryState {
   DeviceBuffer bnd;                 // block boxes (compute_block_bounds) of the cached (scene, time range)
@@ -104,6 +105,10 @@ struct HitQueryState {
   double a_min = 0.0;
   DeviceBuffer io;                  // tor_hit_host: rays, t ranges and hit records on the device (tor_radiance_host: rays, states, colours)
   DeviceBuffer head;                // tor_radiance_device: the persistent waves' work counter (tor_radiance.hip)
+  DeviceBuffer obj_cold;            // tor_scatter_device: the cold records by ORIGINAL index (tor_bounce.hip), cached per scene ...
+  std::vector<double> obj_cold_host;  // ... their host copy (source of the asynchronous upload) ...
+  int64_t obj_scene = -1;           // ... and the scene generation they were built for, -1 = none
+  DeviceBuffer sel;                 // tor_bounce_select_device: the survivor count and the compaction's block offsets
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch
@@ -217,7 +222,7 @@ struct TorContext {
   int64_t n_stalled_frames = 0;  // frames the host-canvas entry points rendered again because the hand-off stalled
   bool last_migrate = false;  // the last launch carried the hand-off (its kMigStalled word means something)
   int32_t last_variant[5] = {-1, -1, -1, -1, -1};  // {seeding, arith, w, f32, blocks} of the last integrate_kernel launch (tor_debug_last_variant)
-  tor::HitQueryState hitq;  // closest-hit and radiance queries (tor_query.hip, tor_radiance.hip)
+  tor::HitQueryState hitq;  // closest-hit and radiance queries and path steps (tor_query.hip, tor_radiance.hip, tor_bounce.hip)
 };
 
 namespace tor {

@@ -99,6 +99,8 @@ HitQueryState::~HitQueryState() {
   bnd.release();
   io.release();
   head.release();
+  obj_cold.release();
+  sel.release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 

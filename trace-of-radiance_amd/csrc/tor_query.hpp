@@ -144,18 +144,13 @@ void hit_reach(const tor::HostAccel& acc, const std::vector<double>& bnd, tor::H
   hq.a_min = 0x1p-1000 / (r_min * r_min);
 }
 
-// The host side of a query launch on `stream` (the caller has checked its arguments): the one-stream-per-context rule, the layouts
-// and the block bounds cached per (scene, time range), and the scene part of p -- the culling layout's (blocks = true) when mode is
-// not TOR_HIT_BRUTE and the scene has one with finite bounds and a usable margin, else the flat layout's (`why` says why, if mode
-// asked for the blocks).  Used by the hit queries (tor_query.hip) and the radiance queries (tor_radiance.hip).
-int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi, int32_t mode, hipStream_t stream, QParams& p,
-                bool& blocks, std::string& why) {
+// The one-stream-per-context rule of a query launch on `stream` (tor_render.h): neither the context's last render launch nor its
+// last query may still be running on another stream.  Creates the event the launch records when it is done.
+int query_stream_rule(const char* who, TorContext* ctx, hipStream_t stream) {
   using tor::fail;
   using tor::fail_hip;
   const std::string w = who;
   tor::HitQueryState& hq = ctx->hitq;
-  // one stream per context while launches are in flight (tor_render.h): neither the context's last render launch nor its last query
-  // may still be running on another stream
   if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != (void*)stream) {
     const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
     if (q == hipErrorNotReady)
@@ -171,6 +166,22 @@ int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi
     if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
   }
   if (!hq.ev_done) HIP_TRY(hipEventCreateWithFlags(&hq.ev_done, hipEventDisableTiming));
+  return TOR_OK;
+}
+
+// The host side of a query launch on `stream` (the caller has checked its arguments): the one-stream-per-context rule, the layouts
+// and the block bounds cached per (scene, time range), and the scene part of p -- the culling layout's (blocks = true) when mode is
+// not TOR_HIT_BRUTE and the scene has one with finite bounds and a usable margin, else the flat layout's (`why` says why, if mode
+// asked for the blocks).  Used by the hit queries (tor_query.hip), the radiance queries (tor_radiance.hip) and the path steps
+// (tor_bounce.hip).
+int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi, int32_t mode, hipStream_t stream, QParams& p,
+                bool& blocks, std::string& why) {
+  using tor::fail;
+  tor::HitQueryState& hq = ctx->hitq;
+  {
+    const int rc = query_stream_rule(who, ctx, stream);
+    if (rc != TOR_OK) return rc;
+  }
 
   blocks = false;
   why.clear();

@@ -5,9 +5,10 @@
 // Exactness.  A bounce is world.hit(r, 0.001, +inf, rec): the hit query's exact test, slab test and block / super-box descent
 // (tor_query.hpp, tor_query_descent.inc), whose result is the sequential closest_so_far loop's whatever the visiting order (the
 // head of tor_query.hip).  The shading restates materials.nim:21-96 with tor_device.hpp's helpers, operation for operation and
-// draw for draw, as the integrator's integrate_shade.inc and the CPU oracle's scatter do: the same cold records (1 / radius, the
-// material flags, the host's eta = 1 / ri and Schlick r0 per side), the portable sin/cos and pow5, float64 unfused.  The state a
-// lane writes back is its generator after the path's last draw, so a caller can chain samples on one stream as render.nim:59-67 does.
+// draw for draw (tor_shade_scatter.inc, the one text of the scatter, shared with the path steps of tor_bounce.hip), as the
+// integrator's integrate_shade.inc and the CPU oracle's scatter do: the same cold records (1 / radius, the material flags, the
+// host's eta = 1 / ri and Schlick r0 per side), the portable sin/cos and pow5, float64 unfused.  The state a lane writes back is its
+// generator after the path's last draw, so a caller can chain samples on one stream as render.nim:59-67 does.
 //
 // Persistent waves with refill.  Paths end after 1 .. max_depth bounces (random_scene averages 2.6 queries per path).  A lane whose
 // path ended writes its colour and state and takes the next ray index of its wave's batch; a wave takes 64 indices per atomicAdd on
@@ -25,6 +26,7 @@
 #include "tor_context.hpp"
 #include "tor_device.hpp"
 #include "tor_query.hpp"
+#include "tor_shade.hpp"
 
 static_assert(sizeof(TorRng) == 32 && offsetof(TorRng, s1) == 8 && offsetof(TorRng, s2) == 16 && offsetof(TorRng, s3) == 24,
               "TorRng: Rng (support/rng.nim:18-19)");
@@ -46,11 +48,6 @@ struct RParams {
   long long n_rays;
   int max_depth;             // >= 1 (max_depth 0 never launches)
 };
-
-__device__ __forceinline__ void set_ray(QRay& r, V3 o, V3 d) {
-  r.ox = o.x; r.oy = o.y; r.oz = o.z;
-  r.dx = d.x; r.dy = d.y; r.dz = d.z;
-}
 
 template <bool BLOCKS>
 __global__ __launch_bounds__(kRadThreads) __attribute__((amdgpu_waves_per_eu(4))) void radiance_kernel(const RParams P) {
@@ -128,35 +125,7 @@ __global__ __launch_bounds__(kRadThreads) __attribute__((amdgpu_waves_per_eu(4))
       const V3 outward = (hp - v3(cx, cy, cz)) * c[6];                 // spheres.nim:43 (c[6] = 1.0 / radius)
       const bool front = dot(d, outward) < 0.0;                        // core.nim:47-49
       const V3 n = front ? outward : -outward;
-      const int flags = (int)__double_as_longlong(c[13]);
-      const int mat = (flags >> 8) & 0xff;
-      const V3 albedo = v3(c[9], c[10], c[11]);
-      if (mat == kLambertian) {  // materials.nim:24-30: the scattered ray keeps r_in.time
-        set_ray(r, hp, n + random_unit_vector(g));
-        att = mul_att(att, albedo);  // render.nim:35
-      } else if (mat == kMetal) {  // materials.nim:39-47
-        const V3 nd = reflect(ud, n) + random_in_unit_sphere(g) * c[12];
-        set_ray(r, hp, nd);
-        r.time = 0.0;  // rays.nim:19 default
-        if (dot(nd, n) > 0.0) att = mul_att(att, albedo);
-        else ended = true;  // render.nim:38: absorbed -> black
-      } else {  // materials.nim:62-86
-        const double eta = front ? c[9] : c[12];  // 1.0 / ri : ri (tor_scene.cpp fill_material)
-        const double dn = dot(-ud, n);
-        const double cos_theta = (dn <= 1.0) ? dn : 1.0;
-        const double sin_theta = __builtin_sqrt(1.0 - cos_theta * cos_theta);
-        V3 nd;
-        if (eta * sin_theta > 1.0) {
-          nd = reflect(ud, n);
-        } else {
-          const double reflect_prob = schlick_r0(cos_theta, front ? c[10] : c[11]);
-          if (uniform01(g) < reflect_prob) nd = reflect(ud, n);
-          else nd = refract(ud, n, eta);
-        }
-        set_ray(r, hp, nd);
-        r.time = 0.0;
-        // (the attenuation (1, 1, 1): x * 1.0 == x, the product is not formed)
-      }
+#include "tor_shade_scatter.inc"
       if (!ended) {
         depth += 1;
         if (depth >= P.max_depth) ended = true;  // render.nim:25,47: loop exhausted -> black
