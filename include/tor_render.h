@@ -317,6 +317,46 @@ TOR_API int tor_resolve_device(TorContext* ctx, const double* d_sums, int64_t n_
 TOR_API int tor_accum_noise_device(TorContext* ctx, const double* d_sums, const double* d_moments, int64_t npix,
                                    int64_t total_samples, double* d_err, double out[2], void* hip_stream);
 
+/* ---- resumable rendering on the reference's per-pixel streams (TOR_SEED_PIXEL only) -------------------------------------
+ * render.nim:59-67 gives every pixel ONE generator, seeded from (row, col), draws the pixel's spp samples from it one after
+ * the other and sums them in float64 in that order.  The first k samples do not depend on spp (it only enters Canvas.draw's
+ * final scale), so a pixel that has run k samples and kept {generator state, raw sum} IS the reference's pixel at k spp and
+ * goes on being the reference's pixel at any n > k.  tor_render_resume_device makes that state three caller-owned DEVICE
+ * buffers in the shard's compact row layout of tor_render_device (shard_index / shard_count / row_tile work as there):
+ *   d_rng      one TorRng per pixel: the state the reference's `var Rng` of that pixel has after the samples run so far
+ *   d_sums     3 float64 per pixel: the RAW sequential sum ((0 + c0) + c1) + ... of render.nim:67 -- not quantised, not scaled
+ *   d_moments  (nullable) 3 float64 per pixel: the sequential float64 sum of c * c per channel (one rounding for the
+ *              product, one for the add, nothing fused) -- the input of tor_accum_noise_device, whose formula only needs
+ *              S, M and N and serves this mode as it is
+ * first_sample == 0 STARTS the pixels: the kernel seeds seed2(row, col) itself and starts the sums at 0 -- none of the three
+ * buffers is read, none needs clearing.  first_sample > 0 CONTINUES them: every pixel loads its state and sums, runs
+ * n_samples more samples of the same stream and stores both back.  The library cannot check that the buffers really hold
+ * first_sample samples of this camera, scene and size: a caller that passes anything else gets a different image, not an error.
+ * After any sequence of calls that covers [0, n), d_sums holds the same bits as the raw sums of a one-shot tor_render_device
+ * with samples_per_pixel = n before its finalize, and tor_resolve_device(d_sums, ..., total_samples = n, gamma) gives that
+ * call's canvas bit for bit (it performs Canvas.draw's operations, canvas.nim:47-54).
+ * No draw is ever skipped: with max_depth <= 0 and with an empty scene the reference still draws the pixel jitter and the
+ * camera's lens and time samples of every sample (render.nim:63-65, cameras.nim:47-57), the states advance exactly so, and
+ * an empty scene's sky colours depend on them.  (tor_render_accumulate_device may leave its buffers untouched in those cases
+ * because its streams are stateless; this entry never does.)
+ * Every accel value and every pixel_kernel value is accepted and gives the same bits.  LANE runs the one-lane-per-pixel kernel
+ * (tor_debug_last_variant: seeding 5, or 6 with d_moments), WAVE the one-wave-per-pixel kernel; AUTO picks as tor_render_device
+ * does from the pass's n_samples (cost probe and tile order from 32 samples per pass, shared frames, wave kernel on small
+ * frames) with ONE exception: a resume pass never uses the chain hand-off.  A stalled hand-off launch leaves holes
+ * (tor_context_handoff_stalled); here the state lives in place, so the holes would be pixels still at first_sample next to
+ * pixels already at first_sample + n_samples, and the pass could not be repeated.  Frames that tor_render_device would hand
+ * off are shared between the two kernels instead (tor_debug_last_split_tiles says how) or run one lane per pixel; tor_context_handoff_stalled therefore
+ * always reports 0 after this entry and no re-render rule applies to it.
+ * Asynchronous on hip_stream, with the one-stream-per-context rule of the other render entries; tor_last_kernel_ms and the
+ * stats calls report this launch.  TOR_ERR_INVALID_ARGUMENT, nothing written: opt->seeding != TOR_SEED_PIXEL (sample streams:
+ * tor_render_accumulate_device), first_sample < 0, n_samples < 1, first_sample + n_samples > 2^17 (131072 -- NOT an exactness
+ * bound here: it is the range tor_resolve_device and tor_accum_noise_device accept, so that both serve this mode unchanged),
+ * NULL d_rng / d_sums, nrows < 2 or ncols < 2, a context without a scene upload. */
+struct TorRng;  /* defined with the radiance queries below: Rng -- support/rng.nim:18-19, 4 x uint64 */
+TOR_API int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                                     int32_t first_sample, int32_t n_samples, int64_t max_depth, const TorOptions* opt,
+                                     struct TorRng* d_rng, double* d_sums, double* d_moments, void* hip_stream);
+
 /* ---- adaptive sampling (TOR_SEED_SAMPLE only): samples where the noise is ------------------------------------------------
  * An adaptive render is a sequence of passes over a shrinking ACTIVE LIST of pixels.  Every listed pixel holds exactly N samples
  * [0, N) before a pass and receives the same range [N, N + k); a select then tests each listed pixel at N + k samples, records
@@ -641,11 +681,16 @@ TOR_API int tor_debug_accel_layout(TorHittableList world, double t_lo, double t_
                                    int32_t* two_level_out);
 
 /* The integrate_kernel variant that the context's last render launch chose (tor_render_device, tor_render_accumulate_device,
- * tor_render_accumulate_list_device, ...): out = {seeding, arith, w, f32, blocks} -- seeding 0 | 1 | 3 (sample streams + second
- * moments) | 4 (... over a pixel list); arith 0, or 2 behind the FMA screen; w = 2 (256 VGPRs) or 3 (168 VGPRs); f32 0 | 1; blocks
+ * tor_render_accumulate_list_device, tor_render_resume_device, ...): out = {seeding, arith, w, f32, blocks} -- seeding 0 | 1 | 3
+ * (sample streams + second moments) | 4 (... over a pixel list) | 5 (resumable pixel streams) | 6 (... + second moments); arith 0, or 2 behind the FMA screen; w = 2 (256 VGPRs) or 3 (168 VGPRs); f32 0 | 1; blocks
  * 0 | 1 | 2 (two-level layout).  All -1 until the context has launched one; a launch that traces nothing (an empty list) or runs
  * the wave-per-pixel kernel leaves it as it was.  Host only, no synchronisation. */
 TOR_API int tor_debug_last_variant(TorContext* ctx, int32_t out[5]);
+/* Split mode of the context's last render launch (TOR_SEED_PIXEL, TOR_PIXEL_KERNEL_AUTO: the frame shared between the lane kernel and
+ * the wave-per-pixel kernel on a second stream): *tiles_out = the number of 64-pixel tiles, most expensive first by the probe's
+ * count, that the wave-per-pixel kernel rendered; 0 when the launch ran one kernel for the whole frame.  Blocks until that launch
+ * has finished. */
+TOR_API int tor_debug_last_split_tiles(TorContext* ctx, int64_t* tiles_out);
 
 /* TOR_ACCEL_F32 over a whole scene on the HOST: builds the layout tor_scene_upload builds and walks its float32
  * segments for each ray (origin o, direction d, time) exactly as the kernel does.

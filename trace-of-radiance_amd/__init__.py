@@ -158,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
     "tor_hit_device", "tor_hit_host", "tor_radiance_device", "tor_radiance_host", "tor_camera_rays_device",
     "tor_bounce_device", "tor_bounce_host", "tor_scatter_device", "tor_scatter_host", "tor_sky_device", "tor_bounce_select_device",
+    "tor_render_resume_device", "tor_debug_last_split_tiles",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
@@ -308,6 +309,10 @@ def lib():
         _bind_radiance(L)
     if hasattr(L, "tor_bounce_device"):  # (... and one older than the path steps)
         _bind_bounce(L)
+    if hasattr(L, "tor_render_resume_device"):  # (... and one older than resumable pixel streams)
+        L.tor_render_resume_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                               C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tor_debug_last_split_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -713,6 +718,16 @@ class Context:
                                                   C.byref(options), C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr),
                                                   C.c_void_p(stream_ptr)))
 
+    def resume_device(self, cam: Camera, nrows: int, ncols: int, first_sample: int, n_samples: int, max_depth: int,
+                      options: Options, d_rng_ptr: int, d_sums_ptr: int, d_moments_ptr: int = 0, stream_ptr: int = 0):
+        """Runs samples [first_sample, first_sample + n_samples) of every pixel's own stream (TOR_SEED_PIXEL only): first_sample == 0
+        seeds the pixels and starts the sums, > 0 continues from the generator states at d_rng_ptr (one TorRng per pixel) and the raw
+        sequential sums at d_sums_ptr (and the sums of c * c at d_moments_ptr, 0 = none); all three are stored back.  Asynchronous on
+        the given hipStream_t."""
+        _check(lib().tor_render_resume_device(self._h, C.byref(cam), nrows, ncols, first_sample, n_samples, int(max_depth),
+                                              C.byref(options), C.c_void_p(d_rng_ptr), C.c_void_p(d_sums_ptr),
+                                              C.c_void_p(d_moments_ptr), C.c_void_p(stream_ptr)))
+
     def resolve_device(self, d_sums_ptr: int, n_values: int, total_samples: int, gamma: float, d_pixels_ptr: int,
                        stream_ptr: int = 0):
         """pixels = pow(sums / total_samples, 1 / gamma), the sums left as they are.  Asynchronous on the given hipStream_t."""
@@ -854,6 +869,13 @@ class Context:
         out = (C.c_int32 * 5)()
         _check(lib().tor_debug_last_variant(self._h, out))
         return tuple(int(v) for v in out)
+
+    def last_split_tiles(self) -> int:
+        """Tiles of 64 pixels the wave-per-pixel kernel took in the last launch's split mode, 0 when the launch ran one kernel
+        (tor_debug_last_split_tiles).  Blocking."""
+        out = C.c_int64(0)
+        _check(lib().tor_debug_last_split_tiles(self._h, C.byref(out)))
+        return int(out.value)
 
     def last_stats(self) -> Stats:
         st = Stats()
@@ -1264,15 +1286,23 @@ class Progressive:
 
     The context must have the scene uploaded; all device work runs on torch's current stream of the buffers' device."""
 
+    # what a subclass on other streams changes (PixelProgressive): the seeding it needs, its refusal, its default options
+    _SEEDING = SEED_SAMPLE
+    _REFUSAL = ("Progressive: needs TOR_SEED_SAMPLE (TOR_SEED_PIXEL pixels are sequential chains "
+                "on one generator and cannot be resumed)")
+
+    @staticmethod
+    def _default_options() -> Options:
+        return make_options(seeding=SEED_SAMPLE)
+
     def __init__(self, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None = None,
                  moments: bool = False, device=None):
         import torch
         self.ctx, self.nrows, self.ncols, self.max_depth = ctx, int(nrows), int(ncols), int(max_depth)
         self.cam = Camera.from_buffer_copy(cam)
-        self.options = Options.from_buffer_copy(options if options is not None else make_options(seeding=SEED_SAMPLE))
-        if self.options.seeding != SEED_SAMPLE:
-            raise TorError(ERR_INVALID_ARGUMENT, "Progressive: needs TOR_SEED_SAMPLE (TOR_SEED_PIXEL pixels are sequential chains "
-                                                 "on one generator and cannot be resumed)")
+        self.options = Options.from_buffer_copy(options if options is not None else self._default_options())
+        if self.options.seeding != self._SEEDING:
+            raise TorError(ERR_INVALID_ARGUMENT, self._REFUSAL)
         self.rows = len(shard_rows(self.nrows, max(int(self.options.row_tile), 1), int(self.options.shard_index),
                                    max(int(self.options.shard_count), 1)))
         dev = torch.device("cuda") if device is None else torch.device(device)
@@ -1301,7 +1331,7 @@ class Progressive:
     def to_canvas(self, canvas: Canvas) -> Canvas:
         """Fill a host Canvas (whole frame, unsharded options) with image(canvas.gamma_correction), so export_ppm works."""
         if (canvas.nrows, canvas.ncols) != (self.rows, self.ncols):
-            raise TorError(ERR_INVALID_ARGUMENT, "Progressive.to_canvas: the canvas must have this render's rows and columns")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}.to_canvas: the canvas must have this render's rows and columns")
         canvas.pixels[...] = self.image(canvas.gamma_correction).cpu().numpy()
         canvas.samples_per_pixel = self.samples
         return canvas
@@ -1309,7 +1339,7 @@ class Progressive:
     def noise(self):
         """(mean, max) over the pixels of the largest per-channel standard error of the mean, linear units.  Blocking."""
         if self.moments is None:
-            raise TorError(ERR_INVALID_ARGUMENT, "Progressive.noise: created without moments=True")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}.noise: created without moments=True")
         return self.ctx.accum_noise_device(self.sums.data_ptr(), self.moments.data_ptr(), self.rows * self.ncols, self.samples, 0,
                                            self._stream())
 
@@ -1344,6 +1374,70 @@ class Progressive:
 
 
 MAX_ACCUM_SAMPLES = 1 << 17  # exactness bound of the progressive sums (tor_render.h)
+
+
+class PixelProgressive(Progressive):
+    """Progressive's surface on the REFERENCE's streams (TOR_SEED_PIXEL): owns, for this shard's rows, the per-pixel generator
+    states, the raw sequential sums and (moments=True) the sequential sums of c * c.  After any sequence of add() calls totalling
+    n samples, image() is the reference's n-spp canvas -- what a one-shot n-spp render_device(SEED_PIXEL) gives, bit for bit.
+
+        pp = PixelProgressive(ctx, cam, 1080, 1920, 50, moments=True)
+        pp.add(16); preview = pp.image(); pp.render_until(max_se=1e-3, max_samples=4096, pass_samples=128)
+
+    Default options: TOR_SEED_PIXEL with both exact accelerations (tor_render()'s default).  The first add() starts the pixels, so
+    no buffer needs clearing.  The context must have the scene uploaded; device work runs on torch's current stream."""
+
+    _SEEDING = SEED_PIXEL
+    _REFUSAL = ("PixelProgressive: needs TOR_SEED_PIXEL (it continues the reference's per-pixel "
+                "streams); passes of TOR_SEED_SAMPLE streams are Progressive's")
+
+    @staticmethod
+    def _default_options() -> Options:
+        return make_options(seeding=SEED_PIXEL, accel=ACCEL_BLOCKS | ACCEL_F32)
+
+    def __init__(self, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None = None,
+                 moments: bool = False, device=None):
+        import torch
+        super().__init__(ctx, cam, nrows, ncols, max_depth, options, moments, device)
+        # one TorRng per pixel: the four xoshiro256+ words (held as int64 bit patterns; state() hands them out as uint64)
+        self.rng = torch.zeros((self.rows, self.ncols, 4), dtype=torch.int64, device=self.sums.device)
+
+    def add(self, n: int) -> "PixelProgressive":
+        """Run the next n samples of every pixel's stream (asynchronous on the current stream)."""
+        self.ctx.resume_device(self.cam, self.nrows, self.ncols, self.samples, int(n), self.max_depth, self.options,
+                               self.rng.data_ptr(), self.sums.data_ptr(), self.moments.data_ptr() if self.moments is not None else 0,
+                               self._stream())
+        self.samples += int(n)
+        return self
+
+    def state(self) -> dict:
+        """Checkpoint: Progressive.state() plus the per-pixel generator states as a (rows, ncols, 4) uint64 array."""
+        st = super().state()
+        st["rng"] = self.rng.cpu().numpy().view(np.uint64)
+        return st
+
+    @classmethod
+    def from_state(cls, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None,
+                   state: dict, device=None) -> "PixelProgressive":
+        """Resume a checkpoint (state()) on this context -- any process, any GPU with the same scene uploaded."""
+        import torch
+        rng = np.asarray(state.get("rng"))
+        pp = cls(ctx, cam, nrows, ncols, max_depth, options, moments=state.get("moments") is not None, device=device)
+        if rng.dtype != np.uint64 or rng.shape != tuple(pp.rng.shape):
+            raise TorError(ERR_INVALID_ARGUMENT, f"PixelProgressive.from_state: generator states of dtype {rng.dtype}, shape {rng.shape}; "
+                                                 f"expected uint64 {tuple(pp.rng.shape)}")
+        sums = np.ascontiguousarray(state["sums"], dtype=np.float64)
+        if sums.shape != tuple(pp.sums.shape):
+            raise TorError(ERR_INVALID_ARGUMENT, f"PixelProgressive.from_state: sums of shape {sums.shape}, expected {tuple(pp.sums.shape)}")
+        pp.sums.copy_(torch.from_numpy(sums))
+        if pp.moments is not None:
+            mom = np.ascontiguousarray(state["moments"], dtype=np.float64)
+            if mom.shape != tuple(pp.moments.shape):
+                raise TorError(ERR_INVALID_ARGUMENT, f"PixelProgressive.from_state: moments of shape {mom.shape}, expected {tuple(pp.moments.shape)}")
+            pp.moments.copy_(torch.from_numpy(mom))
+        pp.rng.copy_(torch.from_numpy(np.ascontiguousarray(rng).view(np.int64)))
+        pp.samples = int(state["samples"])
+        return pp
 
 
 def adaptive_select_host(sums, moments, pixels, n: int, abs_tol: float, rel_tol: float) -> np.ndarray:

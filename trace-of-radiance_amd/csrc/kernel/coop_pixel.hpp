@@ -55,8 +55,10 @@ __device__ __forceinline__ int wave_min_i32(int v) {
             mn(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
-template <int ARITH>
-__global__ __launch_bounds__(kThreads) void coop_pixel_kernel(const KParams p) {
+// (the body of coop_pixel_kernel and of coop_pixel_resume_kernel below.  RESUME: the pixel starts from / ends in caller-owned
+// state -- KParams.rstate, out, and mom when it is not null -- as integrate_kernel's SEEDING 5 / 6 do: tor_render_resume_device)
+template <int ARITH, bool RESUME>
+__device__ __forceinline__ void coop_pixel_body(const KParams& p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* soa = reinterpret_cast<double*>(smem_raw);
   const int n_pad = p.coop_slots;  // multiple of 64, >= cold slots
@@ -128,6 +130,14 @@ __global__ __launch_bounds__(kThreads) void coop_pixel_kernel(const KParams p) {
     Rng rng;
     seed2(rng, (uint64_t)(int64_t)row, (uint64_t)(int64_t)col);  // render.nim:59-60
     V3 acc = v3(0.0, 0.0, 0.0);
+    V3 mom = v3(0.0, 0.0, 0.0);  // RESUME with KParams.mom: the sequential sums of c * c
+    if (RESUME && p.first_sample > 0) {  // a continued pixel (every lane loads the same words)
+      const unsigned long long* st = p.rstate + (size_t)pl * 4;
+      rng.s0 = st[0]; rng.s1 = st[1]; rng.s2 = st[2]; rng.s3 = st[3];
+      const double* so = p.out + (size_t)pl * 3;
+      acc = v3(so[0], so[1], so[2]);
+      if (p.mom != nullptr) { const double* mo = p.mom + (size_t)pl * 3; mom = v3(mo[0], mo[1], mo[2]); }
+    }
     for (int s = 0; s < p.spp; ++s) {
       // render.nim:64-66
       const double u = ((double)col + uniform01(rng)) / w_div;
@@ -262,9 +272,21 @@ __global__ __launch_bounds__(kThreads) void coop_pixel_kernel(const KParams p) {
         if (absorbed) break;  // render.nim:38
       }
       acc = acc + radiance;  // render.nim:67
+      if (RESUME) mom = v3(mom.x + radiance.x * radiance.x, mom.y + radiance.y * radiance.y, mom.z + radiance.z * radiance.z);  // (two roundings each)
     }
     double* out = p.out + (size_t)pl * 3;  // every lane holds the same sum
     out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
+    if (RESUME) {  // ... and the same state: the stream behind the pass's last sample
+      unsigned long long* st = p.rstate + (size_t)pl * 4;
+      st[0] = rng.s0; st[1] = rng.s1; st[2] = rng.s2; st[3] = rng.s3;
+      if (p.mom != nullptr) { double* mo = p.mom + (size_t)pl * 3; mo[0] = mom.x; mo[1] = mom.y; mo[2] = mom.z; }
+    }
   }
 }
+
+template <int ARITH>
+__global__ __launch_bounds__(kThreads) void coop_pixel_kernel(const KParams p) { coop_pixel_body<ARITH, false>(p); }
+
+// tor_render_resume_device's wave-per-pixel kernel: the same chain walk from / into caller-owned per-pixel state
+__global__ __launch_bounds__(kThreads) void coop_pixel_resume_kernel(const KParams p) { coop_pixel_body<0, true>(p); }
 

@@ -147,10 +147,10 @@
         // (whole pixels per grab where the chunk allows it: a pixel's samples then meet in ONE wave's LDS accumulator
         // and reach HBM in one flush instead of one per wave that touched the pixel -- 5.7x less write traffic at
         // 1000 spp; the tail of the guided schedule shrinks below a pixel and splits it again, which is fine)
-        unsigned grab = (SEEDING == 0) ? p.chunk : next_chunk;
-        if (SEEDING != 0 && grab >= (unsigned)p.spp) grab = TOR_UDIV(grab, p.spp, p.inv_spp) * (unsigned)p.spp;
+        unsigned grab = kPixel ? p.chunk : next_chunk;
+        if (!kPixel && grab >= (unsigned)p.spp) grab = TOR_UDIV(grab, p.spp, p.inv_spp) * (unsigned)p.spp;
         unsigned long long base = 0;
-        if (SEEDING == 0) {
+        if (kPixel) {
           // tiles in chain-length-descending order (tile_order_kernel): the longest chains start first, everybody ends on the cheapest
           // tiles.  (Rounds 2-4 cut the order into two regions and kept the waves of slow hardware slots out of the first; with the
           // screened object loop a bounce costs a slot-2 wave far less than the 177 us that was built against, the cut cost the brute
@@ -168,7 +168,7 @@
         } else {
           w_next = base;
           w_end = (base + grab < p.total_work) ? base + grab : p.total_work;
-          if (SEEDING == 0) {
+          if (kPixel) {
             // work index space = tiles of kTilePixels pixels, optionally in cost order (LPT): the
             // k-th fetch renders tile order[k]
             unsigned tile = (unsigned)(base / kTilePixels);
@@ -196,11 +196,12 @@
         const bool got = need_fetch && prefix < take;
         if (got) {
           unsigned pl;
-          if (SEEDING == 0) {
+          if (kPixel) {
             pl = cur_pl + prefix;
             s = 0;
             if (kAccInLds) { pix_acc[0] = 0.0; pix_acc[64] = 0.0; pix_acc[128] = 0.0; }
             else acc = v3(0, 0, 0);
+            if (kResMom) { pix_mom[0] = 0.0; pix_mom[64] = 0.0; pix_mom[128] = 0.0; }
           } else {  // sample and probe
             const unsigned t = cur_s + prefix;
             const unsigned dp = TOR_UDIV(t, p.spp, p.inv_spp);
@@ -227,13 +228,23 @@
             if (off_shard) pix = -1;  // deposits nothing (tag -1: never flushed)
           }
           have_item = true;
-          if (SEEDING == 0) {
-            seed2(rng, (uint64_t)(int64_t)row, (uint64_t)(int64_t)col);  // render.nim:59-60
+          if (kPixel) {
+            if (kResume && p.first_sample > 0) {
+              // a continued pixel: the state its stream had after first_sample samples and the raw sums so far, once per pixel and pass
+              const unsigned long long* st = p.rstate + (size_t)pl * 4;
+              rng.s0 = st[0]; rng.s1 = st[1]; rng.s2 = st[2]; rng.s3 = st[3];
+              const double* so = p.out + (size_t)pl * 3;
+              if (kAccInLds) { pix_acc[0] = so[0]; pix_acc[64] = so[1]; pix_acc[128] = so[2]; }
+              else acc = v3(so[0], so[1], so[2]);
+              if (kResMom) { const double* mo = p.mom + (size_t)pl * 3; pix_mom[0] = mo[0]; pix_mom[64] = mo[1]; pix_mom[128] = mo[2]; }
+            } else {
+              seed2(rng, (uint64_t)(int64_t)row, (uint64_t)(int64_t)col);  // render.nim:59-60
+            }
             if (kPrio) pix_iters = 0;
           }
         }
         w_next += take;
-        if (SEEDING == 0) {
+        if (kPixel) {
           cur_pl += take;
         } else {
           const unsigned t = cur_s + take;
@@ -244,7 +255,7 @@
       }
     }
     if (!active && have_item) {
-      if (SEEDING != 0) seed3(rng, (uint64_t)row, (uint64_t)col, (uint64_t)((unsigned)p.first_sample + (unsigned)s));  // (progressive passes: the frame's sample index)
+      if (!kPixel) seed3(rng, (uint64_t)row, (uint64_t)col, (uint64_t)((unsigned)p.first_sample + (unsigned)s));  // (progressive passes: the frame's sample index)
       have_item = false;  // the pending sample is consumed by starting its path
       // render.nim:64-66
       const double u = ((double)col + uniform01(rng)) / w_div;

@@ -7,7 +7,11 @@
       // (ARITH 2: the screen's normalised direction IS unit_vector(d) -- d * (1.0 / sqrt(dx*dx + dy*dy + dz*dz)), the same operations
       // on the same ray (vec3s.nim:19-20,93-94,106-107; tor_screen.hpp screen2_ray) -- so the square root and the division run once per bounce)
       const V3 ud_ray = kScreen ? v3(sray.dnx, sray.dny, sray.dnz) : unit_vector(d);
-      if (best_idx < 0) {
+      if (kResume && p.max_depth <= 0) {
+        // render.nim:25: the bounce loop does not run -- the sample is black, and the camera ray's draws (render.nim:63-65,
+        // cameras.nim:47-57) were the sample's only draws (a resume pass must leave the stream where the reference leaves it)
+        ended = true;
+      } else if (best_idx < 0) {
         radiance = sky_unit(ud_ray, get_att());  // render.nim:41-45
         ended = true;
       } else {
@@ -76,13 +80,22 @@
           atomicAdd(p.pixel_cost + (unsigned)pix, (unsigned)path_q);
           path_q = 0;
         }
-        if (SEEDING == 0) {
+        if (kPixel) {
           if (kAccInLds) acc = v3(pix_acc[0], pix_acc[64], pix_acc[128]);
           acc = acc + radiance;  // render.nim:67
+          if (kResMom) {  // the second moments, in sample order: one rounding for the product, one for the sum
+            pix_mom[0] = pix_mom[0] + radiance.x * radiance.x; pix_mom[64] = pix_mom[64] + radiance.y * radiance.y;
+            pix_mom[128] = pix_mom[128] + radiance.z * radiance.z;
+          }
           s += 1;
           if (s >= p.spp) {
             double* out = p.out + (size_t)pix * 3;
             out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
+            if (kResume) {  // the pixel's pass is over: the stream's state behind its last sample (and the moments) go back to the caller
+              unsigned long long* st = p.rstate + (size_t)pix * 4;
+              st[0] = rng.s0; st[1] = rng.s1; st[2] = rng.s2; st[3] = rng.s3;
+              if (kResMom) { double* mo = p.mom + (size_t)pix * 3; mo[0] = pix_mom[0]; mo[1] = pix_mom[64]; mo[2] = pix_mom[128]; }
+            }
           } else {
             if (kAccInLds) { pix_acc[0] = acc.x; pix_acc[64] = acc.y; pix_acc[128] = acc.z; }
             have_item = true;  // next sample of the same pixel, same stream

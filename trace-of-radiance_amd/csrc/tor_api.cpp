@@ -424,6 +424,18 @@ int tor_debug_last_variant(TorContext* ctx, int32_t out[5]) {
   return TOR_OK;
 }
 
+int tor_debug_last_split_tiles(TorContext* ctx, int64_t* tiles_out) {
+  if (!ctx || !tiles_out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_last_split_tiles: NULL argument");
+  *tiles_out = 0;
+  if (!ctx->last_split) return TOR_OK;  // the last launch ran one kernel for the whole frame
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+  unsigned long long w = 0;  // slot word 6: the split point tile_order_kernel chose (tiles of the cost order the wave kernel took)
+  HIP_TRY(hipMemcpy(&w, (unsigned long long*)ctx->counters.ptr + (size_t)ctx->last_slot * TorContext::kSlotWords + 6, sizeof w, hipMemcpyDeviceToHost));
+  *tiles_out = (int64_t)w;
+  return TOR_OK;
+}
+
 int tor_context_scene_counters(TorContext* ctx, int64_t out[3]) {
   if (!ctx || !out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_context_scene_counters: NULL argument");
   out[0] = ctx->n_uploads;
@@ -496,7 +508,8 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
                               int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
                               double* d_pixels, void* hip_stream, const tor::AccumLaunch* acc) {
   const bool listed = acc && acc->list;
-  const std::string who = listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device");
+  const bool resume = acc && acc->rng;  // tor_render_resume_device: a pass on the pixel streams from / into caller-owned state
+  const std::string who = resume ? "tor_render_resume_device" : (listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device"));
   if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
   if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": no scene uploaded");
   // The reference divides by (ncols-1) and (nrows-1) (render.nim:64-65) and by spp
@@ -507,12 +520,15 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   TorOptions o;
   if (!valid_options(opt, o, false)) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": bad TorOptions: " + tor::options_why());
   if (o.device_count > 1) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": one context renders on one device (device lists: tor_render_opt)");
-  if (acc && o.seeding != TOR_SEED_SAMPLE)
+  if (resume && o.seeding != TOR_SEED_PIXEL)
+    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_PIXEL -- it continues the reference's per-pixel streams (render.nim:59-67) from per-pixel "
+                                                "generator states; passes of TOR_SEED_SAMPLE streams are tor_render_accumulate_device's");
+  if (acc && !resume && o.seeding != TOR_SEED_SAMPLE)
     return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
                                                 "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
   // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them, over a pixel list (4)
-  // for adaptive ones
-  const int kseed = listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding);
+  // for adaptive ones; resume passes on the pixel streams run 5, or 6 with second moments
+  const int kseed = resume ? (acc->moments ? 6 : 5) : (listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding));
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipSetDevice(ctx->device));
 
@@ -523,6 +539,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   ctx->timing_valid = false;
   ctx->last_samples = 0;
   ctx->last_migrate = false;
+  ctx->last_split = false;
   if (work_pix == 0) return TOR_OK;
 
   // a ring slot (events, camera, bounds, counters, tile schedule) is reused every kRing launches: its previous
@@ -543,7 +560,9 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   ctx->last_stream_valid = true;
   unsigned long long* const slot_counters = (unsigned long long*)ctx->counters.ptr + (size_t)slot * TorContext::kSlotWords;
   HIP_TRY(hipMemsetAsync(slot_counters, 0, TorContext::kSlotWords * sizeof(unsigned long long), stream));
-  if (max_depth <= 0 || ctx->n_objects < 0) {
+  // (a resume pass takes no shortcut: with max_depth <= 0 the reference still draws every sample's pixel jitter, lens and time
+  // samples -- render.nim:63-65, cameras.nim:47-57 -- and the states must advance exactly so; its kernels end such a sample black)
+  if (!resume && (max_depth <= 0 || ctx->n_objects < 0)) {
     if (acc) return TOR_OK;  // every sample is black: the pass adds zeros, the sums (and moments) stay as they are
     // render.nim:25: the bounce loop does not run -> every sample is black -> pow(0, g) = 0
     HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
@@ -723,7 +742,8 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   // (ADVICE r3).
   bool migrate = false;
   if (o.seeding == TOR_SEED_PIXEL && o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->mig_mode != 0 && o.accel == (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32) &&
-      ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && npix > tor::kTilePixelsHost && !ctx->collect_stats && ctx->n_objects > 0) {
+      ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && npix > tor::kTilePixelsHost && !ctx->collect_stats && ctx->n_objects > 0 &&
+      !resume) {  // (no hand-off for resume passes: a stalled launch would leave some pixels advanced in place and others not -- DESIGN 4.11)
     const int rc = configure_frame();
     if (rc != TOR_OK) return rc;
     const tor::HostAccel& ha = ctx->accel[1];
@@ -750,6 +770,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       wp.n_pixels = (unsigned)npix;
       wp.work_counter = slot_counters;
       wp.out = d_pixels;
+      if (resume) { wp.first_sample = acc->first_sample; wp.mom = acc->moments; wp.rstate = acc->rng; }
       ctx->cam_host[slot] = *cam;
       wp.cam_dev = (const double*)((char*)ctx->cam_ring.ptr + (size_t)slot * sizeof(TorCamera));
       HIP_TRY(hipMemcpyAsync((void*)wp.cam_dev, &ctx->cam_host[slot], sizeof(TorCamera), hipMemcpyHostToDevice, stream));
@@ -763,6 +784,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       ctx->last_slot = slot;
       ctx->timing_valid = true;
       ctx->last_samples = (int64_t)npix * spp;
+      if (resume) return TOR_OK;  // raw sums: tor_resolve_device finalizes
       HIP_TRY(tor::launch_finalize(d_pixels, n_values, 1.0 / (double)spp, 1.0 / (double)gamma_correction, stream));
       return TOR_OK;
     }
@@ -782,6 +804,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   p.first_sample = acc ? acc->first_sample : 0;
   p.mom = acc ? acc->moments : nullptr;
   p.pixel_list = listed ? acc->list : nullptr;
+  p.rstate = resume ? acc->rng : nullptr;
 
   long long waves;
   p.n_pixels = (unsigned)npix;
@@ -955,8 +978,10 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
       ctx->launches += 1;
       ctx->last_slot = slot;
+      ctx->last_split = true;
       ctx->timing_valid = true;
       ctx->last_samples = (int64_t)npix * spp;
+      if (resume) return TOR_OK;  // raw sums: tor_resolve_device finalizes
       HIP_TRY(tor::launch_finalize(d_pixels, n_values, 1.0 / (double)spp, 1.0 / (double)gamma_correction, stream));
       return TOR_OK;
     }
@@ -1015,6 +1040,22 @@ int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t 
                                           "<= 2^17 (131072): beyond that the 2^-36-granular float64 sums are no longer exact");
   if (!ctx || !cam || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_accumulate_device: NULL argument");
   const tor::AccumLaunch acc{first_sample, d_moments};
+  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+}
+
+// ---- resumable rendering on the reference's per-pixel streams (TOR_SEED_PIXEL) -----------------------------------------
+// The first k samples of a pixel do not depend on spp (it only enters Canvas.draw's final scale), so a pixel that has run k samples and
+// kept {generator state, raw sequential sum} IS the reference's pixel at k spp and goes on being the reference's pixel at any n > k.
+// The 2^17 bound is not an exactness bound here (the sums are plain sequential float64 sums in sample order, as render.nim:67 forms
+// them): it is the range tor_resolve_device and tor_accum_noise_device accept, so that both serve this mode unchanged.
+int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols, int32_t first_sample, int32_t n_samples,
+                             int64_t max_depth, const TorOptions* opt, TorRng* d_rng, double* d_sums, double* d_moments, void* hip_stream) {
+  if (first_sample < 0 || n_samples < 1 || (int64_t)first_sample + n_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_resume_device: need first_sample >= 0, n_samples >= 1 and first_sample + n_samples <= 2^17 "
+                                          "(131072): the range tor_resolve_device and tor_accum_noise_device accept");
+  if (!ctx || !cam || !d_rng || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_resume_device: NULL argument");
+  tor::AccumLaunch acc{first_sample, d_moments};
+  acc.rng = (unsigned long long*)d_rng;
   return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
 }
 

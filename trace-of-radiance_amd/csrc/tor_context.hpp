@@ -220,6 +220,7 @@ struct TorContext {
   // the way out when they are not.  The host-canvas entry points then render the frame again without the hand-off.
   double mig_stall_s = 60.0;
   int64_t n_stalled_frames = 0;  // frames the host-canvas entry points rendered again because the hand-off stalled
+  bool last_split = false;    // the last launch shared the frame between the lane and the wave-per-pixel kernel (split mode: tor_debug_last_split_tiles)
   bool last_migrate = false;  // the last launch carried the hand-off (its kMigStalled word means something)
   int32_t last_variant[5] = {-1, -1, -1, -1, -1};  // {seeding, arith, w, f32, blocks} of the last integrate_kernel launch (tor_debug_last_variant)
   tor::HitQueryState hitq;  // closest-hit and radiance queries and path steps (tor_query.hip, tor_radiance.hip, tor_bounce.hip)
@@ -234,6 +235,9 @@ struct AccumLaunch {
   double* moments;
   const int32_t* list = nullptr;  // tor_render_accumulate_list_device: the pixel list (kernel variant SEEDING 4) ...
   int32_t n_list = 0;             // ... and its length
+  // tor_render_resume_device: the per-pixel generator states (4 x u64 per pixel) -- not null turns the pass into a resume pass on the
+  // reference's pixel streams (kernel variants SEEDING 5 / 6, coop_pixel_resume_kernel), the sums then being raw sequential sums
+  unsigned long long* rng = nullptr;
 };
 
 // Options with defaults applied; false when malformed.  `for_drop_in`: NULL options take tor_render()'s

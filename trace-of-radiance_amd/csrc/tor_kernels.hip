@@ -25,6 +25,11 @@
 //       SEEDING 4 (adaptive: SEEDING 3 over a pixel list): work item = list slot-sample; the slot's pixel is
 //                        KParams.pixel_list[slot] (tor_render_accumulate_list_device).
 //     Sample streams are seeded with KParams.first_sample + the launch's sample index (progressive passes).
+//       SEEDING 5 (resume: SEEDING 0 whose pixels start from / end in caller-owned state): a pixel loads {generator state, raw sum}
+//                        when KParams.first_sample > 0 (else seeds and zeroes as SEEDING 0) and stores both after its spp samples
+//                        (tor_render_resume_device; no chain hand-off: DESIGN 4.11).
+//       SEEDING 6 (resume + second moments): SEEDING 5 that also carries the sequential float64 sum of c * c per channel
+//                        (KParams.mom), in LDS between samples.
 //
 //     Objects are wave-uniform inside the hot loop, so their records come through the scalar data
 //     path (s_load into SGPRs, constant-bus operand of the VALU op): no VGPRs, no LDS bandwidth,
@@ -47,6 +52,7 @@
 //
 //   coop_pixel_kernel  TOR_SEED_PIXEL, one WAVE per pixel chain: whole small frames, or -- split mode -- the most
 //                      expensive tiles of a mid-size frame while integrate_kernel renders the rest (DESIGN 4.7 (HISTORY 4.7-4.8)
+//   coop_pixel_resume_kernel  the same chain walk from / into caller-owned per-pixel state (tor_render_resume_device)
 //   tile_order_kernel  counting sort of the SEED_PIXEL tiles by probed cost (LPT schedule) + the split point
 //   gather_rows_kernel multi-GPU assembly: rank-major row shards -> frame in image order
 //   finalize_kernel    canvas.nim:47-54 (draw): pow(sum * 1/spp, 1/gamma)
@@ -159,12 +165,17 @@ constexpr int coop_bytes(int blocks) { return (blocks ? 2 : 1) * kCoopList * 4 +
 constexpr bool sample_variant(int seeding) { return seeding == 1 || seeding == 3 || seeding == 4; }  // per-sample streams, quantised deposit
 constexpr bool moment_variant(int seeding) { return seeding == 3 || seeding == 4; }
 constexpr bool list_variant(int seeding) { return seeding == 4; }  // work over KParams.pixel_list (adaptive sampling)
+constexpr bool pixel_variant(int seeding) { return seeding == 0 || seeding == 5 || seeding == 6; }  // the reference's streams: one sequential chain per pixel
+constexpr bool resume_variant(int seeding) { return seeding == 5 || seeding == 6; }  // ... that starts from and ends in KParams.rstate / out (/ mom)
+constexpr bool resume_moment_variant(int seeding) { return seeding == 6; }
 constexpr bool reservoir_variant(int seeding, int f32, int blocks) { return sample_variant(seeding) && f32 == 0 && blocks == 0; }
 constexpr int kResBytes = 9 * 64 * 8 + 64 + 16;
 // (moment variants: the second-moment cache [kAccSlots][3] f64 at the END of the wave's carve-out, so every other offset stays)
-constexpr int wave_lds_bytes(int blocks, int coop = 0, int res = 0, int mom = 0) {
+// (resume + moments, SEEDING 6: the lanes' running sums of c * c, [3][64] f64, at the END of the carve-out as well -- touched once per
+// sample; as registers they are six more live across the bounce loop)
+constexpr int wave_lds_bytes(int blocks, int coop = 0, int res = 0, int mom = 0, int rmom = 0) {
   return queue_cap(blocks) * 64 * 4 + kAccSlots * 3 * 8 + kAccSlots * 4 + kProfSlots * 8 + (coop ? coop_bytes(blocks) + 64 : 0) + (res ? kResBytes : 0) +
-         (mom ? kAccSlots * 3 * 8 : 0);
+         (mom ? kAccSlots * 3 * 8 : 0) + (rmom ? 3 * 64 * 8 : 0);
 }
 // Which kernel variants resolve cooperatively: TOR_ACCEL_BLOCKS | TOR_ACCEL_F32.  (The code also runs the variants
 // without boxes -- `blocks == 0 || f32 != 0` passes every parity test -- but there the candidates are few (1.25-1.43
@@ -240,15 +251,19 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   // SEED_PIXEL cooperative variants keep the pixel's running sum in LDS too (touched once per sample; as registers it is
   // six of the 168, and the variant spills inside the bounce loop): it takes the upper half of the queue -- 4 entries are
   // enough there, the box hits live in registers -- plus the SAMPLE accumulator cache this seeding does not use
-  constexpr bool kAccInLds = SEEDING == 0 && coop_variant(F32, BLOCKS);
+  constexpr bool kPixel = pixel_variant(SEEDING);    // the reference's per-pixel streams (SEEDING 0, and the resume variants 5 / 6)
+  constexpr bool kResume = resume_variant(SEEDING);
+  constexpr bool kResMom = resume_moment_variant(SEEDING);
+  constexpr bool kAccInLds = kPixel && coop_variant(F32, BLOCKS);
   constexpr int kQLayout = queue_cap(BLOCKS);          // queue entries the LDS layout reserves
   constexpr int kQCap = kAccInLds ? 4 : kQLayout;      // ... and the ones this variant uses
   constexpr int kAccPad = coop_variant(F32, BLOCKS) ? 64 : 0;
   constexpr bool kRes = reservoir_variant(SEEDING, F32, BLOCKS);
   constexpr bool kMom = moment_variant(SEEDING);
   constexpr bool kList = list_variant(SEEDING);
-  constexpr int kWaveLdsBytes = wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes, kMom);
+  constexpr int kWaveLdsBytes = wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes, kMom, kResMom);
   unsigned char* wave_lds = smem_raw + wave * kWaveLdsBytes;
+  double* pix_mom = reinterpret_cast<double*>(wave_lds + wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes, kMom)) + lane;  // [3][64] (kResMom variants)
   double* mom_lds = reinterpret_cast<double*>(wave_lds + wave_lds_bytes(BLOCKS, coop_variant(F32, BLOCKS), kRes));  // [kAccSlots][3] (kMom variants)
   unsigned* q = reinterpret_cast<unsigned*>(wave_lds) + lane;  // q[k * 64]: k-th entry of this lane
   double* acc_lds = reinterpret_cast<double*>(wave_lds + kQLayout * 64 * 4);          // [kAccSlots][3]
@@ -348,11 +363,11 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   const unsigned prio_slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4);  // HW_ID.wave_id: the wave's slot in its SIMD
   unsigned prio_now = 0;
   // a pixel chain is HOT when, extrapolated from its samples so far, it needs more than hot_iters bounce iterations
-  const unsigned hot_iters = (SEEDING == 0 && p.sched != nullptr) ? (unsigned)p.sched[0] : 0u;
+  const unsigned hot_iters = (kPixel && p.sched != nullptr) ? (unsigned)p.sched[0] : 0u;
   unsigned pix_iters = 0;  // bounce iterations the lane has spent on its current pixel
   // arbiter priorities (below): every SEED_PIXEL variant.  (In the cooperative variants the lane's iteration counter was
   // one register too many while the pixel sum still lived in registers: 1-2 % slower then, 1-2 % faster at 100 spp now.)
-  constexpr bool kPrio = SEEDING == 0;
+  constexpr bool kPrio = kPixel;
   bool exhausted = false;
   // ---- chain hand-off (DESIGN 4.7 (HISTORY 4.10)) -------------------------------------------------------------------------------
   // A pixel is a sequential chain of spp samples (render.nim:59-67) and a lane needs ~16 us per bounce of it, so a frame
@@ -757,7 +772,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
 // ---------------------------------------------------------------------------------------
 // host-side launchers (called from tor_api.cpp)
 // ---------------------------------------------------------------------------------------
-// variant table: [seeding 0|1|2|3|4 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only; 4: 3 over a pixel list)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
+// variant table: [seeding 0|1|2|3|4|5|6 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only; 4: 3 over a pixel list; 5: resumable SEED_PIXEL; 6: 5 + second moments)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
 // [blocks 0|1|2 (2: two-level layouts, cooperative variants only)].  The block-expansion code (an unrolled 8-object stage per lane)
 // is what makes the 168-register variants spill; launches without TOR_ACCEL_BLOCKS use kernels compiled without it (no scratch
 // traffic at all).  (Round 5: the 20 TOR_ARITH_FUSED instantiations -- `arith 1`, not the reference's rounding -- are gone.)
@@ -770,10 +785,13 @@ static IntegrateFn integrate_variant(int seeding, int arith, int w, int f32, int
   TOR_V4(2, 0, 3)   // cost probe of the SEED_PIXEL tile schedule
   TOR_V4(3, 0, 2) TOR_V4(3, 0, 3)  // progressive launches that also sum the second moments (tor_render_accumulate_device)
   TOR_V4(4, 0, 2) TOR_V4(4, 0, 3)  // ... over a pixel list (adaptive sampling: tor_render_accumulate_list_device)
+  TOR_V4(5, 0, 2) TOR_V4(5, 0, 3)  // resumable pixel streams (tor_render_resume_device)
+  TOR_V4(6, 0, 2) TOR_V4(6, 0, 3)  // ... with second moments
   // arith 2: the reference's arithmetic behind the conservative FMA screen (brute-force layouts only)
   TOR_V(0, 2, 2, 0, 0) TOR_V(0, 2, 3, 0, 0) TOR_V(1, 2, 2, 0, 0) TOR_V(1, 2, 3, 0, 0) TOR_V(2, 2, 3, 0, 0)
   TOR_V(3, 2, 2, 0, 0) TOR_V(3, 2, 3, 0, 0)
   TOR_V(4, 2, 2, 0, 0) TOR_V(4, 2, 3, 0, 0)
+  TOR_V(5, 2, 2, 0, 0) TOR_V(5, 2, 3, 0, 0) TOR_V(6, 2, 2, 0, 0) TOR_V(6, 2, 3, 0, 0)
   // (round 5: a 128-register build <1, 2, 4, 0, 0> for a 4th workgroup per CU now runs 2.4 x SLOWER -- 1097 against 2613 Msamples/s
   // at configs[1]: stage two's per-lane state spills inside the loops; not built)
   // (a 128-register build of <1, 2, W, 0, 0> for a 4th workgroup per CU was measured in round 4: 1951 against 1961 Msamples/s at
@@ -792,7 +810,7 @@ static int wants_f32(const KParams& p) { return (p.hot32 != nullptr || p.shot32 
 static int wants_blocks(const KParams& p) { return p.bnd != nullptr ? ((p.two_level != 0 && wants_f32(p) != 0) ? 2 : 1) : 0; }
 static size_t dynamic_lds(const KParams& p, int seeding) {
   return (size_t)wave_lds_bytes(wants_blocks(p), coop_variant(wants_f32(p), wants_blocks(p)), reservoir_variant(seeding, wants_f32(p), wants_blocks(p)),
-                                moment_variant(seeding)) * (kThreads / 64) + (size_t)p.shot_lds_doubles * 8 + (size_t)p.shot32_lds_floats * 4 +
+                                moment_variant(seeding), resume_moment_variant(seeding)) * (kThreads / 64) + (size_t)p.shot_lds_doubles * 8 + (size_t)p.shot32_lds_floats * 4 +
          (size_t)p.bnd32_lds_floats * 4 +
          // (the second-form table of stage two: only the ARITH 2 variants -- brute-force layouts behind the screen -- stage it)
          ((p.screen != 0 && wants_f32(p) == 0 && wants_blocks(p) == 0) ? (size_t)p.xrec_lds_doubles * 8 : (size_t)0);
@@ -857,14 +875,14 @@ size_t coop_lds_bytes(int coop_slots) { return (size_t)kCoopArrays * 8 * (size_t
 int coop_blocks_per_cu(const KParams& p, int arith) {
   int n = 0;
   (void)arith;
-  auto fn = coop_pixel_kernel<0>;
+  auto fn = p.rstate != nullptr ? coop_pixel_resume_kernel : coop_pixel_kernel<0>;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kThreads, coop_lds_bytes(p.coop_slots)) != hipSuccess) n = 0;
   return n;
 }
 
 hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream) {
   (void)arith;
-  auto fn = coop_pixel_kernel<0>;
+  auto fn = p.rstate != nullptr ? coop_pixel_resume_kernel : coop_pixel_kernel<0>;
   const size_t lds = coop_lds_bytes(p.coop_slots);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -875,7 +893,7 @@ hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stre
 }
 
 int integrate_fixed_lds_bytes(int blocks, int f32, int seeding) {
-  return wave_lds_bytes(blocks, coop_variant(f32, blocks), reservoir_variant(seeding, f32, blocks), moment_variant(seeding)) * (kThreads / 64);
+  return wave_lds_bytes(blocks, coop_variant(f32, blocks), reservoir_variant(seeding, f32, blocks), moment_variant(seeding), resume_moment_variant(seeding)) * (kThreads / 64);
 }
 
 hipError_t launch_finalize(double* pixels, long long n_values, double scale, double gamma, hipStream_t stream) {

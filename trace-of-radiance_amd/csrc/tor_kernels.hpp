@@ -114,6 +114,11 @@ struct KParams {
   // adaptive sampling (tor_render_accumulate_list_device; SEEDING 4 = SEEDING 3 over a pixel list): work index = list slot x spp + sample,
   // the slot's pixel is pixel_list[slot] (shard-local, in out's layout); an entry >= n_pixels deposits nothing; else null
   const int32_t* pixel_list;
+  // resumable rendering on the pixel streams (tor_render_resume_device; SEEDING 5 / 6 and coop_pixel_resume_kernel): this launch runs
+  // samples [first_sample, first_sample + spp) of every pixel's own stream.  first_sample == 0: the kernel seeds seed2(row, col) and
+  // starts the sums at 0; > 0: it loads {rstate, out[, mom]} of the pixel.  At the end of the pixel's pass it stores the generator
+  // state (4 x u64 per pixel), the RAW sequential sum to out and -- mom != null -- the sequential sum of c * c to mom; else null
+  unsigned long long* rstate;
 };
 
 // Control words of the hand-off, one 128-byte line per access pattern (thousands of waiting servers poll their flags and,
@@ -147,8 +152,8 @@ hipError_t launch_integrate(const KParams& p, int seeding, int arith, int waves_
 int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_per_simd);
 size_t coop_lds_bytes(int coop_slots);
 int coop_blocks_per_cu(const KParams& p, int arith);  // 0: the objects do not fit LDS
-hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream);
-int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir) (+ the moment cache, seeding 3)
+hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream);  // p.rstate != null: coop_pixel_resume_kernel
+int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir) (+ the moment cache, seeding 3) (+ the pixels' moment sums, seeding 6)
 hipError_t launch_probe(const KParams& p, int blocks, hipStream_t stream);
 // schedule of the chain hand-off, computed on the device from the probe's total (tile_order_kernel): l_avg = probed queries x
 // lavg_scale = bounce iterations an average lane runs in this frame; dedicated server workgroups = srv_frac x blocks when a
