@@ -308,7 +308,8 @@ TOR_API int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nro
  * tor_accum_noise_device: from sums S, moments M of total_samples = N >= 2 samples, each channel's standard error of the
  * mean sqrt(max(0, (M - S*S/N) / (N - 1)) / N) in linear (pre-gamma) units; d_err (nullable, npix float64) receives the
  * per-pixel maximum over the three channels, out[0] / out[1] the frame's mean / maximum of it, reduced in a fixed order
- * (repeated calls return the same bits).  Blocking: returns when out is filled. */
+ * (repeated calls return the same bits).  Blocking: returns when out is filled.  (The formula needs S, M and N only: the
+ * raw moments of tor_render_resume_device and tor_render_resume_list_device are served as they are.) */
 TOR_API int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                                          int32_t first_sample, int32_t n_samples, int64_t max_depth,
                                          const TorOptions* opt, double* d_sums, double* d_moments, void* hip_stream);
@@ -367,19 +368,21 @@ TOR_API int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int3
  * tor_render_accumulate_list_device: tor_render_accumulate_device over the n_list pixels of d_list only (DEVICE int32,
  * shard-local indices in d_sums' layout, strictly ascending, unique -- ascending keeps neighbouring pixels in one wave).  Sums
  * AND moments are required.  n_list == 0 is a no-op.  An entry outside the shard deposits nothing.  The same rejections as
- * tor_render_accumulate_device (TOR_SEED_PIXEL, sample ranges, the 2^17 bound), and n_list < 0 or above the shard's pixel
- * count.  Asynchronous on hip_stream.
+ * tor_render_accumulate_device (TOR_SEED_PIXEL -- listed passes on the reference's streams are tor_render_resume_list_device's,
+ * below --, sample ranges, the 2^17 bound), and n_list < 0 or above the shard's pixel count.  Asynchronous on hip_stream.
  *
  * tor_adaptive_select_device: the convergence test at total_samples = n (2 <= n <= 2^17) of every listed pixel.  Per channel
  * c, mean_c = S_c / n and se_c = sqrt(max(0, (M_c - S_c*S_c/n) / (n - 1)) / n) -- tor_accum_noise_device's standard error --
  * each operation one IEEE float64 rounding, nothing fused; the pixel has converged iff se_c <= abs_tol + rel_tol * mean_c for
  * all three channels.  d_counts[p] = n for every listed p (npix int32, the sample map), the unconverged pixels to d_list_out in
  * input order (an ordered compaction: d_list_out must not alias d_list_in), their number to *n_out.  Every entry must be a pixel
- * of d_sums.  abs_tol, rel_tol >= 0, not NaN.  n_in == 0 gives *n_out = 0.  Blocking: returns when *n_out is known.
+ * of d_sums.  abs_tol, rel_tol >= 0, not NaN.  n_in == 0 gives *n_out = 0.  Blocking: returns when *n_out is known.  It reads
+ * S, M and n only, so it serves the raw sums and moments of tor_render_resume_list_device (TOR_SEED_PIXEL) as it is.
  *
  * tor_resolve_counts_device: d_pixels[i] = pow(d_sums[i] / counts[i / 3], 1 / gamma_correction) for npix pixels, computed as
  * (1.0 / counts) * sum -- tor_resolve_device's operations with total_samples = counts[i / 3], so the same bits.  Every count
- * must lie in [1, 2^17].  d_pixels == d_sums resolves in place.  Asynchronous on hip_stream. */
+ * must lie in [1, 2^17].  d_pixels == d_sums resolves in place.  Asynchronous on hip_stream.  On the raw sums of
+ * tor_render_resume_list_device it gives, per pixel, the reference's pixel at counts[p] samples per pixel. */
 TOR_API int tor_render_accumulate_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                                               const int32_t* d_list, int32_t n_list, int32_t first_sample, int32_t n_samples,
                                               int64_t max_depth, const TorOptions* opt, double* d_sums, double* d_moments,
@@ -389,6 +392,34 @@ TOR_API int tor_adaptive_select_device(TorContext* ctx, const double* d_sums, co
                                        int32_t* d_counts, int32_t* n_out, void* hip_stream);
 TOR_API int tor_resolve_counts_device(TorContext* ctx, const double* d_sums, const int32_t* d_counts, int64_t npix,
                                       float gamma_correction, double* d_pixels, void* hip_stream);
+
+/* ---- adaptive sampling on the reference's per-pixel streams (TOR_SEED_PIXEL only) ----------------------------------------
+ * tor_render_resume_list_device: tor_render_resume_device over the n_list pixels of d_list only.  The list rules are
+ * tor_render_accumulate_list_device's: DEVICE int32, shard-local indices in the compact row layout, strictly ascending and
+ * unique; an entry outside the shard is skipped -- nothing read, nothing written, nothing drawn; n_list == 0 is a no-op.
+ * first_sample == 0 STARTS the listed pixels (the kernel seeds seed2(row, col) and zeroes the sums itself; the buffers are not
+ * read for them), first_sample > 0 CONTINUES them from their stored state.  A pixel that is NOT listed keeps every bit of its
+ * d_rng, d_sums and d_moments.  d_rng, d_sums and d_moments are all required (the moments are what the select reads).  No draw
+ * is skipped for max_depth <= 0 or an empty scene, exactly as in tor_render_resume_device.
+ * The guarantee: after passes over lists such that listed pixel p has received exactly the prefix [0, counts[p]) of its stream,
+ * tor_resolve_counts_device(d_sums, d_counts, ...) gives, per pixel, the canvas value of a one-shot tor_render_device with
+ * TOR_SEED_PIXEL and samples_per_pixel = counts[p] -- which is also the CPU oracle's value and the unmodified reference
+ * program's -- bit for bit, for every accel and every pixel_kernel value.  tor_adaptive_select_device, tor_resolve_counts_device
+ * and tor_accum_noise_device serve this mode unchanged.
+ * Kernels: LANE runs the one-lane-per-pixel kernel over tiles of 64 consecutive list slots (tor_debug_last_variant: seeding 7),
+ * WAVE the one-wave-per-pixel kernel with one list slot per work item (LANE when the scene does not fit LDS); AUTO applies
+ * tor_render_device's rule with n_list in place of the pixel count and three quarters of its threshold: the wave kernel up to
+ * 3/4 x TOR_COOP_MAX_PIXELS (86 016) listed pixels, the lane kernel above (measured: DESIGN 4.12).  A listed pass runs no cost
+ * probe, no tile ordering and no split mode (tor_debug_last_split_tiles gives 0) and, like every resume pass, no chain hand-off:
+ * tor_context_handoff_stalled reports 0 afterwards.
+ * Asynchronous on hip_stream, with the one-stream-per-context rule of the other render entries (a pass on a second stream while
+ * one is in flight is refused before any state moves); tor_last_kernel_ms and the stats calls report this launch.
+ * TOR_ERR_INVALID_ARGUMENT, nothing written: everything tor_render_resume_device rejects, NULL d_list with n_list > 0, NULL
+ * d_moments, n_list < 0 or above the shard's pixel count. */
+TOR_API int tor_render_resume_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
+                                          const int32_t* d_list, int32_t n_list, int32_t first_sample, int32_t n_samples,
+                                          int64_t max_depth, const TorOptions* opt, struct TorRng* d_rng, double* d_sums,
+                                          double* d_moments, void* hip_stream);
 
 /* ---- closest-hit queries: `hit()` of the uploaded list for the caller's rays ---------------------------------------------
  * Every Hittable provides hit(r, t_min, t_max, rec) (physics/core.nim:38-42); these entries answer batches of rays with the uploaded
@@ -681,8 +712,8 @@ TOR_API int tor_debug_accel_layout(TorHittableList world, double t_lo, double t_
                                    int32_t* two_level_out);
 
 /* The integrate_kernel variant that the context's last render launch chose (tor_render_device, tor_render_accumulate_device,
- * tor_render_accumulate_list_device, tor_render_resume_device, ...): out = {seeding, arith, w, f32, blocks} -- seeding 0 | 1 | 3
- * (sample streams + second moments) | 4 (... over a pixel list) | 5 (resumable pixel streams) | 6 (... + second moments); arith 0, or 2 behind the FMA screen; w = 2 (256 VGPRs) or 3 (168 VGPRs); f32 0 | 1; blocks
+ * tor_render_accumulate_list_device, tor_render_resume_device, tor_render_resume_list_device, ...): out = {seeding, arith, w, f32, blocks} -- seeding 0 | 1 | 3
+ * (sample streams + second moments) | 4 (... over a pixel list) | 5 (resumable pixel streams) | 6 (... + second moments) | 7 (... over a pixel list); arith 0, or 2 behind the FMA screen; w = 2 (256 VGPRs) or 3 (168 VGPRs); f32 0 | 1; blocks
  * 0 | 1 | 2 (two-level layout).  All -1 until the context has launched one; a launch that traces nothing (an empty list) or runs
  * the wave-per-pixel kernel leaves it as it was.  Host only, no synchronisation. */
 TOR_API int tor_debug_last_variant(TorContext* ctx, int32_t out[5]);

@@ -158,7 +158,7 @@ EXPORTED_SYMBOLS = [
     "tor_render_accumulate_list_device", "tor_adaptive_select_device", "tor_resolve_counts_device", "tor_debug_last_variant",
     "tor_hit_device", "tor_hit_host", "tor_radiance_device", "tor_radiance_host", "tor_camera_rays_device",
     "tor_bounce_device", "tor_bounce_host", "tor_scatter_device", "tor_scatter_host", "tor_sky_device", "tor_bounce_select_device",
-    "tor_render_resume_device", "tor_debug_last_split_tiles",
+    "tor_render_resume_device", "tor_debug_last_split_tiles", "tor_render_resume_list_device",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
@@ -313,6 +313,9 @@ def lib():
         L.tor_render_resume_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                                C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.tor_debug_last_split_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(L, "tor_render_resume_list_device"):  # (... and one older than adaptive sampling on the pixel streams)
+        L.tor_render_resume_list_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -750,6 +753,16 @@ class Context:
         _check(lib().tor_render_accumulate_list_device(self._h, C.byref(cam), nrows, ncols, C.c_void_p(d_list_ptr), int(n_list),
                                                        int(first_sample), int(n_samples), int(max_depth), C.byref(options),
                                                        C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr), C.c_void_p(stream_ptr)))
+
+    def resume_list_device(self, cam: Camera, nrows: int, ncols: int, d_list_ptr: int, n_list: int, first_sample: int, n_samples: int,
+                           max_depth: int, options: Options, d_rng_ptr: int, d_sums_ptr: int, d_moments_ptr: int, stream_ptr: int = 0):
+        """resume_device over the n_list pixels of the device int32 list at d_list_ptr (shard-local, strictly ascending, unique):
+        generator states, sums and moments all required; a pixel that is not listed keeps every bit of the three.  TOR_SEED_PIXEL
+        only.  Asynchronous on the given hipStream_t."""
+        _check(lib().tor_render_resume_list_device(self._h, C.byref(cam), nrows, ncols, C.c_void_p(d_list_ptr), int(n_list),
+                                                   int(first_sample), int(n_samples), int(max_depth), C.byref(options),
+                                                   C.c_void_p(d_rng_ptr), C.c_void_p(d_sums_ptr), C.c_void_p(d_moments_ptr),
+                                                   C.c_void_p(stream_ptr)))
 
     def adaptive_select_device(self, d_sums_ptr: int, d_moments_ptr: int, d_list_in_ptr: int, n_in: int, total_samples: int,
                                abs_tol: float, rel_tol: float, d_list_out_ptr: int, d_counts_ptr: int, stream_ptr: int = 0) -> int:
@@ -1466,22 +1479,30 @@ class Adaptive:
 
     The context must have the scene uploaded; all device work runs on torch's current stream of the buffers' device."""
 
+    # what a subclass on other streams changes (PixelAdaptive): the seeding it needs, its refusal, its default options, its pass
+    _SEEDING = SEED_SAMPLE
+    _REFUSAL = ("Adaptive: needs TOR_SEED_SAMPLE (adaptive sampling on the reference's TOR_SEED_PIXEL streams "
+                "is PixelAdaptive's)")
+
+    @staticmethod
+    def _default_options() -> Options:
+        return make_options(seeding=SEED_SAMPLE)
+
     def __init__(self, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None = None,
                  abs_tol: float = 0.0, rel_tol: float = 0.05, min_samples: int = 16, pass_samples: int = 16, max_samples: int = 4096,
                  device=None):
         self.ctx, self.nrows, self.ncols, self.max_depth = ctx, int(nrows), int(ncols), int(max_depth)
         self.cam = Camera.from_buffer_copy(cam)
-        self.options = Options.from_buffer_copy(options if options is not None else make_options(seeding=SEED_SAMPLE))
-        if self.options.seeding != SEED_SAMPLE:
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: needs TOR_SEED_SAMPLE (TOR_SEED_PIXEL pixels are sequential chains "
-                                                 "on one generator and cannot be resumed)")
+        self.options = Options.from_buffer_copy(options if options is not None else self._default_options())
+        if self.options.seeding != self._SEEDING:
+            raise TorError(ERR_INVALID_ARGUMENT, self._REFUSAL)
         self.abs_tol, self.rel_tol = float(abs_tol), float(rel_tol)
         if not (self.abs_tol >= 0.0 and self.rel_tol >= 0.0):
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: abs_tol and rel_tol must be >= 0 (and not NaN)")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}: abs_tol and rel_tol must be >= 0 (and not NaN)")
         self.min_samples, self.pass_samples, self.max_samples = int(min_samples), int(pass_samples), int(max_samples)
         if self.min_samples < 2 or self.pass_samples < 1 or not 1 <= self.max_samples <= MAX_ACCUM_SAMPLES:
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive: need min_samples >= 2 (the variance needs two samples), pass_samples >= 1 "
-                                                 "and 1 <= max_samples <= 2^17")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}: need min_samples >= 2 (the variance needs two samples), "
+                                                 "pass_samples >= 1 and 1 <= max_samples <= 2^17")
         self.rows = self._shard_rows(self.nrows, self.options)
         self.npix = self.rows * self.ncols
         self._alloc(device)
@@ -1525,8 +1546,7 @@ class Adaptive:
         if self.active == 0 or k <= 0:
             return self
         st = self._stream()
-        self.ctx.accumulate_list_device(self.cam, self.nrows, self.ncols, self._list.data_ptr(), self.active, self.samples, k,
-                                        self.max_depth, self.options, self.sums.data_ptr(), self.moments.data_ptr(), st)
+        self._pass(k, st)
         self.samples += k
         if self.samples >= self.min_samples:
             n = self.ctx.adaptive_select_device(self.sums.data_ptr(), self.moments.data_ptr(), self._list.data_ptr(), self.active,
@@ -1537,6 +1557,11 @@ class Adaptive:
         else:  # (no select yet: every listed pixel simply has N samples)
             self._counts.view(-1).index_fill_(0, self._list[: self.active].long(), self.samples)
         return self
+
+    def _pass(self, k: int, stream: int) -> None:
+        """Samples [N, N + k) of the active list's pixels."""
+        self.ctx.accumulate_list_device(self.cam, self.nrows, self.ncols, self._list.data_ptr(), self.active, self.samples, k,
+                                        self.max_depth, self.options, self.sums.data_ptr(), self.moments.data_ptr(), stream)
 
     def run(self) -> int:
         """step() until the list is empty or max_samples is reached; the survivors then hold max_samples.  Returns N."""
@@ -1561,7 +1586,7 @@ class Adaptive:
         """Each pixel resolved at its own count: a new device float64 tensor (rows of this shard, ncols, 3)."""
         import torch
         if self.samples == 0:
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.image: no pass has run yet")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}.image: no pass has run yet")
         out = torch.empty_like(self.sums)
         self.ctx.resolve_counts_device(self.sums.data_ptr(), self._counts.data_ptr(), self.npix, gamma, out.data_ptr(), self._stream())
         return out
@@ -1570,7 +1595,7 @@ class Adaptive:
         """Fill a host Canvas (whole frame, unsharded options) with image(canvas.gamma_correction), so export_ppm works.  Its
         samples_per_pixel is N, the largest count."""
         if (canvas.nrows, canvas.ncols) != (self.rows, self.ncols):
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.to_canvas: the canvas must have this render's rows and columns")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{type(self).__name__}.to_canvas: the canvas must have this render's rows and columns")
         canvas.pixels[...] = self.image(canvas.gamma_correction).cpu().numpy()
         canvas.samples_per_pixel = self.samples
         return canvas
@@ -1586,7 +1611,7 @@ class Adaptive:
         """Resume a checkpoint (state()) on this context -- any process, any GPU with the same scene uploaded.  policy: the
         constructor's abs_tol, rel_tol, min_samples, pass_samples, max_samples."""
         import torch
-        opts = options if options is not None else make_options(seeding=SEED_SAMPLE)
+        opts = options if options is not None else cls._default_options()
         npix = cls._shard_rows(nrows, opts) * int(ncols)
         lst = cls.validate_list(state["list"], npix)  # before any device work
         ad = cls(ctx, cam, nrows, ncols, max_depth, options, device=device, **policy)
@@ -1594,13 +1619,69 @@ class Adaptive:
         for key, (dst, dt) in arrays.items():
             a = np.ascontiguousarray(state[key], dtype=dt)
             if a.shape != tuple(dst.shape):
-                raise TorError(ERR_INVALID_ARGUMENT, f"Adaptive.from_state: {key} of shape {a.shape}, expected {tuple(dst.shape)}")
+                raise TorError(ERR_INVALID_ARGUMENT, f"{cls.__name__}.from_state: {key} of shape {a.shape}, expected {tuple(dst.shape)}")
             dst.copy_(torch.from_numpy(a))
         ad.samples = int(state["samples"])
         if lst.size and not np.all(np.asarray(state["counts"]).reshape(-1)[lst] == ad.samples):
-            raise TorError(ERR_INVALID_ARGUMENT, "Adaptive.from_state: every listed pixel must hold exactly N samples")
+            raise TorError(ERR_INVALID_ARGUMENT, f"{cls.__name__}.from_state: every listed pixel must hold exactly N samples")
         ad._list[: lst.size].copy_(torch.from_numpy(lst))
         ad.active = int(lst.size)
+        return ad
+
+
+class PixelAdaptive(Adaptive):
+    """Adaptive's surface on the REFERENCE's streams (TOR_SEED_PIXEL): owns, for this shard's rows, the per-pixel generator states
+    next to the raw sequential sums, the sums of c * c, the counts and the active list.  A pass runs the next pass_samples samples
+    of the LISTED pixels' own streams; a pixel that left the list keeps every bit of its state.  Pixel p of image() is the
+    reference's pixel p at counts[p] samples per pixel -- what a one-shot counts[p]-spp render_device(SEED_PIXEL) gives there,
+    bit for bit, whatever the schedule, accel and pixel_kernel.
+
+        ad = PixelAdaptive(ctx, cam, 1080, 1920, 50, rel_tol=0.05, max_samples=1024)
+        ad.run(); frame = ad.image(); spp_map = ad.counts()
+
+    Default options: TOR_SEED_PIXEL with both exact accelerations (tor_render()'s default).  The first pass starts the pixels, so
+    no buffer needs clearing.  The context must have the scene uploaded; device work runs on torch's current stream."""
+
+    _SEEDING = SEED_PIXEL
+    _REFUSAL = ("PixelAdaptive: needs TOR_SEED_PIXEL (it continues the reference's per-pixel streams); "
+                "adaptive sampling on TOR_SEED_SAMPLE streams is Adaptive's")
+
+    @staticmethod
+    def _default_options() -> Options:
+        return make_options(seeding=SEED_PIXEL, accel=ACCEL_BLOCKS | ACCEL_F32)
+
+    def _alloc(self, device) -> None:
+        import torch
+        super()._alloc(device)
+        # one TorRng per pixel: the four xoshiro256+ words (held as int64 bit patterns; state() hands them out as uint64)
+        self.rng = torch.zeros((self.rows, self.ncols, 4), dtype=torch.int64, device=self.sums.device)
+
+    def _pass(self, k: int, stream: int) -> None:
+        """Samples [N, N + k) of the listed pixels' own streams (N == 0 starts them)."""
+        self.ctx.resume_list_device(self.cam, self.nrows, self.ncols, self._list.data_ptr(), self.active, self.samples, k,
+                                    self.max_depth, self.options, self.rng.data_ptr(), self.sums.data_ptr(), self.moments.data_ptr(),
+                                    stream)
+
+    def state(self) -> dict:
+        """Checkpoint: Adaptive.state() plus the per-pixel generator states as a (rows, ncols, 4) uint64 array."""
+        st = super().state()
+        st["rng"] = self.rng.cpu().numpy().view(np.uint64)
+        return st
+
+    @classmethod
+    def from_state(cls, ctx: Context, cam: Camera, nrows: int, ncols: int, max_depth: int, options: Options | None, state: dict,
+                   device=None, **policy) -> "PixelAdaptive":
+        """Resume a checkpoint (state()) on this context -- any process, any GPU with the same scene uploaded.  policy: the
+        constructor's abs_tol, rel_tol, min_samples, pass_samples, max_samples."""
+        import torch
+        opts = options if options is not None else cls._default_options()
+        want = (cls._shard_rows(nrows, opts), int(ncols), 4)
+        rng = np.asarray(state.get("rng"))
+        if rng.dtype != np.uint64 or rng.shape != want:  # before any device work
+            raise TorError(ERR_INVALID_ARGUMENT, f"PixelAdaptive.from_state: generator states of dtype {rng.dtype}, shape {rng.shape}; "
+                                                 f"expected uint64 {want}")
+        ad = super().from_state(ctx, cam, nrows, ncols, max_depth, options, state, device=device, **policy)
+        ad.rng.copy_(torch.from_numpy(np.ascontiguousarray(rng).view(np.int64)))
         return ad
 
 

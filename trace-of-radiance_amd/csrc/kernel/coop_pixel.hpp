@@ -56,8 +56,11 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 }
 
 // (the body of coop_pixel_kernel and of coop_pixel_resume_kernel below.  RESUME: the pixel starts from / ends in caller-owned
-// state -- KParams.rstate, out, and mom when it is not null -- as integrate_kernel's SEEDING 5 / 6 do: tor_render_resume_device)
-template <int ARITH, bool RESUME>
+// state -- KParams.rstate, out, and mom when it is not null -- as integrate_kernel's SEEDING 5 / 6 do: tor_render_resume_device.
+// LIST: work item k is list slot k, its pixel KParams.pixel_list[k] -- tor_render_resume_list_device.  An instantiation of its own and not
+// a wave-uniform branch on p.pixel_list in the resume kernel: that keeps coop_pixel_resume_kernel's code, and with it its registers,
+// exactly as they were, and a shrinking list is where this kernel runs most)
+template <int ARITH, bool RESUME, bool LIST = false>
 __device__ __forceinline__ void coop_pixel_body(const KParams& p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* soa = reinterpret_cast<double*>(smem_raw);
@@ -106,7 +109,7 @@ __device__ __forceinline__ void coop_pixel_body(const KParams& p) {
   const cdptr cold = as_const(p.cold);
   // work items: every pixel of the (shard's) frame, or -- split mode -- the pixels of the first *p.split tiles of the
   // cost-ordered list (the lane kernel renders the others at the same time)
-  const unsigned long long n_items =
+  const unsigned long long n_items = LIST ? p.total_work :
       p.split != nullptr ? bcast_first_u64(*(const volatile unsigned long long*)p.split) * (unsigned long long)kTilePixels : (unsigned long long)p.n_pixels;
 
   for (;;) {
@@ -121,6 +124,10 @@ __device__ __forceinline__ void coop_pixel_body(const KParams& p) {
     if (p.split != nullptr) {  // the k-th item is pixel (k mod 64) of the (k / 64)-th most expensive tile
       pl = p.order[pl64 >> 6] * (unsigned)kTilePixels + (unsigned)(pl64 & 63);
       if (pl >= p.n_pixels) continue;  // the frame's last tile may be partial
+    }
+    if (LIST) {  // (the same word in every lane: a scalar load)
+      pl = (unsigned)p.pixel_list[pl64];
+      if (pl >= p.n_pixels) continue;  // an entry outside the shard: nothing read, nothing written, nothing drawn
     }
     const unsigned lrow = pl / (unsigned)p.ncols;
     const int col = (int)(pl - lrow * (unsigned)p.ncols);
@@ -289,4 +296,7 @@ __global__ __launch_bounds__(kThreads) void coop_pixel_kernel(const KParams p) {
 
 // tor_render_resume_device's wave-per-pixel kernel: the same chain walk from / into caller-owned per-pixel state
 __global__ __launch_bounds__(kThreads) void coop_pixel_resume_kernel(const KParams p) { coop_pixel_body<0, true>(p); }
+
+// tor_render_resume_list_device's: work item k is slot k of KParams.pixel_list (KParams.total_work slots)
+__global__ __launch_bounds__(kThreads) void coop_pixel_resume_list_kernel(const KParams p) { coop_pixel_body<0, true, true>(p); }
 

@@ -3,6 +3,8 @@
 // SEED_SAMPLE / probe: guided chunks) dealt out by ballot + prefix count -- and start its camera ray (render.nim:59-66).  The float64
 // brute force with sample streams (kRes) starts its camera rays 64 at a time into a per-wave LDS reservoir instead and pops from it.
 // SEEDING 4 (kList) walks a pixel list: the work index is list slot x spp + sample, and both seeding sites look the slot's pixel up.
+// SEEDING 7 (kList on the pixel streams) walks it in tiles of 64 consecutive list slots (KParams.total_work = the list's length; the last
+// tile may be partial): state is loaded and stored by the slot's PIXEL, and an entry outside the shard never becomes a work item.
 // Reads / writes the lane state declared in integrate_kernel (active, have_item, o, d, time, rng, row, col, s, pix, acc, ...).
     // ================= (A) refill lanes that have no live path =========================
     // (the cooperative variants -- both exact accelerations, 168 registers and none to spare -- keep the integer division: the
@@ -175,7 +177,7 @@
             if (p.order != nullptr) tile = p.order[tile];
             cur_pl = tile * kTilePixels;
             cur_s = 0;
-            const unsigned left_px = p.n_pixels - cur_pl;
+            const unsigned left_px = ((kList ? (unsigned)p.total_work : p.n_pixels)) - cur_pl;  // (kList: list slots, not pixels)
             w_end = base + ((left_px < (unsigned)kTilePixels) ? left_px : (unsigned)kTilePixels);
           } else {  // one 64-bit division per chunk, wave-uniform
             unsigned long long pl0 = base / (unsigned)p.spp;
@@ -227,8 +229,11 @@
           if constexpr (kList) {
             if (off_shard) pix = -1;  // deposits nothing (tag -1: never flushed)
           }
-          have_item = true;
-          if (kPixel) {
+          // (kList on the pixel streams: an entry outside the shard is dropped here -- nothing read, nothing drawn, nothing written.  The
+          // lane took the slot but holds no item: it stays idle through this bounce iteration and asks again at the next refill; the
+          // sums it zeroed above and the row / column of pixel 0 it computed are never used, and pix = -1 is never read)
+          have_item = !(kPixel && off_shard);
+          if (kPixel && !off_shard) {
             if (kResume && p.first_sample > 0) {
               // a continued pixel: the state its stream had after first_sample samples and the raw sums so far, once per pixel and pass
               const unsigned long long* st = p.rstate + (size_t)pl * 4;

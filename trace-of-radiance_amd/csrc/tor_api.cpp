@@ -509,7 +509,8 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
                               double* d_pixels, void* hip_stream, const tor::AccumLaunch* acc) {
   const bool listed = acc && acc->list;
   const bool resume = acc && acc->rng;  // tor_render_resume_device: a pass on the pixel streams from / into caller-owned state
-  const std::string who = resume ? "tor_render_resume_device" : (listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device"));
+  const bool rlist = resume && listed;  // tor_render_resume_list_device: ... over the listed pixels only
+  const std::string who = rlist ? "tor_render_resume_list_device" : resume ? "tor_render_resume_device" : (listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device"));
   if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
   if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": no scene uploaded");
   // The reference divides by (ncols-1) and (nrows-1) (render.nim:64-65) and by spp
@@ -527,8 +528,8 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
     return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
                                                 "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
   // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them, over a pixel list (4)
-  // for adaptive ones; resume passes on the pixel streams run 5, or 6 with second moments
-  const int kseed = resume ? (acc->moments ? 6 : 5) : (listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding));
+  // for adaptive ones; resume passes on the pixel streams run 5, or 6 with second moments, or 7 over a pixel list (always with moments)
+  const int kseed = rlist ? 7 : resume ? (acc->moments ? 6 : 5) : (listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding));
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipSetDevice(ctx->device));
 
@@ -751,9 +752,14 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
               use_accel && n_tiles > 1 && tor::integrate_variant_serves_chains(p, o.seeding) && resident_waves >= 8;
   }
   const bool split_applies = !migrate && o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && split_frac > 0.0f && ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp &&
-                             npix >= ctx->split_min_pixels && npix <= ctx->split_max_pixels && !ctx->collect_stats && ctx->n_objects > 0;
+                             npix >= ctx->split_min_pixels && npix <= ctx->split_max_pixels && !ctx->collect_stats && ctx->n_objects > 0 &&
+                             !rlist;  // (a listed pass has no tile schedule to split: no probe, no order -- see below)
+  // (a listed pass: the list's length stands in for the pixel count -- what decides is how many chains can run side by side -- against
+  // three quarters of the threshold: measured at 1080p the two kernels cross at ~95 000 listed pixels, below the whole-frame rule's
+  // 114 688, because a listed lane pass has no probe to pay for and no tile order to lose)
+  const long long coop_max_listed = ctx->coop_max_pixels / 4 * 3;
   const bool want_wave_kernel = o.pixel_kernel == TOR_PIXEL_KERNEL_WAVE ||
-                                (o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->coop_max_pixels > 0 && npix <= ctx->coop_max_pixels && !split_applies && !migrate);
+                                (o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->coop_max_pixels > 0 && (rlist ? work_pix <= coop_max_listed : npix <= ctx->coop_max_pixels) && !split_applies && !migrate);
   if (o.seeding == TOR_SEED_PIXEL && !ctx->collect_stats && want_wave_kernel && ctx->n_objects > 0) {
     const int rc = tor::ensure_layouts(ctx, 0);
     if (rc != TOR_OK) return rc;
@@ -771,10 +777,11 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       wp.work_counter = slot_counters;
       wp.out = d_pixels;
       if (resume) { wp.first_sample = acc->first_sample; wp.mom = acc->moments; wp.rstate = acc->rng; }
+      if (rlist) { wp.pixel_list = acc->list; wp.total_work = (unsigned long long)work_pix; }  // work item k = list slot k
       ctx->cam_host[slot] = *cam;
       wp.cam_dev = (const double*)((char*)ctx->cam_ring.ptr + (size_t)slot * sizeof(TorCamera));
       HIP_TRY(hipMemcpyAsync((void*)wp.cam_dev, &ctx->cam_host[slot], sizeof(TorCamera), hipMemcpyHostToDevice, stream));
-      long long blocks = (npix + (tor::kThreads / 64) - 1) / (tor::kThreads / 64);
+      long long blocks = ((rlist ? work_pix : npix) + (tor::kThreads / 64) - 1) / (tor::kThreads / 64);
       const long long resident = (long long)ctx->num_cus * bpc;
       if (blocks > resident) blocks = resident;
       HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
@@ -783,7 +790,7 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       ctx->launches += 1;
       ctx->last_slot = slot;
       ctx->timing_valid = true;
-      ctx->last_samples = (int64_t)npix * spp;
+      ctx->last_samples = (int64_t)(rlist ? work_pix : npix) * spp;
       if (resume) return TOR_OK;  // raw sums: tor_resolve_device finalizes
       HIP_TRY(tor::launch_finalize(d_pixels, n_values, 1.0 / (double)spp, 1.0 / (double)gamma_correction, stream));
       return TOR_OK;
@@ -812,7 +819,11 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
   p.pixel_cost = nullptr;
   ctx->last_probe_pixels = 0;
   p.sched = nullptr;
-  if (o.seeding == TOR_SEED_PIXEL) {
+  if (rlist) {
+    p.total_work = (unsigned long long)work_pix;  // list slots, in tiles of 64 consecutive ones (the last may be partial)
+    p.chunk = tor::kTilePixelsHost;
+    waves = (work_pix + tor::kTilePixelsHost - 1) / tor::kTilePixelsHost;
+  } else if (o.seeding == TOR_SEED_PIXEL) {
     p.total_work = (unsigned long long)n_tiles * tor::kTilePixelsHost;  // tiles of 64 pixels
     p.chunk = tor::kTilePixelsHost;
     waves = n_tiles;
@@ -851,7 +862,9 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
     if (p.bnd32)
       HIP_TRY(hipMemcpyAsync((void*)p.bnd32, ctx->bnd32_host[slot].data(), ctx->bnd32_host[slot].size() * 4, hipMemcpyHostToDevice, stream));
   }
-  if (o.seeding == TOR_SEED_PIXEL && ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && n_tiles > 1) {
+  // (a listed pass runs no probe and no tile order: the probe costs 2 samples of EVERY pixel of the shard -- more than a pass of 16 over a
+  // list of a few per cent of them -- and its tiles are tiles of pixels, not of list slots)
+  if (o.seeding == TOR_SEED_PIXEL && ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && n_tiles > 1 && !rlist) {
     // Cost-ordered schedule: a 2-spp probe (per-sample streams; it only counts closest-hit queries
     // per tile, it never touches the canvas) + a counting sort; ~2/spp of extra work.
     // (one buffer per context, not per ring slot: only the probe and the two sort kernels touch it, and the launches of a
@@ -1055,6 +1068,34 @@ int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int32_t nrow
                                           "(131072): the range tor_resolve_device and tor_accum_noise_device accept");
   if (!ctx || !cam || !d_rng || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_resume_device: NULL argument");
   tor::AccumLaunch acc{first_sample, d_moments};
+  acc.rng = (unsigned long long*)d_rng;
+  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+}
+
+// ... over a pixel list: adaptive sampling on the reference's streams.  The list rules are tor_render_accumulate_list_device's; the pass
+// is tor_render_resume_device's for the listed pixels and leaves every other pixel's state, sums and moments alone.
+int tor_render_resume_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols, const int32_t* d_list, int32_t n_list,
+                                  int32_t first_sample, int32_t n_samples, int64_t max_depth, const TorOptions* opt, TorRng* d_rng,
+                                  double* d_sums, double* d_moments, void* hip_stream) {
+  const char* who = "tor_render_resume_list_device";
+  if (first_sample < 0 || n_samples < 1 || (int64_t)first_sample + n_samples > kMaxAccumSamples)
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": need first_sample >= 0, n_samples >= 1 and first_sample + n_samples <= 2^17 "
+                                          "(131072): the range tor_adaptive_select_device, tor_resolve_counts_device and tor_accum_noise_device accept");
+  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": n_list < 0");
+  {  // (checked before the context is touched: the list may not be longer than the shard)
+    TorOptions o;
+    if (nrows >= 2 && ncols >= 2 && valid_options(opt, o, false)) {
+      const long long npix = (long long)tor_shard_rows(nrows, o.row_tile, o.shard_index, o.shard_count, nullptr) * ncols;
+      if ((long long)n_list > npix)
+        return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": n_list = " + std::to_string(n_list) + " is above the shard's " +
+                                              std::to_string(npix) + " pixels");
+    }
+  }
+  if (!ctx || !cam || !d_rng || !d_sums || !d_moments || (!d_list && n_list > 0))
+    return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument (generator states, sums and moments are all required, and the list unless n_list is 0)");
+  // (an empty pass takes the common path up to its no-op return, so that it is checked like any other; its list is never read)
+  static const int32_t empty_list[1] = {0};
+  tor::AccumLaunch acc{first_sample, d_moments, n_list > 0 ? d_list : empty_list, n_list};
   acc.rng = (unsigned long long*)d_rng;
   return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
 }

@@ -236,7 +236,8 @@ struct AccumLaunch {
   const int32_t* list = nullptr;  // tor_render_accumulate_list_device: the pixel list (kernel variant SEEDING 4) ...
   int32_t n_list = 0;             // ... and its length
   // tor_render_resume_device: the per-pixel generator states (4 x u64 per pixel) -- not null turns the pass into a resume pass on the
-  // reference's pixel streams (kernel variants SEEDING 5 / 6, coop_pixel_resume_kernel), the sums then being raw sequential sums
+  // reference's pixel streams (kernel variants SEEDING 5 / 6, coop_pixel_resume_kernel), the sums then being raw sequential sums.
+  // Together with `list` (tor_render_resume_list_device): such a pass over the listed pixels only (SEEDING 7, coop_pixel_resume_list_kernel)
   unsigned long long* rng = nullptr;
 };
 

@@ -30,6 +30,9 @@
 //                        (tor_render_resume_device; no chain hand-off: DESIGN 4.11).
 //       SEEDING 6 (resume + second moments): SEEDING 5 that also carries the sequential float64 sum of c * c per channel
 //                        (KParams.mom), in LDS between samples.
+//       SEEDING 7 (adaptive on the pixel streams: SEEDING 6 over a pixel list): work item = a tile of 64 consecutive LIST SLOTS, the
+//                        slot's pixel is KParams.pixel_list[slot]; state is loaded and stored by pixel, an entry outside the shard is
+//                        never started (tor_render_resume_list_device).
 //
 //     Objects are wave-uniform inside the hot loop, so their records come through the scalar data
 //     path (s_load into SGPRs, constant-bus operand of the VALU op): no VGPRs, no LDS bandwidth,
@@ -53,6 +56,7 @@
 //   coop_pixel_kernel  TOR_SEED_PIXEL, one WAVE per pixel chain: whole small frames, or -- split mode -- the most
 //                      expensive tiles of a mid-size frame while integrate_kernel renders the rest (DESIGN 4.7 (HISTORY 4.7-4.8)
 //   coop_pixel_resume_kernel  the same chain walk from / into caller-owned per-pixel state (tor_render_resume_device)
+//   coop_pixel_resume_list_kernel  ... over the pixels of a list, one list slot per work item (tor_render_resume_list_device)
 //   tile_order_kernel  counting sort of the SEED_PIXEL tiles by probed cost (LPT schedule) + the split point
 //   gather_rows_kernel multi-GPU assembly: rank-major row shards -> frame in image order
 //   finalize_kernel    canvas.nim:47-54 (draw): pow(sum * 1/spp, 1/gamma)
@@ -164,10 +168,10 @@ constexpr int coop_bytes(int blocks) { return (blocks ? 2 : 1) * kCoopList * 4 +
 // the batch's first pixel (+ that pixel, 16-byte padded)
 constexpr bool sample_variant(int seeding) { return seeding == 1 || seeding == 3 || seeding == 4; }  // per-sample streams, quantised deposit
 constexpr bool moment_variant(int seeding) { return seeding == 3 || seeding == 4; }
-constexpr bool list_variant(int seeding) { return seeding == 4; }  // work over KParams.pixel_list (adaptive sampling)
-constexpr bool pixel_variant(int seeding) { return seeding == 0 || seeding == 5 || seeding == 6; }  // the reference's streams: one sequential chain per pixel
-constexpr bool resume_variant(int seeding) { return seeding == 5 || seeding == 6; }  // ... that starts from and ends in KParams.rstate / out (/ mom)
-constexpr bool resume_moment_variant(int seeding) { return seeding == 6; }
+constexpr bool list_variant(int seeding) { return seeding == 4 || seeding == 7; }  // work over KParams.pixel_list (adaptive sampling)
+constexpr bool pixel_variant(int seeding) { return seeding == 0 || seeding == 5 || seeding == 6 || seeding == 7; }  // the reference's streams: one sequential chain per pixel
+constexpr bool resume_variant(int seeding) { return seeding == 5 || seeding == 6 || seeding == 7; }  // ... that starts from and ends in KParams.rstate / out (/ mom)
+constexpr bool resume_moment_variant(int seeding) { return seeding == 6 || seeding == 7; }
 constexpr bool reservoir_variant(int seeding, int f32, int blocks) { return sample_variant(seeding) && f32 == 0 && blocks == 0; }
 constexpr int kResBytes = 9 * 64 * 8 + 64 + 16;
 // (moment variants: the second-moment cache [kAccSlots][3] f64 at the END of the wave's carve-out, so every other offset stays)
@@ -251,7 +255,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   // SEED_PIXEL cooperative variants keep the pixel's running sum in LDS too (touched once per sample; as registers it is
   // six of the 168, and the variant spills inside the bounce loop): it takes the upper half of the queue -- 4 entries are
   // enough there, the box hits live in registers -- plus the SAMPLE accumulator cache this seeding does not use
-  constexpr bool kPixel = pixel_variant(SEEDING);    // the reference's per-pixel streams (SEEDING 0, and the resume variants 5 / 6)
+  constexpr bool kPixel = pixel_variant(SEEDING);    // the reference's per-pixel streams (SEEDING 0, and the resume variants 5 / 6 / 7)
   constexpr bool kResume = resume_variant(SEEDING);
   constexpr bool kResMom = resume_moment_variant(SEEDING);
   constexpr bool kAccInLds = kPixel && coop_variant(F32, BLOCKS);
@@ -772,7 +776,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
 // ---------------------------------------------------------------------------------------
 // host-side launchers (called from tor_api.cpp)
 // ---------------------------------------------------------------------------------------
-// variant table: [seeding 0|1|2|3|4|5|6 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only; 4: 3 over a pixel list; 5: resumable SEED_PIXEL; 6: 5 + second moments)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
+// variant table: [seeding 0|1|2|3|4|5|6|7 (2: the cost probe; 3: SEED_SAMPLE + second moments, progressive launches only; 4: 3 over a pixel list; 5: resumable SEED_PIXEL; 6: 5 + second moments; 7: 6 over a pixel list)][arith 0 | 2 (2: behind the FMA screen, brute-force layouts only)][W 2|3][f32 0|1]
 // [blocks 0|1|2 (2: two-level layouts, cooperative variants only)].  The block-expansion code (an unrolled 8-object stage per lane)
 // is what makes the 168-register variants spill; launches without TOR_ACCEL_BLOCKS use kernels compiled without it (no scratch
 // traffic at all).  (Round 5: the 20 TOR_ARITH_FUSED instantiations -- `arith 1`, not the reference's rounding -- are gone.)
@@ -787,11 +791,12 @@ static IntegrateFn integrate_variant(int seeding, int arith, int w, int f32, int
   TOR_V4(4, 0, 2) TOR_V4(4, 0, 3)  // ... over a pixel list (adaptive sampling: tor_render_accumulate_list_device)
   TOR_V4(5, 0, 2) TOR_V4(5, 0, 3)  // resumable pixel streams (tor_render_resume_device)
   TOR_V4(6, 0, 2) TOR_V4(6, 0, 3)  // ... with second moments
+  TOR_V4(7, 0, 2) TOR_V4(7, 0, 3)  // ... over a pixel list (adaptive sampling on the pixel streams: tor_render_resume_list_device)
   // arith 2: the reference's arithmetic behind the conservative FMA screen (brute-force layouts only)
   TOR_V(0, 2, 2, 0, 0) TOR_V(0, 2, 3, 0, 0) TOR_V(1, 2, 2, 0, 0) TOR_V(1, 2, 3, 0, 0) TOR_V(2, 2, 3, 0, 0)
   TOR_V(3, 2, 2, 0, 0) TOR_V(3, 2, 3, 0, 0)
   TOR_V(4, 2, 2, 0, 0) TOR_V(4, 2, 3, 0, 0)
-  TOR_V(5, 2, 2, 0, 0) TOR_V(5, 2, 3, 0, 0) TOR_V(6, 2, 2, 0, 0) TOR_V(6, 2, 3, 0, 0)
+  TOR_V(5, 2, 2, 0, 0) TOR_V(5, 2, 3, 0, 0) TOR_V(6, 2, 2, 0, 0) TOR_V(6, 2, 3, 0, 0) TOR_V(7, 2, 2, 0, 0) TOR_V(7, 2, 3, 0, 0)
   // (round 5: a 128-register build <1, 2, 4, 0, 0> for a 4th workgroup per CU now runs 2.4 x SLOWER -- 1097 against 2613 Msamples/s
   // at configs[1]: stage two's per-lane state spills inside the loops; not built)
   // (a 128-register build of <1, 2, W, 0, 0> for a 4th workgroup per CU was measured in round 4: 1951 against 1961 Msamples/s at
@@ -872,17 +877,24 @@ int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_
 // One wave per pixel (TOR_SEED_PIXEL, small frames).  Returns hipErrorInvalidValue when the objects do not fit LDS.
 size_t coop_lds_bytes(int coop_slots) { return (size_t)kCoopArrays * 8 * (size_t)coop_slots; }
 
+// the wave-per-pixel kernel of a launch: the resume kernels when it carries per-pixel state, the listed one when it carries a list too
+typedef void (*CoopFn)(const KParams);
+static CoopFn coop_variant_fn(const KParams& p) {
+  if (p.rstate == nullptr) return coop_pixel_kernel<0>;
+  return p.pixel_list != nullptr ? coop_pixel_resume_list_kernel : coop_pixel_resume_kernel;
+}
+
 int coop_blocks_per_cu(const KParams& p, int arith) {
   int n = 0;
   (void)arith;
-  auto fn = p.rstate != nullptr ? coop_pixel_resume_kernel : coop_pixel_kernel<0>;
+  CoopFn fn = coop_variant_fn(p);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kThreads, coop_lds_bytes(p.coop_slots)) != hipSuccess) n = 0;
   return n;
 }
 
 hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream) {
   (void)arith;
-  auto fn = p.rstate != nullptr ? coop_pixel_resume_kernel : coop_pixel_kernel<0>;
+  CoopFn fn = coop_variant_fn(p);
   const size_t lds = coop_lds_bytes(p.coop_slots);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

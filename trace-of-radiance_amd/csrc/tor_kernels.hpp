@@ -112,7 +112,9 @@ struct KParams {
   int first_sample;
   double* mom;  // SEEDING 3 (sample streams + second moments): per pixel and channel, the sum of quantize36(q * q) over the samples; else null
   // adaptive sampling (tor_render_accumulate_list_device; SEEDING 4 = SEEDING 3 over a pixel list): work index = list slot x spp + sample,
-  // the slot's pixel is pixel_list[slot] (shard-local, in out's layout); an entry >= n_pixels deposits nothing; else null
+  // the slot's pixel is pixel_list[slot] (shard-local, in out's layout); an entry >= n_pixels deposits nothing; else null.
+  // With rstate (tor_render_resume_list_device; SEEDING 7 and coop_pixel_resume_list_kernel): total_work is the list's length, a work item
+  // is a tile of 64 list slots (lane kernel) or one slot (wave kernel), and an entry >= n_pixels is never started
   const int32_t* pixel_list;
   // resumable rendering on the pixel streams (tor_render_resume_device; SEEDING 5 / 6 and coop_pixel_resume_kernel): this launch runs
   // samples [first_sample, first_sample + spp) of every pixel's own stream.  first_sample == 0: the kernel seeds seed2(row, col) and
@@ -152,8 +154,8 @@ hipError_t launch_integrate(const KParams& p, int seeding, int arith, int waves_
 int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_per_simd);
 size_t coop_lds_bytes(int coop_slots);
 int coop_blocks_per_cu(const KParams& p, int arith);  // 0: the objects do not fit LDS
-hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream);  // p.rstate != null: coop_pixel_resume_kernel
-int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir) (+ the moment cache, seeding 3) (+ the pixels' moment sums, seeding 6)
+hipError_t launch_coop(const KParams& p, int arith, int blocks, hipStream_t stream);  // p.rstate != null: coop_pixel_resume_kernel (with p.pixel_list: coop_pixel_resume_list_kernel)
+int integrate_fixed_lds_bytes(int blocks, int f32, int seeding = 0);  // per workgroup: queues, accumulator cache, debug counters (+ cooperative-resolve lists | the camera-ray reservoir) (+ the moment cache, seeding 3) (+ the pixels' moment sums, seedings 6 / 7)
 hipError_t launch_probe(const KParams& p, int blocks, hipStream_t stream);
 // schedule of the chain hand-off, computed on the device from the probe's total (tile_order_kernel): l_avg = probed queries x
 // lavg_scale = bounce iterations an average lane runs in this frame; dedicated server workgroups = srv_frac x blocks when a
