@@ -551,6 +551,35 @@ TOR_API int tor_sky_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays
 TOR_API int tor_bounce_select_device(TorContext* ctx, int64_t n_rays, const int32_t* d_status, const int32_t* d_list_in, int64_t n_in,
                                      int32_t* d_list_out, int64_t* n_out, void* hip_stream);
 
+/* ---- any-hit queries: is anything in the way?  One bit per shadow ray ----------------------------------------------------------
+ * A host that treats objects as emitters casts shadow rays towards them and keeps one bit of each answer.  These entries give
+ * that bit without the closest hit's cost: no smallest root, no record, 4 bytes out per ray, and the kernel stops at the first
+ * accepted root.  The bit is the reference's, exactly: HittableList.hit (hittables_lists.nim:48-55) returns hit_anything, and the
+ * closest_so_far it shrinks on the way only rejects roots of later objects after an earlier one has been accepted, so
+ *   occluded(r, t_min, t_max) = OR over the list of Sphere.hit / MovingSphere.hit(r, t_min, t_max)
+ * (spheres.nim:28-49, moving_spheres.nim:39-67), in any visiting order and under any early exit.
+ *
+ * tor_occluded_device: d_occluded[i] (DEVICE int32, one per ray, indexed by the ray) = 1 iff world.hit(rays[i], t_min, t_max, rec)
+ * returns true on the uploaded list, else 0.  d_t_range (nullable, DEVICE): 2 float64 per ray {t_min, t_max}, indexed by the ray;
+ * NULL = render.nim's (0.001, +inf).  A shadow segment from p to q is origin p, direction q - p, range (0.001, 1.0); both
+ * comparisons are strict, as in the reference.  d_list / n_list follow the path steps' rules: NULL = every ray (n_list must be
+ * n_rays); entries outside [0, n_rays) are skipped (nothing read, nothing written); entries must be unique; rays that are not
+ * listed keep every bit of d_occluded; n_list == 0 and n_rays == 0 are no-ops.  mode and [time_lo, time_hi] work as in
+ * tor_hit_device (a speed hint only): a ray whose time lies outside the range (or is NaN), whose t_min is not >= 0, whose origin
+ * lies beyond the reach of the boxes' margin or whose |direction|^2 is below its floor walks every spatial slot instead, so every
+ * bit is exact whatever the hint.  With the blocks a box the segment ends in front of is not entered, so short segments cost
+ * little.  tor_last_note(): "occluded: blocks" | "occluded: brute force (...)".  Asynchronous on hip_stream, one stream per
+ * context as for the other queries; a query leaves every render state alone.  TOR_ERR_INVALID_ARGUMENT (nothing written) for
+ * what tor_hit_device refuses, n_list < 0, a NULL list with n_list != n_rays, NULL rays or output with work to do.
+ * WHICH object occludes a ray is not exposed: with the early exit it depends on the visiting order, so the reference does not
+ * define it (tor_hit_device answers that question).
+ * tor_occluded_host: the same on host arrays, blocking (every array copied in, the query, the output copied out); it waits for
+ * the context's last render launch and last query as tor_hit_host does. */
+TOR_API int tor_occluded_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
+                                int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, void* hip_stream);
+TOR_API int tor_occluded_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
+                              int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

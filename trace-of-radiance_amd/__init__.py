@@ -159,6 +159,7 @@ EXPORTED_SYMBOLS = [
     "tor_hit_device", "tor_hit_host", "tor_radiance_device", "tor_radiance_host", "tor_camera_rays_device",
     "tor_bounce_device", "tor_bounce_host", "tor_scatter_device", "tor_scatter_host", "tor_sky_device", "tor_bounce_select_device",
     "tor_render_resume_device", "tor_debug_last_split_tiles", "tor_render_resume_list_device",
+    "tor_occluded_device", "tor_occluded_host",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
@@ -316,6 +317,8 @@ def lib():
     if hasattr(L, "tor_render_resume_list_device"):  # (... and one older than adaptive sampling on the pixel streams)
         L.tor_render_resume_list_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                     C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "tor_occluded_device"):  # (... and one older than the any-hit queries)
+        _bind_occluded(L)
     _lib = L
     return L
 
@@ -343,6 +346,12 @@ def _bind_bounce(L) -> None:
     L.tor_scatter_host.argtypes = [v, i64, v, v, v, v, i64, v, v]
     L.tor_sky_device.argtypes = [v, i64, v, v, i64, v, v]
     L.tor_bounce_select_device.argtypes = [v, i64, v, v, i64, v, C.POINTER(C.c_int64), v]
+
+
+def _bind_occluded(L) -> None:
+    v, i64 = C.c_void_p, C.c_int64
+    L.tor_occluded_device.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v]
+    L.tor_occluded_host.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -1203,6 +1212,90 @@ class Context:
                                               C.byref(n_out), C.c_void_p(torch.cuda.current_stream(status.device).cuda_stream)))
         return lst[:int(n_out.value)]
 
+    def occluded(self, rays, t_range=None, index=None, time_range=None, mode="auto", out=None) -> "OccludedResult":
+        """Any-hit query for shadow rays (tor_occluded_device / tor_occluded_host): per listed ray ONE bit, whether
+        world.hit(r, t_min, t_max, rec) of the reference returns true on the uploaded scene -- the reference's bit, exactly, at a
+        fraction of hit()'s cost: the kernel stops at the first accepted root and writes 4 bytes per ray.
+
+        rays: (n, 7) float64 -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or anything numpy takes
+        (copied, blocking).  t_range: None ((0.001, +inf)) or (n, 2) {t_min, t_max} of the same kind; the segment p -> q is origin
+        p, direction q - p, range (0.001, 1.0) (visible() builds these).  index: the rays to answer (int32, unique; entries outside
+        [0, n) are skipped), None = all.  time_range and mode as for hit().  out: an OccludedResult of an earlier call on as many
+        rays, or its raw int32 array, written again (rays that are not listed keep what it holds); otherwise a new one (0).
+        Returns an OccludedResult: occluded (bool view), raw (int32) and mode.  Which object occludes is not defined; ask hit()."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        raw = out.raw if hasattr(out, "raw") else out
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            rays, _, dev, stream = self._step_tensors("occluded", rays, None)
+            n = int(rays.shape[0])
+            if t_range is not None:
+                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
+                        or t_range.device != dev:
+                    raise ValueError("Context.occluded: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
+                t_range = t_range.contiguous()
+            index, n_list, p_list = self._step_index(index, n, dev)
+            tr = self._time_range_of(rays, time_range)
+            if raw is None:
+                raw = torch.zeros((n,), dtype=torch.int32, device=dev)
+            elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.int32 or tuple(raw.shape) != (n,) or raw.device != dev \
+                    or not raw.is_contiguous():
+                raise ValueError("Context.occluded: with tensor rays, out must be a contiguous (n,) int32 tensor on the rays' device")
+            _check(lib().tor_occluded_device(self._h, n, C.c_void_p(rays.data_ptr()),
+                                             C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list, tr[0], tr[1], m,
+                                             C.c_void_p(raw.data_ptr()), C.c_void_p(stream)))
+            note = last_note() if n and n_list else "occluded: nothing to do"
+            return OccludedResult(raw, raw.view(torch.bool).view(n, 4)[:, 0], note, keep=(rays, t_range, index))
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.occluded: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        if t_range is not None:
+            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
+            if t_range.shape != (n, 2):
+                raise ValueError("Context.occluded: t_range must have shape (n, 2)")
+        index, n_list, p_list = self._step_index(index, n)
+        tr = self._time_range_of(rays, time_range)
+        if raw is None:
+            raw = np.zeros((n,), dtype=np.int32)
+        elif not isinstance(raw, np.ndarray) or raw.dtype != np.int32 or raw.shape != (n,) or not raw.flags.c_contiguous:
+            raise ValueError("Context.occluded: out must be a contiguous (n,) int32 array")
+        _check(lib().tor_occluded_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
+                                       C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0), p_list, n_list, tr[0], tr[1], m,
+                                       C.c_void_p(raw.ctypes.data if n else 0)))
+        note = last_note() if n and n_list else "occluded: nothing to do"
+        return OccludedResult(raw, raw.view(np.bool_).reshape(n, 4)[:, 0], note)
+
+    @staticmethod
+    def shadow_segments(p, q, time=0.0, t_min=0.001):
+        """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
+        `time` (a scalar or one per segment), (n, 2) ranges (t_min, 1.0)) -- torch tensors when p is one, else numpy arrays."""
+        if type(p).__module__.startswith("torch"):
+            import torch
+            p = p.reshape(-1, 3)
+            q = torch.as_tensor(q, dtype=p.dtype, device=p.device).reshape(-1, 3)
+            n = int(p.shape[0])
+            rays = torch.empty((n, 7), dtype=torch.float64, device=p.device)
+            rays[:, 0:3], rays[:, 3:6] = p, q - p
+            rays[:, 6] = torch.as_tensor(time, dtype=torch.float64, device=p.device)
+            tr = torch.empty((n, 2), dtype=torch.float64, device=p.device)
+            tr[:, 0], tr[:, 1] = float(t_min), 1.0
+            return rays, tr
+        p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
+        q = np.asarray(q, dtype=np.float64).reshape(-1, 3)
+        n = p.shape[0]
+        rays = np.empty((n, 7), dtype=np.float64)
+        rays[:, 0:3], rays[:, 3:6], rays[:, 6] = p, q - p, time
+        tr = np.empty((n, 2), dtype=np.float64)
+        tr[:, 0], tr[:, 1] = t_min, 1.0
+        return rays, tr
+
+    def visible(self, p, q, time=0.0, t_min=0.001, **kw):
+        """Is q visible from p?  Sugar over occluded(): the rays p -> q - p with range (t_min, 1.0) (shadow_segments), and
+        ~occluded of them -- a bool tensor / array, one per segment.  kw: index, time_range, mode of occluded()."""
+        rays, tr = self.shadow_segments(p, q, time, t_min)
+        return ~self.occluded(rays, tr, **kw).occluded
+
     def trace(self, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None):
         """A wavefront path tracer on top of bounce(): radiance()'s loop (render.nim:21-47) one step per launch, open where the
         reference is closed.  att = 1; per step: bounce the live rays; a miss ends with sky * att; with `emission` every hit adds
@@ -1287,6 +1380,16 @@ class BounceResult(HitResult):
         super().__init__(raw, words, note, keep=keep)
         self.attenuation, self.status, self.rays, self.rng = attenuation, status, rays, rng
         self.mode = _mode_of(note, "bounce: ")
+
+
+class OccludedResult:
+    """Any-hit answers of Context.occluded, one per ray: `occluded` is a bool view of `raw` ((n,) int32, 1 = world.hit returns true,
+    as the library wrote it; rays that were not listed keep what `out` held) -- torch tensors or numpy arrays, as the rays were.
+    `mode` is what ran: "blocks" or "brute force (...)" (tor_last_note)."""
+
+    def __init__(self, raw, occluded, note: str, keep=None):
+        self.raw, self.occluded, self._keep = raw, occluded, keep   # (keep: the operands' contiguous copies stay alive while the query may run)
+        self.mode = _mode_of(note, "occluded: ")
 
 
 class Progressive:
