@@ -580,6 +580,45 @@ TOR_API int tor_occluded_device(TorContext* ctx, int64_t n_rays, const TorRay* d
 TOR_API int tor_occluded_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
                               int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded);
 
+/* ---- visibility groups and per-ray masks: the hit, any-hit and step queries on a sub-list of the scene --------------------------
+ * Shadow rays that skip glass, shadow segments towards a lamp that ignore the lamp, lamps the camera does not see: every object
+ * of the uploaded list carries a 32-bit GROUP word, every ray of a masked query a 32-bit MASK, and
+ *   object j takes part for ray i  iff  groups[j] & mask_i != 0.
+ * The meaning is exact in the reference's terms: a masked query is world.hit(r, t_min, t_max, rec) (hittables_lists.nim:48-55) on
+ * the sub-list of the objects the ray sees, in list order.  Each masked entry equals its unmasked entry on a context that
+ * uploaded only those objects, bit for bit, with `object` reported as the index in the FULL list; so ties go to the lowest
+ * visible index.  A ray with mask 0 misses (object = -1, the rest 0), is not occluded, and its step has status
+ * TOR_BOUNCE_MISS, draws nothing and leaves ray and state untouched.
+ *
+ * tor_scene_groups: one word per object of the uploaded list, in list order, from a HOST array.  groups == NULL resets every
+ * object to 0xFFFFFFFF: the state after every tor_scene_upload that replaces the scene (an upload of a byte-identical list is a
+ * no-op and keeps the words).  n_objects must equal the uploaded count: otherwise, and for a context without a scene,
+ * TOR_ERR_INVALID_ARGUMENT and nothing changes.  The call waits for the context's last query before it replaces the words.  The
+ * render entries and the unmasked queries never read them.
+ *
+ * tor_hit_masked_device / tor_occluded_masked_device / tor_bounce_masked_device: the arguments of tor_hit_device /
+ * tor_occluded_device / tor_bounce_device, then d_mask (nullable, DEVICE: one word per ray, indexed by the ray as every other
+ * per-ray array is) and mask (the mask of every ray when d_mask is NULL; ignored otherwise).  tor_bounce_masked_device scatters off
+ * the visible winner with the reference's draws; its d_hits is tor_hit_masked_device's.  Lists, d_t_range, mode, the time-range
+ * hint, the walk of the rays the boxes do not hold for, the one-stream rule and the refusals are the unmasked entries'.  With the
+ * blocks a ray does not enter a box that holds nothing it sees.  tor_last_note(): "hit (masked): blocks" | "hit (masked): brute
+ * force (...)", and likewise "occluded (masked): ..." and "bounce (masked): ...".
+ * tor_hit_masked_host / tor_occluded_masked_host: the same on host arrays (masks: nullable, HOST), blocking, as tor_hit_host. */
+TOR_API int tor_scene_groups(TorContext* ctx, int64_t n_objects, const uint32_t* groups);
+TOR_API int tor_hit_masked_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, double time_lo,
+                                  double time_hi, int32_t mode, TorHit* d_hits, void* hip_stream, const uint32_t* d_mask, uint32_t mask);
+TOR_API int tor_hit_masked_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo,
+                                double time_hi, int32_t mode, TorHit* hits, const uint32_t* masks, uint32_t mask);
+TOR_API int tor_occluded_masked_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range,
+                                       const int32_t* d_list, int64_t n_list, double time_lo, double time_hi, int32_t mode,
+                                       int32_t* d_occluded, void* hip_stream, const uint32_t* d_mask, uint32_t mask);
+TOR_API int tor_occluded_masked_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
+                                     int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded,
+                                     const uint32_t* masks, uint32_t mask);
+TOR_API int tor_bounce_masked_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list,
+                                     int64_t n_list, double time_lo, double time_hi, int32_t mode, TorHit* d_hits,
+                                     double* d_attenuation, int32_t* d_status, void* hip_stream, const uint32_t* d_mask, uint32_t mask);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

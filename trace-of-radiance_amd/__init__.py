@@ -160,10 +160,13 @@ EXPORTED_SYMBOLS = [
     "tor_bounce_device", "tor_bounce_host", "tor_scatter_device", "tor_scatter_host", "tor_sky_device", "tor_bounce_select_device",
     "tor_render_resume_device", "tor_debug_last_split_tiles", "tor_render_resume_list_device",
     "tor_occluded_device", "tor_occluded_host",
+    "tor_scene_groups", "tor_hit_masked_device", "tor_hit_masked_host", "tor_occluded_masked_device", "tor_occluded_masked_host",
+    "tor_bounce_masked_device",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
+MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2   # Material kinds (TOR_LAMBERTIAN ..): groups_by_material gives 1 << kind
 
 _lib = None
 
@@ -319,6 +322,8 @@ def lib():
                                                     C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "tor_occluded_device"):  # (... and one older than the any-hit queries)
         _bind_occluded(L)
+    if hasattr(L, "tor_scene_groups"):  # (... and one older than the visibility groups)
+        _bind_masked(L)
     _lib = L
     return L
 
@@ -352,6 +357,16 @@ def _bind_occluded(L) -> None:
     v, i64 = C.c_void_p, C.c_int64
     L.tor_occluded_device.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v]
     L.tor_occluded_host.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v]
+
+
+def _bind_masked(L) -> None:
+    v, i64, u32 = C.c_void_p, C.c_int64, C.c_uint32
+    L.tor_scene_groups.argtypes = [v, i64, v]
+    L.tor_hit_masked_device.argtypes = list(L.tor_hit_device.argtypes) + [v, u32]
+    L.tor_hit_masked_host.argtypes = list(L.tor_hit_host.argtypes) + [v, u32]
+    L.tor_occluded_masked_device.argtypes = list(L.tor_occluded_device.argtypes) + [v, u32]
+    L.tor_occluded_masked_host.argtypes = list(L.tor_occluded_host.argtypes) + [v, u32]
+    L.tor_bounce_masked_device.argtypes = list(L.tor_bounce_device.argtypes) + [v, u32]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -712,6 +727,7 @@ class Context:
 
     def upload(self, world: HittableList):
         _check(lib().tor_scene_upload(self._h, world))
+        self._n_uploaded = int(world.len)
 
     def set_stats(self, enable: bool):
         _check(lib().tor_context_set_stats(self._h, int(enable)))
@@ -904,14 +920,46 @@ class Context:
         _check(lib().tor_last_stats(self._h, C.byref(st)))
         return st
 
-    def hit(self, rays, t_range=None, time_range=None, mode="auto") -> "HitResult":
+    def set_groups(self, groups):
+        """The visibility groups of the uploaded scene (tor_scene_groups): one 32-bit word per object, in list order -- anything
+        numpy takes, uint32 or int32 (by its bits); None resets every object to 0xFFFFFFFF, the state after every upload that
+        replaces the scene.  Object j takes part in a query of ray i with mask m_i iff groups[j] & m_i != 0 (the `mask` keyword of
+        hit / occluded / visible / bounce / trace).  Renders and queries without a mask never read the words."""
+        if groups is None:
+            _check(lib().tor_scene_groups(self._h, getattr(self, "_n_uploaded", -1), C.c_void_p(0)))
+            return
+        g = _mask_words(np.asarray(groups).reshape(-1))
+        _check(lib().tor_scene_groups(self._h, int(g.size), C.c_void_p(g.ctypes.data or 16)))
+
+    @staticmethod
+    def _mask_arg(who, mask, n, device=None):
+        """The mask operands of a masked entry: (what to keep alive, the address of the per-ray words or 0, the scalar word)."""
+        if isinstance(mask, (int, np.integer)):
+            return None, C.c_void_p(0), int(mask) & 0xFFFFFFFF
+        is_torch = type(mask).__module__.startswith("torch")
+        if device is not None:
+            import torch
+            if not is_torch:
+                mask = torch.from_numpy(_mask_words(np.asarray(mask).reshape(-1)).view(np.int32))
+            if mask.dtype not in (torch.int32, torch.uint32) or tuple(mask.shape) != (n,):
+                raise ValueError(f"Context.{who}: a per-ray mask must be an (n,) uint32 / int32 tensor or array")
+            mask = mask.to(device).contiguous()
+            return mask, C.c_void_p(mask.data_ptr() or 16), 0
+        words = _mask_words(mask.cpu().numpy() if is_torch else np.asarray(mask))
+        if words.shape != (n,):
+            raise ValueError(f"Context.{who}: a per-ray mask must be an (n,) uint32 / int32 tensor or array")
+        return words, C.c_void_p(words.ctypes.data or 16), 0
+
+    def hit(self, rays, t_range=None, time_range=None, mode="auto", mask=None) -> "HitResult":
         """Closest hits of a batch of rays against the uploaded scene: world.hit(r, t_min, t_max, rec) of the reference
         (hittables_lists.nim:48-55), bit for bit, per ray (tor_hit_device / tor_hit_host).
 
         rays: (n, 7) float64 {origin xyz, direction xyz, time} -- a torch CUDA tensor (zero-copy, asynchronous on torch's current
         stream) or anything numpy takes (copied, blocking).  t_range: None (render.nim's (0.001, +inf)) or (n, 2) {t_min, t_max} of
         the same kind; t_min >= 0 lets a ray use the block culling.  time_range: (lo, hi) the block bounds are built for (a speed hint:
-        rays outside it are still exact); None = the finite min / max of the rays' times.  mode: "auto" | "brute" | "blocks"."""
+        rays outside it are still exact); None = the finite min / max of the rays' times.  mode: "auto" | "brute" | "blocks".
+        mask: None (every object), or an int / a per-ray (n,) uint32 or int32 tensor or array: ray i sees object j iff
+        groups[j] & mask_i != 0 (set_groups) -- world.hit on the sub-list it sees, `object` the index in the full list."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
         if type(rays).__module__.startswith("torch"):
             import torch
@@ -933,9 +981,14 @@ class Context:
                 time_range = (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
             raw = torch.empty((n, 8), dtype=torch.float64, device=rays.device)
             stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(lib().tor_hit_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0),
-                                        float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream)))
-            return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range))
+            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0),
+                    float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream))
+            if mask is None:
+                _check(lib().tor_hit_device(*args))
+                return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range))
+            mk, p_mask, word = self._mask_arg("hit", mask, n, rays.device)
+            _check(lib().tor_hit_masked_device(*args, p_mask, word))
+            return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range, mk))
         rays = np.ascontiguousarray(rays, dtype=np.float64)
         if rays.ndim != 2 or rays.shape[1] != 7:
             raise ValueError("Context.hit: rays must have shape (n, 7)")
@@ -948,9 +1001,13 @@ class Context:
             times = rays[:, 6][np.isfinite(rays[:, 6])]
             time_range = (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
         raw = np.zeros((n, 8), dtype=np.float64)
-        _check(lib().tor_hit_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
-                                  C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
-                                  float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.ctypes.data if n else 0)))
+        args = (self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
+                float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.ctypes.data if n else 0))
+        if mask is None:
+            _check(lib().tor_hit_host(*args))
+        else:
+            _mk, p_mask, word = self._mask_arg("hit", mask, n)
+            _check(lib().tor_hit_masked_host(*args, p_mask, word))
         return HitResult(raw, raw.view(np.int32), last_note())
 
 
@@ -1087,7 +1144,7 @@ class Context:
             raise ValueError(f"Context.{who}: rng must be an (n, 4) array of 64-bit integers")
         return np.ascontiguousarray(st).view(np.uint64).copy()
 
-    def bounce(self, rays, rng, index=None, time_range=None, mode="auto", out=None) -> "BounceResult":
+    def bounce(self, rays, rng, index=None, time_range=None, mode="auto", out=None, mask=None) -> "BounceResult":
         """One iteration of radiance()'s loop (render.nim:26-38) for the listed rays, bit for bit (tor_bounce_device /
         tor_bounce_host): world.hit(ray, 0.001, +inf, rec), then rec.material.scatter(ray, rec, rng, attenuation, scattered).
 
@@ -1097,7 +1154,9 @@ class Context:
         skipped), None = all.  Arrays are indexed by the ray, so a host keeps full-size arrays and a shrinking index.  Returns a
         BounceResult: HitResult's fields, attenuation (n, 3), status (n,) int32 (BOUNCE_MISS / BOUNCE_SCATTERED / BOUNCE_ABSORBED),
         rays and rng (the updated arrays) and the mode that ran.  out: a BounceResult of an earlier step on as many rays, whose
-        arrays are written again (rays that are not listed keep what they hold); otherwise new ones (object -1, the rest 0)."""
+        arrays are written again (rays that are not listed keep what they hold); otherwise new ones (object -1, the rest 0).
+        mask: as for hit() (per-ray words are indexed by the ray): the closest VISIBLE object scatters; a ray that sees nothing
+        misses, draws nothing and keeps its ray and state."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
         if type(rays).__module__.startswith("torch"):
             import torch
@@ -1112,11 +1171,32 @@ class Context:
                 raw.view(torch.int32)[:, 14] = -1
                 att = torch.zeros((n, 3), dtype=torch.float64, device=dev)
                 status = torch.zeros((n,), dtype=torch.int32, device=dev)
-            _check(lib().tor_bounce_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), p_list, n_list,
-                                           tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(att.data_ptr()),
-                                           C.c_void_p(status.data_ptr()), C.c_void_p(stream)))
+            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), p_list, n_list, tr[0], tr[1], m,
+                    C.c_void_p(raw.data_ptr()), C.c_void_p(att.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream))
+            mk = None
+            if mask is None:
+                _check(lib().tor_bounce_device(*args))
+            else:
+                mk, p_mask, word = self._mask_arg("bounce", mask, n, dev)
+                _check(lib().tor_bounce_masked_device(*args, p_mask, word))
             note = last_note() if n and n_list else "bounce: nothing to do"
-            return BounceResult(raw, raw.view(torch.int32), note, att, status, rays, rng, keep=index)
+            return BounceResult(raw, raw.view(torch.int32), note, att, status, rays, rng, keep=(index, mk))
+        if mask is not None:   # (the masked step has no blocking entry: through the device and back)
+            import torch
+            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+
+            def to(a):
+                return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            r = to(np.array(rays, dtype=np.float64).reshape(-1, 7))
+            s = to(self._step_states("bounce", rng, int(r.shape[0])).view(np.int64))
+            if out is not None and isinstance(out.raw, np.ndarray):
+                raw = to(out.raw)
+                out = BounceResult(raw, raw.view(torch.int32), "", to(out.attenuation), to(out.status), None, None)
+            res = self.bounce(r, s, index, time_range, mode, out, mask)
+            torch.cuda.synchronize(dev)
+            raw = res.raw.cpu().numpy()
+            return BounceResult(raw, raw.view(np.int32), "bounce: " + res.mode, res.attenuation.cpu().numpy(), res.status.cpu().numpy(),
+                                res.rays.cpu().numpy(), res.rng.cpu().numpy().view(np.uint64))
         rays = np.array(rays, dtype=np.float64, order="C")
         if rays.ndim != 2 or rays.shape[1] != 7:
             raise ValueError("Context.bounce: rays must have shape (n, 7)")
@@ -1212,7 +1292,7 @@ class Context:
                                               C.byref(n_out), C.c_void_p(torch.cuda.current_stream(status.device).cuda_stream)))
         return lst[:int(n_out.value)]
 
-    def occluded(self, rays, t_range=None, index=None, time_range=None, mode="auto", out=None) -> "OccludedResult":
+    def occluded(self, rays, t_range=None, index=None, time_range=None, mode="auto", out=None, mask=None) -> "OccludedResult":
         """Any-hit query for shadow rays (tor_occluded_device / tor_occluded_host): per listed ray ONE bit, whether
         world.hit(r, t_min, t_max, rec) of the reference returns true on the uploaded scene -- the reference's bit, exactly, at a
         fraction of hit()'s cost: the kernel stops at the first accepted root and writes 4 bytes per ray.
@@ -1222,7 +1302,8 @@ class Context:
         p, direction q - p, range (0.001, 1.0) (visible() builds these).  index: the rays to answer (int32, unique; entries outside
         [0, n) are skipped), None = all.  time_range and mode as for hit().  out: an OccludedResult of an earlier call on as many
         rays, or its raw int32 array, written again (rays that are not listed keep what it holds); otherwise a new one (0).
-        Returns an OccludedResult: occluded (bool view), raw (int32) and mode.  Which object occludes is not defined; ask hit()."""
+        Returns an OccludedResult: occluded (bool view), raw (int32) and mode.  Which object occludes is not defined; ask hit().
+        mask: as for hit() (per-ray words are indexed by the ray): only the objects a ray sees can occlude it."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
         raw = out.raw if hasattr(out, "raw") else out
         if type(rays).__module__.startswith("torch"):
@@ -1241,11 +1322,16 @@ class Context:
             elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.int32 or tuple(raw.shape) != (n,) or raw.device != dev \
                     or not raw.is_contiguous():
                 raise ValueError("Context.occluded: with tensor rays, out must be a contiguous (n,) int32 tensor on the rays' device")
-            _check(lib().tor_occluded_device(self._h, n, C.c_void_p(rays.data_ptr()),
-                                             C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list, tr[0], tr[1], m,
-                                             C.c_void_p(raw.data_ptr()), C.c_void_p(stream)))
+            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list,
+                    tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream))
+            mk = None
+            if mask is None:
+                _check(lib().tor_occluded_device(*args))
+            else:
+                mk, p_mask, word = self._mask_arg("occluded", mask, n, dev)
+                _check(lib().tor_occluded_masked_device(*args, p_mask, word))
             note = last_note() if n and n_list else "occluded: nothing to do"
-            return OccludedResult(raw, raw.view(torch.bool).view(n, 4)[:, 0], note, keep=(rays, t_range, index))
+            return OccludedResult(raw, raw.view(torch.bool).view(n, 4)[:, 0], note, keep=(rays, t_range, index, mk))
         rays = np.ascontiguousarray(rays, dtype=np.float64)
         if rays.ndim != 2 or rays.shape[1] != 7:
             raise ValueError("Context.occluded: rays must have shape (n, 7)")
@@ -1260,9 +1346,13 @@ class Context:
             raw = np.zeros((n,), dtype=np.int32)
         elif not isinstance(raw, np.ndarray) or raw.dtype != np.int32 or raw.shape != (n,) or not raw.flags.c_contiguous:
             raise ValueError("Context.occluded: out must be a contiguous (n,) int32 array")
-        _check(lib().tor_occluded_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
-                                       C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0), p_list, n_list, tr[0], tr[1], m,
-                                       C.c_void_p(raw.ctypes.data if n else 0)))
+        args = (self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
+                p_list, n_list, tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0))
+        if mask is None:
+            _check(lib().tor_occluded_host(*args))
+        else:
+            _mk, p_mask, word = self._mask_arg("occluded", mask, n)
+            _check(lib().tor_occluded_masked_host(*args, p_mask, word))
         note = last_note() if n and n_list else "occluded: nothing to do"
         return OccludedResult(raw, raw.view(np.bool_).reshape(n, 4)[:, 0], note)
 
@@ -1290,13 +1380,17 @@ class Context:
         tr[:, 0], tr[:, 1] = t_min, 1.0
         return rays, tr
 
-    def visible(self, p, q, time=0.0, t_min=0.001, **kw):
+    def visible(self, p, q, time=0.0, t_min=0.001, mask=None, **kw):
         """Is q visible from p?  Sugar over occluded(): the rays p -> q - p with range (t_min, 1.0) (shadow_segments), and
-        ~occluded of them -- a bool tensor / array, one per segment.  kw: index, time_range, mode of occluded()."""
+        ~occluded of them -- a bool tensor / array, one per segment.  mask: what may stand in the way, as for occluded() -- a
+        segment towards a lamp leaves the lamp's group out instead of stopping short of its surface.  kw: index, time_range,
+        mode of occluded()."""
         rays, tr = self.shadow_segments(p, q, time, t_min)
+        if mask is not None:
+            kw["mask"] = mask
         return ~self.occluded(rays, tr, **kw).occluded
 
-    def trace(self, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None):
+    def trace(self, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None, mask=None):
         """A wavefront path tracer on top of bounce(): radiance()'s loop (render.nim:21-47) one step per launch, open where the
         reference is closed.  att = 1; per step: bounce the live rays; a miss ends with sky * att; with `emission` every hit adds
         att * emission[object] (before the attenuation is updated); att *= attenuation for the rays that scattered, which stay
@@ -1308,7 +1402,9 @@ class Context:
         emission: (n_objects, 3) float64.  on_bounce(step, index, result): called after every step with the list that was
         stepped (int32 tensor) and its BounceResult (result.rays are the scattered rays) -- the hook for feature buffers.
         rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the device and come
-        back as numpy.  One time range for all steps: time_range, or the rays' finite times (the library adds 0)."""
+        back as numpy.  One time range for all steps: time_range, or the rays' finite times (the library adds 0).
+        mask: as for bounce(), for every step; or a callable mask(step) -> int | per-ray words, so that step 0 (the camera's rays)
+        sees other objects than the later steps."""
         import torch
         as_numpy = not type(rays).__module__.startswith("torch")
         if as_numpy:
@@ -1329,7 +1425,7 @@ class Context:
         for step in range(int(max_depth)):
             if live.numel() == 0:
                 break
-            res = self.bounce(work, rng, live, tr, mode, out=res)
+            res = self.bounce(work, rng, live, tr, mode, out=res, mask=mask(step) if callable(mask) else mask)
             ran = ran or res.mode
             idx = live.long()
             st = res.status[idx]
@@ -1356,7 +1452,29 @@ class Context:
 
 
 def _mode_of(note: str, prefix: str) -> str:
-    return note[len(prefix):] if note.startswith(prefix) else note
+    for p in (prefix, prefix[:-2] + " (masked): "):
+        if note.startswith(p):
+            return note[len(p):]
+    return note
+
+
+def _mask_words(a: np.ndarray) -> np.ndarray:
+    """Group / mask words as contiguous uint32: int32 words count by their bits, wider integers must fit 32 bits."""
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise ValueError("group and mask words must be integers")
+    if a.dtype.itemsize == 4:
+        return np.ascontiguousarray(a).view(np.uint32)
+    if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError("group and mask words must fit 32 bits")
+    return np.ascontiguousarray((a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32))
+
+
+def groups_by_material(scene) -> np.ndarray:
+    """One group word per object of `scene` (a Scene or its (n, 16) records): 1 << material kind (MAT_LAMBERTIAN 0, MAT_METAL 1,
+    MAT_DIELECTRIC 2), for Context.set_groups.  Shadow rays that skip glass: mask = ~(1 << MAT_DIELECTRIC) & 0xFFFFFFFF."""
+    recs = scene.to_records() if hasattr(scene, "to_records") else np.asarray(scene, dtype=np.float64).reshape(-1, 16)
+    return (np.uint32(1) << recs[:, 10].astype(np.uint32)).astype(np.uint32)
 
 
 class HitResult:
@@ -1368,7 +1486,7 @@ class HitResult:
         self.raw, self._keep = raw, keep   # (keep: the rays' contiguous copy stays alive while the query may run)
         self.p, self.normal, self.t = raw[:, 0:3], raw[:, 3:6], raw[:, 6]
         self.object, self.front_face = words[:, 14], words[:, 15]
-        self.mode = note[len("hit: "):] if note.startswith("hit: ") else note
+        self.mode = _mode_of(note, "hit: ")
 
 
 class BounceResult(HitResult):

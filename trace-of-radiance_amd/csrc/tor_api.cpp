@@ -475,6 +475,8 @@ int tor_scene_upload(TorContext* ctx, TorHittableList world) {
   ctx->n_objects = world.len;
   for (int v = 0; v < 2; ++v) ctx->flat_built[v] = ctx->accel_built[v] = false;
   ctx->f32_built = false;
+  ctx->hitq.groups.clear();  // a new scene: every object in every group (tor_scene_groups)
+  ctx->hitq.groups_gen += 1;
   ctx->scene_ready = true;
   return TOR_OK;
 }

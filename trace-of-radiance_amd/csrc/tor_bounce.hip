@@ -130,6 +130,61 @@ __global__ __launch_bounds__(kStepThreads) void bounce_kernel(const BParams P) {
   write_scatter(P, i, r, g, att, ended);
 }
 
+// bounce_kernel with visibility groups (tor_bounce_masked_device): the closest VISIBLE object scatters.  A kernel of its own,
+// statement for statement bounce_kernel's but for `vis` (hit_masked_kernel, tor_query.hip, says why).
+template <bool BLOCKS>
+__global__ __launch_bounds__(kStepThreads) void bounce_masked_kernel(const BParams P, const MParams mk) {
+  const QParams& p = P.q;
+  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  const bool live = i >= 0;
+  unsigned r_mask = 0u;  // (lanes without a ray see nothing)
+  if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
+  const Sees<true> vis{mk.grp, mk.box_or, r_mask};  // the descent's `vis`
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) {
+    const double* q = P.rays + 7 * i;
+    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+    r.time = q[6];
+    r.t_min = 0.001;  // render.nim:28
+    r.t_max = __builtin_inf();
+  }
+  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
+  QBest b{r.t_max, INT_MAX, -1};
+#include "tor_query_descent.inc"
+  if (!live) return;
+  double* h = P.hits + 8 * i;
+  if (b.slot < 0) {  // miss: the record tor_hit_device writes; ray and state untouched, nothing drawn
+    for (int k = 0; k < 7; ++k) h[k] = 0.0;
+    h[7] = __longlong_as_double((long long)0xffffffffull);
+    write_miss(P, i);
+    return;
+  }
+  // the record, with hit_kernel's operations (tor_query.hip)
+  const double* c = p.cold + 16 * (size_t)b.slot;
+  double cx, cy, cz;
+  centre_at(c, r.time, cx, cy, cz);                                 // moving_spheres.nim:39-44
+  const V3 o = v3(r.ox, r.oy, r.oz), d = v3(r.dx, r.dy, r.dz);
+  const V3 hp = o + d * b.t;                                       // rays.nim:24-25
+  const V3 outward = (hp - v3(cx, cy, cz)) * c[6];                 // spheres.nim:43 (c[6] = 1.0 / radius)
+  const bool front = dot(d, outward) < 0.0;                        // core.nim:47-49
+  const V3 n = front ? outward : -outward;
+  h[0] = hp.x; h[1] = hp.y; h[2] = hp.z;
+  h[3] = n.x; h[4] = n.y; h[5] = n.z;
+  h[6] = b.t;
+  h[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)b.orig));
+  // the scatter
+  const unsigned long long* s = P.rng + 4 * i;
+  Rng g{s[0], s[1], s[2], s[3]};
+  const V3 ud = unit_vector(d);  // materials.nim:40,68
+  V3 att = v3(1.0, 1.0, 1.0);
+  bool ended = false;
+  {
+#include "tor_shade_scatter.inc"
+  }
+  write_scatter(P, i, r, g, att, ended);
+}
+
 // rec.material.scatter for the caller's record: material of hits[i].object, and p, normal, front_face as given
 __global__ __launch_bounds__(kStepThreads) void scatter_kernel(const BParams P) {
   const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
@@ -304,7 +359,8 @@ int query_done(TorContext* ctx, hipStream_t stream) {
 
 // the launches; the arguments are checked, n_rays > 0 and n_list > 0
 int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays, void* d_rng, const int32_t* d_list, int64_t n_list,
-                  double time_lo, double time_hi, int32_t mode, void* d_hits, double* d_att, int32_t* d_status, hipStream_t stream) {
+                  double time_lo, double time_hi, int32_t mode, void* d_hits, double* d_att, int32_t* d_status, hipStream_t stream,
+                  bool masked = false, const uint32_t* d_mask = nullptr, uint32_t mask = 0) {
   // scattered Metal and Dielectric rays carry time 0: the boxes are built for a range that holds it, as radiance_launch builds
   // them, so a chain of steps called with one range looks up ONE cached set of block bounds
   const double lo = time_lo < 0.0 ? time_lo : 0.0, hi = time_hi > 0.0 ? time_hi : 0.0;
@@ -321,13 +377,22 @@ int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays
   P.hits = (double*)d_hits;
   P.att = d_att;
   P.status = d_status;
-  if (blocks) hipLaunchKernelGGL(tor::bounce_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
-  else hipLaunchKernelGGL(tor::bounce_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  if (masked) {
+    tor::MParams mk{};
+    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
+    if (rm != TOR_OK) return rm;
+    if (blocks) hipLaunchKernelGGL(tor::bounce_masked_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P, mk);
+    else hipLaunchKernelGGL(tor::bounce_masked_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P, mk);
+  } else if (blocks) {
+    hipLaunchKernelGGL(tor::bounce_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  } else {
+    hipLaunchKernelGGL(tor::bounce_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
+  }
   HIP_TRY(hipGetLastError());
   const int rd = query_done(ctx, stream);
   if (rd != TOR_OK) return rd;
-  tor::set_last_note(blocks ? std::string("bounce: blocks")
-                            : std::string("bounce: brute force") + (why.empty() ? std::string() : " (" + why + ")"));
+  const std::string what = masked ? "bounce (masked): " : "bounce: ";
+  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
   return TOR_OK;
 }
 
@@ -421,6 +486,18 @@ int tor_bounce_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d
   HIP_TRY(hipSetDevice(ctx->device));
   return bounce_launch("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_attenuation,
                        d_status, (hipStream_t)hip_stream);
+}
+
+int tor_bounce_masked_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
+                             double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_attenuation, int32_t* d_status,
+                             void* hip_stream, const uint32_t* d_mask, uint32_t mask) {
+  const int rc = bounce_args("tor_bounce_masked_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
+                             d_attenuation, d_status);
+  if (rc != TOR_OK) return rc;
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return bounce_launch("tor_bounce_masked_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
+                       d_attenuation, d_status, (hipStream_t)hip_stream, true, d_mask, mask);
 }
 
 int tor_scatter_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, const TorHit* d_hits, TorRng* d_rng, const int32_t* d_list,

@@ -109,6 +109,12 @@ struct HitQueryState {
   std::vector<double> obj_cold_host;  // ... their host copy (source of the asynchronous upload) ...
   int64_t obj_scene = -1;           // ... and the scene generation they were built for, -1 = none
   DeviceBuffer sel;                 // tor_bounce_select_device: the survivor count and the compaction's block offsets
+  // visibility groups (tor_scene_groups; read by the masked queries alone)
+  std::vector<uint32_t> groups;     // one word per object in list order; empty = every object 0xFFFFFFFF
+  int64_t groups_gen = 0;           // bumped whenever the words change (tor_scene_groups, an upload that replaces the scene)
+  DeviceBuffer grp[2];              // the words in slot order, padding slots 0: [0] the flat layout's; [1] the culling layout's, then one
+  std::vector<uint32_t> grp_host[2];  // OR-word per box record of `bnd` (block boxes, slack, super boxes); their host copies (upload source) ...
+  int64_t grp_scene[2] = {-1, -1}, grp_gen[2] = {-1, -1};  // ... and the scene generation and groups_gen they were built for
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

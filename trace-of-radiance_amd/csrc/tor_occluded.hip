@@ -184,6 +184,96 @@ __global__ __launch_bounds__(kHitThreads) void occluded_kernel(const OParams P) 
   if (live) P.occluded[i] = found ? 1 : 0;
 }
 
+// occluded_kernel with visibility groups (tor_occluded_masked_device): only the objects a ray sees can occlude it.  The OR of the file
+// head, over the sub-list.  A kernel of its own (hit_masked_kernel, tor_query.hip, says why); it keeps every early exit, and an exit
+// counts a lane as settled only once it has FOUND an occluder: a lane whose mask rejects a slot or a box is simply not tested there.
+template <bool BLOCKS>
+__global__ __launch_bounds__(kHitThreads) void occluded_masked_kernel(const OParams P, const MParams mk) {
+  const QParams& p = P.q;
+  const long long e = (long long)blockIdx.x * kHitThreads + threadIdx.x;
+  long long i = -1;  // the ray of list entry e; -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
+  if (e < P.n_list) {
+    const long long v = P.list ? (long long)P.list[e] : e;
+    if (v >= 0 && v < p.n_rays) i = v;
+  }
+  const bool live = i >= 0;
+  unsigned r_mask = 0u;  // (lanes without a ray see nothing)
+  if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
+  const Sees<true> vis{mk.grp, mk.box_or, r_mask};
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) {
+    const double* q = p.rays + 7 * i;
+    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+    r.time = q[6];
+    if (p.t_range) {
+      r.t_min = p.t_range[2 * i];
+      r.t_max = p.t_range[2 * i + 1];
+    } else {
+      r.t_min = 0.001;  // render.nim:34
+      r.t_max = __builtin_inf();
+    }
+  }
+  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
+  bool found = false;
+  // wave-uniform: every unsettled lane that sees the slot tests the same record; the wave leaves when no unsettled lane is left (a
+  // lane that does not see a slot stays unsettled)
+  for (int s = 0; s < p.n_uniform; ++s) {
+    if (__ballot(live && !found) == 0) break;
+    if (live && !found && vis.slot_u(s)) found = occludes((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)s), r);
+  }
+  if constexpr (BLOCKS) {
+    const double ex = r.ox - p.org[0], ey = r.oy - p.org[1], ez = r.oz - p.org[2];
+    const bool boxed = live && (r.t_min >= 0.0) && (r.time >= p.time_lo) && (r.time <= p.time_hi) &&
+                       (ex * ex + ey * ey + ez * ez <= p.reach2) && (r.a >= p.a_min);
+    const bool walk = live && !boxed;
+    // rays the boxes do not hold for: every spatial slot, wave-uniform, until all of them are settled
+    for (int s = 0; s < p.n_spatial; ++s) {
+      if (__ballot(walk && !found) == 0) break;
+      if (walk && !found && vis.slot_u(p.spatial_base + s)) found = occludes((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)(p.spatial_base + s)), r);
+    }
+    if (boxed && !found) {
+      const double ix = 1.0 / r.dx, iy = 1.0 / r.dy, iz = 1.0 / r.dz;
+      auto test_box = [&](int box) {  // the blocks behind block box `box`, 8 objects each
+        for (int fk = 0; fk < p.fanout && !found; ++fk) {
+          const int slot0 = p.spatial_base + 8 * (box * p.fanout + fk);
+          bool any = false;
+          for (int k = 0; k < 8; ++k)
+            if (vis.slot(slot0 + k)) any |= occludes((qgdptr)(uintptr_t)(p.cold + 16 * (size_t)(slot0 + k)), r);
+          found = any;
+        }
+      };
+      const int n_top = p.two_level ? p.n_super : p.n_boxes;
+      const int top0 = p.two_level ? p.super0 : 0;
+      // the top-level boxes 64 at a time (scalar loads); then the ones the ray's segment enters
+      for (int c0 = 0; c0 < n_top && !found; c0 += 64) {
+        const int cn = n_top - c0 < 64 ? n_top - c0 : 64;
+        unsigned long long m = 0;
+        for (int j = 0; j < cn; ++j)
+          if (vis.box_u(top0 + c0 + j) && slab_clipped((qcdptr)(uintptr_t)(p.bnd + 8 * (size_t)(top0 + c0 + j)), r, ix, iy, iz)) m |= 1ull << j;
+        while (m != 0 && !found) {
+          const int top = c0 + __builtin_ctzll(m);
+          m &= m - 1;
+          if (!p.two_level) {
+            test_box(top);
+            continue;
+          }
+          // super box `top`: its 8 block boxes (NaN padding boxes are never entered)
+          unsigned m8 = 0;
+          for (int k = 0; k < 8; ++k)
+            if (vis.box(8 * top + k) && slab_clipped((qgdptr)(uintptr_t)(p.bnd + 8 * (size_t)(8 * top + k)), r, ix, iy, iz)) m8 |= 1u << k;
+          while (m8 != 0 && !found) {
+            const int k = __builtin_ctz(m8);
+            m8 &= m8 - 1;
+            test_box(8 * top + k);
+          }
+        }
+      }
+    }
+  }
+  if (live) P.occluded[i] = found ? 1 : 0;
+}
+
 }  // namespace
 }  // namespace tor
 
@@ -213,7 +303,8 @@ int occluded_args(const char* who, TorContext* ctx, int64_t n_rays, const void* 
 
 // the launch; the arguments are checked, n_rays > 0 and n_list > 0
 int occluded_launch(const char* who, TorContext* ctx, int64_t n_rays, const void* d_rays, const double* d_t_range, const int32_t* d_list,
-                    int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, hipStream_t stream) {
+                    int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, hipStream_t stream,
+                    bool masked = false, const uint32_t* d_mask = nullptr, uint32_t mask = 0) {
   tor::HitQueryState& hq = ctx->hitq;
   tor::OParams P{};
   bool blocks = false;
@@ -227,14 +318,58 @@ int occluded_launch(const char* who, TorContext* ctx, int64_t n_rays, const void
   P.n_list = (long long)n_list;
   P.occluded = d_occluded;
   const unsigned grid = (unsigned)((n_list + tor::kHitThreads - 1) / tor::kHitThreads);
-  if (blocks) hipLaunchKernelGGL(tor::occluded_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
-  else hipLaunchKernelGGL(tor::occluded_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
+  if (masked) {
+    tor::MParams mk{};
+    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
+    if (rm != TOR_OK) return rm;
+    if (blocks) hipLaunchKernelGGL(tor::occluded_masked_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
+    else hipLaunchKernelGGL(tor::occluded_masked_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
+  } else if (blocks) {
+    hipLaunchKernelGGL(tor::occluded_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
+  } else {
+    hipLaunchKernelGGL(tor::occluded_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(hq.ev_done, stream));
   hq.launched = true;
   hq.stream = (void*)stream;
-  tor::set_last_note(blocks ? std::string("occluded: blocks")
-                            : std::string("occluded: brute force") + (why.empty() ? std::string() : " (" + why + ")"));
+  const std::string what = masked ? "occluded (masked): " : "occluded: ";
+  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
+  return TOR_OK;
+}
+
+// tor_occluded_host / tor_occluded_masked_host (masks: nullable host words, staged with the other arrays)
+int occluded_host(const char* who, TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
+                  int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded, bool masked, const uint32_t* masks,
+                  uint32_t mask) {
+  int rc = occluded_args(who, ctx, n_rays, rays, list, n_list, time_lo, time_hi, mode, occluded);
+  if (rc != TOR_OK) return rc;
+  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  tor::HitQueryState& hq = ctx->hitq;
+  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
+  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
+  // rays, t ranges, the list, the output (rays that are not listed keep what the caller holds) and the masks in, each padded to 64
+  // bytes; the query on the default stream; the output back
+  const size_t n = (size_t)n_rays;
+  const size_t bytes[5] = {n * sizeof(TorRay), t_range ? n * 16 : 0, list ? (size_t)n_list * 4 : 0, n * 4, masked && masks ? n * 4 : 0};
+  const void* const host[5] = {rays, t_range, list, occluded, masks};
+  size_t off[5], total = 0;
+  for (int k = 0; k < 5; ++k) {
+    off[k] = total;
+    total += (bytes[k] + 63) / 64 * 64;
+  }
+  HIP_TRY(hq.io.ensure(total));
+  char* base = (char*)hq.io.ptr;
+  for (int k = 0; k < 5; ++k)
+    if (bytes[k]) HIP_TRY(hipMemcpy(base + off[k], host[k], bytes[k], hipMemcpyHostToDevice));
+  rc = occluded_launch(who, ctx, n_rays, base + off[0], t_range ? (const double*)(base + off[1]) : nullptr,
+                       list ? (const int32_t*)(base + off[2]) : nullptr, n_list, time_lo, time_hi, mode, (int32_t*)(base + off[3]), nullptr,
+                       masked, bytes[4] ? (const uint32_t*)(base + off[4]) : nullptr, mask);
+  if (rc != TOR_OK) return rc;
+  HIP_TRY(hipMemcpy(occluded, base + off[3], bytes[3], hipMemcpyDeviceToHost));
   return TOR_OK;
 }
 
@@ -255,34 +390,26 @@ int tor_occluded_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, c
 
 int tor_occluded_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list, int64_t n_list,
                       double time_lo, double time_hi, int32_t mode, int32_t* occluded) {
-  int rc = occluded_args("tor_occluded_host", ctx, n_rays, rays, list, n_list, time_lo, time_hi, mode, occluded);
+  return occluded_host("tor_occluded_host", ctx, n_rays, rays, t_range, list, n_list, time_lo, time_hi, mode, occluded, false, nullptr, 0);
+}
+
+int tor_occluded_masked_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
+                               int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, void* hip_stream,
+                               const uint32_t* d_mask, uint32_t mask) {
+  const int rc = occluded_args("tor_occluded_masked_device", ctx, n_rays, d_rays, d_list, n_list, time_lo, time_hi, mode, d_occluded);
   if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_occluded_host: no scene uploaded");
+  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_occluded_masked_device: no scene uploaded");
   if (n_rays == 0 || n_list == 0) return TOR_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  tor::HitQueryState& hq = ctx->hitq;
-  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
-  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
-  // rays, t ranges, the list and the output in (rays that are not listed keep what the caller holds), each padded to 64 bytes; the
-  // query on the default stream; the output back
-  const size_t n = (size_t)n_rays;
-  const size_t bytes[4] = {n * sizeof(TorRay), t_range ? n * 16 : 0, list ? (size_t)n_list * 4 : 0, n * 4};
-  const void* const host[4] = {rays, t_range, list, occluded};
-  size_t off[4], total = 0;
-  for (int k = 0; k < 4; ++k) {
-    off[k] = total;
-    total += (bytes[k] + 63) / 64 * 64;
-  }
-  HIP_TRY(hq.io.ensure(total));
-  char* base = (char*)hq.io.ptr;
-  for (int k = 0; k < 4; ++k)
-    if (bytes[k]) HIP_TRY(hipMemcpy(base + off[k], host[k], bytes[k], hipMemcpyHostToDevice));
-  rc = occluded_launch("tor_occluded_host", ctx, n_rays, base + off[0], t_range ? (const double*)(base + off[1]) : nullptr,
-                       list ? (const int32_t*)(base + off[2]) : nullptr, n_list, time_lo, time_hi, mode, (int32_t*)(base + off[3]), nullptr);
-  if (rc != TOR_OK) return rc;
-  HIP_TRY(hipMemcpy(occluded, base + off[3], bytes[3], hipMemcpyDeviceToHost));
-  return TOR_OK;
+  return occluded_launch("tor_occluded_masked_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded,
+                         (hipStream_t)hip_stream, true, d_mask, mask);
+}
+
+int tor_occluded_masked_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
+                             int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded, const uint32_t* masks,
+                             uint32_t mask) {
+  return occluded_host("tor_occluded_masked_host", ctx, n_rays, rays, t_range, list, n_list, time_lo, time_hi, mode, occluded, true, masks,
+                       mask);
 }
 
 }  // extern "C"

@@ -44,6 +44,43 @@ struct QParams {
   double a_min;             // smallest |d|^2 that may use the boxes
 };
 
+// visibility groups (tor_scene_groups): what a masked kernel gets next to its QParams
+struct MParams {
+  const unsigned* grp;       // one group word per cold slot of the layout p.cold belongs to (padding slots: 0)
+  const unsigned* box_or;    // blocks only: per box record of p.bnd the OR of the words behind it (block box: its fanout * 8 slots)
+  const unsigned* ray_mask;  // one mask per ray, or null: every ray uses `mask`
+  unsigned mask;
+};
+
+typedef const unsigned __attribute__((address_space(4))) * qcuptr;  // scalar view of the group words, as qcdptr is of the records
+
+// What the descent (tor_query_descent.inc) asks before it touches a slot or a box: does this lane's ray see anything there?
+// _u: wave-uniform index, read through a scalar load.  Sees<false> answers yes without reading anything.
+template <bool MASKED>
+struct Sees {
+  const unsigned* grp;
+  const unsigned* box_or;
+  unsigned m;  // the lane's mask
+  __device__ __forceinline__ bool slot_u(int s) const {
+    if constexpr (MASKED) return (((qcuptr)(uintptr_t)grp)[s] & m) != 0u;
+    else return true;
+  }
+  __device__ __forceinline__ bool slot(int s) const {
+    if constexpr (MASKED) return (grp[s] & m) != 0u;
+    else return true;
+  }
+  __device__ __forceinline__ bool box_u(int rec) const {
+    if constexpr (MASKED) return (((qcuptr)(uintptr_t)box_or)[rec] & m) != 0u;
+    else return true;
+  }
+  __device__ __forceinline__ bool box(int rec) const {
+    if constexpr (MASKED) return (box_or[rec] & m) != 0u;
+    else return true;
+  }
+};
+// the descent's `vis` in a kernel without masks; a masked kernel declares a local Sees<true> vis in its place
+constexpr Sees<false> vis{nullptr, nullptr, 0u};
+
 struct QRay {
   double ox, oy, oz, dx, dy, dz, time, t_min, t_max, a;
 };
@@ -243,6 +280,64 @@ int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi
     p.cold = ctx->flat[0].cold;
     p.n_uniform = ctx->flat[0].n_sorted;
   }
+  return TOR_OK;
+}
+
+// The group words of a masked launch, after query_setup (`blocks`: which layout p.cold belongs to), into mk: one word per cold slot
+// of that layout -- the object's word (tor_scene_groups; 0xFFFFFFFF without any), 0 for a padding slot -- and, for the culling
+// layout, behind them one OR-word per box record of `bnd`: a block box over the fanout * 8 slots it stands for, a super box over its
+// 8 block boxes, 0 for padding and slack records.  Cached per layout; rebuilt when the words or the scene change.
+int masked_setup(TorContext* ctx, bool blocks, const uint32_t* d_mask, uint32_t mask, hipStream_t stream, MParams& mk) {
+  tor::HitQueryState& hq = ctx->hitq;
+  const int lay = blocks ? 1 : 0;
+  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
+  const tor::HostAccel& acc = ctx->accel[0];
+  const size_t n_slots = blocks ? acc.spatial_base + acc.n_blocks * tor::kPad : (size_t)ctx->flat[0].n_sorted;
+  if (hq.grp_scene[lay] != gen || hq.grp_gen[lay] != hq.groups_gen) {
+    hq.grp_scene[lay] = -1;
+    if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
+    const int64_t n = ctx->n_objects;
+    auto word_of = [&](const double* c) -> uint32_t {  // of the object in cold record c
+      if (c[15] == -1.0) return 0u;                    // padding slot
+      int64_t orig;
+      std::memcpy(&orig, &c[14], 8);
+      if (orig < 0 || orig >= n) return 0u;
+      return hq.groups.empty() ? 0xFFFFFFFFu : hq.groups[(size_t)orig];
+    };
+    std::vector<uint32_t>& w = hq.grp_host[lay];
+    if (blocks) {
+      if (acc.cold.size() < 16 * n_slots) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: the culling layout's cold records are short");
+      const size_t n_bnd_p = tor::accel_boxes_padded(acc), n_super_p = (n_bnd_p / tor::kPad + tor::kPad - 1) / tor::kPad * tor::kPad;
+      w.assign(n_slots + n_bnd_p + 1 + n_super_p + 1, 0u);
+      for (size_t s = 0; s < n_slots; ++s) w[s] = word_of(&acc.cold[16 * s]);
+      uint32_t* box = w.data() + n_slots;
+      const size_t fan = acc.fanout > 0 ? (size_t)acc.fanout : 1;
+      for (size_t b = 0; b < acc.n_boxes; ++b)
+        for (size_t s = b * fan * tor::kPad; s < (b + 1) * fan * tor::kPad && s < acc.n_blocks * tor::kPad; ++s)
+          box[b] |= w[acc.spatial_base + s];
+      for (size_t b = 0; b < acc.n_boxes; ++b) box[n_bnd_p + 1 + b / tor::kPad] |= box[b];
+    } else {
+      // the flat layout's slot order: the layout ensure_layouts built, built again on the host (its cold records name the objects)
+      std::vector<int64_t> ids((size_t)n);
+      for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
+      tor::HostLayout flat;
+      std::string err;
+      if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, flat, err, nullptr))
+        return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: " + err);
+      if (flat.n_sorted != n_slots || flat.cold.size() < 16 * n_slots)
+        return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: the flat layout's slots do not match the device's");
+      w.assign(n_slots, 0u);
+      for (size_t s = 0; s < n_slots; ++s) w[s] = word_of(&flat.cold[16 * s]);
+    }
+    HIP_TRY(hq.grp[lay].ensure(w.size() * 4 + 64));
+    if (!w.empty()) HIP_TRY(hipMemcpyAsync(hq.grp[lay].ptr, w.data(), w.size() * 4, hipMemcpyHostToDevice, stream));
+    hq.grp_scene[lay] = gen;
+    hq.grp_gen[lay] = hq.groups_gen;
+  }
+  mk.grp = (const unsigned*)hq.grp[lay].ptr;
+  mk.box_or = mk.grp + n_slots;
+  mk.ray_mask = (const unsigned*)d_mask;
+  mk.mask = mask;
   return TOR_OK;
 }
 
