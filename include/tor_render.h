@@ -619,6 +619,49 @@ TOR_API int tor_bounce_masked_device(TorContext* ctx, int64_t n_rays, TorRay* d_
                                      int64_t n_list, double time_lo, double time_hi, int32_t mode, TorHit* d_hits,
                                      double* d_attenuation, int32_t* d_status, void* hip_stream, const uint32_t* d_mask, uint32_t mask);
 
+/* ---- ordered multi-hit queries: the first K surface crossings of a ray, in order ------------------------------------------------
+ * Transparent shadows (which surfaces a segment crosses, how long it runs inside glass), depth peeling and layered feature buffers,
+ * thickness and inside / outside parity, picking through glass: one walk of the scene where K chained tor_hit_device launches with
+ * a moving t_min take K walks and cannot tell two surfaces at the same t apart.
+ * For ray r, range (t_min, t_max) and object j of the uploaded list the roots are the reference's (spheres.nim:29-48,
+ * moving_spheres.nim:39-66): s0 = (-half_b - sqrt(disc)) / a and s1 = (-half_b + sqrt(disc)) / a when disc > 0 (strict), float64,
+ * unfused, correctly rounded `/` and sqrt -- the arithmetic of tor_hit_device.
+ *   crossing  a triple (t, object, which), one for EACH root with t_min < t < t_max (both strict, as in the reference): which = 0
+ *             for s0, 1 for s1; both roots of one object count; NaN and infinite roots are no crossings
+ *   order     t ascending, compared as doubles; equal t: the lower object first, then which 0 before 1
+ *   result    d_cross[i * k + m], m < d_count[i] = min(total, k): the first crossings in that order; entries d_count[i] .. k - 1
+ *             hold t = 0, object = -1, which = 0.  A host that must know whether MORE than k crossings exist asks for k + 1.
+ *   records   d_records (nullable, DEVICE): one TorHit per stored crossing, d_records[i * k + m]: p = origin + direction * t
+ *             (rays.nim:24-25), normal and front_face by tor_hit_device's formula for that (t, object) (vec3s.nim:93-94,
+ *             core.nim:47-49; negative radii go through it as they are); unused entries hold the miss record (object = -1, the rest 0)
+ * 1 <= k <= TOR_CROSSINGS_MAX.  Bit for bit: crossing 0 and its record are tor_hit_device's answer and d_count[i] == 0 exactly on a
+ * miss; d_count[i] > 0 is tor_occluded_device's bit; on a ray without equal-t crossings, crossing m + 1 is what tor_hit_device
+ * returns with t_min := crossing m's t.
+ * Visibility groups: with d_mask (nullable, DEVICE: one word per ray, indexed by the ray) or mask (the mask of every ray when d_mask
+ * is NULL) object j takes part for ray i iff groups[j] & mask_i != 0 (tor_scene_groups); `object` is the index in the FULL list; a
+ * ray with mask 0 has no crossings.  d_mask == NULL with mask == 0xFFFFFFFF is the unmasked query: it neither builds nor reads any
+ * group state.
+ * d_t_range (nullable, DEVICE): 2 float64 per ray {t_min, t_max}; NULL = render.nim's (0.001, +inf).  d_list / n_list follow
+ * tor_occluded_device's rules: NULL = every ray (n_list must be n_rays); entries outside [0, n_rays) are skipped; entries must be
+ * unique; rays that are not listed keep what d_cross, d_count and d_records hold; n_list == 0 and n_rays == 0 are no-ops.  mode and
+ * [time_lo, time_hi] work as in tor_hit_device (a speed hint only): rays the boxes do not hold for walk every spatial slot, so every
+ * result is exact whatever the hint.  With the blocks a box is entered only while its entry lies at or below the k-th crossing found
+ * so far, so small k costs little.  tor_last_note(): "crossings: blocks" | "crossings: brute force (...)" ("crossings (masked): ..."
+ * with masks).  Asynchronous on hip_stream, one stream per context as for the other queries; a query leaves every render state
+ * alone.  TOR_ERR_INVALID_ARGUMENT (nothing written) for n_rays < 0, k outside 1 .. TOR_CROSSINGS_MAX, a context without a scene, a
+ * non-finite or inverted time range, a mode outside 0..2, n_list < 0, a NULL list with n_list != n_rays, NULL d_rays, d_cross or
+ * d_count with work to do.
+ * tor_crossings_host: the same on host arrays (masks: nullable, HOST), blocking (every array copied in, the query, the outputs
+ * copied out); it waits for the context's last render launch and last query as tor_hit_host does. */
+enum { TOR_CROSSINGS_MAX = 16 };
+typedef struct TorCrossing { double t; int32_t object; int32_t which; } TorCrossing;  /* 16 B */
+TOR_API int tor_crossings_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
+                                 int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi,
+                                 int32_t mode, TorCrossing* d_cross, int32_t* d_count, TorHit* d_records, void* hip_stream);
+TOR_API int tor_crossings_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
+                               int64_t n_list, int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi,
+                               int32_t mode, TorCrossing* cross, int32_t* count, TorHit* records);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

@@ -162,10 +162,12 @@ EXPORTED_SYMBOLS = [
     "tor_occluded_device", "tor_occluded_host",
     "tor_scene_groups", "tor_hit_masked_device", "tor_hit_masked_host", "tor_occluded_masked_device", "tor_occluded_masked_host",
     "tor_bounce_masked_device",
+    "tor_crossings_device", "tor_crossings_host",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
+CROSSINGS_MAX = 16   # TOR_CROSSINGS_MAX: the most crossings per ray Context.crossings keeps
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2   # Material kinds (TOR_LAMBERTIAN ..): groups_by_material gives 1 << kind
 
 _lib = None
@@ -324,6 +326,8 @@ def lib():
         _bind_occluded(L)
     if hasattr(L, "tor_scene_groups"):  # (... and one older than the visibility groups)
         _bind_masked(L)
+    if hasattr(L, "tor_crossings_device"):  # (... and one older than the ordered multi-hit queries)
+        _bind_crossings(L)
     _lib = L
     return L
 
@@ -367,6 +371,12 @@ def _bind_masked(L) -> None:
     L.tor_occluded_masked_device.argtypes = list(L.tor_occluded_device.argtypes) + [v, u32]
     L.tor_occluded_masked_host.argtypes = list(L.tor_occluded_host.argtypes) + [v, u32]
     L.tor_bounce_masked_device.argtypes = list(L.tor_bounce_device.argtypes) + [v, u32]
+
+
+def _bind_crossings(L) -> None:
+    v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
+    L.tor_crossings_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v, v]
+    L.tor_crossings_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -1356,6 +1366,93 @@ class Context:
         note = last_note() if n and n_list else "occluded: nothing to do"
         return OccludedResult(raw, raw.view(np.bool_).reshape(n, 4)[:, 0], note)
 
+    def crossings(self, rays, k, t_range=None, index=None, time_range=None, mode="auto", mask=None, records=False,
+                  out=None) -> "CrossingsResult":
+        """Ordered multi-hit query (tor_crossings_device / tor_crossings_host): per listed ray the first k surface crossings in
+        (t_min, t_max), in order -- what transparent shadows, depth peeling, thickness / inside parity and picking through glass
+        need, in one walk of the scene instead of k chained hit() calls.
+
+        A crossing is (t, object, which): one for EACH root of the reference's sphere test (spheres.nim:29-48,
+        moving_spheres.nim:39-66) with t_min < t < t_max, which = 0 for the near root (-half_b - sqrt(disc)) / a and 1 for the far
+        one; ordered by t, then object, then which.  count (n,) is min(total, k); entries count .. k - 1 hold t = 0, object = -1,
+        which = 0.  To learn whether MORE than k crossings exist, ask for k + 1.  Crossing 0 is hit()'s answer and count > 0 is
+        occluded()'s bit, bit for bit.  1 <= k <= CROSSINGS_MAX.
+
+        rays: (n, 7) float64 -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or anything numpy takes
+        (copied, blocking).  t_range, index, time_range and mode as for occluded().  mask: as for hit() -- only the objects a ray
+        sees are crossed, `object` stays the index in the full list; None is the unmasked query and reads no group state.
+        records=True adds one TorHit per stored crossing (hits, (n, k, 8) raw records as hit() writes them; unused entries hold the
+        miss record).  out: a CrossingsResult of an earlier call with the same n, k and records, written again (rays that are not
+        listed keep what it holds); otherwise a new one (every entry unused, count 0).
+        Returns a CrossingsResult: t (n, k), object, which, count (n,), raw, hits (None without records) and mode."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        k = int(k)
+        if not 1 <= k <= CROSSINGS_MAX:
+            raise ValueError(f"Context.crossings: k must be in 1 .. {CROSSINGS_MAX}")
+        if out is not None and not isinstance(out, CrossingsResult):
+            raise ValueError("Context.crossings: out must be a CrossingsResult")
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            rays, _, dev, stream = self._step_tensors("crossings", rays, None)
+            n = int(rays.shape[0])
+            if t_range is not None:
+                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
+                        or t_range.device != dev:
+                    raise ValueError("Context.crossings: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
+                t_range = t_range.contiguous()
+            index, n_list, p_list = self._step_index(index, n, dev)
+            tr = self._time_range_of(rays, time_range)
+            if out is None:
+                raw = torch.zeros((n, k, 2), dtype=torch.float64, device=dev)
+                raw.view(torch.int32)[:, :, 2] = -1
+                count = torch.zeros((n,), dtype=torch.int32, device=dev)
+                hits = None
+                if records:
+                    hits = torch.zeros((n, k, 8), dtype=torch.float64, device=dev)
+                    hits.view(torch.int32)[:, :, 14] = -1
+            else:
+                raw, count, hits = out.raw, out.count, out.hits
+                if not isinstance(raw, torch.Tensor) or raw.device != dev or tuple(raw.shape) != (n, k, 2) or not raw.is_contiguous() \
+                        or tuple(count.shape) != (n,) or not count.is_contiguous() or (hits is not None) != bool(records):
+                    raise ValueError("Context.crossings: out must come from a call on the rays' device with the same n, k and records")
+            mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("crossings", mask, n, dev)
+            _check(lib().tor_crossings_device(self._h, n, C.c_void_p(rays.data_ptr()),
+                                              C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list, k, p_mask, word,
+                                              tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(count.data_ptr()),
+                                              C.c_void_p(hits.data_ptr() if hits is not None else 0), C.c_void_p(stream)))
+            note = last_note() if n and n_list else "crossings: nothing to do"
+            return CrossingsResult(raw, raw.view(torch.int32), count, hits, note, keep=(rays, t_range, index, mk))
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 7:
+            raise ValueError("Context.crossings: rays must have shape (n, 7)")
+        n = int(rays.shape[0])
+        if t_range is not None:
+            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
+            if t_range.shape != (n, 2):
+                raise ValueError("Context.crossings: t_range must have shape (n, 2)")
+        index, n_list, p_list = self._step_index(index, n)
+        tr = self._time_range_of(rays, time_range)
+        if out is None:
+            raw = np.zeros((n, k, 2), dtype=np.float64)
+            raw.view(np.int32)[:, :, 2] = -1
+            count = np.zeros((n,), dtype=np.int32)
+            hits = None
+            if records:
+                hits = np.zeros((n, k, 8), dtype=np.float64)
+                hits.view(np.int32)[:, :, 14] = -1
+        else:
+            raw, count, hits = out.raw, out.count, out.hits
+            if not isinstance(raw, np.ndarray) or raw.shape != (n, k, 2) or not raw.flags.c_contiguous or count.shape != (n,) \
+                    or not count.flags.c_contiguous or (hits is not None) != bool(records):
+                raise ValueError("Context.crossings: out must come from a numpy call with the same n, k and records")
+        _mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("crossings", mask, n)
+        _check(lib().tor_crossings_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
+                                        C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0), p_list, n_list, k, p_mask, word,
+                                        tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0), C.c_void_p(count.ctypes.data if n else 0),
+                                        C.c_void_p(hits.ctypes.data if hits is not None and n else 0)))
+        note = last_note() if n and n_list else "crossings: nothing to do"
+        return CrossingsResult(raw, raw.view(np.int32), count, hits, note)
+
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
@@ -1508,6 +1605,19 @@ class OccludedResult:
     def __init__(self, raw, occluded, note: str, keep=None):
         self.raw, self.occluded, self._keep = raw, occluded, keep   # (keep: the operands' contiguous copies stay alive while the query may run)
         self.mode = _mode_of(note, "occluded: ")
+
+
+class CrossingsResult:
+    """Ordered crossings of Context.crossings, k per ray (TorCrossing, include/tor_render.h): t (n, k) float64, object (n, k) int32
+    (-1 = unused entry) and which (n, k) int32 (0 = the near root, 1 = the far one) are views of `raw` ((n, k, 2) float64, the
+    entries as the library wrote them); count (n,) int32 is how many entries of a ray are crossings; hits is None, or with
+    records=True the (n, k, 8) raw TorHit records (HitResult's layout per crossing).  Torch tensors or numpy arrays, as the rays
+    were.  `mode` is what ran: "blocks" or "brute force (...)" (tor_last_note)."""
+
+    def __init__(self, raw, words, count, hits, note: str, keep=None):
+        self.raw, self.count, self.hits, self._keep = raw, count, hits, keep   # (keep: the operands stay alive while the query may run)
+        self.t, self.object, self.which = raw[:, :, 0], words[:, :, 2], words[:, :, 3]
+        self.mode = _mode_of(note, "crossings: ")
 
 
 class Progressive:

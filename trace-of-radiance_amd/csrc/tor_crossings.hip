@@ -1,0 +1,513 @@
+// tor_crossings.hip -- batched ordered multi-hit queries against the uploaded scene (tor_crossings_device / tor_crossings_host,
+// include/tor_render.h): for each listed ray the first K surface crossings in (t_min, t_max), in order, on gfx950.  What a host asks
+// for transparent shadows (the surfaces a segment crosses, or the path length inside glass), depth peeling, thickness and inside /
+// outside parity, and picking through glass -- in one walk of the scene where K dependent tor_hit_device launches take K.
+//
+// What a crossing is.  For ray r and object j the reference computes (spheres.nim:29-48 / moving_spheres.nim:39-66)
+//     s0 = (-half_b - sqrt(disc)) / a,  s1 = (-half_b + sqrt(disc)) / a     when disc > 0 (strict),
+// in float64, unfused, with correctly rounded `/` and sqrt: exact_test's operations in exact_test's order (tor_query.hpp).  Every
+// root with t_min < s < t_max (both strict, as in the reference) is a crossing (t, object, which): which = 0 for s0, 1 for s1; BOTH
+// roots of one object count.  NaN and infinite roots fail the comparisons; padding slots have none.  The crossings of a ray are
+// ordered by the key (t, object, which), ascending, t compared as a double; the query returns the first min(total, K) of them.
+//
+// Why the answer is order independent.  The crossings of a ray are a SET of keys, each a function of the ray, the range and one
+// object alone -- no closest_so_far couples the objects.  No two keys are equal (object and which tell them apart), so "the K
+// smallest keys of the set, ascending" is one well-defined list whatever order the objects are visited in.  Inserting the keys one by
+// one into a sorted list that keeps its K smallest gives that list for every insertion order: a key among the final K is never
+// displaced (at most K - 1 keys are smaller), and a key that is not is displaced by the time the last smaller one has arrived.  For
+// the same reason a key may be dropped on sight once K keys that are smaller have been seen, and objects that cannot produce a key
+// among the K smallest may be skipped.  Consequences, bit for bit: crossing 0 is tor_hit_device's (t, object) -- per object the first
+// root in range is never larger than the second, so the smallest accepted root over the list, ties to the lowest index, is the
+// smallest key; count > 0 is tor_occluded_device's bit; and on a ray without equal-t crossings, crossing k + 1 is tor_hit_device's
+// answer with t_min := crossing k's t (same ray, same objects, same roots; only the range moves).
+//
+//   crossings_kernel<false, MASKED, CAP>  brute force: one listed ray per lane; every cold slot of the flat layout in a wave-uniform
+//                                         loop (records through the scalar-load view)
+//   crossings_kernel<true, MASKED, CAP>   blocks: the culling layout's always-objects in the same loop; the rays the boxes do not hold
+//                                         for (time outside the range or NaN, t_min not >= 0, origin beyond `reach`, a < a_min) walk
+//                                         every spatial slot, wave-uniform; the others descend the super boxes, block boxes and blocks
+//                                         per lane, the records of a block loaded and tested as a batch before any is inserted (all 8
+//                                         with CAP = 4; 4 and 4 with CAP = 16, whose list leaves fewer registers)
+//   MASKED                                with visibility groups (Sees<true>, masked_setup): object j takes part for ray i iff
+//                                         groups[j] & mask_i != 0 -- the same set restricted to the objects the ray sees, `object` in
+//                                         the full list's numbering; a box whose OR-word shares no bit with the mask is not entered
+//   CAP                                   4 (K <= 4, the transparent-shadow case) or TOR_CROSSINGS_MAX = 16: the sorted list lives in
+//                                         registers, per entry t and one packed word object * 2 + which, and an insertion is a fully
+//                                         unrolled compare-and-select chain over the CAP entries.  No array is indexed dynamically: the
+//                                         K entries in use are the LAST K of the CAP (the ones in front hold -inf and never move), so
+//                                         the K-th smallest is always entry CAP - 1, a fixed register.  No variant uses scratch.
+//
+// The bound shrinks.  While the list holds fewer than K crossings the bound is t_max; once it is full it is the K-th entry's t, and it
+// only ever decreases.  A per-object root above the bound is dropped; a root EQUAL to it goes through the full key compare (a lower
+// object index at the same t must displace the K-th).  A box is entered iff the slab test passes and t_in * (1 - 2^-40) <= bound --
+// non-strict on the keep side for the same reason.
+//
+// Why the clipped boxes stay exact.  Let `sol` be a root that belongs to the final answer, of a spatial object, for a ray that uses
+// the boxes (0 <= t_min < sol < t_max, time inside the boxes' range, origin within `reach`, a >= a_min), and P = origin + sol *
+// direction.  The final answer's keys are at or below the final bound, and the bound at any earlier moment is no smaller: sol <=
+// bound whenever a box is tested.
+//  (1) P lies in the object's box with a margin.  The head of tor_occluded.hip derives it from sol = (-half_b +- root) / a with
+//      root^2 = disc + rounding and the discriminant's absolute error 12 eps |d|^2 (|oc|^2 + r^2) (head of tor_query.hip): |P -
+//      centre|^2 <= r^2 + 12 eps (|oc|^2 + r^2) up to terms of order eps (|oc| + r), so P is at most 6 eps (|oc|^2 + r^2) / r
+//      outside the sphere, below 1e-6 / 4 within `reach` (hit_reach), and every box is inflated by at least 1e-6.  The derivation
+//      never uses WHICH sign the root carries or that the other root was rejected: it holds for s0 and for s1 of one object at
+//      once, each with its own P, and both points lie in the same box (the box bounds the sphere over the time range, inflated).
+//      Here both roots of an object are candidates at the same time, and both are covered.
+//  (2) So in exact arithmetic the entry parameter of every axis with d_k != 0 is at most sol - m / |d_k| with m >= 0.75e-6, the
+//      computed one is within a relative 4 eps of it (three roundings; an underflowed product is off by less than 2^-1022), and
+//      t_in * (1 - 2^-40) < sol <= bound for t_in > 0; t_in = 0 (the clip at 0) passes because 0 <= t_min < sol <= bound.  Axes
+//      with d_k = 0 or 1 / d_k = +-inf are case (3) of tor_occluded.hip's head, unchanged, and the unclipped test t_in <= t_out
+//      rests on the same cases.
+//  (3) t_max = NaN accepts nothing, the bound is NaN and nothing is entered; t_max = +inf leaves the test unclipped until the list is
+//      full.
+// So a box that holds a crossing of the final answer is entered whenever it is tested -- at the top level against the bound at the
+// start of its chunk of 64, at the block boxes of a super box against the bound when the super box is opened, and once more
+// against the current bound just before a block box is opened, in one-level and two-level layouts alike -- and boxes entered
+// needlessly cost time only.  Boxes are visited in index order, not near to far, so how much the shrinking bound saves depends on
+// the scene.  tests/test_gpu_crossings_query.py steps t_max and t_min across the roots of
+// 200 spheres ulp by ulp, and places coincident duplicates so that entries K and K + 1 share one t, to guard this.
+//
+// Results, and the records rebuilt at the end from the by-object cold records (tor_hit_device's formula for that (t, object):
+// rays.nim:24-25, vec3s.nim:93-94, core.nim:47-49), go out as ordinary per-lane stores.
+//
+// Float64, unfused (-ffp-contract=off), correctly rounded division and square root: exact_test's arithmetic (tor_query.hpp).
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "tor_context.hpp"
+#include "tor_query.hpp"
+#include "tor_scene.hpp"
+
+static_assert(sizeof(TorRay) == 56, "TorRay: origin, direction, time (primitives/rays.nim)");
+static_assert(sizeof(TorCrossing) == 16 && offsetof(TorCrossing, object) == 8 && offsetof(TorCrossing, which) == 12,
+              "TorCrossing: t, object, which");
+static_assert(sizeof(TorHit) == 64 && offsetof(TorHit, t) == 48 && offsetof(TorHit, object) == 56 && offsetof(TorHit, front_face) == 60,
+              "TorHit: HitRecord (physics/core.nim:30-36) with the object index in place of the material");
+static_assert(TOR_CROSSINGS_MAX == 16, "the large capacity variant holds TOR_CROSSINGS_MAX entries");
+
+namespace tor {
+namespace {
+
+constexpr int kCapSmall = 4;
+constexpr int kCapLarge = TOR_CROSSINGS_MAX;
+
+struct XParams {
+  QParams q;               // the scene and its boxes, rays, t_range, n_rays (hits unused)
+  const int* list;         // the rays to answer, or null: entry e is ray e
+  long long n_list;
+  int k;                   // crossings per ray, 1 .. CAP
+  double* cross;           // k TorCrossing per ray, 2 float64 words each: t, then object (low word) and which (high word)
+  int* count;              // one int32 per ray
+  double* records;         // null, or k TorHit per ray, 8 float64 words each
+  const double* obj_cold;  // records only: the cold records by ORIGINAL index, 16 float64 per object
+};
+
+// The first K crossings seen so far, ascending by (t, key), in entries CAP - K .. CAP - 1; the entries in front hold -inf and are
+// never displaced, unused entries hold +inf (no crossing has an infinite t).  Every index below is a compile-time constant.
+template <int CAP>
+struct XList {
+  double t[CAP];
+  unsigned key[CAP];  // object * 2 + which: ascending = the lower object first, then which 0 before 1
+
+  __device__ __forceinline__ void init(int k) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      t[j] = j < CAP - k ? -__builtin_inf() : __builtin_inf();
+      key[j] = 0xffffffffu;
+    }
+  }
+  // t_max while fewer than K crossings are held, else the K-th's t (NaN for t_max = NaN: no compare with it holds)
+  __device__ __forceinline__ double bound(double t_max) const { return t[CAP - 1] < __builtin_inf() ? t[CAP - 1] : t_max; }
+  // one pass of insertion: the new element sinks in where it belongs and carries the displaced ones along; the largest falls off
+  __device__ __forceinline__ void insert(double nt, unsigned nk) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      const bool lt = (nt < t[j]) || (nt == t[j] && nk < key[j]);
+      const double ot = t[j];
+      const unsigned ok = key[j];
+      t[j] = lt ? nt : ot;
+      key[j] = lt ? nk : ok;
+      nt = lt ? ot : nt;
+      nk = lt ? ok : nk;
+    }
+  }
+};
+
+// spheres.nim:29-48 / moving_spheres.nim:47-66 for the object in cold record c: both roots, whether each lies in (t_min, t_max), and
+// the object's key.  exact_test's operations in exact_test's order, without the closest-so-far and without the early choice.
+struct XRoots {
+  double s0, s1;
+  unsigned key;  // object * 2
+  bool ok0, ok1;
+};
+
+template <typename P>
+__device__ __forceinline__ XRoots roots_of(P c, const QRay& r) {
+  XRoots x{0.0, 0.0, 0u, false, false};
+  const double r2 = c[15];
+  if (r2 == -1.0) return x;  // padding slot
+  double cx, cy, cz;
+  centre_at(c, r.time, cx, cy, cz);
+  const double ocx = r.ox - cx, ocy = r.oy - cy, ocz = r.oz - cz;
+  const double hb = ocx * r.dx + ocy * r.dy + ocz * r.dz;
+  const double cc = (ocx * ocx + ocy * ocy + ocz * ocz) - r2;
+  const double disc = hb * hb - r.a * cc;
+  if (disc > 0.0) {
+    const double root = __builtin_sqrt(disc);
+    x.s0 = (-hb - root) / r.a;
+    x.s1 = (-hb + root) / r.a;
+    x.ok0 = (r.t_min < x.s0) && (x.s0 < r.t_max);
+    x.ok1 = (r.t_min < x.s1) && (x.s1 < r.t_max);
+    x.key = (unsigned)(int)__double_as_longlong(c[14]) << 1;
+  }
+  return x;
+}
+
+// a root above the bound is dropped; one equal to it goes through the key compare
+template <int CAP>
+__device__ __forceinline__ void take(XList<CAP>& L, const XRoots& x, const QRay& r) {
+  if (x.ok0 && !(x.s0 > L.bound(r.t_max))) L.insert(x.s0, x.key);
+  if (x.ok1 && !(x.s1 > L.bound(r.t_max))) L.insert(x.s1, x.key | 1u);
+}
+
+// slab (tor_query.hpp) with the entry clipped at the shrinking bound; the file head says why it stays exact
+template <typename P>
+__device__ __forceinline__ bool slab_bound(P bx, const QRay& r, double ix, double iy, double iz, double bound) {
+  const double tx0 = (bx[0] - r.ox) * ix, tx1 = (bx[3] - r.ox) * ix;
+  const double ty0 = (bx[1] - r.oy) * iy, ty1 = (bx[4] - r.oy) * iy;
+  const double tz0 = (bx[2] - r.oz) * iz, tz1 = (bx[5] - r.oz) * iz;
+  const double t_in = __builtin_fmax(__builtin_fmax(__builtin_fmin(tx0, tx1), __builtin_fmin(ty0, ty1)),
+                                     __builtin_fmax(__builtin_fmin(tz0, tz1), 0.0));
+  const double t_out = __builtin_fmin(__builtin_fmin(__builtin_fmax(tx0, tx1), __builtin_fmax(ty0, ty1)), __builtin_fmax(tz0, tz1));
+  return (t_in <= t_out) && (t_in * (1.0 - 0x1p-40) <= bound);
+}
+
+// TorHit for the crossing (t, object): tor_hit_device's record for that root of that object (the end of hit_kernel, tor_query.hip)
+__device__ __forceinline__ void write_record(double* o, const double* obj_cold, const QRay& r, double t, unsigned key) {
+  const int object = (int)(key >> 1);
+  const qgdptr c = (qgdptr)(uintptr_t)(obj_cold + 16 * (size_t)object);
+  double cx, cy, cz;
+  centre_at(c, r.time, cx, cy, cz);
+  const double px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;  // rays.nim:24-25 origin + t * direction
+  const double inv_r = c[6];                                                     // vec3s.nim:93-94: `/ radius` is `* (1.0 / radius)`
+  double nx = (px - cx) * inv_r, ny = (py - cy) * inv_r, nz = (pz - cz) * inv_r;
+  const bool front = (r.dx * nx + r.dy * ny + r.dz * nz) < 0.0;  // core.nim:47-49
+  if (!front) {
+    nx = -nx; ny = -ny; nz = -nz;
+  }
+  o[0] = px; o[1] = py; o[2] = pz;
+  o[3] = nx; o[4] = ny; o[5] = nz;
+  o[6] = t;
+  o[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)object));
+}
+
+template <bool BLOCKS, bool MASKED, int CAP>
+__global__ __launch_bounds__(kHitThreads) void crossings_kernel(const XParams P, const MParams mk) {
+  const QParams& p = P.q;
+  const long long e = (long long)blockIdx.x * kHitThreads + threadIdx.x;
+  long long i = -1;  // the ray of list entry e; -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
+  if (e < P.n_list) {
+    const long long v = P.list ? (long long)P.list[e] : e;
+    if (v >= 0 && v < p.n_rays) i = v;
+  }
+  const bool live = i >= 0;
+  unsigned r_mask = 0u;  // (lanes without a ray see nothing)
+  if constexpr (MASKED) {
+    if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
+  }
+  const Sees<MASKED> vis{mk.grp, mk.box_or, r_mask};
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) {
+    const double* q = p.rays + 7 * i;
+    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+    r.time = q[6];
+    if (p.t_range) {
+      r.t_min = p.t_range[2 * i];
+      r.t_max = p.t_range[2 * i + 1];
+    } else {
+      r.t_min = 0.001;  // render.nim:34
+      r.t_max = __builtin_inf();
+    }
+  }
+  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
+  const int K = P.k < CAP ? P.k : CAP;
+  // records of a block tested per batch: all 8 with the small list; 4 with the large one, whose registers a batch of 8 would push
+  // past two waves per SIMD
+  constexpr int kBatch = CAP <= kCapSmall ? 8 : 4;
+  XList<CAP> L;
+  L.init(K);
+  // wave-uniform: every live lane that sees the slot tests the same record
+  for (int s = 0; s < p.n_uniform; ++s)
+    if (live && vis.slot_u(s)) take(L, roots_of((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)s), r), r);
+  if constexpr (BLOCKS) {
+    const double ex = r.ox - p.org[0], ey = r.oy - p.org[1], ez = r.oz - p.org[2];
+    const bool boxed = live && (r.t_min >= 0.0) && (r.time >= p.time_lo) && (r.time <= p.time_hi) &&
+                       (ex * ex + ey * ey + ez * ez <= p.reach2) && (r.a >= p.a_min);
+    const bool walk = live && !boxed;
+    if (__ballot(walk) != 0) {  // rays the boxes do not hold for: every spatial slot, wave-uniform
+      for (int s = 0; s < p.n_spatial; ++s) {
+        const int slot = p.spatial_base + s;
+        if (walk && vis.slot_u(slot)) take(L, roots_of((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)slot), r), r);
+      }
+    }
+    if (boxed) {
+      const double ix = 1.0 / r.dx, iy = 1.0 / r.dy, iz = 1.0 / r.dz;
+      auto test_box = [&](int box) {  // the blocks behind block box `box`, 8 objects each
+        for (int fk = 0; fk < p.fanout; ++fk) {
+          const int slot0 = p.spatial_base + 8 * (box * p.fanout + fk);
+          // the records' loads go out as one batch: no insertion (a branch) between them
+#pragma unroll 1
+          for (int k0 = 0; k0 < 8; k0 += kBatch) {
+            XRoots x[kBatch];
+#pragma unroll
+            for (int k = 0; k < kBatch; ++k) {
+              x[k] = XRoots{0.0, 0.0, 0u, false, false};
+              if (vis.slot(slot0 + k0 + k)) x[k] = roots_of((qgdptr)(uintptr_t)(p.cold + 16 * (size_t)(slot0 + k0 + k)), r);
+            }
+#pragma unroll
+            for (int k = 0; k < kBatch; ++k) take(L, x[k], r);
+          }
+        }
+      };
+      const int n_top = p.two_level ? p.n_super : p.n_boxes;
+      const int top0 = p.two_level ? p.super0 : 0;
+      // the top-level boxes 64 at a time (scalar loads); then the ones the ray's segment enters below the bound
+      for (int c0 = 0; c0 < n_top; c0 += 64) {
+        const int cn = n_top - c0 < 64 ? n_top - c0 : 64;
+        const double b0 = L.bound(r.t_max);
+        unsigned long long m = 0;
+        for (int j = 0; j < cn; ++j)
+          if (vis.box_u(top0 + c0 + j) && slab_bound((qcdptr)(uintptr_t)(p.bnd + 8 * (size_t)(top0 + c0 + j)), r, ix, iy, iz, b0))
+            m |= 1ull << j;
+        while (m != 0) {
+          const int top = c0 + __builtin_ctzll(m);
+          m &= m - 1;
+          // one level: block box `top` itself.  Two levels: super box `top`, its 8 block boxes (NaN padding boxes are never
+          // entered), against the bound as it stands now.  (One call of test_box for both: the insertion chains are long.)
+          unsigned m8 = 1u;
+          int box0 = top;
+          if (p.two_level) {
+            const double b1 = L.bound(r.t_max);
+            m8 = 0u;
+            box0 = 8 * top;
+            for (int k = 0; k < 8; ++k)
+              if (vis.box(box0 + k) && slab_bound((qgdptr)(uintptr_t)(p.bnd + 8 * (size_t)(box0 + k)), r, ix, iy, iz, b1)) m8 |= 1u << k;
+          }
+          // the bound may have shrunk since the box passed its test (b0 is a chunk old, b1 a super box old): a block box is
+          // opened only if it still lies at or below the bound as it stands now
+          while (m8 != 0) {
+            const int k = __builtin_ctz(m8);
+            m8 &= m8 - 1;
+            if (slab_bound((qgdptr)(uintptr_t)(p.bnd + 8 * (size_t)(box0 + k)), r, ix, iy, iz, L.bound(r.t_max))) test_box(box0 + k);
+          }
+        }
+      }
+    }
+  }
+  if (!live) return;
+  // entries CAP - K .. CAP - 1 are crossings 0 .. K - 1; unused ones hold t = 0, object = -1, which = 0 (and the miss record)
+  double* out = P.cross + 2 * (size_t)i * (size_t)P.k;
+  double* rec = P.records ? P.records + 8 * (size_t)i * (size_t)P.k : nullptr;
+  int count = 0;
+#pragma unroll
+  for (int j = 0; j < CAP; ++j) {
+    const int m = j - (CAP - K);
+    if (m < 0) continue;
+    const bool has = L.t[j] < __builtin_inf();
+    count += has ? 1 : 0;
+    const unsigned long long w = has ? (((unsigned long long)(L.key[j] & 1u) << 32) | (unsigned long long)(L.key[j] >> 1)) : 0xffffffffull;
+    out[2 * m] = has ? L.t[j] : 0.0;
+    out[2 * m + 1] = __longlong_as_double((long long)w);
+    if (rec) {
+      double* o = rec + 8 * m;
+      if (has) {
+        write_record(o, P.obj_cold, r, L.t[j], L.key[j]);
+      } else {  // the miss record: object -1, every other field 0
+        for (int k = 0; k < 7; ++k) o[k] = 0.0;
+        o[7] = __longlong_as_double((long long)0xffffffffull);
+      }
+    }
+  }
+  P.count[i] = count;
+}
+
+}  // namespace
+}  // namespace tor
+
+namespace {
+
+constexpr int64_t kMaxItems = (int64_t)0x7fffffff * tor::kHitThreads;  // one lane per entry, at most 2^31 - 1 workgroups
+
+// every check that needs no device and does not read *ctx (the CPU suite runs these): what tor_occluded_device refuses, and k
+int crossings_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* list, int64_t n_list, int32_t k,
+                   double time_lo, double time_hi, int32_t mode, const void* cross, const void* count) {
+  using tor::fail;
+  const std::string w = who;
+  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
+  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
+  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
+  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
+  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
+  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
+  if (k < 1 || k > TOR_CROSSINGS_MAX)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": k must be in 1 .. TOR_CROSSINGS_MAX (" + std::to_string(TOR_CROSSINGS_MAX) + ")");
+  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
+  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
+  if (n_rays > 0 && n_list > 0 && (!rays || !cross || !count)) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, cross or count");
+  return TOR_OK;
+}
+
+// the cold records by ORIGINAL index, for the records rebuilt at the end: the cache tor_scatter_device keeps (ensure_obj_cold,
+// tor_bounce.hip), filled the same way, so whichever of the two runs first fills it for both.  A TWIN of ensure_obj_cold: the two
+// must stay in step by hand (tor_bounce.hip and tor_query.hpp stay byte-identical in this change, so it could not move to a shared
+// place; DESIGN section 9 lists the merge)
+int crossings_obj_cold(const char* who, TorContext* ctx, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
+  if (hq.obj_scene == gen) return TOR_OK;
+  hq.obj_scene = -1;
+  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
+  const int64_t n = ctx->n_objects;
+  std::vector<int64_t> ids((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
+  tor::HostLayout lay;
+  std::string err;
+  if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, lay, err, nullptr))
+    return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": " + err);
+  hq.obj_cold_host.assign((size_t)(n > 0 ? n : 1) * 16, 0.0);
+  for (size_t s = 0; s < lay.n_sorted && n > 0; ++s) {
+    const double* c = &lay.cold[16 * s];
+    if (c[15] == -1.0) continue;  // padding slot
+    int64_t orig;
+    std::memcpy(&orig, &c[14], 8);
+    if (orig >= 0 && orig < n) std::memcpy(&hq.obj_cold_host[16 * (size_t)orig], c, 16 * sizeof(double));
+  }
+  const size_t bytes = hq.obj_cold_host.size() * sizeof(double);
+  HIP_TRY(hq.obj_cold.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(hq.obj_cold.ptr, hq.obj_cold_host.data(), bytes, hipMemcpyHostToDevice, stream));
+  hq.obj_scene = gen;
+  return TOR_OK;
+}
+
+template <bool BLOCKS, bool MASKED>
+void crossings_dispatch(unsigned grid, hipStream_t stream, const tor::XParams& P, const tor::MParams& mk) {
+  if (P.k <= tor::kCapSmall)
+    hipLaunchKernelGGL((tor::crossings_kernel<BLOCKS, MASKED, tor::kCapSmall>), dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
+  else
+    hipLaunchKernelGGL((tor::crossings_kernel<BLOCKS, MASKED, tor::kCapLarge>), dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
+}
+
+// the launch; the arguments are checked, n_rays > 0 and n_list > 0.  A call without per-ray masks whose mask is 0xFFFFFFFF sees
+// every object whatever the group words hold: it runs the unmasked kernels and neither builds nor reads any group state.
+int crossings_launch(const char* who, TorContext* ctx, int64_t n_rays, const void* d_rays, const double* d_t_range, const int32_t* d_list,
+                     int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi, int32_t mode,
+                     TorCrossing* d_cross, int32_t* d_count, TorHit* d_records, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  tor::XParams P{};
+  bool blocks = false;
+  std::string why;
+  const int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, P.q, blocks, why);
+  if (rc != TOR_OK) return rc;
+  P.q.rays = (const double*)d_rays;
+  P.q.t_range = d_t_range;
+  P.q.n_rays = (long long)n_rays;
+  P.list = d_list;
+  P.n_list = (long long)n_list;
+  P.k = k;
+  P.cross = (double*)d_cross;
+  P.count = d_count;
+  P.records = (double*)d_records;
+  if (d_records) {
+    const int ro = crossings_obj_cold(who, ctx, stream);
+    if (ro != TOR_OK) return ro;
+    P.obj_cold = (const double*)hq.obj_cold.ptr;
+  }
+  const unsigned grid = (unsigned)((n_list + tor::kHitThreads - 1) / tor::kHitThreads);
+  const bool masked = d_mask != nullptr || mask != 0xFFFFFFFFu;
+  tor::MParams mk{};
+  if (masked) {
+    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
+    if (rm != TOR_OK) return rm;
+    if (blocks) crossings_dispatch<true, true>(grid, stream, P, mk);
+    else crossings_dispatch<false, true>(grid, stream, P, mk);
+  } else if (blocks) {
+    crossings_dispatch<true, false>(grid, stream, P, mk);
+  } else {
+    crossings_dispatch<false, false>(grid, stream, P, mk);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(hq.ev_done, stream));
+  hq.launched = true;
+  hq.stream = (void*)stream;
+  const std::string what = masked ? "crossings (masked): " : "crossings: ";
+  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
+  return TOR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tor_crossings_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
+                         int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi, int32_t mode,
+                         TorCrossing* d_cross, int32_t* d_count, TorHit* d_records, void* hip_stream) {
+  const int rc = crossings_args("tor_crossings_device", ctx, n_rays, d_rays, d_list, n_list, k, time_lo, time_hi, mode, d_cross, d_count);
+  if (rc != TOR_OK) return rc;
+  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_crossings_device: no scene uploaded");
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return crossings_launch("tor_crossings_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, k, d_mask, mask, time_lo, time_hi, mode,
+                          d_cross, d_count, d_records, (hipStream_t)hip_stream);
+}
+
+int tor_crossings_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list, int64_t n_list,
+                       int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi, int32_t mode, TorCrossing* cross,
+                       int32_t* count, TorHit* records) {
+  const char* who = "tor_crossings_host";
+  int rc = crossings_args(who, ctx, n_rays, rays, list, n_list, k, time_lo, time_hi, mode, cross, count);
+  if (rc != TOR_OK) return rc;
+  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
+  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  tor::HitQueryState& hq = ctx->hitq;
+  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
+  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
+  // rays, t ranges, the list, the masks and the outputs (rays that are not listed keep what the caller holds) in, each padded to 64
+  // bytes; the query on the default stream; the outputs back
+  const size_t n = (size_t)n_rays, nk = n * (size_t)k;
+  constexpr int kParts = 7;
+  const size_t bytes[kParts] = {n * sizeof(TorRay), t_range ? n * 16 : 0, list ? (size_t)n_list * 4 : 0, masks ? n * 4 : 0,
+                                nk * sizeof(TorCrossing), n * 4, records ? nk * sizeof(TorHit) : 0};
+  const void* const host[kParts] = {rays, t_range, list, masks, cross, count, records};
+  size_t off[kParts], total = 0;
+  for (int p = 0; p < kParts; ++p) {
+    off[p] = total;
+    total += (bytes[p] + 63) / 64 * 64;
+  }
+  HIP_TRY(hq.io.ensure(total));
+  char* base = (char*)hq.io.ptr;
+  for (int p = 0; p < kParts; ++p)
+    if (bytes[p]) HIP_TRY(hipMemcpy(base + off[p], host[p], bytes[p], hipMemcpyHostToDevice));
+  rc = crossings_launch(who, ctx, n_rays, base + off[0], t_range ? (const double*)(base + off[1]) : nullptr,
+                        list ? (const int32_t*)(base + off[2]) : nullptr, n_list, k, masks ? (const uint32_t*)(base + off[3]) : nullptr, mask,
+                        time_lo, time_hi, mode, (TorCrossing*)(base + off[4]), (int32_t*)(base + off[5]),
+                        records ? (TorHit*)(base + off[6]) : nullptr, nullptr);
+  if (rc != TOR_OK) return rc;
+  HIP_TRY(hipMemcpy(cross, base + off[4], bytes[4], hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(count, base + off[5], bytes[5], hipMemcpyDeviceToHost));
+  if (records) HIP_TRY(hipMemcpy(records, base + off[6], bytes[6], hipMemcpyDeviceToHost));
+  return TOR_OK;
+}
+
+}  // extern "C"
