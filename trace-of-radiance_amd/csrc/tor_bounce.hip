@@ -5,11 +5,12 @@
 // render.nim:41-44, and the ordered compaction of the rays that scattered, on gfx950.
 //
 // Exactness.  The closest hit is the hit query's (tor_query.hpp, tor_query_descent.inc: the head of tor_query.hip says why the
-// descent gives the sequential closest_so_far loop's record), and the record is built with hit_kernel's operations, so d_hits is
-// what tor_hit_device writes.  The scatter is tor_shade_scatter.inc, the text radiance_kernel (tor_radiance.hip) includes: the same
-// cold records, helpers, draws and operation order, float64 unfused.  Driven the reference's way -- att = 1; per step att *=
-// attenuation, a miss ends with sky * att, an absorbed ray with black, max_depth steps -- the steps are radiance_kernel's
-// iterations one launch at a time: colours and states equal tor_radiance_device's bit for bit.
+// descent gives the sequential closest_so_far loop's record; bounce_kernel<BLOCKS, MASKED> is hit_kernel's pair of flags), and
+// the record is built with hit_kernel's operations, so d_hits is what tor_hit_device writes.  The scatter is
+// tor_shade_scatter.inc, the text radiance_kernel (tor_radiance.hip) includes: the same cold records, helpers, draws and
+// operation order, float64 unfused.  Driven the reference's way -- att = 1; per step att *= attenuation, a miss ends with sky *
+// att, an absorbed ray with black, max_depth steps -- the steps are radiance_kernel's iterations one launch at a time: colours
+// and states equal tor_radiance_device's bit for bit.
 //
 // One ray per lane: every lane does exactly one bounce, so there is no refill queue.  Arrays are indexed by the ray, not by the
 // position in the list; the lanes of entries outside [0, n_rays) and past the end of the list take part in the descent with
@@ -53,11 +54,9 @@ struct BParams {
   long long n_objects;
 };
 
-// the ray of list entry `e`, or -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
-__device__ __forceinline__ long long listed_ray(const BParams& P, long long e) {
-  if (e >= P.n_list) return -1;
-  const long long i = P.list ? (long long)P.list[e] : e;
-  return (i >= 0 && i < P.n_rays) ? i : -1;
+// the ray of this lane's list entry, or -1 (listed_ray, tor_query.hpp)
+__device__ __forceinline__ long long step_ray(const BParams& P) {
+  return listed_ray(P.list, P.n_list, P.n_rays, (long long)blockIdx.x * kStepThreads + threadIdx.x);
 }
 
 __device__ __forceinline__ void write_miss(const BParams& P, long long i) {
@@ -80,87 +79,32 @@ __device__ __forceinline__ void write_scatter(const BParams& P, long long i, con
   P.status[i] = ended ? TOR_BOUNCE_ABSORBED : TOR_BOUNCE_SCATTERED;
 }
 
-template <bool BLOCKS>
-__global__ __launch_bounds__(kStepThreads) void bounce_kernel(const BParams P) {
+// MASKED: with visibility groups (tor_bounce_masked_device) the closest VISIBLE object scatters
+template <bool BLOCKS, bool MASKED>
+__global__ __launch_bounds__(kStepThreads) void bounce_kernel(const KArgs<BParams, MASKED> A) {
+  const BParams& P = A.P;
   const QParams& p = P.q;
-  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  const long long i = step_ray(P);
   const bool live = i >= 0;
-  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = P.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    r.t_min = 0.001;  // render.nim:28
-    r.t_max = __builtin_inf();
+  Sees<MASKED> vis{nullptr, nullptr, 0u};  // (lanes without a ray see nothing)
+  if constexpr (MASKED) {
+    if (live) vis.m = A.mk.ray_mask ? A.mk.ray_mask[i] : A.mk.mask;
+    vis.grp = A.mk.grp;
+    vis.box_or = A.mk.box_or;
   }
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) load_ray(r, P.rays, nullptr, i);  // render.nim:28: (0.001, +inf)
   r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
   QBest b{r.t_max, INT_MAX, -1};
 #include "tor_query_descent.inc"
   if (!live) return;
   double* h = P.hits + 8 * i;
   if (b.slot < 0) {  // miss: the record tor_hit_device writes; ray and state untouched, nothing drawn
-    for (int k = 0; k < 7; ++k) h[k] = 0.0;
-    h[7] = __longlong_as_double((long long)0xffffffffull);
+    write_miss_record(h);
     write_miss(P, i);
     return;
   }
-  // the record, with hit_kernel's operations (tor_query.hip)
-  const double* c = p.cold + 16 * (size_t)b.slot;
-  double cx, cy, cz;
-  centre_at(c, r.time, cx, cy, cz);                                 // moving_spheres.nim:39-44
-  const V3 o = v3(r.ox, r.oy, r.oz), d = v3(r.dx, r.dy, r.dz);
-  const V3 hp = o + d * b.t;                                       // rays.nim:24-25
-  const V3 outward = (hp - v3(cx, cy, cz)) * c[6];                 // spheres.nim:43 (c[6] = 1.0 / radius)
-  const bool front = dot(d, outward) < 0.0;                        // core.nim:47-49
-  const V3 n = front ? outward : -outward;
-  h[0] = hp.x; h[1] = hp.y; h[2] = hp.z;
-  h[3] = n.x; h[4] = n.y; h[5] = n.z;
-  h[6] = b.t;
-  h[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)b.orig));
-  // the scatter
-  const unsigned long long* s = P.rng + 4 * i;
-  Rng g{s[0], s[1], s[2], s[3]};
-  const V3 ud = unit_vector(d);  // materials.nim:40,68
-  V3 att = v3(1.0, 1.0, 1.0);
-  bool ended = false;
-  {
-#include "tor_shade_scatter.inc"
-  }
-  write_scatter(P, i, r, g, att, ended);
-}
-
-// bounce_kernel with visibility groups (tor_bounce_masked_device): the closest VISIBLE object scatters.  A kernel of its own,
-// statement for statement bounce_kernel's but for `vis` (hit_masked_kernel, tor_query.hip, says why).
-template <bool BLOCKS>
-__global__ __launch_bounds__(kStepThreads) void bounce_masked_kernel(const BParams P, const MParams mk) {
-  const QParams& p = P.q;
-  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
-  const bool live = i >= 0;
-  unsigned r_mask = 0u;  // (lanes without a ray see nothing)
-  if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
-  const Sees<true> vis{mk.grp, mk.box_or, r_mask};  // the descent's `vis`
-  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = P.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    r.t_min = 0.001;  // render.nim:28
-    r.t_max = __builtin_inf();
-  }
-  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
-  QBest b{r.t_max, INT_MAX, -1};
-#include "tor_query_descent.inc"
-  if (!live) return;
-  double* h = P.hits + 8 * i;
-  if (b.slot < 0) {  // miss: the record tor_hit_device writes; ray and state untouched, nothing drawn
-    for (int k = 0; k < 7; ++k) h[k] = 0.0;
-    h[7] = __longlong_as_double((long long)0xffffffffull);
-    write_miss(P, i);
-    return;
-  }
-  // the record, with hit_kernel's operations (tor_query.hip)
+  // the record, with tor_query_record.inc's operations through V3: the scatter goes on with hp, n and front
   const double* c = p.cold + 16 * (size_t)b.slot;
   double cx, cy, cz;
   centre_at(c, r.time, cx, cy, cz);                                 // moving_spheres.nim:39-44
@@ -187,7 +131,7 @@ __global__ __launch_bounds__(kStepThreads) void bounce_masked_kernel(const BPara
 
 // rec.material.scatter for the caller's record: material of hits[i].object, and p, normal, front_face as given
 __global__ __launch_bounds__(kStepThreads) void scatter_kernel(const BParams P) {
-  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  const long long i = step_ray(P);
   if (i < 0) return;
   const double* h = P.hits + 8 * i;
   const unsigned long long w7 = (unsigned long long)__double_as_longlong(h[7]);
@@ -217,7 +161,7 @@ __global__ __launch_bounds__(kStepThreads) void scatter_kernel(const BParams P) 
 
 // render.nim:41-44 without the attenuation (sky()'s product with (1, 1, 1) is exact)
 __global__ __launch_bounds__(kStepThreads) void sky_kernel(const BParams P) {
-  const long long i = listed_ray(P, (long long)blockIdx.x * kStepThreads + threadIdx.x);
+  const long long i = step_ray(P);
   if (i < 0) return;
   const double* q = P.rays + 7 * i;
   const V3 col = sky(v3(q[3], q[4], q[5]), v3(1.0, 1.0, 1.0));
@@ -305,57 +249,29 @@ __global__ __launch_bounds__(256) void select_scatter_kernel(const int* status, 
 
 namespace {
 
-constexpr int64_t kMaxItems = (int64_t)0x7fffffff * 256;  // at most 2^31 - 1 workgroups of 256 lanes
-
-// the checks every step shares; none needs a device or reads *ctx
-int list_args(const std::string& w, TorContext* ctx, int64_t n_rays, const void* list, int64_t n_list) {
-  using tor::fail;
-  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
-  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
-  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
-  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
-  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
-  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
-  return TOR_OK;
-}
-
-int bounce_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* rng, const void* list, int64_t n_list,
-                double time_lo, double time_hi, int32_t mode, const void* hits, const void* att, const void* status) {
-  using tor::fail;
+// the checks every step shares (tor::list_args) and a step's own; none needs a device or reads *ctx.  Then the scene.
+int bounce_check(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* rng, const void* list, int64_t n_list,
+                 double time_lo, double time_hi, int32_t mode, const void* hits, const void* att, const void* status) {
   const std::string w = who;
-  const int rc = list_args(w, ctx, n_rays, list, n_list);
+  int rc = tor::list_args(w, ctx, n_rays, list, n_list);
+  if (rc == TOR_OK) rc = tor::range_args(w, time_lo, time_hi, mode);
   if (rc != TOR_OK) return rc;
-  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
-  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
   if (n_rays > 0 && n_list > 0 && (!rays || !rng || !hits || !att || !status))
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, rng, hits, attenuation or status");
-  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": no scene uploaded");
-  return TOR_OK;
+    return tor::fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, rng, hits, attenuation or status");
+  return tor::scene_args(who, ctx);
 }
 
-int scatter_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* hits, const void* rng, const void* list,
-                 int64_t n_list, const void* att, const void* status) {
-  using tor::fail;
+int scatter_check(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* hits, const void* rng, const void* list,
+                  int64_t n_list, const void* att, const void* status) {
   const std::string w = who;
-  const int rc = list_args(w, ctx, n_rays, list, n_list);
+  const int rc = tor::list_args(w, ctx, n_rays, list, n_list);
   if (rc != TOR_OK) return rc;
   if (n_rays > 0 && n_list > 0 && (!rays || !hits || !rng || !att || !status))
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, hits, rng, attenuation or status");
-  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": no scene uploaded");
-  return TOR_OK;
+    return tor::fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, hits, rng, attenuation or status");
+  return tor::scene_args(who, ctx);
 }
 
 unsigned step_grid(int64_t n_list) { return (unsigned)((n_list + tor::kStepThreads - 1) / tor::kStepThreads); }
-
-int query_done(TorContext* ctx, hipStream_t stream) {
-  tor::HitQueryState& hq = ctx->hitq;
-  HIP_TRY(hipEventRecord(hq.ev_done, stream));
-  hq.launched = true;
-  hq.stream = (void*)stream;
-  return TOR_OK;
-}
 
 // the launches; the arguments are checked, n_rays > 0 and n_list > 0
 int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays, void* d_rng, const int32_t* d_list, int64_t n_list,
@@ -365,9 +281,11 @@ int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays
   // them, so a chain of steps called with one range looks up ONE cached set of block bounds
   const double lo = time_lo < 0.0 ? time_lo : 0.0, hi = time_hi > 0.0 ? time_hi : 0.0;
   tor::BParams P{};
+  tor::MParams mk{};
   bool blocks = false;
   std::string why;
-  const int rc = tor::query_setup(who, ctx, lo, hi, mode, stream, P.q, blocks, why);
+  int rc = tor::query_setup(who, ctx, lo, hi, mode, stream, P.q, blocks, why);
+  if (rc == TOR_OK && masked) rc = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
   if (rc != TOR_OK) return rc;
   P.rays = (double*)d_rays;
   P.rng = (unsigned long long*)d_rng;
@@ -377,60 +295,18 @@ int bounce_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays
   P.hits = (double*)d_hits;
   P.att = d_att;
   P.status = d_status;
-  if (masked) {
-    tor::MParams mk{};
-    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
-    if (rm != TOR_OK) return rm;
-    if (blocks) hipLaunchKernelGGL(tor::bounce_masked_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P, mk);
-    else hipLaunchKernelGGL(tor::bounce_masked_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P, mk);
-  } else if (blocks) {
-    hipLaunchKernelGGL(tor::bounce_kernel<true>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
-  } else {
-    hipLaunchKernelGGL(tor::bounce_kernel<false>, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
-  }
-  HIP_TRY(hipGetLastError());
-  const int rd = query_done(ctx, stream);
-  if (rd != TOR_OK) return rd;
-  const std::string what = masked ? "bounce (masked): " : "bounce: ";
-  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
-  return TOR_OK;
-}
-
-// the cold records by ORIGINAL index (scatter_kernel looks the material up by TorHit.object), cached per scene
-int ensure_obj_cold(TorContext* ctx, hipStream_t stream) {
-  tor::HitQueryState& hq = ctx->hitq;
-  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
-  if (hq.obj_scene == gen) return TOR_OK;
-  hq.obj_scene = -1;
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
-  const int64_t n = ctx->n_objects;
-  std::vector<int64_t> ids((size_t)n);
-  for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
-  tor::HostLayout lay;
-  std::string err;
-  if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, lay, err, nullptr))
-    return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_scatter_device: " + err);
-  hq.obj_cold_host.assign((size_t)(n > 0 ? n : 1) * 16, 0.0);
-  for (size_t k = 0; k < lay.n_sorted && n > 0; ++k) {
-    const double* c = &lay.cold[16 * k];
-    if (c[15] == -1.0) continue;  // padding slot
-    int64_t orig;
-    std::memcpy(&orig, &c[14], 8);
-    if (orig >= 0 && orig < n) std::memcpy(&hq.obj_cold_host[16 * (size_t)orig], c, 16 * sizeof(double));
-  }
-  const size_t bytes = hq.obj_cold_host.size() * sizeof(double);
-  HIP_TRY(hq.obj_cold.ensure(bytes));
-  HIP_TRY(hipMemcpyAsync(hq.obj_cold.ptr, hq.obj_cold_host.data(), bytes, hipMemcpyHostToDevice, stream));
-  hq.obj_scene = gen;
-  return TOR_OK;
+  tor::for_variant(blocks, masked, [&](auto B, auto M) {
+    hipLaunchKernelGGL((tor::bounce_kernel<decltype(B)::value, decltype(M)::value>), dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0,
+                       stream, tor::kargs<decltype(M)::value>(P, mk));
+  });
+  return tor::query_finish(ctx, stream, "bounce", masked, blocks, why);
 }
 
 int scatter_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_rays, const void* d_hits, void* d_rng, const int32_t* d_list,
                    int64_t n_list, double* d_att, int32_t* d_status, hipStream_t stream) {
   tor::BParams P{};
   int rc = tor::query_stream_rule(who, ctx, stream);  // (no layout and no box: the scatter reads the by-object records alone)
-  if (rc != TOR_OK) return rc;
-  rc = ensure_obj_cold(ctx, stream);
+  if (rc == TOR_OK) rc = tor::ensure_obj_cold("tor_scatter_device", ctx, stream);
   if (rc != TOR_OK) return rc;
   P.rays = (double*)d_rays;
   P.rng = (unsigned long long*)d_rng;
@@ -443,33 +319,34 @@ int scatter_launch(const char* who, TorContext* ctx, int64_t n_rays, void* d_ray
   P.obj_cold = (const double*)ctx->hitq.obj_cold.ptr;
   P.n_objects = (long long)ctx->n_objects;
   hipLaunchKernelGGL(tor::scatter_kernel, dim3(step_grid(n_list)), dim3(tor::kStepThreads), 0, stream, P);
-  HIP_TRY(hipGetLastError());
-  rc = query_done(ctx, stream);
+  rc = tor::query_done(ctx, stream);
   if (rc != TOR_OK) return rc;
   tor::set_last_note("scatter");
   return TOR_OK;
 }
 
-// the blocking twins stage every per-ray array of the call in hitq.io, in this order (each padded to 64 bytes)
-struct Staging {
-  size_t off[6], bytes[6], total;
-  Staging(int64_t n_rays, int64_t n_list, bool with_list) {
-    const size_t n = (size_t)n_rays;
-    const size_t want[6] = {n * sizeof(TorRay), n * sizeof(TorRng), with_list ? (size_t)n_list * 4 : 0, n * sizeof(TorHit), n * 24, n * 4};
-    total = 0;
-    for (int k = 0; k < 6; ++k) {
-      off[k] = total;
-      bytes[k] = want[k];
-      total += (want[k] + 63) / 64 * 64;
-    }
-  }
-};
+// tor_bounce_device / tor_bounce_masked_device
+int bounce_device(const char* who, TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
+                  double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_att, int32_t* d_status, void* hip_stream,
+                  bool masked, const uint32_t* d_mask, uint32_t mask) {
+  const int rc = bounce_check(who, ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_att, d_status);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return bounce_launch(who, ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_att, d_status,
+                       (hipStream_t)hip_stream, masked, d_mask, mask);
+}
 
-int host_wait(TorContext* ctx) {
-  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
-  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-  if (ctx->hitq.launched) HIP_TRY(hipEventSynchronize(ctx->hitq.ev_done));
-  return TOR_OK;
+// the per-ray arrays the blocking twins stage, in this order: every one goes in (rays that are not listed keep what the caller
+// holds); hits_out: tor_bounce_host writes the records, tor_scatter_host only reads them
+void step_parts(tor::HostPart* st, int64_t n_rays, int64_t n_list, const void* rays, const void* rng, const void* list, const void* hits,
+                bool hits_out, const void* att, const void* status) {
+  const size_t n = (size_t)n_rays;
+  st[0] = {rays, n * sizeof(TorRay), true, true};
+  st[1] = {rng, n * sizeof(TorRng), true, true};
+  st[2] = {list, list ? (size_t)n_list * 4 : 0, true, false};
+  st[3] = {hits, n * sizeof(TorHit), true, hits_out};
+  st[4] = {att, n * 24, true, true};
+  st[5] = {status, n * 4, true, true};
 }
 
 }  // namespace
@@ -479,32 +356,21 @@ extern "C" {
 int tor_bounce_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
                       double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_attenuation, int32_t* d_status,
                       void* hip_stream) {
-  const int rc = bounce_args("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
-                             d_attenuation, d_status);
-  if (rc != TOR_OK) return rc;
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return bounce_launch("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_attenuation,
-                       d_status, (hipStream_t)hip_stream);
+  return bounce_device("tor_bounce_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits, d_attenuation,
+                       d_status, hip_stream, false, nullptr, 0);
 }
 
 int tor_bounce_masked_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, TorRng* d_rng, const int32_t* d_list, int64_t n_list,
                              double time_lo, double time_hi, int32_t mode, TorHit* d_hits, double* d_attenuation, int32_t* d_status,
                              void* hip_stream, const uint32_t* d_mask, uint32_t mask) {
-  const int rc = bounce_args("tor_bounce_masked_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
-                             d_attenuation, d_status);
-  if (rc != TOR_OK) return rc;
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return bounce_launch("tor_bounce_masked_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
-                       d_attenuation, d_status, (hipStream_t)hip_stream, true, d_mask, mask);
+  return bounce_device("tor_bounce_masked_device", ctx, n_rays, d_rays, d_rng, d_list, n_list, time_lo, time_hi, mode, d_hits,
+                       d_attenuation, d_status, hip_stream, true, d_mask, mask);
 }
 
 int tor_scatter_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, const TorHit* d_hits, TorRng* d_rng, const int32_t* d_list,
                        int64_t n_list, double* d_attenuation, int32_t* d_status, void* hip_stream) {
-  const int rc = scatter_args("tor_scatter_device", ctx, n_rays, d_rays, d_hits, d_rng, d_list, n_list, d_attenuation, d_status);
-  if (rc != TOR_OK) return rc;
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  const int rc = scatter_check("tor_scatter_device", ctx, n_rays, d_rays, d_hits, d_rng, d_list, n_list, d_attenuation, d_status);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   return scatter_launch("tor_scatter_device", ctx, n_rays, d_rays, d_hits, d_rng, d_list, n_list, d_attenuation, d_status,
                         (hipStream_t)hip_stream);
@@ -512,53 +378,38 @@ int tor_scatter_device(TorContext* ctx, int64_t n_rays, TorRay* d_rays, const To
 
 int tor_bounce_host(TorContext* ctx, int64_t n_rays, TorRay* rays, TorRng* rng, const int32_t* list, int64_t n_list, double time_lo,
                     double time_hi, int32_t mode, TorHit* hits, double* attenuation, int32_t* status) {
-  int rc = bounce_args("tor_bounce_host", ctx, n_rays, rays, rng, list, n_list, time_lo, time_hi, mode, hits, attenuation, status);
-  if (rc != TOR_OK) return rc;
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  int rc = bounce_check("tor_bounce_host", ctx, n_rays, rays, rng, list, n_list, time_lo, time_hi, mode, hits, attenuation, status);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  rc = host_wait(ctx);
+  // every array in, the step on the default stream, every output back
+  tor::HostPart st[6];
+  step_parts(st, n_rays, n_list, rays, rng, list, hits, true, attenuation, status);
+  rc = tor::stage_in(ctx, st, 6);
   if (rc != TOR_OK) return rc;
-  // every array in (rays that are not listed keep what the caller holds), the step on the default stream, every output back
-  const Staging st(n_rays, n_list, list != nullptr);
-  HIP_TRY(ctx->hitq.io.ensure(st.total));
-  char* base = (char*)ctx->hitq.io.ptr;
-  void* const host[6] = {rays, rng, (void*)list, hits, attenuation, status};
-  for (int k = 0; k < 6; ++k)
-    if (st.bytes[k]) HIP_TRY(hipMemcpy(base + st.off[k], host[k], st.bytes[k], hipMemcpyHostToDevice));
-  rc = bounce_launch("tor_bounce_host", ctx, n_rays, base + st.off[0], base + st.off[1], list ? (const int32_t*)(base + st.off[2]) : nullptr,
-                     n_list, time_lo, time_hi, mode, base + st.off[3], (double*)(base + st.off[4]), (int32_t*)(base + st.off[5]), nullptr);
+  rc = bounce_launch("tor_bounce_host", ctx, n_rays, st[0].dev, st[1].dev, st[2].as<const int32_t>(), n_list, time_lo, time_hi, mode,
+                     st[3].dev, st[4].as<double>(), st[5].as<int32_t>(), nullptr);
   if (rc != TOR_OK) return rc;
-  for (int k = 0; k < 6; ++k)
-    if (k != 2) HIP_TRY(hipMemcpy(host[k], base + st.off[k], st.bytes[k], hipMemcpyDeviceToHost));
-  return TOR_OK;
+  return tor::stage_out(st, 6);
 }
 
 int tor_scatter_host(TorContext* ctx, int64_t n_rays, TorRay* rays, const TorHit* hits, TorRng* rng, const int32_t* list, int64_t n_list,
                      double* attenuation, int32_t* status) {
-  int rc = scatter_args("tor_scatter_host", ctx, n_rays, rays, hits, rng, list, n_list, attenuation, status);
-  if (rc != TOR_OK) return rc;
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  int rc = scatter_check("tor_scatter_host", ctx, n_rays, rays, hits, rng, list, n_list, attenuation, status);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  rc = host_wait(ctx);
+  tor::HostPart st[6];
+  step_parts(st, n_rays, n_list, rays, rng, list, hits, false, attenuation, status);
+  rc = tor::stage_in(ctx, st, 6);
   if (rc != TOR_OK) return rc;
-  const Staging st(n_rays, n_list, list != nullptr);
-  HIP_TRY(ctx->hitq.io.ensure(st.total));
-  char* base = (char*)ctx->hitq.io.ptr;
-  void* const host[6] = {rays, rng, (void*)list, (void*)hits, attenuation, status};
-  for (int k = 0; k < 6; ++k)
-    if (st.bytes[k]) HIP_TRY(hipMemcpy(base + st.off[k], host[k], st.bytes[k], hipMemcpyHostToDevice));
-  rc = scatter_launch("tor_scatter_host", ctx, n_rays, base + st.off[0], base + st.off[3], base + st.off[1],
-                      list ? (const int32_t*)(base + st.off[2]) : nullptr, n_list, (double*)(base + st.off[4]), (int32_t*)(base + st.off[5]),
-                      nullptr);
+  rc = scatter_launch("tor_scatter_host", ctx, n_rays, st[0].dev, st[3].dev, st[1].dev, st[2].as<const int32_t>(), n_list,
+                      st[4].as<double>(), st[5].as<int32_t>(), nullptr);
   if (rc != TOR_OK) return rc;
-  for (int k = 0; k < 6; ++k)
-    if (k != 2 && k != 3) HIP_TRY(hipMemcpy(host[k], base + st.off[k], st.bytes[k], hipMemcpyDeviceToHost));
-  return TOR_OK;
+  return tor::stage_out(st, 6);
 }
 
 int tor_sky_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const int32_t* d_list, int64_t n_list, double* d_color,
                    void* hip_stream) {
-  const int rc = list_args("tor_sky_device", ctx, n_rays, d_list, n_list);
+  const int rc = tor::list_args("tor_sky_device", ctx, n_rays, d_list, n_list);
   if (rc != TOR_OK) return rc;
   if (n_rays > 0 && n_list > 0 && (!d_rays || !d_color)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_sky_device: NULL rays or color");
   if (n_rays == 0 || n_list == 0) return TOR_OK;

@@ -189,29 +189,18 @@ __device__ __forceinline__ bool slab_bound(P bx, const QRay& r, double ix, doubl
   return (t_in <= t_out) && (t_in * (1.0 - 0x1p-40) <= bound);
 }
 
-// TorHit for the crossing (t, object): tor_hit_device's record for that root of that object (the end of hit_kernel, tor_query.hip)
+// TorHit for the crossing (t, object): tor_hit_device's record for that root of that object, from the by-object cold records
 __device__ __forceinline__ void write_record(double* o, const double* obj_cold, const QRay& r, double t, unsigned key) {
   const int object = (int)(key >> 1);
   const qgdptr c = (qgdptr)(uintptr_t)(obj_cold + 16 * (size_t)object);
-  double cx, cy, cz;
-  centre_at(c, r.time, cx, cy, cz);
-  const double px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;  // rays.nim:24-25 origin + t * direction
-  const double inv_r = c[6];                                                     // vec3s.nim:93-94: `/ radius` is `* (1.0 / radius)`
-  double nx = (px - cx) * inv_r, ny = (py - cy) * inv_r, nz = (pz - cz) * inv_r;
-  const bool front = (r.dx * nx + r.dy * ny + r.dz * nz) < 0.0;  // core.nim:47-49
-  if (!front) {
-    nx = -nx; ny = -ny; nz = -nz;
-  }
-  o[0] = px; o[1] = py; o[2] = pz;
-  o[3] = nx; o[4] = ny; o[5] = nz;
-  o[6] = t;
-  o[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)object));
+#include "tor_query_record.inc"
 }
 
 template <bool BLOCKS, bool MASKED, int CAP>
 __global__ __launch_bounds__(kHitThreads) void crossings_kernel(const XParams P, const MParams mk) {
   const QParams& p = P.q;
   const long long e = (long long)blockIdx.x * kHitThreads + threadIdx.x;
+  // listed_ray's rule (tor_query.hpp), spelled out: through the function two instructions of the blocks variants change places
   long long i = -1;  // the ray of list entry e; -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
   if (e < P.n_list) {
     const long long v = P.list ? (long long)P.list[e] : e;
@@ -224,19 +213,7 @@ __global__ __launch_bounds__(kHitThreads) void crossings_kernel(const XParams P,
   }
   const Sees<MASKED> vis{mk.grp, mk.box_or, r_mask};
   QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = p.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    if (p.t_range) {
-      r.t_min = p.t_range[2 * i];
-      r.t_max = p.t_range[2 * i + 1];
-    } else {
-      r.t_min = 0.001;  // render.nim:34
-      r.t_max = __builtin_inf();
-    }
-  }
+  if (live) load_ray(r, p.rays, p.t_range, i);
   r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
   const int K = P.k < CAP ? P.k : CAP;
   // records of a block tested per batch: all 8 with the small list; 4 with the large one, whose registers a batch of 8 would push
@@ -330,7 +307,7 @@ __global__ __launch_bounds__(kHitThreads) void crossings_kernel(const XParams P,
       double* o = rec + 8 * m;
       if (has) {
         write_record(o, P.obj_cold, r, L.t[j], L.key[j]);
-      } else {  // the miss record: object -1, every other field 0
+      } else {  // write_miss_record's stores (tor_query.hpp), spelled out for the same reason
         for (int k = 0; k < 7; ++k) o[k] = 0.0;
         o[7] = __longlong_as_double((long long)0xffffffffull);
       }
@@ -344,59 +321,19 @@ __global__ __launch_bounds__(kHitThreads) void crossings_kernel(const XParams P,
 
 namespace {
 
-constexpr int64_t kMaxItems = (int64_t)0x7fffffff * tor::kHitThreads;  // one lane per entry, at most 2^31 - 1 workgroups
-
-// every check that needs no device and does not read *ctx (the CPU suite runs these): what tor_occluded_device refuses, and k
-int crossings_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* list, int64_t n_list, int32_t k,
-                   double time_lo, double time_hi, int32_t mode, const void* cross, const void* count) {
+// the checks that need no device and do not read *ctx: what tor_occluded_device refuses, and k; then the scene
+int crossings_check(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* list, int64_t n_list, int32_t k,
+                    double time_lo, double time_hi, int32_t mode, const void* cross, const void* count) {
   using tor::fail;
   const std::string w = who;
-  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
-  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
-  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
-  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
-  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
-  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
+  int rc = tor::list_args(w, ctx, n_rays, list, n_list);
+  if (rc != TOR_OK) return rc;
   if (k < 1 || k > TOR_CROSSINGS_MAX)
     return fail(TOR_ERR_INVALID_ARGUMENT, w + ": k must be in 1 .. TOR_CROSSINGS_MAX (" + std::to_string(TOR_CROSSINGS_MAX) + ")");
-  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
-  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
+  rc = tor::range_args(w, time_lo, time_hi, mode);
+  if (rc != TOR_OK) return rc;
   if (n_rays > 0 && n_list > 0 && (!rays || !cross || !count)) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays, cross or count");
-  return TOR_OK;
-}
-
-// the cold records by ORIGINAL index, for the records rebuilt at the end: the cache tor_scatter_device keeps (ensure_obj_cold,
-// tor_bounce.hip), filled the same way, so whichever of the two runs first fills it for both.  A TWIN of ensure_obj_cold: the two
-// must stay in step by hand (tor_bounce.hip and tor_query.hpp stay byte-identical in this change, so it could not move to a shared
-// place; DESIGN section 9 lists the merge)
-int crossings_obj_cold(const char* who, TorContext* ctx, hipStream_t stream) {
-  tor::HitQueryState& hq = ctx->hitq;
-  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
-  if (hq.obj_scene == gen) return TOR_OK;
-  hq.obj_scene = -1;
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
-  const int64_t n = ctx->n_objects;
-  std::vector<int64_t> ids((size_t)n);
-  for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
-  tor::HostLayout lay;
-  std::string err;
-  if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, lay, err, nullptr))
-    return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": " + err);
-  hq.obj_cold_host.assign((size_t)(n > 0 ? n : 1) * 16, 0.0);
-  for (size_t s = 0; s < lay.n_sorted && n > 0; ++s) {
-    const double* c = &lay.cold[16 * s];
-    if (c[15] == -1.0) continue;  // padding slot
-    int64_t orig;
-    std::memcpy(&orig, &c[14], 8);
-    if (orig >= 0 && orig < n) std::memcpy(&hq.obj_cold_host[16 * (size_t)orig], c, 16 * sizeof(double));
-  }
-  const size_t bytes = hq.obj_cold_host.size() * sizeof(double);
-  HIP_TRY(hq.obj_cold.ensure(bytes));
-  HIP_TRY(hipMemcpyAsync(hq.obj_cold.ptr, hq.obj_cold_host.data(), bytes, hipMemcpyHostToDevice, stream));
-  hq.obj_scene = gen;
-  return TOR_OK;
+  return tor::scene_args(who, ctx);
 }
 
 template <bool BLOCKS, bool MASKED>
@@ -412,11 +349,14 @@ void crossings_dispatch(unsigned grid, hipStream_t stream, const tor::XParams& P
 int crossings_launch(const char* who, TorContext* ctx, int64_t n_rays, const void* d_rays, const double* d_t_range, const int32_t* d_list,
                      int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi, int32_t mode,
                      TorCrossing* d_cross, int32_t* d_count, TorHit* d_records, hipStream_t stream) {
-  tor::HitQueryState& hq = ctx->hitq;
   tor::XParams P{};
+  tor::MParams mk{};
   bool blocks = false;
   std::string why;
-  const int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, P.q, blocks, why);
+  const bool masked = d_mask != nullptr || mask != 0xFFFFFFFFu;
+  int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, P.q, blocks, why);
+  if (rc == TOR_OK && d_records) rc = tor::ensure_obj_cold(who, ctx, stream);  // the records are rebuilt from the by-object records
+  if (rc == TOR_OK && masked) rc = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
   if (rc != TOR_OK) return rc;
   P.q.rays = (const double*)d_rays;
   P.q.t_range = d_t_range;
@@ -427,31 +367,11 @@ int crossings_launch(const char* who, TorContext* ctx, int64_t n_rays, const voi
   P.cross = (double*)d_cross;
   P.count = d_count;
   P.records = (double*)d_records;
-  if (d_records) {
-    const int ro = crossings_obj_cold(who, ctx, stream);
-    if (ro != TOR_OK) return ro;
-    P.obj_cold = (const double*)hq.obj_cold.ptr;
-  }
+  if (d_records) P.obj_cold = (const double*)ctx->hitq.obj_cold.ptr;
   const unsigned grid = (unsigned)((n_list + tor::kHitThreads - 1) / tor::kHitThreads);
-  const bool masked = d_mask != nullptr || mask != 0xFFFFFFFFu;
-  tor::MParams mk{};
-  if (masked) {
-    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
-    if (rm != TOR_OK) return rm;
-    if (blocks) crossings_dispatch<true, true>(grid, stream, P, mk);
-    else crossings_dispatch<false, true>(grid, stream, P, mk);
-  } else if (blocks) {
-    crossings_dispatch<true, false>(grid, stream, P, mk);
-  } else {
-    crossings_dispatch<false, false>(grid, stream, P, mk);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(hq.ev_done, stream));
-  hq.launched = true;
-  hq.stream = (void*)stream;
-  const std::string what = masked ? "crossings (masked): " : "crossings: ";
-  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
-  return TOR_OK;
+  tor::for_variant(blocks, masked,
+                   [&](auto B, auto M) { crossings_dispatch<decltype(B)::value, decltype(M)::value>(grid, stream, P, mk); });
+  return tor::query_finish(ctx, stream, "crossings", masked, blocks, why);
 }
 
 }  // namespace
@@ -461,10 +381,8 @@ extern "C" {
 int tor_crossings_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
                          int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi, int32_t mode,
                          TorCrossing* d_cross, int32_t* d_count, TorHit* d_records, void* hip_stream) {
-  const int rc = crossings_args("tor_crossings_device", ctx, n_rays, d_rays, d_list, n_list, k, time_lo, time_hi, mode, d_cross, d_count);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_crossings_device: no scene uploaded");
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  const int rc = crossings_check("tor_crossings_device", ctx, n_rays, d_rays, d_list, n_list, k, time_lo, time_hi, mode, d_cross, d_count);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   return crossings_launch("tor_crossings_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, k, d_mask, mask, time_lo, time_hi, mode,
                           d_cross, d_count, d_records, (hipStream_t)hip_stream);
@@ -474,40 +392,26 @@ int tor_crossings_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, cons
                        int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi, int32_t mode, TorCrossing* cross,
                        int32_t* count, TorHit* records) {
   const char* who = "tor_crossings_host";
-  int rc = crossings_args(who, ctx, n_rays, rays, list, n_list, k, time_lo, time_hi, mode, cross, count);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  int rc = crossings_check(who, ctx, n_rays, rays, list, n_list, k, time_lo, time_hi, mode, cross, count);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  tor::HitQueryState& hq = ctx->hitq;
-  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
-  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
-  // rays, t ranges, the list, the masks and the outputs (rays that are not listed keep what the caller holds) in, each padded to 64
-  // bytes; the query on the default stream; the outputs back
+  // every array in -- the outputs too, rays that are not listed keep what the caller holds --, the query on the default stream, the
+  // outputs back
   const size_t n = (size_t)n_rays, nk = n * (size_t)k;
-  constexpr int kParts = 7;
-  const size_t bytes[kParts] = {n * sizeof(TorRay), t_range ? n * 16 : 0, list ? (size_t)n_list * 4 : 0, masks ? n * 4 : 0,
-                                nk * sizeof(TorCrossing), n * 4, records ? nk * sizeof(TorHit) : 0};
-  const void* const host[kParts] = {rays, t_range, list, masks, cross, count, records};
-  size_t off[kParts], total = 0;
-  for (int p = 0; p < kParts; ++p) {
-    off[p] = total;
-    total += (bytes[p] + 63) / 64 * 64;
-  }
-  HIP_TRY(hq.io.ensure(total));
-  char* base = (char*)hq.io.ptr;
-  for (int p = 0; p < kParts; ++p)
-    if (bytes[p]) HIP_TRY(hipMemcpy(base + off[p], host[p], bytes[p], hipMemcpyHostToDevice));
-  rc = crossings_launch(who, ctx, n_rays, base + off[0], t_range ? (const double*)(base + off[1]) : nullptr,
-                        list ? (const int32_t*)(base + off[2]) : nullptr, n_list, k, masks ? (const uint32_t*)(base + off[3]) : nullptr, mask,
-                        time_lo, time_hi, mode, (TorCrossing*)(base + off[4]), (int32_t*)(base + off[5]),
-                        records ? (TorHit*)(base + off[6]) : nullptr, nullptr);
+  tor::HostPart st[7] = {{rays, n * sizeof(TorRay), true, false},
+                         {t_range, t_range ? n * 16 : 0, true, false},
+                         {list, list ? (size_t)n_list * 4 : 0, true, false},
+                         {masks, masks ? n * 4 : 0, true, false},
+                         {cross, nk * sizeof(TorCrossing), true, true},
+                         {count, n * 4, true, true},
+                         {records, records ? nk * sizeof(TorHit) : 0, true, true}};
+  rc = tor::stage_in(ctx, st, 7);
   if (rc != TOR_OK) return rc;
-  HIP_TRY(hipMemcpy(cross, base + off[4], bytes[4], hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(count, base + off[5], bytes[5], hipMemcpyDeviceToHost));
-  if (records) HIP_TRY(hipMemcpy(records, base + off[6], bytes[6], hipMemcpyDeviceToHost));
-  return TOR_OK;
+  rc = crossings_launch(who, ctx, n_rays, st[0].dev, st[1].as<const double>(), st[2].as<const int32_t>(), n_list, k,
+                        st[3].as<const uint32_t>(), mask, time_lo, time_hi, mode, st[4].as<TorCrossing>(), st[5].as<int32_t>(),
+                        st[6].as<TorHit>(), nullptr);
+  if (rc != TOR_OK) return rc;
+  return tor::stage_out(st, 7);
 }
 
 }  // extern "C"

@@ -11,13 +11,15 @@
 // block boxes, with their margin, `reach` and a_min, skip only those).  WHICH object occludes depends on the order, so it is not
 // reported.
 //
-//   occluded_kernel<false>  brute force: one listed ray per lane; the cold slots of the flat layout in a wave-uniform loop (scalar
+//   occluded_kernel<false, MASKED>  brute force: one listed ray per lane; the cold slots of the flat layout in a wave-uniform loop (scalar
 //                           loads) that the wave leaves once every live lane has its answer
-//   occluded_kernel<true>   blocks: the culling layout's always-objects first, in the same loop (in random_scene they hold the
+//   occluded_kernel<true, MASKED>   blocks: the culling layout's always-objects first, in the same loop (in random_scene they hold the
 //                           ground sphere, which settles most downward rays); then the rays the boxes do not hold for walk the
 //                           spatial slots, wave-uniform, until all of them are settled; the others descend the block / super boxes
 //                           per lane and leave at every level once their flag is set.  The 8 records of a block are tested
 //                           together: their loads go out as one batch, and a branch between them would serialise eight round trips.
+//   MASKED                  with visibility groups: the OR over the objects the ray sees (the kernel's comment; KArgs and Sees,
+//                           tor_query.hpp)
 //
 // The slab test's exit is clipped at the ray's t_max (slab_clipped): a box the segment ends in front of is not entered.  Why that
 // stays conservative.  Let `sol` be a root the reference accepts for an object of the box, for a ray that uses the boxes
@@ -102,122 +104,26 @@ __device__ __forceinline__ bool slab_clipped(P bx, const QRay& r, double ix, dou
   return (t_in <= t_out) && (t_in * (1.0 - 0x1p-40) <= r.t_max);
 }
 
-template <bool BLOCKS>
-__global__ __launch_bounds__(kHitThreads) void occluded_kernel(const OParams P) {
+// MASKED: with visibility groups (tor_occluded_masked_device) only the objects a ray sees can occlude it: the OR of the file head,
+// over the sub-list.  Every early exit counts a lane as settled only once it has FOUND an occluder: a lane whose mask rejects a
+// slot or a box is simply not tested there and stays unsettled.
+template <bool BLOCKS, bool MASKED>
+__global__ __launch_bounds__(kHitThreads) void occluded_kernel(const KArgs<OParams, MASKED> A) {
+  const OParams& P = A.P;
   const QParams& p = P.q;
-  const long long e = (long long)blockIdx.x * kHitThreads + threadIdx.x;
-  long long i = -1;  // the ray of list entry e; -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
-  if (e < P.n_list) {
-    const long long v = P.list ? (long long)P.list[e] : e;
-    if (v >= 0 && v < p.n_rays) i = v;
-  }
+  const long long i = listed_ray(P.list, P.n_list, p.n_rays, (long long)blockIdx.x * kHitThreads + threadIdx.x);
   const bool live = i >= 0;
-  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = p.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    if (p.t_range) {
-      r.t_min = p.t_range[2 * i];
-      r.t_max = p.t_range[2 * i + 1];
-    } else {
-      r.t_min = 0.001;  // render.nim:34
-      r.t_max = __builtin_inf();
-    }
+  Sees<MASKED> vis{nullptr, nullptr, 0u};  // (lanes without a ray see nothing)
+  if constexpr (MASKED) {
+    if (live) vis.m = A.mk.ray_mask ? A.mk.ray_mask[i] : A.mk.mask;
+    vis.grp = A.mk.grp;
+    vis.box_or = A.mk.box_or;
   }
+  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
+  if (live) load_ray(r, p.rays, p.t_range, i);
   r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
   bool found = false;
-  // wave-uniform: every unsettled lane tests the same record; the wave leaves when none is left
-  for (int s = 0; s < p.n_uniform; ++s) {
-    if (__ballot(live && !found) == 0) break;
-    if (live && !found) found = occludes((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)s), r);
-  }
-  if constexpr (BLOCKS) {
-    const double ex = r.ox - p.org[0], ey = r.oy - p.org[1], ez = r.oz - p.org[2];
-    const bool boxed = live && (r.t_min >= 0.0) && (r.time >= p.time_lo) && (r.time <= p.time_hi) &&
-                       (ex * ex + ey * ey + ez * ez <= p.reach2) && (r.a >= p.a_min);
-    const bool walk = live && !boxed;
-    // rays the boxes do not hold for: every spatial slot, wave-uniform, until all of them are settled
-    for (int s = 0; s < p.n_spatial; ++s) {
-      if (__ballot(walk && !found) == 0) break;
-      if (walk && !found) found = occludes((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)(p.spatial_base + s)), r);
-    }
-    if (boxed && !found) {
-      const double ix = 1.0 / r.dx, iy = 1.0 / r.dy, iz = 1.0 / r.dz;
-      auto test_box = [&](int box) {  // the blocks behind block box `box`, 8 objects each
-        for (int fk = 0; fk < p.fanout && !found; ++fk) {
-          const int slot0 = p.spatial_base + 8 * (box * p.fanout + fk);
-          bool any = false;
-          for (int k = 0; k < 8; ++k) any |= occludes((qgdptr)(uintptr_t)(p.cold + 16 * (size_t)(slot0 + k)), r);
-          found = any;
-        }
-      };
-      const int n_top = p.two_level ? p.n_super : p.n_boxes;
-      const int top0 = p.two_level ? p.super0 : 0;
-      // the top-level boxes 64 at a time (scalar loads); then the ones the ray's segment enters
-      for (int c0 = 0; c0 < n_top && !found; c0 += 64) {
-        const int cn = n_top - c0 < 64 ? n_top - c0 : 64;
-        unsigned long long m = 0;
-        for (int j = 0; j < cn; ++j)
-          if (slab_clipped((qcdptr)(uintptr_t)(p.bnd + 8 * (size_t)(top0 + c0 + j)), r, ix, iy, iz)) m |= 1ull << j;
-        while (m != 0 && !found) {
-          const int top = c0 + __builtin_ctzll(m);
-          m &= m - 1;
-          if (!p.two_level) {
-            test_box(top);
-            continue;
-          }
-          // super box `top`: its 8 block boxes (NaN padding boxes are never entered)
-          unsigned m8 = 0;
-          for (int k = 0; k < 8; ++k)
-            if (slab_clipped((qgdptr)(uintptr_t)(p.bnd + 8 * (size_t)(8 * top + k)), r, ix, iy, iz)) m8 |= 1u << k;
-          while (m8 != 0 && !found) {
-            const int k = __builtin_ctz(m8);
-            m8 &= m8 - 1;
-            test_box(8 * top + k);
-          }
-        }
-      }
-    }
-  }
-  if (live) P.occluded[i] = found ? 1 : 0;
-}
-
-// occluded_kernel with visibility groups (tor_occluded_masked_device): only the objects a ray sees can occlude it.  The OR of the file
-// head, over the sub-list.  A kernel of its own (hit_masked_kernel, tor_query.hip, says why); it keeps every early exit, and an exit
-// counts a lane as settled only once it has FOUND an occluder: a lane whose mask rejects a slot or a box is simply not tested there.
-template <bool BLOCKS>
-__global__ __launch_bounds__(kHitThreads) void occluded_masked_kernel(const OParams P, const MParams mk) {
-  const QParams& p = P.q;
-  const long long e = (long long)blockIdx.x * kHitThreads + threadIdx.x;
-  long long i = -1;  // the ray of list entry e; -1: past the end of the list, or an entry outside [0, n_rays) (skipped)
-  if (e < P.n_list) {
-    const long long v = P.list ? (long long)P.list[e] : e;
-    if (v >= 0 && v < p.n_rays) i = v;
-  }
-  const bool live = i >= 0;
-  unsigned r_mask = 0u;  // (lanes without a ray see nothing)
-  if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
-  const Sees<true> vis{mk.grp, mk.box_or, r_mask};
-  QRay r{};  // (lanes without a ray: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = p.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    if (p.t_range) {
-      r.t_min = p.t_range[2 * i];
-      r.t_max = p.t_range[2 * i + 1];
-    } else {
-      r.t_min = 0.001;  // render.nim:34
-      r.t_max = __builtin_inf();
-    }
-  }
-  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30
-  bool found = false;
-  // wave-uniform: every unsettled lane that sees the slot tests the same record; the wave leaves when no unsettled lane is left (a
-  // lane that does not see a slot stays unsettled)
+  // wave-uniform: every unsettled lane that sees the slot tests the same record; the wave leaves when no unsettled lane is left
   for (int s = 0; s < p.n_uniform; ++s) {
     if (__ballot(live && !found) == 0) break;
     if (live && !found && vis.slot_u(s)) found = occludes((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)s), r);
@@ -279,37 +185,28 @@ __global__ __launch_bounds__(kHitThreads) void occluded_masked_kernel(const OPar
 
 namespace {
 
-constexpr int64_t kMaxItems = (int64_t)0x7fffffff * tor::kHitThreads;  // one lane per entry, at most 2^31 - 1 workgroups
-
-// every check that needs no device and does not read *ctx (the CPU suite runs these): what tor_hit_device refuses, and the path
-// steps' list rules
-int occluded_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* list, int64_t n_list, double time_lo,
-                  double time_hi, int32_t mode, const void* occluded) {
-  using tor::fail;
+// the checks that need no device and do not read *ctx: what tor_hit_device refuses, and the path steps' list rules;
+// then the scene
+int occluded_check(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, const void* list, int64_t n_list, double time_lo,
+                   double time_hi, int32_t mode, const void* occluded) {
   const std::string w = who;
-  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
-  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
-  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
-  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
-  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
-  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
-  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
-  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
-  if (n_rays > 0 && n_list > 0 && (!rays || !occluded)) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays or occluded");
-  return TOR_OK;
+  int rc = tor::list_args(w, ctx, n_rays, list, n_list);
+  if (rc == TOR_OK) rc = tor::range_args(w, time_lo, time_hi, mode);
+  if (rc != TOR_OK) return rc;
+  if (n_rays > 0 && n_list > 0 && (!rays || !occluded)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays or occluded");
+  return tor::scene_args(who, ctx);
 }
 
 // the launch; the arguments are checked, n_rays > 0 and n_list > 0
 int occluded_launch(const char* who, TorContext* ctx, int64_t n_rays, const void* d_rays, const double* d_t_range, const int32_t* d_list,
-                    int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, hipStream_t stream,
-                    bool masked = false, const uint32_t* d_mask = nullptr, uint32_t mask = 0) {
-  tor::HitQueryState& hq = ctx->hitq;
+                    int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, hipStream_t stream, bool masked,
+                    const uint32_t* d_mask, uint32_t mask) {
   tor::OParams P{};
+  tor::MParams mk{};
   bool blocks = false;
   std::string why;
-  const int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, P.q, blocks, why);
+  int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, P.q, blocks, why);
+  if (rc == TOR_OK && masked) rc = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
   if (rc != TOR_OK) return rc;
   P.q.rays = (const double*)d_rays;
   P.q.t_range = d_t_range;
@@ -318,59 +215,44 @@ int occluded_launch(const char* who, TorContext* ctx, int64_t n_rays, const void
   P.n_list = (long long)n_list;
   P.occluded = d_occluded;
   const unsigned grid = (unsigned)((n_list + tor::kHitThreads - 1) / tor::kHitThreads);
-  if (masked) {
-    tor::MParams mk{};
-    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
-    if (rm != TOR_OK) return rm;
-    if (blocks) hipLaunchKernelGGL(tor::occluded_masked_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
-    else hipLaunchKernelGGL(tor::occluded_masked_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P, mk);
-  } else if (blocks) {
-    hipLaunchKernelGGL(tor::occluded_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
-  } else {
-    hipLaunchKernelGGL(tor::occluded_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, P);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(hq.ev_done, stream));
-  hq.launched = true;
-  hq.stream = (void*)stream;
-  const std::string what = masked ? "occluded (masked): " : "occluded: ";
-  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
-  return TOR_OK;
+  tor::for_variant(blocks, masked, [&](auto B, auto M) {
+    hipLaunchKernelGGL((tor::occluded_kernel<decltype(B)::value, decltype(M)::value>), dim3(grid), dim3(tor::kHitThreads), 0, stream,
+                       tor::kargs<decltype(M)::value>(P, mk));
+  });
+  return tor::query_finish(ctx, stream, "occluded", masked, blocks, why);
 }
 
-// tor_occluded_host / tor_occluded_masked_host (masks: nullable host words, staged with the other arrays)
+// tor_occluded_device / tor_occluded_masked_device
+int occluded_device(const char* who, TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
+                    int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, void* hip_stream, bool masked,
+                    const uint32_t* d_mask, uint32_t mask) {
+  const int rc = occluded_check(who, ctx, n_rays, d_rays, d_list, n_list, time_lo, time_hi, mode, d_occluded);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return occluded_launch(who, ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded, (hipStream_t)hip_stream,
+                         masked, d_mask, mask);
+}
+
+// tor_occluded_host / tor_occluded_masked_host (masks: nullable host words): every array in -- the output too, rays that are not
+// listed keep what the caller holds --, the query on the default stream, the output back
 int occluded_host(const char* who, TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,
                   int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* occluded, bool masked, const uint32_t* masks,
                   uint32_t mask) {
-  int rc = occluded_args(who, ctx, n_rays, rays, list, n_list, time_lo, time_hi, mode, occluded);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
+  int rc = occluded_check(who, ctx, n_rays, rays, list, n_list, time_lo, time_hi, mode, occluded);
+  if (rc != TOR_OK || n_rays == 0 || n_list == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  tor::HitQueryState& hq = ctx->hitq;
-  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run (tor_hit_host)
-  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
-  // rays, t ranges, the list, the output (rays that are not listed keep what the caller holds) and the masks in, each padded to 64
-  // bytes; the query on the default stream; the output back
   const size_t n = (size_t)n_rays;
-  const size_t bytes[5] = {n * sizeof(TorRay), t_range ? n * 16 : 0, list ? (size_t)n_list * 4 : 0, n * 4, masked && masks ? n * 4 : 0};
-  const void* const host[5] = {rays, t_range, list, occluded, masks};
-  size_t off[5], total = 0;
-  for (int k = 0; k < 5; ++k) {
-    off[k] = total;
-    total += (bytes[k] + 63) / 64 * 64;
-  }
-  HIP_TRY(hq.io.ensure(total));
-  char* base = (char*)hq.io.ptr;
-  for (int k = 0; k < 5; ++k)
-    if (bytes[k]) HIP_TRY(hipMemcpy(base + off[k], host[k], bytes[k], hipMemcpyHostToDevice));
-  rc = occluded_launch(who, ctx, n_rays, base + off[0], t_range ? (const double*)(base + off[1]) : nullptr,
-                       list ? (const int32_t*)(base + off[2]) : nullptr, n_list, time_lo, time_hi, mode, (int32_t*)(base + off[3]), nullptr,
-                       masked, bytes[4] ? (const uint32_t*)(base + off[4]) : nullptr, mask);
+  tor::HostPart st[5] = {{rays, n * sizeof(TorRay), true, false},
+                         {t_range, t_range ? n * 16 : 0, true, false},
+                         {list, list ? (size_t)n_list * 4 : 0, true, false},
+                         {occluded, n * 4, true, true},
+                         {masks, masked && masks ? n * 4 : 0, true, false}};
+  rc = tor::stage_in(ctx, st, 5);
   if (rc != TOR_OK) return rc;
-  HIP_TRY(hipMemcpy(occluded, base + off[3], bytes[3], hipMemcpyDeviceToHost));
-  return TOR_OK;
+  rc = occluded_launch(who, ctx, n_rays, st[0].dev, st[1].as<const double>(), st[2].as<const int32_t>(), n_list, time_lo, time_hi, mode,
+                       st[3].as<int32_t>(), nullptr, masked, st[4].as<const uint32_t>(), mask);
+  if (rc != TOR_OK) return rc;
+  return tor::stage_out(st, 5);
 }
 
 }  // namespace
@@ -379,13 +261,8 @@ extern "C" {
 
 int tor_occluded_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
                         int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, void* hip_stream) {
-  const int rc = occluded_args("tor_occluded_device", ctx, n_rays, d_rays, d_list, n_list, time_lo, time_hi, mode, d_occluded);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_occluded_device: no scene uploaded");
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return occluded_launch("tor_occluded_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded,
-                         (hipStream_t)hip_stream);
+  return occluded_device("tor_occluded_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded,
+                         hip_stream, false, nullptr, 0);
 }
 
 int tor_occluded_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list, int64_t n_list,
@@ -396,13 +273,8 @@ int tor_occluded_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const
 int tor_occluded_masked_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, const int32_t* d_list,
                                int64_t n_list, double time_lo, double time_hi, int32_t mode, int32_t* d_occluded, void* hip_stream,
                                const uint32_t* d_mask, uint32_t mask) {
-  const int rc = occluded_args("tor_occluded_masked_device", ctx, n_rays, d_rays, d_list, n_list, time_lo, time_hi, mode, d_occluded);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_occluded_masked_device: no scene uploaded");
-  if (n_rays == 0 || n_list == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return occluded_launch("tor_occluded_masked_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded,
-                         (hipStream_t)hip_stream, true, d_mask, mask);
+  return occluded_device("tor_occluded_masked_device", ctx, n_rays, d_rays, d_t_range, d_list, n_list, time_lo, time_hi, mode, d_occluded,
+                         hip_stream, true, d_mask, mask);
 }
 
 int tor_occluded_masked_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, const int32_t* list,

@@ -1,8 +1,8 @@
 // tor_query.hip -- batched closest-hit queries against the uploaded scene (tor_hit_device / tor_hit_host, include/tor_render.h):
 // the reference's HittableList.hit (hittables_lists.nim:48-55 over spheres.nim:28-49 / moving_spheres.nim:39-67) for rays the
 // caller supplies, on gfx950.  Kernels, parameter struct and entry points of their own: nothing here is shared with the integrator
-// (tor_kernels.hip, KParams, kernel/*.inc), whose kernels stay as they are.  The exact test, the slab test, the descent and the host
-// setup live in tor_query.hpp / tor_query_descent.inc, shared with the radiance queries (tor_radiance.hip).
+// (tor_kernels.hip, KParams, kernel/*.inc), whose kernels stay as they are.  The exact test, the slab test, the descent, the record
+// and the host glue live in tor_query.hpp / tor_query_descent.inc / tor_query_record.inc, shared with the other query families.
 //
 // The sequential `closest_so_far` loop is order independent.  An object replaces the record iff its accepted root in (t_min, t_max)
 // -- the first root if it lies in the interval, else the second -- is below the closest so far: the first root is never larger than
@@ -10,16 +10,18 @@
 // ties to the lowest ORIGINAL index, whatever order the objects are visited in and whichever objects are skipped because they cannot
 // be hit.  The record (p, normal, front_face) is then built once, for the winner, with the reference's operations.
 //
-//   hit_kernel<false>  brute force: one ray per lane; every cold slot of the flat layout in a wave-uniform loop (scalar loads)
-//   hit_kernel<true>   blocks: the culling layout's always-objects in the same loop; then per lane a float64 slab test of the block
-//                      boxes (two-level scenes: the super boxes, then the 8 block boxes of each super box entered) and the exact test for
-//                      the 8 objects of every block entered.  A ray the boxes cannot answer for walks every spatial slot instead:
-//                      its time lies outside the range the boxes were built for (or is NaN), its t_min is not >= 0 (the slab test
-//                      clips at 0), or its origin lies beyond the reach of the boxes' margin (below).
-//   hit_masked_kernel<>  the same two with visibility groups (tor_scene_groups): object j takes part for ray i iff groups[j] &
-//                      mask_i != 0.  The order independence above is what makes this exact: the closest hit over the objects a ray sees
-//                      is the sequential loop on the sub-list of those objects, ties to the lowest index among them.  Skipping a box
-//                      whose OR-word shares no bit with the ray's mask skips only objects the ray does not see.
+//   hit_kernel<false, MASKED>  brute force: one ray per lane; every cold slot of the flat layout in a wave-uniform loop (scalar loads)
+//   hit_kernel<true, MASKED>   blocks: the culling layout's always-objects in the same loop; then per lane a float64 slab test of the
+//                      block boxes (two-level scenes: the super boxes, then the 8 block boxes of each super box entered) and the exact
+//                      test for the 8 objects of every block entered.  A ray the boxes cannot answer for walks every spatial slot
+//                      instead: its time lies outside the range the boxes were built for (or is NaN), its t_min is not >= 0 (the
+//                      slab test clips at 0), or its origin lies beyond the reach of the boxes' margin (below).
+//   MASKED             with visibility groups (tor_scene_groups): object j takes part for ray i iff groups[j] & mask_i != 0.  The
+//                      order independence above is what makes this exact: the closest hit over the objects a ray sees is the
+//                      sequential loop on the sub-list of those objects, ties to the lowest index among them.  Skipping a box whose
+//                      OR-word shares no bit with the ray's mask skips only objects the ray does not see.  One kernel text for both:
+//                      the argument (KArgs, tor_query.hpp) carries the group words only when MASKED, `vis` is a Sees<MASKED>, and
+//                      the unmasked instantiations compile to what they were without the parameter.
 //
 // Why the boxes' margin needs a reach.  The reference's own test rounds: disc = half_b^2 - a * c carries an absolute error of at most
 // ~12 eps |d|^2 (|oc|^2 + r^2) (eps = 2^-53; half_b^2 and a * c each within 5 roundings, then the difference), and the exact value is
@@ -52,100 +54,32 @@ static_assert(sizeof(TorHit) == 64 && offsetof(TorHit, normal) == 24 && offsetof
 namespace tor {
 namespace {
 
-template <bool BLOCKS>
-__global__ __launch_bounds__(kHitThreads) void hit_kernel(const QParams p) {
+template <bool BLOCKS, bool MASKED>
+__global__ __launch_bounds__(kHitThreads) void hit_kernel(const KArgs<QParams, MASKED> A) {
+  const QParams& p = A.P;
   const long long i = (long long)blockIdx.x * kHitThreads + threadIdx.x;
   const bool live = i < p.n_rays;
-  QRay r{};  // (lanes past the end: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = p.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    if (p.t_range) {
-      r.t_min = p.t_range[2 * i];
-      r.t_max = p.t_range[2 * i + 1];
-    } else {
-      r.t_min = 0.001;  // render.nim:34
-      r.t_max = __builtin_inf();
-    }
+  Sees<MASKED> vis{nullptr, nullptr, 0u};  // the descent's `vis` (lanes past the end see nothing)
+  if constexpr (MASKED) {
+    if (live) vis.m = A.mk.ray_mask ? A.mk.ray_mask[i] : A.mk.mask;
+    vis.grp = A.mk.grp;
+    vis.box_or = A.mk.box_or;
   }
+  QRay r{};  // (lanes past the end: t_max = 0 accepts nothing)
+  if (live) load_ray(r, p.rays, p.t_range, i);
   r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30 r.direction.length_squared()
   QBest b{r.t_max, INT_MAX, -1};
 #include "tor_query_descent.inc"
   if (!live) return;
   double* o = p.hits + 8 * i;
-  if (b.slot < 0) {  // miss: object -1, every other field 0
-    for (int k = 0; k < 7; ++k) o[k] = 0.0;
-    o[7] = __longlong_as_double((long long)0xffffffffull);
+  if (b.slot < 0) {
+    write_miss_record(o);
     return;
   }
   const qgdptr c = (qgdptr)(uintptr_t)(p.cold + 16 * (size_t)b.slot);
-  double cx, cy, cz;
-  centre_at(c, r.time, cx, cy, cz);
   const double t = b.t;
-  const double px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;  // rays.nim:24-25 origin + t * direction
-  const double inv_r = c[6];                                                     // vec3s.nim:93-94: `/ radius` is `* (1.0 / radius)`
-  double nx = (px - cx) * inv_r, ny = (py - cy) * inv_r, nz = (pz - cz) * inv_r;
-  const bool front = (r.dx * nx + r.dy * ny + r.dz * nz) < 0.0;  // core.nim:47-49
-  if (!front) {
-    nx = -nx; ny = -ny; nz = -nz;
-  }
-  o[0] = px; o[1] = py; o[2] = pz;
-  o[3] = nx; o[4] = ny; o[5] = nz;
-  o[6] = t;
-  o[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)b.orig));
-}
-
-// hit_kernel with visibility groups.  A kernel of its own, statement for statement hit_kernel's but for `vis`: sharing the body
-// through a function or a second template parameter changes hit_kernel's name or its register allocation, and the unmasked kernels
-// stay byte-identical.
-template <bool BLOCKS>
-__global__ __launch_bounds__(kHitThreads) void hit_masked_kernel(const QParams p, const MParams mk) {
-  const long long i = (long long)blockIdx.x * kHitThreads + threadIdx.x;
-  const bool live = i < p.n_rays;
-  unsigned r_mask = 0u;  // (lanes past the end see nothing)
-  if (live) r_mask = mk.ray_mask ? mk.ray_mask[i] : mk.mask;
-  const Sees<true> vis{mk.grp, mk.box_or, r_mask};  // the descent's `vis`
-  QRay r{};  // (lanes past the end: t_max = 0 accepts nothing)
-  if (live) {
-    const double* q = p.rays + 7 * i;
-    r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
-    r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
-    r.time = q[6];
-    if (p.t_range) {
-      r.t_min = p.t_range[2 * i];
-      r.t_max = p.t_range[2 * i + 1];
-    } else {
-      r.t_min = 0.001;  // render.nim:34
-      r.t_max = __builtin_inf();
-    }
-  }
-  r.a = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;  // spheres.nim:30 r.direction.length_squared()
-  QBest b{r.t_max, INT_MAX, -1};
-#include "tor_query_descent.inc"
-  if (!live) return;
-  double* o = p.hits + 8 * i;
-  if (b.slot < 0) {  // miss: object -1, every other field 0
-    for (int k = 0; k < 7; ++k) o[k] = 0.0;
-    o[7] = __longlong_as_double((long long)0xffffffffull);
-    return;
-  }
-  const qgdptr c = (qgdptr)(uintptr_t)(p.cold + 16 * (size_t)b.slot);
-  double cx, cy, cz;
-  centre_at(c, r.time, cx, cy, cz);
-  const double t = b.t;
-  const double px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;  // rays.nim:24-25 origin + t * direction
-  const double inv_r = c[6];                                                     // vec3s.nim:93-94: `/ radius` is `* (1.0 / radius)`
-  double nx = (px - cx) * inv_r, ny = (py - cy) * inv_r, nz = (pz - cz) * inv_r;
-  const bool front = (r.dx * nx + r.dy * ny + r.dz * nz) < 0.0;  // core.nim:47-49
-  if (!front) {
-    nx = -nx; ny = -ny; nz = -nz;
-  }
-  o[0] = px; o[1] = py; o[2] = pz;
-  o[3] = nx; o[4] = ny; o[5] = nz;
-  o[6] = t;
-  o[7] = __longlong_as_double((long long)(((unsigned long long)(front ? 1u : 0u) << 32) | (unsigned)b.orig));
+  const int object = b.orig;
+#include "tor_query_record.inc"
 }
 
 }  // namespace
@@ -165,86 +99,65 @@ HitQueryState::~HitQueryState() {
 
 namespace {
 
-constexpr int64_t kMaxHitRays = (int64_t)0x7fffffff * tor::kHitThreads;  // one lane per ray, at most 2^31 - 1 workgroups
-
-// every check that needs no device and does not read *ctx (the CPU suite runs these)
-int hit_args(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, double time_lo, double time_hi, int32_t mode,
-             const void* hits) {
-  using tor::fail;
+// the checks that need no device and do not read *ctx; then the scene
+int hit_check(const char* who, TorContext* ctx, int64_t n_rays, const void* rays, double time_lo, double time_hi, int32_t mode,
+              const void* hits) {
   const std::string w = who;
-  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
-  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
-  if (n_rays > kMaxHitRays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
-  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
-  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
-    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
-  if (n_rays > 0 && (!rays || !hits)) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays or hits");
-  return TOR_OK;
+  int rc = tor::count_args(w, ctx, n_rays);
+  if (rc == TOR_OK) rc = tor::range_args(w, time_lo, time_hi, mode);
+  if (rc != TOR_OK) return rc;
+  if (n_rays > 0 && (!rays || !hits)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, w + ": NULL rays or hits");
+  return tor::scene_args(who, ctx);
 }
 
 // the launch; the arguments are checked and n_rays > 0.  masked: with the visibility groups and d_mask / mask (tor_hit_masked_device)
 int hit_launch(const char* who, TorContext* ctx, int64_t n_rays, const void* d_rays, const double* d_t_range, double time_lo,
-               double time_hi, int32_t mode, void* d_hits, hipStream_t stream, bool masked = false, const uint32_t* d_mask = nullptr,
-               uint32_t mask = 0) {
-  tor::HitQueryState& hq = ctx->hitq;
+               double time_hi, int32_t mode, void* d_hits, hipStream_t stream, bool masked, const uint32_t* d_mask, uint32_t mask) {
   tor::QParams p{};
+  tor::MParams mk{};
   bool blocks = false;
   std::string why;
-  const int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, p, blocks, why);
+  int rc = tor::query_setup(who, ctx, time_lo, time_hi, mode, stream, p, blocks, why);
+  if (rc == TOR_OK && masked) rc = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
   if (rc != TOR_OK) return rc;
   p.rays = (const double*)d_rays;
   p.t_range = d_t_range;
   p.hits = (double*)d_hits;
   p.n_rays = (long long)n_rays;
   const unsigned grid = (unsigned)((n_rays + tor::kHitThreads - 1) / tor::kHitThreads);
-  if (masked) {
-    tor::MParams mk{};
-    const int rm = tor::masked_setup(ctx, blocks, d_mask, mask, stream, mk);
-    if (rm != TOR_OK) return rm;
-    if (blocks) hipLaunchKernelGGL(tor::hit_masked_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, p, mk);
-    else hipLaunchKernelGGL(tor::hit_masked_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, p, mk);
-  } else if (blocks) {
-    hipLaunchKernelGGL(tor::hit_kernel<true>, dim3(grid), dim3(tor::kHitThreads), 0, stream, p);
-  } else {
-    hipLaunchKernelGGL(tor::hit_kernel<false>, dim3(grid), dim3(tor::kHitThreads), 0, stream, p);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(hq.ev_done, stream));
-  hq.launched = true;
-  hq.stream = (void*)stream;
-  const std::string what = masked ? "hit (masked): " : "hit: ";
-  tor::set_last_note(blocks ? what + "blocks" : what + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
-  return TOR_OK;
+  tor::for_variant(blocks, masked, [&](auto B, auto M) {
+    hipLaunchKernelGGL((tor::hit_kernel<decltype(B)::value, decltype(M)::value>), dim3(grid), dim3(tor::kHitThreads), 0, stream,
+                       tor::kargs<decltype(M)::value>(p, mk));
+  });
+  return tor::query_finish(ctx, stream, "hit", masked, blocks, why);
 }
 
-// tor_hit_host / tor_hit_masked_host (masks: nullable host words, staged behind the records)
+// tor_hit_device / tor_hit_masked_device
+int hit_device(const char* who, TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, double time_lo,
+               double time_hi, int32_t mode, TorHit* d_hits, void* hip_stream, bool masked, const uint32_t* d_mask, uint32_t mask) {
+  const int rc = hit_check(who, ctx, n_rays, d_rays, time_lo, time_hi, mode, d_hits);
+  if (rc != TOR_OK || n_rays == 0) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return hit_launch(who, ctx, n_rays, d_rays, d_t_range, time_lo, time_hi, mode, d_hits, (hipStream_t)hip_stream, masked, d_mask, mask);
+}
+
+// tor_hit_host / tor_hit_masked_host (masks: nullable host words): copy in, the device query on the default stream, copy out
 int hit_host(const char* who, TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo, double time_hi,
              int32_t mode, TorHit* hits, bool masked, const uint32_t* masks, uint32_t mask) {
-  int rc = hit_args(who, ctx, n_rays, rays, time_lo, time_hi, mode, hits);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
-  if (n_rays == 0) return TOR_OK;
+  int rc = hit_check(who, ctx, n_rays, rays, time_lo, time_hi, mode, hits);
+  if (rc != TOR_OK || n_rays == 0) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  // copy in, the device query on the default stream, copy out (blocking)
-  const size_t ray_bytes = (size_t)n_rays * sizeof(TorRay), range_bytes = t_range ? (size_t)n_rays * 16 : 0;
-  const size_t hit_bytes = (size_t)n_rays * sizeof(TorHit), mask_bytes = masked && masks ? (size_t)n_rays * 4 : 0;
-  tor::HitQueryState& hq = ctx->hitq;
-  // blocking entry: it waits for the context's last render launch and last query, on whatever stream they run, where the
-  // asynchronous entry would refuse a different stream (the staging buffer below may be reallocated too)
-  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));
-  HIP_TRY(hq.io.ensure(ray_bytes + range_bytes + hit_bytes + mask_bytes));
-  char* base = (char*)hq.io.ptr;
-  char* d_masks = base + ray_bytes + range_bytes + hit_bytes;  // (every part before it is a multiple of 8 bytes)
-  HIP_TRY(hipMemcpy(base, rays, ray_bytes, hipMemcpyHostToDevice));
-  if (t_range) HIP_TRY(hipMemcpy(base + ray_bytes, t_range, range_bytes, hipMemcpyHostToDevice));
-  if (mask_bytes) HIP_TRY(hipMemcpy(d_masks, masks, mask_bytes, hipMemcpyHostToDevice));
-  rc = hit_launch(who, ctx, n_rays, base, t_range ? (const double*)(base + ray_bytes) : nullptr, time_lo, time_hi, mode,
-                  base + ray_bytes + range_bytes, nullptr, masked, mask_bytes ? (const uint32_t*)d_masks : nullptr, mask);
+  const size_t n = (size_t)n_rays;
+  tor::HostPart st[4] = {{rays, n * sizeof(TorRay), true, false},
+                         {t_range, t_range ? n * 16 : 0, true, false},
+                         {hits, n * sizeof(TorHit), false, true},
+                         {masks, masked && masks ? n * 4 : 0, true, false}};
+  rc = tor::stage_in(ctx, st, 4);
   if (rc != TOR_OK) return rc;
-  HIP_TRY(hipMemcpy(hits, base + ray_bytes + range_bytes, hit_bytes, hipMemcpyDeviceToHost));
-  return TOR_OK;
+  rc = hit_launch(who, ctx, n_rays, st[0].dev, st[1].as<const double>(), time_lo, time_hi, mode, st[2].dev, nullptr, masked,
+                  st[3].as<const uint32_t>(), mask);
+  if (rc != TOR_OK) return rc;
+  return tor::stage_out(st, 4);
 }
 
 }  // namespace
@@ -253,12 +166,7 @@ extern "C" {
 
 int tor_hit_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, double time_lo, double time_hi,
                    int32_t mode, TorHit* d_hits, void* hip_stream) {
-  int rc = hit_args("tor_hit_device", ctx, n_rays, d_rays, time_lo, time_hi, mode, d_hits);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_hit_device: no scene uploaded");
-  if (n_rays == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return hit_launch("tor_hit_device", ctx, n_rays, d_rays, d_t_range, time_lo, time_hi, mode, d_hits, (hipStream_t)hip_stream);
+  return hit_device("tor_hit_device", ctx, n_rays, d_rays, d_t_range, time_lo, time_hi, mode, d_hits, hip_stream, false, nullptr, 0);
 }
 
 int tor_hit_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo, double time_hi,
@@ -268,13 +176,8 @@ int tor_hit_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const doub
 
 int tor_hit_masked_device(TorContext* ctx, int64_t n_rays, const TorRay* d_rays, const double* d_t_range, double time_lo, double time_hi,
                           int32_t mode, TorHit* d_hits, void* hip_stream, const uint32_t* d_mask, uint32_t mask) {
-  int rc = hit_args("tor_hit_masked_device", ctx, n_rays, d_rays, time_lo, time_hi, mode, d_hits);
-  if (rc != TOR_OK) return rc;
-  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "tor_hit_masked_device: no scene uploaded");
-  if (n_rays == 0) return TOR_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  return hit_launch("tor_hit_masked_device", ctx, n_rays, d_rays, d_t_range, time_lo, time_hi, mode, d_hits, (hipStream_t)hip_stream,
-                    true, d_mask, mask);
+  return hit_device("tor_hit_masked_device", ctx, n_rays, d_rays, d_t_range, time_lo, time_hi, mode, d_hits, hip_stream, true, d_mask,
+                    mask);
 }
 
 int tor_hit_masked_host(TorContext* ctx, int64_t n_rays, const TorRay* rays, const double* t_range, double time_lo, double time_hi,

@@ -1,6 +1,9 @@
-// tor_query.hpp -- the closest-hit query's exact test, slab test and block / super-box descent (the head of tor_query.hip says why
-// they are exact), shared by the hit kernels (tor_query.hip) and the radiance kernels (tor_radiance.hip), and the host setup of
-// their launches (stream rule, layouts, cached block bounds).  The descent itself is tor_query_descent.inc.
+// tor_query.hpp -- what the query families (tor_query.hip, tor_radiance.hip, tor_bounce.hip, tor_occluded.hip, tor_crossings.hip)
+// share.  Device: the closest-hit query's exact test and slab test (the head of tor_query.hip says why they are exact; the descent
+// itself is tor_query_descent.inc), the visibility test `Sees`, the kernel argument struct with its optional mask part, a kernel's
+// prologue (list entry -> ray, the ray's load) and the TorHit record's stores.  Host: the one copy of the glue around a launch --
+// argument checks, stream rule, layouts and cached block bounds, group words, by-object records, the
+// launch's tail and note, the blocking entries' wait and staging.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +14,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "tor_context.hpp"
@@ -78,8 +82,18 @@ struct Sees {
     else return true;
   }
 };
-// the descent's `vis` in a kernel without masks; a masked kernel declares a local Sees<true> vis in its place
-constexpr Sees<false> vis{nullptr, nullptr, 0u};
+
+// A kernel's single argument: the family's parameters and, in a masked instantiation only, the group words behind them (so the
+// unmasked kernarg segment holds the parameters alone)
+template <typename PARAMS, bool MASKED>
+struct KArgs {
+  PARAMS P;
+};
+template <typename PARAMS>
+struct KArgs<PARAMS, true> {
+  PARAMS P;
+  MParams mk;
+};
 
 struct QRay {
   double ox, oy, oz, dx, dy, dz, time, t_min, t_max, a;
@@ -90,6 +104,31 @@ struct QBest {
   int orig;  // original index of the winner (ties: the lowest)
   int slot;  // its cold slot, -1 = no hit
 };
+
+// the ray of list entry `e` (list null: entry e is ray e), or -1: past the end of the list, or an entry outside [0, n_rays) (skipped).
+// The fields come by reference so that each is read where it is used, as in the kernels' own text: by value the compiler orders two
+// compares the other way round.
+__device__ __forceinline__ long long listed_ray(const int* const& list, const long long& n_list, const long long& n_rays, long long e) {
+  if (e >= n_list) return -1;
+  const long long i = list ? (long long)list[e] : e;
+  return (i >= 0 && i < n_rays) ? i : -1;
+}
+
+// ray i of `rays` (7 float64 per ray) with its range from t_range, or render.nim:34's (0.001, +inf) without one; r.a stays with the
+// caller, who computes it for every lane
+__device__ __forceinline__ void load_ray(QRay& r, const double* rays, const double* t_range, long long i) {
+  const double* q = rays + 7 * i;
+  r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+  r.dx = q[3]; r.dy = q[4]; r.dz = q[5];
+  r.time = q[6];
+  if (t_range) {
+    r.t_min = t_range[2 * i];
+    r.t_max = t_range[2 * i + 1];
+  } else {
+    r.t_min = 0.001;
+    r.t_max = __builtin_inf();
+  }
+}
 
 // centre of the object in cold record c at the ray's time: moving_spheres.nim:39-44 (center0 + (time - time0) / (time1 - time0) *
 // (center1 - center0); the record carries center1 - center0 and time1 - time0), or the sphere's centre
@@ -133,6 +172,12 @@ __device__ __forceinline__ void exact_test(P c, int slot, const QRay& r, QBest& 
   }
 }
 
+// TorHit for a miss: object -1, every other field 0
+__device__ __forceinline__ void write_miss_record(double* o) {
+  for (int k = 0; k < 7; ++k) o[k] = 0.0;
+  o[7] = __longlong_as_double((long long)0xffffffffull);
+}
+
 // float64 slab test of box record bx, clipped at t = 0: the integrator's test (integrate_loop_boxes64.inc); conservative for the
 // inflated boxes of compute_block_bounds
 template <typename P>
@@ -147,6 +192,45 @@ __device__ __forceinline__ bool slab(P bx, const QRay& r, double ix, double iy, 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
+
+constexpr int64_t kMaxItems = (int64_t)0x7fffffff * kHitThreads;  // one lane per ray or list entry, at most 2^31 - 1 workgroups
+
+// The argument checks the entries share; none needs a device or reads *ctx (the CPU suite runs these).  Each entry calls them in the
+// order its refusals are documented in and adds its own NULL-pointer (and k) check.
+int count_args(const std::string& w, TorContext* ctx, int64_t n_rays) {
+  using tor::fail;
+  if (!ctx) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": ctx is NULL");
+  if (n_rays < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays < 0");
+  if (n_rays > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_rays above 2^31 - 1 workgroups of 256 rays");
+  return TOR_OK;
+}
+
+// count_args and the list rule
+int list_args(const std::string& w, TorContext* ctx, int64_t n_rays, const void* list, int64_t n_list) {
+  using tor::fail;
+  const int rc = count_args(w, ctx, n_rays);
+  if (rc != TOR_OK) return rc;
+  if (n_list < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list < 0");
+  if (!list && n_list != n_rays) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": without a list n_list must be n_rays");
+  if (n_list > kMaxItems) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": n_list above 2^31 - 1 workgroups of 256 entries");
+  return TOR_OK;
+}
+
+// the time range and the mode
+int range_args(const std::string& w, double time_lo, double time_hi, int32_t mode) {
+  using tor::fail;
+  if (!std::isfinite(time_lo) || !std::isfinite(time_hi) || time_lo > time_hi)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the time range must be finite with time_lo <= time_hi");
+  if (mode < TOR_HIT_AUTO || mode > TOR_HIT_BLOCKS)
+    return fail(TOR_ERR_INVALID_ARGUMENT, w + ": mode must be TOR_HIT_AUTO (0), TOR_HIT_BRUTE (1) or TOR_HIT_BLOCKS (2)");
+  return TOR_OK;
+}
+
+// the last of an entry's checks: a scene must be uploaded (the entry then returns on an empty call and sets the context's device)
+int scene_args(const char* who, TorContext* ctx) {
+  if (!ctx->scene_ready) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": no scene uploaded");
+  return TOR_OK;
+}
 
 // Where the boxes of `bnd` (compute_block_bounds for acc) hold for the reference's rounding (the head of tor_query.hip): a hit the reference
 // accepts on a spatial object of radius r from an origin at distance |oc| lies at most 6 eps (|oc|^2 + r^2) / r outside the sphere, and
@@ -283,6 +367,14 @@ int query_setup(const char* who, TorContext* ctx, double time_lo, double time_hi
   return TOR_OK;
 }
 
+// the flat layout over the whole uploaded list, built on the host: its cold records name the objects
+bool flat_host_layout(TorContext* ctx, tor::HostLayout& lay, std::string& err) {
+  const int64_t n = ctx->n_objects;
+  std::vector<int64_t> ids((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
+  return tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, lay, err, nullptr);
+}
+
 // The group words of a masked launch, after query_setup (`blocks`: which layout p.cold belongs to), into mk: one word per cold slot
 // of that layout -- the object's word (tor_scene_groups; 0xFFFFFFFF without any), 0 for a padding slot -- and, for the culling
 // layout, behind them one OR-word per box record of `bnd`: a block box over the fanout * 8 slots it stands for, a super box over its
@@ -317,13 +409,10 @@ int masked_setup(TorContext* ctx, bool blocks, const uint32_t* d_mask, uint32_t 
           box[b] |= w[acc.spatial_base + s];
       for (size_t b = 0; b < acc.n_boxes; ++b) box[n_bnd_p + 1 + b / tor::kPad] |= box[b];
     } else {
-      // the flat layout's slot order: the layout ensure_layouts built, built again on the host (its cold records name the objects)
-      std::vector<int64_t> ids((size_t)n);
-      for (int64_t i = 0; i < n; ++i) ids[(size_t)i] = i;
+      // the flat layout's slot order: the layout ensure_layouts built, built again on the host
       tor::HostLayout flat;
       std::string err;
-      if (!tor::build_layout((const TorHittableVariant*)ctx->scene_bytes.data(), ids, flat, err, nullptr))
-        return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: " + err);
+      if (!flat_host_layout(ctx, flat, err)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: " + err);
       if (flat.n_sorted != n_slots || flat.cold.size() < 16 * n_slots)
         return tor::fail(TOR_ERR_INVALID_ARGUMENT, "masked query: the flat layout's slots do not match the device's");
       w.assign(n_slots, 0u);
@@ -338,6 +427,112 @@ int masked_setup(TorContext* ctx, bool blocks, const uint32_t* d_mask, uint32_t 
   mk.box_or = mk.grp + n_slots;
   mk.ray_mask = (const unsigned*)d_mask;
   mk.mask = mask;
+  return TOR_OK;
+}
+
+// The cold records by ORIGINAL index, 16 float64 per object, in hitq.obj_cold: what scatter_kernel looks the material up in by
+// TorHit.object and crossings_kernel rebuilds its records from.  Cached per scene; this is its only filler.  `who` prefixes a
+// layout error.
+int ensure_obj_cold(const char* who, TorContext* ctx, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  const int64_t gen = ctx->n_uploads - ctx->n_cache_hits;
+  if (hq.obj_scene == gen) return TOR_OK;
+  hq.obj_scene = -1;
+  if (hq.launched) HIP_TRY(hipEventSynchronize(hq.ev_done));  // the last query may still read the buffer and its host source
+  const int64_t n = ctx->n_objects;
+  tor::HostLayout lay;
+  std::string err;
+  if (!flat_host_layout(ctx, lay, err)) return tor::fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": " + err);
+  hq.obj_cold_host.assign((size_t)(n > 0 ? n : 1) * 16, 0.0);
+  for (size_t s = 0; s < lay.n_sorted && n > 0; ++s) {
+    const double* c = &lay.cold[16 * s];
+    if (c[15] == -1.0) continue;  // padding slot
+    int64_t orig;
+    std::memcpy(&orig, &c[14], 8);
+    if (orig >= 0 && orig < n) std::memcpy(&hq.obj_cold_host[16 * (size_t)orig], c, 16 * sizeof(double));
+  }
+  const size_t bytes = hq.obj_cold_host.size() * sizeof(double);
+  HIP_TRY(hq.obj_cold.ensure(bytes));
+  HIP_TRY(hipMemcpyAsync(hq.obj_cold.ptr, hq.obj_cold_host.data(), bytes, hipMemcpyHostToDevice, stream));
+  hq.obj_scene = gen;
+  return TOR_OK;
+}
+
+// f(BLOCKS, MASKED) with the two flags as std::bool_constant: a launch picks its kernel's instantiation in one place
+template <typename F>
+void for_variant(bool blocks, bool masked, F&& f) {
+  if (blocks && masked) f(std::true_type{}, std::true_type{});
+  else if (blocks) f(std::true_type{}, std::false_type{});
+  else if (masked) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+
+// the kernel argument of a launch: P and, for a masked instantiation, mk
+template <bool MASKED, typename PARAMS>
+KArgs<PARAMS, MASKED> kargs(const PARAMS& P, const MParams& mk) {
+  if constexpr (MASKED) return {P, mk};
+  else return {P};
+}
+
+// After a query's launch on `stream`: the launch's error, the event the stream rule and the caches wait for.
+int query_done(TorContext* ctx, hipStream_t stream) {
+  tor::HitQueryState& hq = ctx->hitq;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(hq.ev_done, stream));
+  hq.launched = true;
+  hq.stream = (void*)stream;
+  return TOR_OK;
+}
+
+// query_done and tor_last_note's "<what>[ (masked)]: blocks | brute force[ (<why>)]" (blocks, why: query_setup's)
+int query_finish(TorContext* ctx, hipStream_t stream, const char* what, bool masked, bool blocks, const std::string& why) {
+  const int rc = query_done(ctx, stream);
+  if (rc != TOR_OK) return rc;
+  const std::string w = std::string(what) + (masked ? " (masked): " : ": ");
+  tor::set_last_note(blocks ? w + "blocks" : w + "brute force" + (why.empty() ? std::string() : " (" + why + ")"));
+  return TOR_OK;
+}
+
+// A blocking entry waits for the context's last render launch and last query, on whatever stream they run, where the asynchronous
+// entry would refuse a different stream (the staging buffer may be reallocated too).
+int host_wait(TorContext* ctx) {
+  if (ctx->launches > 0) HIP_TRY(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+  if (ctx->hitq.launched) HIP_TRY(hipEventSynchronize(ctx->hitq.ev_done));
+  return TOR_OK;
+}
+
+// One host array of a blocking entry, staged in hitq.io: `bytes` may be 0 (an absent optional array: dev stays null); `in` copies it
+// to the device before the launch (an output is staged in where unlisted rays must keep the caller's values), `out` back after it.
+struct HostPart {
+  const void* host;
+  size_t bytes;
+  bool in, out;
+  char* dev;
+  template <typename T>
+  T* as() const { return (T*)dev; }
+};
+
+// host_wait, then the parts laid out in hitq.io in order, each padded to 64 bytes, and the `in` parts copied (blocking)
+int stage_in(TorContext* ctx, HostPart* parts, int n_parts) {
+  const int rc = host_wait(ctx);
+  if (rc != TOR_OK) return rc;
+  size_t total = 0;
+  for (int k = 0; k < n_parts; ++k) total += (parts[k].bytes + 63) / 64 * 64;
+  HIP_TRY(ctx->hitq.io.ensure(total));
+  char* at = (char*)ctx->hitq.io.ptr;
+  for (int k = 0; k < n_parts; ++k) {
+    HostPart& h = parts[k];
+    h.dev = h.bytes ? at : nullptr;
+    if (h.bytes && h.in) HIP_TRY(hipMemcpy(h.dev, h.host, h.bytes, hipMemcpyHostToDevice));
+    at += (h.bytes + 63) / 64 * 64;
+  }
+  return TOR_OK;
+}
+
+// the `out` parts back to the host (blocking: it waits for the launch on the default stream)
+int stage_out(const HostPart* parts, int n_parts) {
+  for (int k = 0; k < n_parts; ++k)
+    if (parts[k].bytes && parts[k].out) HIP_TRY(hipMemcpy((void*)parts[k].host, parts[k].dev, parts[k].bytes, hipMemcpyDeviceToHost));
   return TOR_OK;
 }
 

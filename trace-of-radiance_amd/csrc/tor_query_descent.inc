@@ -1,11 +1,12 @@
-// tor_query_descent.inc -- the closest hit of ray `r` over the scene of `p` (QParams) into `b` (QBest, starting at {r.t_max, INT_MAX,
-// -1}): the wave-uniform slots, then (BLOCKS) the walk of the rays the boxes do not hold for and the block / super-box descent of those
-// they do.  Included in the body of hit_kernel (tor_query.hip) and radiance_kernel (tor_radiance.hip), with p, r, b, `live` and
-// the template parameter BLOCKS in scope.  Every lane of the wave runs it, converged (the uniform loops use scalar loads); lanes with
-// live = false take part with r.t_max = 0, which accepts nothing.  Textual, as the integrator's kernel/*.inc sections are: a function
-// call in its place changes the hit kernels' register allocation.  `vis` (Sees, tor_query.hpp) says whether the lane's ray sees a
-// slot, or anything behind a box: asked before the exact test's arithmetic and before a box's slab test, so a ray does not enter a
-// box that holds nothing it sees.  Without masks it is the namespace's Sees<false>, which answers yes and compiles to nothing.
+// tor_query_descent.inc -- the closest hit of ray `r` over the scene of `p` (QParams) into `b` (QBest, starting at {r.t_max,
+// INT_MAX, -1}): the wave-uniform slots, then (BLOCKS) the walk of the rays the boxes do not hold for and the block / super-box
+// descent of those they do.  Included in the body of hit_kernel (tor_query.hip), radiance_kernel (tor_radiance.hip) and
+// bounce_kernel (tor_bounce.hip), with p, r, b, `live`, `vis` and the template parameter BLOCKS in scope.  Every lane of the
+// wave runs it, converged (the uniform loops use scalar loads); lanes with live = false take part with r.t_max = 0, which accepts
+// nothing.  Textual, as the integrator's kernel/*.inc sections are: a function call in its place changes the hit kernels'
+// register allocation.  `vis` (Sees, tor_query.hpp) says whether the lane's ray sees a slot, or anything behind a box: asked
+// before the exact test's arithmetic and before a box's slab test, so a ray does not enter a box that holds nothing it sees.
+// Every includer declares it as a local; a Sees<false> answers yes and compiles to nothing.
   // wave-uniform: every lane tests the same record
   for (int s = 0; s < p.n_uniform; ++s)
     if (vis.slot_u(s)) exact_test((qcdptr)(uintptr_t)(p.cold + 16 * (size_t)s), s, r, b);

@@ -52,6 +52,7 @@ struct RParams {
 template <bool BLOCKS>
 __global__ __launch_bounds__(kRadThreads) __attribute__((amdgpu_waves_per_eu(4))) void radiance_kernel(const RParams P) {
   const QParams& p = P.q;
+  const Sees<false> vis{nullptr, nullptr, 0u};  // the descent's `vis`: no masks here
   const int lane = threadIdx.x & 63;
   const unsigned long long below = (1ull << lane) - 1ull;
   long long idx = -1;  // this lane's ray, -1: none
