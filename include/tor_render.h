@@ -662,6 +662,52 @@ TOR_API int tor_crossings_host(TorContext* ctx, int64_t n_rays, const TorRay* ra
                                int64_t n_list, int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi,
                                int32_t mode, TorCrossing* cross, int32_t* count, TorHit* records);
 
+/* ---- nearest-surface point queries: the K closest objects to a point ---------------------------------------------------------------
+ * The one question of the query family that starts from a point, not a ray: which objects lie nearest to p at `time`, and how far
+ * away are their surfaces -- the emitters within a radius of a shading point (light culling before the shadow rays; visibility
+ * groups mark the emitters), a distance field for sphere tracing, proximity and contact shading, a contact test.
+ * For point (p, time) and object j of the uploaded list:
+ *     c  = the sphere's centre, or MovingSphere.center(time)   (moving_spheres.nim:39-44)
+ *     oc = p - c
+ *     d  = sqrt(oc.x*oc.x + oc.y*oc.y + oc.z*oc.z) - abs(radius)   (vec3s.nim:23-27 length; unfused float64, correctly rounded sqrt)
+ *   distance    d is the signed distance to the surface, negative inside; a negative radius is a surface at abs(radius) (the
+ *               hollow-glass idiom)
+ *   neighbour   object j is a neighbour of the point iff d is finite and d < d_max (strict, as every range compare of this library);
+ *               NaN and +-inf distances are no neighbours; d_max = NaN accepts nothing
+ *   order       (d, object) ascending, d compared as a double; equal d: the lower index in the full list first
+ *   result      d_near[i * k + m], m < d_count[i] = min(total, k): the first neighbours in that order as TorNear { distance, object,
+ *               inside } with inside = d < 0; entries d_count[i] .. k - 1 hold {0, -1, 0}.  A host that must know whether MORE than
+ *               k neighbours exist asks for k + 1.
+ * Each neighbour is a function of the point and one object alone, so the first k of that set do not depend on the visiting order.
+ * 1 <= k <= TOR_NEAREST_MAX.  d_max_dist (nullable, DEVICE): one float64 per point, indexed by the point; NULL = +inf.
+ * Visibility groups: with d_mask (nullable, DEVICE: one word per point, indexed by the point) or mask (the mask of every point when
+ * d_mask is NULL) object j takes part for point i iff groups[j] & mask_i != 0 (tor_scene_groups); `object` is the index in the FULL
+ * list; a point with mask 0 has no neighbours.  d_mask == NULL with mask == 0xFFFFFFFF is the unmasked query: it neither builds nor
+ * reads any group state.
+ * Everything else follows tor_crossings_device with points in place of rays: d_list / n_list (NULL = every point, n_list must be
+ * n_points; entries outside [0, n_points) are skipped; entries must be unique; points that are not listed keep what d_near and
+ * d_count hold; n_list == 0 and n_points == 0 are no-ops), mode and [time_lo, time_hi] (a speed hint only: points the boxes do not
+ * hold for -- a time outside the range or NaN, a position beyond the reach within which the boxes' margin covers the roundings --
+ * walk every spatial slot, so every result is exact whatever the hint), the one-stream rule, and the refusals in the same order
+ * (their messages name the point count n_rays).  With the blocks a box is entered only while its distance from the point lies at
+ * or below the k-th neighbour found so far and below d_max; a box that holds the point is always entered (distances are signed).
+ * TOR_HIT_AUTO runs the brute force where it measured faster: k > 4 without d_max_dist on a scene whose culling layout has one level.
+ * tor_last_note(): "nearest: blocks" | "nearest: brute force (...)" ("nearest (masked): ..." with masks).  Asynchronous on hip_stream;
+ * a query leaves every render state alone.  TOR_ERR_INVALID_ARGUMENT (nothing written) for n_points < 0, k outside 1 ..
+ * TOR_NEAREST_MAX, a context without a scene, a non-finite or inverted time range, a mode outside 0..2, n_list < 0, a NULL list with
+ * n_list != n_points, NULL d_points, d_near or d_count with work to do.
+ * tor_nearest_host: the same on host arrays (max_dist, masks: nullable, HOST), blocking (every array copied in, the query, the
+ * outputs copied out); it waits for the context's last render launch and last query as tor_hit_host does. */
+typedef struct TorPoint { TorVec3 p; double time; } TorPoint;  /* 32 B */
+enum { TOR_NEAREST_MAX = 16 };
+typedef struct TorNear { double distance; int32_t object; int32_t inside; } TorNear;  /* 16 B */
+TOR_API int tor_nearest_device(TorContext* ctx, int64_t n_points, const TorPoint* d_points, const double* d_max_dist, const int32_t* d_list,
+                               int64_t n_list, int32_t k, const uint32_t* d_mask, uint32_t mask, double time_lo, double time_hi,
+                               int32_t mode, TorNear* d_near, int32_t* d_count, void* hip_stream);
+TOR_API int tor_nearest_host(TorContext* ctx, int64_t n_points, const TorPoint* points, const double* max_dist, const int32_t* list,
+                             int64_t n_list, int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi,
+                             int32_t mode, TorNear* near, int32_t* count);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

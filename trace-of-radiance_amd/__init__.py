@@ -163,11 +163,13 @@ EXPORTED_SYMBOLS = [
     "tor_scene_groups", "tor_hit_masked_device", "tor_hit_masked_host", "tor_occluded_masked_device", "tor_occluded_masked_host",
     "tor_bounce_masked_device",
     "tor_crossings_device", "tor_crossings_host",
+    "tor_nearest_device", "tor_nearest_host",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
 CROSSINGS_MAX = 16   # TOR_CROSSINGS_MAX: the most crossings per ray Context.crossings keeps
+NEAREST_MAX = 16     # TOR_NEAREST_MAX: the most neighbours per point Context.nearest keeps
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2   # Material kinds (TOR_LAMBERTIAN ..): groups_by_material gives 1 << kind
 
 _lib = None
@@ -328,6 +330,8 @@ def lib():
         _bind_masked(L)
     if hasattr(L, "tor_crossings_device"):  # (... and one older than the ordered multi-hit queries)
         _bind_crossings(L)
+    if hasattr(L, "tor_nearest_device"):  # (... and one older than the nearest-surface point queries)
+        _bind_nearest(L)
     _lib = L
     return L
 
@@ -377,6 +381,12 @@ def _bind_crossings(L) -> None:
     v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
     L.tor_crossings_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v, v]
     L.tor_crossings_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
+
+
+def _bind_nearest(L) -> None:
+    v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
+    L.tor_nearest_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
+    L.tor_nearest_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -1453,6 +1463,106 @@ class Context:
         note = last_note() if n and n_list else "crossings: nothing to do"
         return CrossingsResult(raw, raw.view(np.int32), count, hits, note)
 
+    def nearest(self, points, k=1, max_distance=None, index=None, time_range=None, mode="auto", mask=None, out=None) -> "NearestResult":
+        """Nearest-surface point query (tor_nearest_device / tor_nearest_host): per listed point the k objects whose surfaces lie
+        nearest at the point's time, in order -- light culling around a shading point (visibility groups mark the emitters), a
+        distance field for sphere tracing, proximity and contact tests.
+
+        For point (p, time) and object j: d = length(p - centre_j(time)) - abs(radius_j) in float64, the reference's operations
+        (vec3s.nim:23-27, moving_spheres.nim:39-44): the signed distance to the surface, negative inside.  Object j is a neighbour
+        iff d is finite and d < max_distance (strict); neighbours are ordered by (d, object).  count (n,) is min(total, k); entries
+        count .. k - 1 hold distance = 0, object = -1, inside = 0.  1 <= k <= NEAREST_MAX.
+
+        points: (n, 4) float64 {x, y, z, time} -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or
+        anything numpy takes (copied, blocking).  max_distance: None (+inf), a number, or one float64 per point of the points' kind.
+        index, time_range and mode as for crossings() (time_range None: the finite min / max of the points' times).  mask: as for
+        hit() -- only the objects a point sees are neighbours, `object` stays the index in the full list; None is the unmasked query
+        and reads no group state.  out: a NearestResult of an earlier call with the same n and k, written again (points that are
+        not listed keep what it holds); otherwise a new one (every entry unused, count 0).
+        Returns a NearestResult: distance (n, k), object, inside, count (n,), raw and mode."""
+        m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
+        k = int(k)
+        if not 1 <= k <= NEAREST_MAX:
+            raise ValueError(f"Context.nearest: k must be in 1 .. {NEAREST_MAX}")
+        if out is not None and not isinstance(out, NearestResult):
+            raise ValueError("Context.nearest: out must be a NearestResult")
+        if type(points).__module__.startswith("torch"):
+            import torch
+            if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 4 or not points.is_cuda:
+                raise ValueError("Context.nearest: points must be an (n, 4) float64 CUDA tensor")
+            dev = points.device
+            if getattr(self, "_device", None) is not None and dev.index != self._device:
+                raise ValueError(f"Context.nearest: the points are on {dev}, the context on cuda:{self._device}")
+            points = points.contiguous()
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            n = int(points.shape[0])
+            if max_distance is not None:
+                if isinstance(max_distance, (int, float, np.floating, np.integer)):
+                    max_distance = torch.full((n,), float(max_distance), dtype=torch.float64, device=dev)
+                elif not isinstance(max_distance, torch.Tensor) or max_distance.dtype != torch.float64 or tuple(max_distance.shape) != (n,) \
+                        or max_distance.device != dev:
+                    raise ValueError("Context.nearest: with tensor points, max_distance must be a number or an (n,) float64 tensor on the points' device")
+                max_distance = max_distance.contiguous()
+            index, n_list, p_list = self._step_index(index, n, dev)
+            tr = self._point_times(points, time_range)
+            if out is None:
+                raw = torch.zeros((n, k, 2), dtype=torch.float64, device=dev)
+                raw.view(torch.int32)[:, :, 2] = -1
+                count = torch.zeros((n,), dtype=torch.int32, device=dev)
+            else:
+                raw, count = out.raw, out.count
+                if not isinstance(raw, torch.Tensor) or raw.device != dev or tuple(raw.shape) != (n, k, 2) or not raw.is_contiguous() \
+                        or tuple(count.shape) != (n,) or not count.is_contiguous():
+                    raise ValueError("Context.nearest: out must come from a call on the points' device with the same n and k")
+            mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("nearest", mask, n, dev)
+            _check(lib().tor_nearest_device(self._h, n, C.c_void_p(points.data_ptr()),
+                                            C.c_void_p(max_distance.data_ptr() if max_distance is not None else 0), p_list, n_list, k,
+                                            p_mask, word, tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(count.data_ptr()),
+                                            C.c_void_p(stream)))
+            note = last_note() if n and n_list else "nearest: nothing to do"
+            return NearestResult(raw, raw.view(torch.int32), count, note, keep=(points, max_distance, index, mk))
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 4:
+            raise ValueError("Context.nearest: points must have shape (n, 4)")
+        n = int(points.shape[0])
+        if max_distance is not None:
+            if np.ndim(max_distance) == 0:
+                max_distance = np.full((n,), float(max_distance), dtype=np.float64)
+            max_distance = np.ascontiguousarray(max_distance, dtype=np.float64)
+            if max_distance.shape != (n,):
+                raise ValueError("Context.nearest: max_distance must be a number or have shape (n,)")
+        index, n_list, p_list = self._step_index(index, n)
+        tr = self._point_times(points, time_range)
+        if out is None:
+            raw = np.zeros((n, k, 2), dtype=np.float64)
+            raw.view(np.int32)[:, :, 2] = -1
+            count = np.zeros((n,), dtype=np.int32)
+        else:
+            raw, count = out.raw, out.count
+            if not isinstance(raw, np.ndarray) or raw.shape != (n, k, 2) or not raw.flags.c_contiguous or count.shape != (n,) \
+                    or not count.flags.c_contiguous:
+                raise ValueError("Context.nearest: out must come from a numpy call with the same n and k")
+        _mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("nearest", mask, n)
+        _check(lib().tor_nearest_host(self._h, n, C.c_void_p(points.ctypes.data if n else 0),
+                                      C.c_void_p(max_distance.ctypes.data if max_distance is not None and n else 0), p_list, n_list, k,
+                                      p_mask, word, tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0),
+                                      C.c_void_p(count.ctypes.data if n else 0)))
+        note = last_note() if n and n_list else "nearest: nothing to do"
+        return NearestResult(raw, raw.view(np.int32), count, note)
+
+    @staticmethod
+    def _point_times(points, time_range):
+        """_time_range_of for (n, 4) points: the time is column 3."""
+        if time_range is not None:
+            return float(time_range[0]), float(time_range[1])
+        if type(points).__module__.startswith("torch"):
+            import torch
+            times = points[:, 3]
+            times = times[torch.isfinite(times)]
+            return (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
+        times = points[:, 3][np.isfinite(points[:, 3])]
+        return (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
+
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
@@ -1618,6 +1728,19 @@ class CrossingsResult:
         self.raw, self.count, self.hits, self._keep = raw, count, hits, keep   # (keep: the operands stay alive while the query may run)
         self.t, self.object, self.which = raw[:, :, 0], words[:, :, 2], words[:, :, 3]
         self.mode = _mode_of(note, "crossings: ")
+
+
+class NearestResult:
+    """Nearest neighbours of Context.nearest, k per point (TorNear, include/tor_render.h): distance (n, k) float64 (signed, negative
+    inside), object (n, k) int32 (-1 = unused entry) and inside (n, k) int32 (1 = the point lies inside the object) are views of
+    `raw` ((n, k, 2) float64, the entries as the library wrote them); count (n,) int32 is how many entries of a point are
+    neighbours.  Torch tensors or numpy arrays, as the points were.  `mode` is what ran: "blocks" or "brute force (...)"
+    (tor_last_note)."""
+
+    def __init__(self, raw, words, count, note: str, keep=None):
+        self.raw, self.count, self._keep = raw, count, keep   # (keep: the operands stay alive while the query may run)
+        self.distance, self.object, self.inside = raw[:, :, 0], words[:, :, 2], words[:, :, 3]
+        self.mode = _mode_of(note, "nearest: ")
 
 
 class Progressive:

@@ -115,6 +115,13 @@ struct HitQueryState {
   DeviceBuffer grp[2];              // the words in slot order, padding slots 0: [0] the flat layout's; [1] the culling layout's, then one
   std::vector<uint32_t> grp_host[2];  // OR-word per box record of `bnd` (block boxes, slack, super boxes); their host copies (upload source) ...
   int64_t grp_scene[2] = {-1, -1}, grp_gen[2] = {-1, -1};  // ... and the scene generation and groups_gen they were built for
+  // nearest-surface point queries (tor_nearest.hip)
+  DeviceBuffer absr[2];             // abs(radius) per cold slot, padding slots NaN: [0] the flat layout's, [1] the culling layout's ...
+  std::vector<double> absr_host[2];   // ... their host copies (upload source) ...
+  int64_t absr_scene[2] = {-1, -1};   // ... and the scene generation they were built for
+  double pt_reach2 = -1.0;          // squared distance from org within which a POINT may use the boxes (< 0: none may), cached per
+  int64_t pt_scene = -1;            // (scene, time range) like the bounds
+  uint64_t pt_lo = 0, pt_hi = 0;
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

@@ -109,37 +109,6 @@ struct XParams {
   const double* obj_cold;  // records only: the cold records by ORIGINAL index, 16 float64 per object
 };
 
-// The first K crossings seen so far, ascending by (t, key), in entries CAP - K .. CAP - 1; the entries in front hold -inf and are
-// never displaced, unused entries hold +inf (no crossing has an infinite t).  Every index below is a compile-time constant.
-template <int CAP>
-struct XList {
-  double t[CAP];
-  unsigned key[CAP];  // object * 2 + which: ascending = the lower object first, then which 0 before 1
-
-  __device__ __forceinline__ void init(int k) {
-#pragma unroll
-    for (int j = 0; j < CAP; ++j) {
-      t[j] = j < CAP - k ? -__builtin_inf() : __builtin_inf();
-      key[j] = 0xffffffffu;
-    }
-  }
-  // t_max while fewer than K crossings are held, else the K-th's t (NaN for t_max = NaN: no compare with it holds)
-  __device__ __forceinline__ double bound(double t_max) const { return t[CAP - 1] < __builtin_inf() ? t[CAP - 1] : t_max; }
-  // one pass of insertion: the new element sinks in where it belongs and carries the displaced ones along; the largest falls off
-  __device__ __forceinline__ void insert(double nt, unsigned nk) {
-#pragma unroll
-    for (int j = 0; j < CAP; ++j) {
-      const bool lt = (nt < t[j]) || (nt == t[j] && nk < key[j]);
-      const double ot = t[j];
-      const unsigned ok = key[j];
-      t[j] = lt ? nt : ot;
-      key[j] = lt ? nk : ok;
-      nt = lt ? ot : nt;
-      nk = lt ? ok : nk;
-    }
-  }
-};
-
 // spheres.nim:29-48 / moving_spheres.nim:47-66 for the object in cold record c: both roots, whether each lies in (t_min, t_max), and
 // the object's key.  exact_test's operations in exact_test's order, without the closest-so-far and without the early choice.
 struct XRoots {

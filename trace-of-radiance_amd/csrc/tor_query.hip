@@ -92,6 +92,8 @@ HitQueryState::~HitQueryState() {
   sel.release();
   grp[0].release();
   grp[1].release();
+  absr[0].release();
+  absr[1].release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 

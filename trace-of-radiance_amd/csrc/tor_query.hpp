@@ -1,7 +1,8 @@
-// tor_query.hpp -- what the query families (tor_query.hip, tor_radiance.hip, tor_bounce.hip, tor_occluded.hip, tor_crossings.hip)
-// share.  Device: the closest-hit query's exact test and slab test (the head of tor_query.hip says why they are exact; the descent
-// itself is tor_query_descent.inc), the visibility test `Sees`, the kernel argument struct with its optional mask part, a kernel's
-// prologue (list entry -> ray, the ray's load) and the TorHit record's stores.  Host: the one copy of the glue around a launch --
+// tor_query.hpp -- what the query families (tor_query.hip, tor_radiance.hip, tor_bounce.hip, tor_occluded.hip, tor_crossings.hip,
+// tor_nearest.hip) share.  Device: the closest-hit query's exact test and slab test (the head of tor_query.hip says why they are
+// exact; the descent itself is tor_query_descent.inc), the visibility test `Sees`, the kernel argument struct with its optional mask
+// part, a kernel's prologue (list entry -> ray, the ray's load), the TorHit record's stores and the ordered queries' register-resident
+// sorted list `XList`.  Host: the one copy of the glue around a launch --
 // argument checks, stream rule, layouts and cached block bounds, group words, by-object records, the
 // launch's tail and note, the blocking entries' wait and staging.
 #pragma once
@@ -190,6 +191,39 @@ __device__ __forceinline__ bool slab(P bx, const QRay& r, double ix, double iy, 
   const double t_out = __builtin_fmin(__builtin_fmin(__builtin_fmax(tx0, tx1), __builtin_fmax(ty0, ty1)), __builtin_fmax(tz0, tz1));
   return t_in <= t_out;
 }
+
+// The K smallest (t, key) pairs seen so far, ascending, in entries CAP - K .. CAP - 1: the sorted list of the ordered queries
+// (tor_crossings.hip: t a root, key = object * 2 + which; tor_nearest.hip: t a distance, key = object).  The entries in front
+// hold -inf and are never displaced, unused entries hold +inf (no element has an infinite t).  Every index below is a
+// compile-time constant: the list lives in registers.
+template <int CAP>
+struct XList {
+  double t[CAP];
+  unsigned key[CAP];  // ascending at equal t: the lower object first (crossings: then which 0 before 1)
+
+  __device__ __forceinline__ void init(int k) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      t[j] = j < CAP - k ? -__builtin_inf() : __builtin_inf();
+      key[j] = 0xffffffffu;
+    }
+  }
+  // t_max while fewer than K elements are held, else the K-th's t (NaN for t_max = NaN: no compare with it holds)
+  __device__ __forceinline__ double bound(double t_max) const { return t[CAP - 1] < __builtin_inf() ? t[CAP - 1] : t_max; }
+  // one pass of insertion: the new element sinks in where it belongs and carries the displaced ones along; the largest falls off
+  __device__ __forceinline__ void insert(double nt, unsigned nk) {
+#pragma unroll
+    for (int j = 0; j < CAP; ++j) {
+      const bool lt = (nt < t[j]) || (nt == t[j] && nk < key[j]);
+      const double ot = t[j];
+      const unsigned ok = key[j];
+      t[j] = lt ? nt : ot;
+      key[j] = lt ? nk : ok;
+      nt = lt ? ot : nt;
+      nk = lt ? ok : nk;
+    }
+  }
+};
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
