@@ -708,6 +708,38 @@ TOR_API int tor_nearest_host(TorContext* ctx, int64_t n_points, const TorPoint* 
                              int64_t n_list, int32_t k, const uint32_t* masks, uint32_t mask, double time_lo, double time_hi,
                              int32_t mode, TorNear* near, int32_t* count);
 
+/* ---- exact sample deposits: the film of a host-written integrator ------------------------------------------------------------------
+ * The open pipeline (tor_camera_rays_device, tor_radiance_device, the path steps) ends in per-ray colours; the exact film
+ * (tor_render_accumulate_device's sums and moments, tor_resolve_device, tor_accum_noise_device, tor_adaptive_select_device,
+ * tor_resolve_counts_device) is otherwise filled by the library's own integrator only.  tor_deposit_device is the deposit of that
+ * integrator on its own: it ADDS the caller's samples to the caller's buffers in the progressive block's exact arithmetic, so a
+ * host-written integrator gets sums that are reproducible, additive across passes, contexts and GPUs, and served by every entry
+ * named above.  Camera rays of samples [a, b), tor_radiance_device and this entry with max_value = 1 give
+ * tor_render_accumulate_device's d_sums and d_moments for [a, b), bit for bit.
+ *   entries     i = 0 .. n - 1; with d_index (nullable, DEVICE int32) i = d_index[j], j < n_index (n_index is not read
+ *               otherwise, but must not be negative).  A listed i outside [0, n) is skipped; a repeated i deposits again.
+ *   pixel       p = d_pixel[i] (DEVICE int32), in d_sums' layout: the numbering of tor_render_accumulate_list_device's lists; for
+ *               an unsharded frame tor_camera_rays_device's row * ncols + col.  A p outside [0, npix) deposits nothing and is not
+ *               counted anywhere -- how a sharded caller drops the pixels of other shards.
+ *   rejection   c = d_color[3 i .. 3 i + 2] (DEVICE float64).  The sample is rejected AS A WHOLE if any channel is NaN, +inf,
+ *               -inf or < 0 (-0.0 is accepted): it deposits nothing and adds 1 to *d_rejected.
+ *   deposit     otherwise per channel q = quantize36(min(c, max_value)) -- rounded to the nearest multiple of 2^-36, ties to
+ *               even, as (x + 98304.0) - 98304.0 --; d_sums[3 p + ch] += q; d_moments[3 p + ch] += quantize36(q * q) (q * q one
+ *               rounding, nothing fused: the moments of tor_render_accumulate_device); d_counts[p] += 1.
+ *   buffers     d_sums (npix * 3 float64), d_moments (nullable, same size), d_counts (nullable, npix int32), d_rejected (nullable,
+ *               ONE int64): DEVICE, added to, never cleared -- the caller zeroes them once.
+ * 0 < max_value <= 128, not NaN -- derived, not chosen: quantize36 is exact for |x| < 2^15, so q * q <= 2^14 needs q <= 2^7.
+ * Exactness, and with it independence of the order of the entries, of the split into calls and of the GPU, holds while every
+ * pixel has received at most 2^17 / max(max_value, max_value^2) ACCEPTED samples, the samples the library's own passes put into
+ * the same buffers included (max_value = 1: the progressive block's 2^17).  The library cannot check this: a caller that deposits
+ * more gets sums that depend on the order, not an error.
+ * Asynchronous on hip_stream.  It reads no scene and no other state of the context (as tor_camera_rays_device), so the one-stream
+ * rule does not apply to it.  TOR_ERR_INVALID_ARGUMENT, nothing written, tested in this order: n < 0 or n_index < 0; NULL d_color,
+ * d_pixel or d_sums with work to do; npix < 1; max_value outside (0, 128] or NaN.  n == 0, and a list with n_index == 0, are no-ops. */
+TOR_API int tor_deposit_device(TorContext* ctx, int64_t n, const double* d_color, const int32_t* d_pixel, const int32_t* d_index,
+                               int64_t n_index, double max_value, int64_t npix, double* d_sums, double* d_moments, int32_t* d_counts,
+                               int64_t* d_rejected, void* hip_stream);
+
 /* ---- multi-process hosts: one process per GPU, the framebuffer gather inside the library (RCCL) ----------
  * rank 0 calls tor_comm_unique_id and hands the 128 bytes to the other ranks by its own means (bench.py:
  * torch.distributed broadcast); every rank then calls tor_comm_init_rank on its context (ncclCommInitRank).

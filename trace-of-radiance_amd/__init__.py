@@ -164,12 +164,14 @@ EXPORTED_SYMBOLS = [
     "tor_bounce_masked_device",
     "tor_crossings_device", "tor_crossings_host",
     "tor_nearest_device", "tor_nearest_host",
+    "tor_deposit_device",
 ]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
 CROSSINGS_MAX = 16   # TOR_CROSSINGS_MAX: the most crossings per ray Context.crossings keeps
 NEAREST_MAX = 16     # TOR_NEAREST_MAX: the most neighbours per point Context.nearest keeps
+DEPOSIT_MAX_VALUE = 128.0   # tor_deposit_device: the largest clamp (q * q must stay within quantize36's exact range)
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = 0, 1, 2   # Material kinds (TOR_LAMBERTIAN ..): groups_by_material gives 1 << kind
 
 _lib = None
@@ -332,6 +334,8 @@ def lib():
         _bind_crossings(L)
     if hasattr(L, "tor_nearest_device"):  # (... and one older than the nearest-surface point queries)
         _bind_nearest(L)
+    if hasattr(L, "tor_deposit_device"):  # (... and one older than the exact sample deposits)
+        _bind_deposit(L)
     _lib = L
     return L
 
@@ -387,6 +391,11 @@ def _bind_nearest(L) -> None:
     v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
     L.tor_nearest_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
     L.tor_nearest_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v]
+
+
+def _bind_deposit(L) -> None:
+    v, i64 = C.c_void_p, C.c_int64
+    L.tor_deposit_device.argtypes = [v, i64, v, v, v, i64, C.c_double, i64, v, v, v, v, v]
 
 
 def _bind_progressive(L, dp) -> None:
@@ -1550,6 +1559,52 @@ class Context:
         note = last_note() if n and n_list else "nearest: nothing to do"
         return NearestResult(raw, raw.view(np.int32), count, note)
 
+    def deposit(self, colors, pixels, sums, moments=None, counts=None, index=None, max_value=1.0, rejected=None) -> None:
+        """Exact sample deposit (tor_deposit_device): adds the samples (colors[i], pixels[i]) to the film buffers in the progressive
+        renders' arithmetic, so the sums do not depend on the order of the entries, the split into calls or the GPU, and
+        resolve_device, accum_noise_device, adaptive_select_device and resolve_counts_device serve them.
+
+        Per entry i (every entry, or the listed ones: index as for bounce(), entries outside [0, n) skipped, a repeated one deposits
+        again): p = pixels[i]; outside [0, npix) nothing happens.  A colour with a NaN, infinite or negative channel is rejected as a
+        whole (-0.0 passes) and counted in rejected.  Otherwise per channel q = quantize36(min(c, max_value)), sums[p] += q,
+        moments[p] += quantize36(q * q), counts[p] += 1.  0 < max_value <= DEPOSIT_MAX_VALUE; exact while every pixel holds at most
+        2^17 / max(max_value, max_value^2) accepted samples (the library cannot check that: Film.check_budget does).
+
+        colors: (n, 3) float64, pixels: (n,) int32 -- torch CUDA tensors.  sums: float64, (..., 3), contiguous: npix = sums.numel() // 3
+        pixels in that layout; moments (None or like sums), counts (None or int32 with npix elements), rejected (None or one int64)
+        on the same device, contiguous, all ADDED to.  Asynchronous on torch's current stream."""
+        import torch
+        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float64 or colors.dim() != 2 or colors.shape[1] != 3 \
+                or not colors.is_cuda:
+            raise ValueError("Context.deposit: colors must be an (n, 3) float64 CUDA tensor")
+        dev = colors.device
+        if getattr(self, "_device", None) is not None and dev.index != self._device:
+            raise ValueError(f"Context.deposit: the colors are on {dev}, the context on cuda:{self._device}")
+        n = int(colors.shape[0])
+        if not isinstance(pixels, torch.Tensor) or pixels.dtype != torch.int32 or tuple(pixels.shape) != (n,) or pixels.device != dev:
+            raise ValueError("Context.deposit: pixels must be an (n,) int32 tensor on the colors' device")
+        if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.dim() < 1 or sums.shape[-1] != 3 \
+                or sums.device != dev or not sums.is_contiguous():
+            raise ValueError("Context.deposit: sums must be a contiguous (..., 3) float64 tensor on the colors' device")
+        npix = int(sums.numel()) // 3
+        if moments is not None and (not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64
+                                    or tuple(moments.shape) != tuple(sums.shape) or moments.device != dev or not moments.is_contiguous()):
+            raise ValueError("Context.deposit: moments must be a contiguous float64 tensor of the sums' shape and device")
+        if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or int(counts.numel()) != npix
+                                   or counts.device != dev or not counts.is_contiguous()):
+            raise ValueError("Context.deposit: counts must be a contiguous int32 tensor with one element per pixel on the sums' device")
+        if rejected is not None and (not isinstance(rejected, torch.Tensor) or rejected.dtype != torch.int64 or int(rejected.numel()) != 1
+                                     or rejected.device != dev):
+            raise ValueError("Context.deposit: rejected must be one int64 on the sums' device")
+        colors, pixels = colors.contiguous(), pixels.contiguous()
+        index, n_list, p_list = self._step_index(index, n, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().tor_deposit_device(self._h, n, C.c_void_p(colors.data_ptr()), C.c_void_p(pixels.data_ptr()), p_list,
+                                        n_list if index is not None else 0, float(max_value), npix, C.c_void_p(sums.data_ptr()),
+                                        C.c_void_p(moments.data_ptr() if moments is not None else 0),
+                                        C.c_void_p(counts.data_ptr() if counts is not None else 0),
+                                        C.c_void_p(rejected.data_ptr() if rejected is not None else 0), C.c_void_p(stream)))
+
     @staticmethod
     def _point_times(points, time_range):
         """_time_range_of for (n, 4) points: the time is column 3."""
@@ -1841,6 +1896,140 @@ class Progressive:
 
 
 MAX_ACCUM_SAMPLES = 1 << 17  # exactness bound of the progressive sums (tor_render.h)
+
+
+class Film:
+    """The exact film for host-written integrators: owns the sums (and, where asked for, the second moments, the per-pixel counts)
+    and the rejected counter of a whole nrows x ncols frame, filled by Context.deposit -- progressive, resumable, noise-driven and
+    additive across GPUs like Progressive, whatever produced the colours.
+
+        film = Film(ctx, 1080, 1920, moments=True, max_value=4.0)
+        film.add_pass(cam, 16, tracer=lambda r, g: ctx.trace(r, g, emission=E)[0]); preview = film.image()
+
+    With the default tracer (Context.radiance at max_depth) and max_value = 1, add_pass(cam, k) adds what Progressive.add(k) adds,
+    bit for bit.  max_value clamps every channel (0 < max_value <= DEPOSIT_MAX_VALUE); the sums are exact while every pixel holds
+    at most budget() accepted samples.  All device work runs on torch's current stream of the buffers' device."""
+
+    def __init__(self, ctx: Context, nrows: int, ncols: int, moments: bool = False, counts: bool = False, max_value: float = 1.0,
+                 device=None, max_depth: int = 50):
+        import torch
+        self.ctx, self.nrows, self.ncols, self.max_depth = ctx, int(nrows), int(ncols), int(max_depth)
+        self.max_value = float(max_value)
+        if not 0.0 < self.max_value <= DEPOSIT_MAX_VALUE:
+            raise TorError(ERR_INVALID_ARGUMENT, f"Film: max_value must lie in (0, {DEPOSIT_MAX_VALUE:g}]")
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        self.sums = torch.zeros((self.nrows, self.ncols, 3), dtype=torch.float64, device=dev)
+        self.moments = torch.zeros_like(self.sums) if moments else None
+        self.counts = torch.zeros((self.nrows, self.ncols), dtype=torch.int32, device=dev) if counts else None
+        self._rejected = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.samples = 0       # samples per pixel of the uniform passes (add_pass)
+        self.uniform = True    # only add_pass so far: every pixel holds `samples` samples
+
+    def _stream(self) -> int:
+        import torch
+        return torch.cuda.current_stream(self.sums.device).cuda_stream
+
+    def budget(self) -> int:
+        """The most accepted samples a pixel may hold with exact sums: 2^17 / max(max_value, max_value^2)."""
+        return int(MAX_ACCUM_SAMPLES / max(self.max_value, self.max_value * self.max_value))
+
+    def deposit(self, pixels, colors, index=None) -> "Film":
+        """Deposit arbitrary samples: colors (n, 3) float64 into the flat pixels (n,) row * ncols + col (splatting, light tracing).
+        The pixels then hold unequal numbers of samples: image() needs counts=True (or the caller keeps `samples` right itself)."""
+        import torch
+        pixels = torch.as_tensor(pixels).to(device=self.sums.device, dtype=torch.int32).reshape(-1)
+        self.ctx.deposit(colors, pixels, self.sums, self.moments, self.counts, index, self.max_value, self._rejected)
+        self.uniform = False
+        return self
+
+    def add_pass(self, cam: Camera, k: int, tracer=None, chunk_pixels=None) -> "Film":
+        """Samples [samples, samples + k) of every pixel: over ranges of at most chunk_pixels pixels the library's camera rays
+        (Context.camera_rays, SEED_SAMPLE), colors = tracer(rays, rng) -- default Context.radiance at max_depth; a tracer may return
+        a tuple whose first item is the colours -- and their deposit into pixel chunk[entry // k]."""
+        import torch
+        k = int(k)
+        if k < 1:
+            raise TorError(ERR_INVALID_ARGUMENT, "Film.add_pass: k must be >= 1")
+        npix = self.nrows * self.ncols
+        chunk_pixels = max(1, (1 << 22) // k) if chunk_pixels is None else int(chunk_pixels)
+        if chunk_pixels < 1:
+            raise TorError(ERR_INVALID_ARGUMENT, "Film.add_pass: chunk_pixels must be >= 1")
+        if tracer is None:
+            def tracer(rays, rng):
+                return self.ctx.radiance(rays, rng, self.max_depth)
+        dev = self.sums.device
+        for a in range(0, npix, chunk_pixels):
+            chunk = torch.arange(a, min(a + chunk_pixels, npix), dtype=torch.int32, device=dev)
+            rays, rng = self.ctx.camera_rays(cam, self.nrows, self.ncols, first_sample=self.samples, n_samples=k, pixels=chunk)
+            colors = tracer(rays, rng)
+            if isinstance(colors, (tuple, list)):
+                colors = colors[0]
+            self.ctx.deposit(colors, chunk.repeat_interleave(k), self.sums, self.moments, self.counts, None, self.max_value,
+                             self._rejected)
+        self.samples += k
+        return self
+
+    def image(self, gamma: float = 2.2):
+        """The gamma-corrected canvas so far, a new (nrows, ncols, 3) float64 device tensor: pow(sums / samples, 1 / gamma) after
+        uniform passes (tor_resolve_device); with counts after deposit(), each pixel at its own count (tor_resolve_counts_device),
+        a pixel without samples black."""
+        import torch
+        out = torch.empty_like(self.sums)
+        if self.uniform or self.counts is None:
+            self.ctx.resolve_device(self.sums.data_ptr(), self.sums.numel(), self.samples, gamma, out.data_ptr(), self._stream())
+        else:
+            counts = self.counts.clamp(min=1)   # a copy: count 0 resolves as count 1 (sums 0: black)
+            self.ctx.resolve_counts_device(self.sums.data_ptr(), counts.data_ptr(), self.nrows * self.ncols, gamma, out.data_ptr(),
+                                           self._stream())   # (same stream as the allocator's: `counts` may be dropped)
+        return out
+
+    def noise(self):
+        """(mean, max) over the pixels of the largest per-channel standard error of the mean, as Progressive.noise.  Blocking."""
+        if self.moments is None:
+            raise TorError(ERR_INVALID_ARGUMENT, "Film.noise: created without moments=True")
+        if not self.uniform:
+            raise TorError(ERR_INVALID_ARGUMENT, "Film.noise: the pixels hold unequal numbers of samples (deposit() was used)")
+        return self.ctx.accum_noise_device(self.sums.data_ptr(), self.moments.data_ptr(), self.nrows * self.ncols, self.samples, 0,
+                                           self._stream())
+
+    def rejected(self) -> int:
+        """How many samples were rejected so far (a NaN, infinite or negative channel).  Blocking."""
+        return int(self._rejected.item())
+
+    def check_budget(self) -> int:
+        """Raises when a pixel may hold more accepted samples than budget(), i.e. the sums may have stopped being exact:
+        counts.max() after deposit() with counts, else `samples`.  Returns the number it checked.  Blocking."""
+        n = int(self.counts.max().item()) if (self.counts is not None and not self.uniform) else self.samples
+        if n > self.budget():
+            raise TorError(ERR_INVALID_ARGUMENT, f"Film.check_budget: {n} samples in one pixel, above the exactness bound "
+                                                 f"{self.budget()} of max_value = {self.max_value:g}")
+        return n
+
+    def state(self) -> dict:
+        """Checkpoint: sizes, max_value, the sample count and every buffer as host numpy arrays."""
+        return {"nrows": self.nrows, "ncols": self.ncols, "max_value": self.max_value, "max_depth": self.max_depth,
+                "samples": self.samples, "uniform": self.uniform, "rejected": self.rejected(), "sums": self.sums.cpu().numpy(),
+                "moments": self.moments.cpu().numpy() if self.moments is not None else None,
+                "counts": self.counts.cpu().numpy() if self.counts is not None else None}
+
+    @classmethod
+    def from_state(cls, ctx: Context, state: dict, device=None) -> "Film":
+        """Resume a checkpoint (state()) on this context -- any process, any GPU."""
+        import torch
+        film = cls(ctx, state["nrows"], state["ncols"], moments=state.get("moments") is not None,
+                   counts=state.get("counts") is not None, max_value=state["max_value"], device=device,
+                   max_depth=state.get("max_depth", 50))
+        sums = np.ascontiguousarray(state["sums"], dtype=np.float64)
+        if sums.shape != tuple(film.sums.shape):
+            raise TorError(ERR_INVALID_ARGUMENT, f"Film.from_state: sums of shape {sums.shape}, expected {tuple(film.sums.shape)}")
+        film.sums.copy_(torch.from_numpy(sums))
+        if film.moments is not None:
+            film.moments.copy_(torch.from_numpy(np.ascontiguousarray(state["moments"], dtype=np.float64)))
+        if film.counts is not None:
+            film.counts.copy_(torch.from_numpy(np.ascontiguousarray(state["counts"], dtype=np.int32)))
+        film._rejected.fill_(int(state.get("rejected", 0)))
+        film.samples, film.uniform = int(state["samples"]), bool(state.get("uniform", True))
+        return film
 
 
 class PixelProgressive(Progressive):
