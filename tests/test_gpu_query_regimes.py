@@ -206,3 +206,63 @@ def test_dense2_device_side_consistency_over_65536_rays(tor):
     w = _cut(X.crossings(recs, rays[sub], 16, tr[sub]), 16)
     got = {"t": _np(cr16.t)[sub], "object": _np(cr16.object)[sub], "which": _np(cr16.which)[sub], "count": _np(cr16.count)[sub]}
     assert not X.mismatches(got, w)
+
+
+def _strided(a):
+    """`a` as every other row of a device tensor of twice its rows (the rows in between hold other values): not contiguous."""
+    a = np.ascontiguousarray(a)
+    big = np.full((2 * len(a),) + a.shape[1:], 3, dtype=a.dtype)
+    big[::2] = a
+    big = _dev(big)
+    return big, big[::2]
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+
+def test_non_contiguous_tensors_answer_as_their_contiguous_copies(tor):
+    """Every operand a strided view -- rays, t_range, the per-ray mask, max_distance and the states every other row of a tensor of
+    514 rows, the points the first four columns of (257, 7) rays: each query works on contiguous copies that its result keeps
+    alive, and answers what it answers on .contiguous() copies, bit for bit; a step leaves the caller's strided rays and states
+    alone and its result carries the updated copies.  Nine objects (one block of 8 and one more), 257 rays (a workgroup and one)."""
+    recs = Q.scene("groups", SCENE_SEED)[:9]
+    n = 257
+    rays, tr = Q.rays(recs, n, RAY_SEED)
+    rng = np.random.default_rng(78)
+    (_, s_rays), (_, s_tr), (_, s_mask) = _strided(rays), _strided(tr), _strided(Q.ray_masks(n, RAY_SEED))
+    _, s_dmax = _strided(rng.choice([np.inf, 0.5, 4.0], n))
+    pts = s_rays.contiguous()[:, :4]
+    for t in (s_rays, s_tr, s_mask, s_dmax, pts):
+        assert not t.is_contiguous() and t.shape[0] == n
+    ctx = _ctx(tor, recs)
+    ctx.set_groups(Q.group_words(len(recs)))
+    for m in ("brute", "blocks"):
+        got = ctx.hit(s_rays, s_tr, None, m, mask=s_mask)
+        want = ctx.hit(s_rays.contiguous(), s_tr.contiguous(), None, m, mask=s_mask.contiguous())
+        assert got.mode == want.mode and torch.equal(_bits(got.raw), _bits(want.raw)), ("hit", m)
+        assert 0 < int((want.object >= 0).sum()) < n
+        got = ctx.occluded(s_rays, s_tr, None, TIME_RANGE, m, mask=s_mask)
+        want = ctx.occluded(s_rays.contiguous(), s_tr.contiguous(), None, TIME_RANGE, m, mask=s_mask.contiguous())
+        assert got.mode == want.mode and torch.equal(got.raw, want.raw) and 0 < int(want.raw.sum()) < n, ("occluded", m)
+        got = ctx.crossings(s_rays, 3, s_tr, None, TIME_RANGE, m, s_mask, records=True)
+        want = ctx.crossings(s_rays.contiguous(), 3, s_tr.contiguous(), None, TIME_RANGE, m, s_mask.contiguous(), records=True)
+        assert got.mode == want.mode and torch.equal(got.count, want.count) and int(want.count.max()) > 1, ("crossings", m)
+        assert torch.equal(_bits(got.raw), _bits(want.raw)) and torch.equal(_bits(got.hits), _bits(want.hits)), ("crossings", m)
+        got = ctx.nearest(pts, 2, s_dmax, None, TIME_RANGE, m, s_mask)
+        want = ctx.nearest(pts.contiguous(), 2, s_dmax.contiguous(), None, TIME_RANGE, m, s_mask.contiguous())
+        assert got.mode == want.mode and torch.equal(got.count, want.count) and 0 < int(want.count.sum()) < 2 * n, ("nearest", m)
+        assert torch.equal(_bits(got.raw), _bits(want.raw)), ("nearest", m)
+        # one step: the strided rays and states are copied, the copies updated and returned
+        (big_rays, b_rays), (big_st, b_st) = _strided(rays), _strided(rng.integers(0, 2**63, (n, 4), dtype=np.uint64))
+        before_rays, before_st = big_rays.clone(), big_st.clone()
+        want = ctx.bounce(b_rays.contiguous(), b_st.contiguous(), None, TIME_RANGE, m, mask=s_mask.contiguous())
+        got = ctx.bounce(b_rays, b_st, None, TIME_RANGE, m, mask=s_mask)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(big_rays), _bits(before_rays)) and torch.equal(big_st, before_st), ("bounce: the caller's tensors", m)
+        assert got.mode == want.mode and torch.equal(_bits(got.raw), _bits(want.raw)) and torch.equal(got.status, want.status), ("bounce", m)
+        assert torch.equal(_bits(got.attenuation), _bits(want.attenuation)), ("bounce", m)
+        assert torch.equal(_bits(got.rays), _bits(want.rays)) and torch.equal(got.rng, want.rng), ("bounce", m)
+        assert got.rays.is_contiguous() and got.rng.is_contiguous() and int((want.status == tor.BOUNCE_SCATTERED).sum()) > 0
+        assert not torch.equal(got.rng, b_st)                 # (the step did draw)

@@ -51,7 +51,7 @@ class ParentHit:
         self.L.tor_context_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
         self.L.tor_context_destroy.argtypes = [C.c_void_p]
         self.L.tor_scene_upload.argtypes = [C.c_void_p, tor.HittableList]
-        tor._bind_hit(self.L)
+        tor._bind(self.L, ("tor_hit_device", "tor_hit_host"))
         self.h = C.c_void_p()
         self._ok(self.L.tor_context_create(-1, C.byref(self.h)))
         self._ok(self.L.tor_scene_upload(self.h, scene.list()))

@@ -230,187 +230,131 @@ def lib():
     if ab:  # never silent: every consumer of this process measures / validates ANOTHER binary
         print(f"trace-of-radiance_amd: TOR_AB_LIB set -- loading {ab} instead of the in-tree library", file=sys.stderr, flush=True)
     L = C.CDLL(ab or LIB_PATH)
-    dp = C.POINTER(C.c_double)
-    L.tor_last_error.restype = C.c_char_p
-    L.tor_version.restype = C.c_char_p
-    L.tor_last_note.restype = C.c_char_p
-    L.tor_render.argtypes = [C.POINTER(CanvasStruct), C.POINTER(Camera), HittableList, C.c_int64]
-    L.tor_render_ptr.argtypes = [C.POINTER(CanvasStruct), C.POINTER(Camera), C.POINTER(HittableList), C.c_int64]
-    L.tor_render_opt.argtypes = [C.POINTER(CanvasStruct), C.POINTER(Camera), HittableList, C.c_int64,
-                                 C.POINTER(Options)]
-    L.tor_context_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
-    L.tor_context_destroy.argtypes = [C.c_void_p]
-    L.tor_scene_upload.argtypes = [C.c_void_p, HittableList]
-    L.tor_shard_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    L.tor_shard_rows.restype = C.c_int32
-    L.tor_render_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32,
-                                    C.c_float, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p]
-    L.tor_quantize_rgb8_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.tor_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
-    L.tor_kernel_ms_mean.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    L.tor_context_set_stats.argtypes = [C.c_void_p, C.c_int32]
-    L.tor_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
-    L.tor_last_wave_log.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]
-    L.tor_last_pixel_cost.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]
-    L.tor_last_pixel_cost.restype = C.c_int64
-    L.tor_last_handoff_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.tor_camera_init.argtypes = [C.POINTER(Camera), C.POINTER(Vec3), C.POINTER(Vec3), C.POINTER(Vec3)] + \
-                                 [C.c_double] * 6
-    L.tor_random_scene.argtypes = [C.c_uint64, C.POINTER(HittableVariant), C.c_int64]
-    L.tor_random_scene.restype = C.c_int64
-    L.tor_canvas_to_rgb8.argtypes = [C.POINTER(CanvasStruct), C.POINTER(C.c_uint8)]
-    L.tor_animation_create.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
-                                       C.POINTER(C.c_void_p)]
-    L.tor_animation_destroy.argtypes = [C.c_void_p]
-    L.tor_animation_destroy.restype = None
-    L.tor_animation_object_count.argtypes = [C.c_void_p]
-    L.tor_animation_object_count.restype = C.c_int64
-    L.tor_animation_next.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Camera), C.POINTER(HittableVariant), C.c_int64,
-                                     C.POINTER(C.c_int64), C.POINTER(C.c_float)]
-    L.tor_h264_stream_header.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_int32]
-    L.tor_h264_frame_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.tor_h264_frame_bytes.restype = C.c_int64
-    L.tor_encode_frame_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-    L.tor_render_frame_h264.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int64,
-                                        C.POINTER(Options), C.POINTER(C.c_uint8), C.c_int64]
-    L.tor_mp4_mux_file.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]
-    L.tor_debug_accel_layout.argtypes = [HittableList, C.c_double, C.c_double, C.POINTER(C.c_int64), C.c_int64,
-                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32)]
-    L.tor_selftest_filter32_host.argtypes = [C.c_int64] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32)] + \
-        [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)] * 2
-    L.tor_selftest_screen_host.argtypes = [C.c_int64] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32)] + \
-        [C.POINTER(C.c_double)] * 2 + [C.POINTER(C.c_int32)] * 2
-    L.tor_selftest_screen2_host.argtypes = [C.c_int64] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32)] + \
-        [C.POINTER(C.c_double)] * 2 + [C.c_int32] + [C.POINTER(C.c_int32)] * 2
-    L.tor_selftest_slab32_host.argtypes = [C.c_int64] + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_int32)] * 2
-    L.tor_debug_filter32_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8)]
-    L.tor_debug_screen2_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8), C.POINTER(C.c_int32), C.POINTER(C.c_int8), C.c_int64]
-    L.tor_debug_plane32_scene.argtypes = [HittableList, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    L.tor_debug_layout_segments.argtypes = [HittableList, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]
-    L.tor_selftest_math_device.argtypes = [C.c_int32, dp, dp, dp, dp, C.c_int64, C.c_int32]
-    L.tor_selftest_math_host.argtypes = [C.c_int32, dp, dp, dp, dp, C.c_int64]
-    L.tor_selftest_rng_host.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
-                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int64]
-    L.tor_last_render_timing.argtypes = [dp]
-    L.tor_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
-    L.tor_comm_init_rank.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int32, C.c_int32]
-    L.tor_comm_destroy.argtypes = [C.c_void_p]
-    L.tor_render_gather_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int64,
-                                           C.POINTER(Options), C.c_int32, C.c_void_p, C.c_void_p]
-    L.tor_context_scene_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.tor_knob_count.restype = C.c_int32
-    L.tor_knob_info.argtypes = [C.c_int32] + [C.POINTER(C.c_char_p)] * 5
-    L.tor_last_gather_info.argtypes = [C.POINTER(C.c_int32)]
-    L.tor_last_device_kernel_ms.argtypes = [C.POINTER(C.c_float), C.c_int32]
-    L.tor_last_device_kernel_ms.restype = C.c_int32
-    L.tor_comm_abort.argtypes = [C.c_void_p]
-    L.tor_comm_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    L.tor_context_handoff_stalled.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    if not ab or hasattr(L, "tor_render_accumulate_device"):  # (an A/B build older than progressive rendering lacks these three)
-        _bind_progressive(L, dp)
-    if not ab or hasattr(L, "tor_render_accumulate_list_device"):  # (... and one older than adaptive sampling these three)
-        _bind_adaptive(L)
-    if not ab or hasattr(L, "tor_debug_last_variant"):  # (... and one older than this debug entry)
-        L.tor_debug_last_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    if hasattr(L, "tor_hit_device"):  # (... and one older than the closest-hit queries)
-        _bind_hit(L)
-    if hasattr(L, "tor_radiance_device"):  # (... and one older than the radiance queries)
-        _bind_radiance(L)
-    if hasattr(L, "tor_bounce_device"):  # (... and one older than the path steps)
-        _bind_bounce(L)
-    if hasattr(L, "tor_render_resume_device"):  # (... and one older than resumable pixel streams)
-        L.tor_render_resume_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
-                                               C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.tor_debug_last_split_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    if hasattr(L, "tor_render_resume_list_device"):  # (... and one older than adaptive sampling on the pixel streams)
-        L.tor_render_resume_list_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                                    C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "tor_occluded_device"):  # (... and one older than the any-hit queries)
-        _bind_occluded(L)
-    if hasattr(L, "tor_scene_groups"):  # (... and one older than the visibility groups)
-        _bind_masked(L)
-    if hasattr(L, "tor_crossings_device"):  # (... and one older than the ordered multi-hit queries)
-        _bind_crossings(L)
-    if hasattr(L, "tor_nearest_device"):  # (... and one older than the nearest-surface point queries)
-        _bind_nearest(L)
-    if hasattr(L, "tor_deposit_device"):  # (... and one older than the exact sample deposits)
-        _bind_deposit(L)
+    _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
     _lib = L
     return L
 
 
-def _bind_hit(L) -> None:
-    L.tor_hit_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p,
-                                 C.c_void_p]
-    L.tor_hit_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+def _signatures() -> dict:
+    """The ctypes signature of every entry this module calls: symbol -> argtypes, or (argtypes, restype) where the restype is not
+    int; argtypes None: none are set."""
+    v, i32, i64, u32, u64, d, f, P = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double, C.c_float, C.POINTER
+    dp, cam, opt, obj = P(d), P(Camera), P(Options), P(HittableVariant)
+    frame = [v, cam, i32, i32, i32, f, i64, opt]              # ctx, camera, rows, cols, spp, gamma, depth, options
+    passes = [v, cam, i32, i32, i32, i32, i64, opt]           # ... first sample and samples where spp and gamma are
+    listed = [v, cam, i32, i32, v, i32, i32, i32, i64, opt]   # ... and the pixel list and its length before them
+    return {
+        "tor_last_error": (None, C.c_char_p),
+        "tor_version": (None, C.c_char_p),
+        "tor_last_note": (None, C.c_char_p),
+        "tor_render": [P(CanvasStruct), cam, HittableList, i64],
+        "tor_render_ptr": [P(CanvasStruct), cam, P(HittableList), i64],
+        "tor_render_opt": [P(CanvasStruct), cam, HittableList, i64, opt],
+        "tor_context_create": [i32, P(v)],
+        "tor_context_destroy": [v],
+        "tor_scene_upload": [v, HittableList],
+        "tor_shard_rows": [i32, i32, i32, i32, P(i32)],
+        "tor_render_device": frame + [v, v],
+        "tor_quantize_rgb8_device": [v, v, i64, v, v],
+        "tor_last_kernel_ms": [v, P(f), P(i64)],
+        "tor_kernel_ms_mean": [v, i32, P(f), P(i32)],
+        "tor_context_set_stats": [v, i32],
+        "tor_last_stats": [v, P(Stats)],
+        "tor_last_wave_log": [v, P(u64), i64],
+        "tor_last_pixel_cost": ([v, P(u32), i64], i64),
+        "tor_last_handoff_counters": [v, P(u64)],
+        "tor_camera_init": [cam, P(Vec3), P(Vec3), P(Vec3)] + [d] * 6,
+        "tor_random_scene": ([u64, obj, i64], i64),
+        "tor_canvas_to_rgb8": [P(CanvasStruct), P(C.c_uint8)],
+        "tor_animation_create": [u64, i32, i32, f, f, f, P(v)],
+        "tor_animation_destroy": ([v], None),
+        "tor_animation_object_count": ([v], i64),
+        "tor_animation_next": [v, i32, cam, obj, i64, P(i64), P(f)],
+        "tor_h264_stream_header": [i32, i32, P(C.c_uint8), i32],
+        "tor_h264_frame_bytes": ([i32, i32], i64),
+        "tor_encode_frame_device": [v, v, i32, i32, v, v, v, v, v],
+        "tor_render_frame_h264": frame + [P(C.c_uint8), i64],
+        "tor_mp4_mux_file": [C.c_char_p, C.c_char_p, i32, i32, i32],
+        "tor_debug_accel_layout": [HittableList, d, d, P(i64), i64, dp, dp, i64, P(i32)],
+        "tor_selftest_filter32_host": [i64] + [dp] * 4 + [P(i32)] + [dp] * 3 + [P(i32)] * 2,
+        "tor_selftest_screen_host": [i64] + [dp] * 4 + [P(i32)] + [dp] * 2 + [P(i32)] * 2,
+        "tor_selftest_screen2_host": [i64] + [dp] * 4 + [P(i32)] + [dp] * 2 + [i32] + [P(i32)] * 2,
+        "tor_selftest_slab32_host": [i64] + [dp] * 5 + [P(i32)] * 2,
+        "tor_debug_filter32_scene": [HittableList, i64] + [dp] * 3 + [P(C.c_int8)],
+        "tor_debug_screen2_scene": [HittableList, i64] + [dp] * 3 + [P(C.c_int8), P(i32), P(C.c_int8), i64],
+        "tor_debug_plane32_scene": [HittableList, i64] + [dp] * 3 + [P(C.c_int8), P(i32), P(i64)],
+        "tor_debug_layout_segments": [HittableList, P(i32), i64, P(i64)],
+        "tor_selftest_math_device": [i32, dp, dp, dp, dp, i64, i32],
+        "tor_selftest_math_host": [i32, dp, dp, dp, dp, i64],
+        "tor_selftest_rng_host": [i32, u64, u64, u64, P(u64), P(u64), i64],
+        "tor_last_render_timing": [dp],
+        "tor_comm_unique_id": [P(C.c_uint8)],
+        "tor_comm_init_rank": [v, P(C.c_uint8), i32, i32],
+        "tor_comm_destroy": [v],
+        "tor_render_gather_device": frame + [i32, v, v],
+        "tor_context_scene_counters": [v, P(i64)],
+        "tor_knob_count": (None, i32),
+        "tor_knob_info": [i32] + [P(C.c_char_p)] * 5,
+        "tor_last_gather_info": [P(i32)],
+        "tor_last_device_kernel_ms": [P(f), i32],
+        "tor_comm_abort": [v],
+        "tor_comm_count": [v, P(i32)],
+        "tor_context_handoff_stalled": [v, P(i32), P(i64)],
+        # progressive and adaptive rendering, on the sample streams and on the reference's pixel streams
+        "tor_render_accumulate_device": passes + [v, v, v],
+        "tor_resolve_device": [v, v, i64, i64, f, v, v],
+        "tor_accum_noise_device": [v, v, v, i64, i64, v, dp, v],
+        "tor_render_accumulate_list_device": listed + [v, v, v],
+        "tor_adaptive_select_device": [v, v, v, v, i32, i64, d, d, v, v, P(i32), v],
+        "tor_resolve_counts_device": [v, v, v, i64, f, v, v],
+        "tor_debug_last_variant": [v, P(i32)],
+        "tor_render_resume_device": passes + [v, v, v, v],
+        "tor_debug_last_split_tiles": [v, P(i64)],
+        "tor_render_resume_list_device": listed + [v, v, v, v],
+        # the queries: ctx, n, the arrays ...; a _device entry ends in the stream -- and a _masked_ one in the mask after it
+        "tor_hit_device": [v, i64, v, v, d, d, i32, v, v],
+        "tor_hit_host": [v, i64, v, v, d, d, i32, v],
+        "tor_hit_masked_device": [v, i64, v, v, d, d, i32, v, v, v, u32],
+        "tor_hit_masked_host": [v, i64, v, v, d, d, i32, v, v, u32],
+        "tor_radiance_device": [v, i64, v, v, i32, d, d, i32, v, v],
+        "tor_radiance_host": [v, i64, v, v, i32, d, d, i32, v],
+        "tor_camera_rays_device": [v, cam, i32, i32, v, i64, i32, i32, i32, v, v, v],
+        "tor_bounce_device": [v, i64, v, v, v, i64, d, d, i32, v, v, v, v],
+        "tor_bounce_host": [v, i64, v, v, v, i64, d, d, i32, v, v, v],
+        "tor_bounce_masked_device": [v, i64, v, v, v, i64, d, d, i32, v, v, v, v, v, u32],
+        "tor_scatter_device": [v, i64, v, v, v, v, i64, v, v, v],
+        "tor_scatter_host": [v, i64, v, v, v, v, i64, v, v],
+        "tor_sky_device": [v, i64, v, v, i64, v, v],
+        "tor_bounce_select_device": [v, i64, v, v, i64, v, P(i64), v],
+        "tor_occluded_device": [v, i64, v, v, v, i64, d, d, i32, v, v],
+        "tor_occluded_host": [v, i64, v, v, v, i64, d, d, i32, v],
+        "tor_occluded_masked_device": [v, i64, v, v, v, i64, d, d, i32, v, v, v, u32],
+        "tor_occluded_masked_host": [v, i64, v, v, v, i64, d, d, i32, v, v, u32],
+        "tor_scene_groups": [v, i64, v],
+        "tor_crossings_device": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v, v],
+        "tor_crossings_host": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v],
+        "tor_nearest_device": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v],
+        "tor_nearest_host": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v],
+        "tor_deposit_device": [v, i64, v, v, v, i64, d, i64, v, v, v, v, v],
+    }
 
 
-def _bind_radiance(L) -> None:
-    L.tor_radiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
-                                      C.c_void_p, C.c_void_p]
-    L.tor_radiance_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
-                                    C.c_void_p]
-    L.tor_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
-                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+_SIGNATURES = _signatures()
 
 
-def _bind_bounce(L) -> None:
-    v, i64 = C.c_void_p, C.c_int64
-    L.tor_bounce_device.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v, v, v]
-    L.tor_bounce_host.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v, v]
-    L.tor_scatter_device.argtypes = [v, i64, v, v, v, v, i64, v, v, v]
-    L.tor_scatter_host.argtypes = [v, i64, v, v, v, v, i64, v, v]
-    L.tor_sky_device.argtypes = [v, i64, v, v, i64, v, v]
-    L.tor_bounce_select_device.argtypes = [v, i64, v, v, i64, v, C.POINTER(C.c_int64), v]
-
-
-def _bind_occluded(L) -> None:
-    v, i64 = C.c_void_p, C.c_int64
-    L.tor_occluded_device.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v, v]
-    L.tor_occluded_host.argtypes = [v, i64, v, v, v, i64, C.c_double, C.c_double, C.c_int32, v]
-
-
-def _bind_masked(L) -> None:
-    v, i64, u32 = C.c_void_p, C.c_int64, C.c_uint32
-    L.tor_scene_groups.argtypes = [v, i64, v]
-    L.tor_hit_masked_device.argtypes = list(L.tor_hit_device.argtypes) + [v, u32]
-    L.tor_hit_masked_host.argtypes = list(L.tor_hit_host.argtypes) + [v, u32]
-    L.tor_occluded_masked_device.argtypes = list(L.tor_occluded_device.argtypes) + [v, u32]
-    L.tor_occluded_masked_host.argtypes = list(L.tor_occluded_host.argtypes) + [v, u32]
-    L.tor_bounce_masked_device.argtypes = list(L.tor_bounce_device.argtypes) + [v, u32]
-
-
-def _bind_crossings(L) -> None:
-    v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
-    L.tor_crossings_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v, v]
-    L.tor_crossings_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
-
-
-def _bind_nearest(L) -> None:
-    v, i64, i32, u32, d = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double
-    L.tor_nearest_device.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v]
-    L.tor_nearest_host.argtypes = [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v]
-
-
-def _bind_deposit(L) -> None:
-    v, i64 = C.c_void_p, C.c_int64
-    L.tor_deposit_device.argtypes = [v, i64, v, v, v, i64, C.c_double, i64, v, v, v, v, v]
-
-
-def _bind_progressive(L, dp) -> None:
-    L.tor_render_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
-                                               C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tor_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-    L.tor_accum_noise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, dp, C.c_void_p]
-
-
-def _bind_adaptive(L) -> None:
-    L.tor_render_accumulate_list_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                                    C.c_int32, C.c_int64, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.tor_adaptive_select_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_double,
-                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-    L.tor_resolve_counts_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+def _bind(L, names=None, skip_missing=False) -> None:
+    """Give the named entries of the CDLL `L` (default: every entry of the table) their signatures.  A symbol `L` lacks raises,
+    unless skip_missing (another build of the library, which may be older than the entry)."""
+    for name in _SIGNATURES if names is None else names:
+        if skip_missing and not hasattr(L, name):
+            continue
+        sig = _SIGNATURES[name]
+        argtypes, *restype = sig if isinstance(sig, tuple) else (sig,)
+        fn = getattr(L, name)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        if restype:
+            fn.restype = restype[0]
 
 
 def _check(rc: int) -> None:
@@ -732,6 +676,233 @@ def shard_rows(nrows: int, row_tile: int, shard_index: int, shard_count: int) ->
     return np.array(buf[:n], dtype=np.int32)
 
 
+# --------------------------------------------------------------------------------------
+# The operand layer of the queries: everything a query does differently for CUDA tensors and for numpy arrays
+# --------------------------------------------------------------------------------------
+def _is_tensor(x) -> bool:
+    """The module's one tensor-or-array decision (by the type's module: torch is never imported for a numpy caller)."""
+    return type(x).__module__.startswith("torch")
+
+
+def _shape(tail) -> str:
+    return "(n, " + ", ".join(str(s) for s in tail) + ")" if tail else "(n,)"
+
+
+class _Operands:
+    """The operands of one query call, of the kind of its leading operand (_operands picks the subclass): `lead` is that operand,
+    (n, cols) float64 and contiguous, `n` its rows.  A subclass checks and allocates arrays of its kind, gives their addresses
+    and enters the library.  It knows nothing of the query but its name `who`, which words the refusals and names the entries
+    tor_<who>_* and their note."""
+    __slots__ = ("who", "name", "h", "lead", "n")
+
+    def bad(self, what, must):
+        raise ValueError(f"Context.{self.who}: {what} must be {must}")
+
+    def words(self, buf):
+        """The int32 words of a float64 buffer (object, front_face, which, inside)."""
+        return buf.view(self.xp.int32)
+
+    def times(self, col, time_range):
+        """The time range of a call: the caller's, or the finite min / max of the leading operand's column col ((0, 0): none)."""
+        if time_range is not None:
+            return float(time_range[0]), float(time_range[1])
+        return self._finite_range(self.lead[:, col])
+
+    def mask(self, mask):
+        """A mask that is not None: (what to keep alive, (the address of the per-row words or 0, the scalar word))."""
+        if isinstance(mask, (int, np.integer)):
+            return None, (0, int(mask) & 0xFFFFFFFF)
+        words, address = self._per_row_mask(mask)
+        return words, (address or 16, 0)
+
+    def note(self, n_list) -> str:
+        """tor_last_note of a listed query; one with no row to answer never reaches the code that writes it."""
+        return last_note() if self.n and n_list else f"{self.who}: nothing to do"
+
+    def call(self, *args, masked=None):
+        """tor_<who>_device(ctx, n, *args, stream) or tor_<who>_host(ctx, n, *args); with masked = mask()'s pair the
+        _masked_ twin, which takes the pair last."""
+        name = f"tor_{self.who}{'' if masked is None else '_masked'}{self.suffix}"
+        _check(getattr(lib(), name)(self.h, self.n, *args, *self.tail, *(masked or ())))
+
+
+class _Tensors(_Operands):
+    """CUDA tensors, zero-copy and asynchronous on torch's current stream: a contiguous tensor is the caller's own (what a query
+    updates, it updates in place), another one is copied and the copy is what the result carries."""
+    __slots__ = ("dev", "xp", "tail")
+    suffix = "_device"
+
+    def __init__(self, ctx, who, lead, name, cols, copy=False):
+        import torch
+        if not isinstance(lead, torch.Tensor) or lead.dtype != torch.float64 or lead.dim() != 2 or lead.shape[1] != cols \
+                or not lead.is_cuda:
+            raise ValueError(f"Context.{who}: {name} must be an (n, {cols}) float64 CUDA tensor")
+        dev = getattr(ctx, "_device", None)
+        if dev is not None and lead.device.index != dev:
+            raise ValueError(f"Context.{who}: the {name} are on {lead.device}, the context on cuda:{dev}")
+        self.who, self.name, self.h, self.xp = who, name, ctx._h, torch
+        self.lead, self.n, self.dev = lead.contiguous(), int(lead.shape[0]), lead.device
+        # what a _device entry takes after the arrays: the handle of torch's current stream on the device, read as
+        # torch.cuda.current_stream(device).cuda_stream reads it but without building the Stream object (1 - 2 us of a small call)
+        self.tail = (torch._C._cuda_getCurrentRawStream(lead.device.index),)
+
+    def rows(self, x, what, *tail, dtype="float64", or_number=False):
+        """A secondary operand: None, or an (n, *tail) tensor of dtype on the leading operand's device (or_number: or a number,
+        one value for every row); contiguous."""
+        if x is None:
+            return None
+        torch = self.xp
+        if or_number and isinstance(x, (int, float, np.floating, np.integer)):
+            x = torch.full((self.n,), float(x), dtype=torch.float64, device=self.dev)
+        elif not isinstance(x, torch.Tensor) or x.dtype != getattr(torch, dtype) or tuple(x.shape) != (self.n, *tail) \
+                or x.device != self.dev:
+            self.bad(what, f"{'a number or ' if or_number else ''}an {_shape(tail)} {dtype} tensor on the {self.name}' device")
+        return x.contiguous()
+
+    def states(self, rng):
+        """(n, 4) generator states, int64 holding the u64 bits."""
+        torch = self.xp
+        if not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (self.n, 4) \
+                or rng.device != self.dev:
+            self.bad("rng", f"an (n, 4) int64 tensor on the {self.name}' device")
+        return rng.contiguous()
+
+    def new(self, *shape, dtype="float64", unused=None, zero=True):
+        """An output buffer, zeroed (zero=False: uninitialised), the int32 word `unused` of every entry -1."""
+        torch = self.xp
+        buf = (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, dtype), device=self.dev)
+        if unused is not None:
+            buf.view(torch.int32)[..., unused] = -1
+        return buf
+
+    def fits(self, buf, *shape, dtype="float64") -> bool:
+        """Can a caller's `out` buffer be written again by this call?"""
+        torch = self.xp
+        return isinstance(buf, torch.Tensor) and buf.dtype == getattr(torch, dtype) and tuple(buf.shape) == shape \
+            and buf.device == self.dev and buf.is_contiguous()
+
+    def holds(self, buf) -> bool:
+        """Is buf a tensor of n rows on this device (what a step asks of the `out` it writes again)?"""
+        return isinstance(buf, self.xp.Tensor) and int(buf.shape[0]) == self.n and buf.device == self.dev
+
+    def index(self, index):
+        return _tensor_list(index, self.n, self.dev)
+
+    def as_bool(self, buf):
+        """The low byte of every int32 as a bool view."""
+        return buf.view(self.xp.bool).view(self.n, 4)[:, 0]
+
+    def ptr(self, x) -> int:
+        return 0 if x is None else x.data_ptr()
+
+    def keep(self, *refs):
+        """What a result must keep alive while the query may still run: contiguous copies nobody else holds."""
+        return refs
+
+    def _finite_range(self, t):
+        torch = self.xp
+        t = t[torch.isfinite(t)]
+        return (0.0, 0.0) if t.numel() == 0 else tuple(float(v) for v in torch.aminmax(t))
+
+    def _per_row_mask(self, mask):
+        torch = self.xp
+        if not _is_tensor(mask):
+            mask = torch.from_numpy(_mask_words(np.asarray(mask).reshape(-1)).view(np.int32))
+        if mask.dtype not in (torch.int32, torch.uint32) or tuple(mask.shape) != (self.n,):
+            self.bad("a per-ray mask", "an (n,) uint32 / int32 tensor or array")
+        mask = mask.to(self.dev).contiguous()
+        return mask, mask.data_ptr()
+
+
+class _Arrays(_Operands):
+    """Anything numpy takes, through the blocking _host entries: a read-only query may alias a contiguous float64 input, what a
+    query updates is copied first (copy=True for the leading operand, always for the states), so the caller's arrays are never
+    written.  n == 0 passes NULL for every array."""
+    __slots__ = ()
+    suffix, xp, dev, tail = "_host", np, None, ()
+
+    def __init__(self, ctx, who, lead, name, cols, copy=False):
+        lead = np.array(lead, dtype=np.float64, order="C") if copy else np.ascontiguousarray(lead, dtype=np.float64)
+        if lead.ndim != 2 or lead.shape[1] != cols:
+            raise ValueError(f"Context.{who}: {name} must be an (n, {cols}) float64 array")
+        self.who, self.name, self.h = who, name, ctx._h
+        self.lead, self.n = lead, int(lead.shape[0])
+
+    def rows(self, x, what, *tail, dtype="float64", or_number=False):
+        """A secondary operand: None, or anything numpy makes an (n, *tail) array of dtype from (or_number: or a number, one value
+        for every row); contiguous."""
+        if x is None:
+            return None
+        if or_number and np.ndim(x) == 0:
+            x = np.full((self.n,), float(x), dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.shape != (self.n, *tail):
+            self.bad(what, f"{'a number or ' if or_number else ''}an {_shape(tail)} {dtype} array")
+        return x
+
+    def states(self, rng):
+        """(n, 4) generator states as uint64: a copy."""
+        st = np.asarray(rng)
+        if st.shape != (self.n, 4) or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+            self.bad("rng", "an (n, 4) array of 64-bit integers")
+        return np.ascontiguousarray(st).view(np.uint64).copy()
+
+    def new(self, *shape, dtype="float64", unused=None, zero=True):
+        """An output buffer, zeroed (always: a host entry's caller reads it at once), the int32 word `unused` of every entry -1."""
+        buf = np.zeros(shape, dtype=dtype)
+        if unused is not None:
+            buf.view(np.int32)[..., unused] = -1
+        return buf
+
+    def fits(self, buf, *shape, dtype="float64") -> bool:
+        """Can a caller's `out` buffer be written again by this call?"""
+        return isinstance(buf, np.ndarray) and buf.dtype == dtype and buf.shape == shape and buf.flags.c_contiguous
+
+    def holds(self, buf) -> bool:
+        """Is buf an array of n rows (what a step asks of the `out` it writes again)?"""
+        return isinstance(buf, np.ndarray) and buf.shape[0] == self.n
+
+    def index(self, index):
+        if index is None:
+            return None, self.n, 0
+        index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
+        return index, int(index.size), index.ctypes.data or 16   # (an empty list is a list: never dereferenced)
+
+    def as_bool(self, buf):
+        """The low byte of every int32 as a bool view."""
+        return buf.view(np.bool_).reshape(self.n, 4)[:, 0]
+
+    def ptr(self, x) -> int:
+        return x.ctypes.data if x is not None and self.n else 0
+
+    def keep(self, *refs):
+        """Nothing: a host entry has returned before the result exists."""
+        return None
+
+    def _finite_range(self, t):
+        t = t[np.isfinite(t)]
+        return (0.0, 0.0) if t.size == 0 else (float(t.min()), float(t.max()))
+
+    def _per_row_mask(self, mask):
+        words = _mask_words(mask.cpu().numpy() if _is_tensor(mask) else np.asarray(mask))
+        if words.shape != (self.n,):
+            self.bad("a per-ray mask", "an (n,) uint32 / int32 tensor or array")
+        return words, words.ctypes.data
+
+
+def _operands(ctx, who, lead, name, cols, copy=False) -> _Operands:
+    return (_Tensors if _is_tensor(lead) else _Arrays)(ctx, who, lead, name, cols, copy)
+
+
+def _tensor_list(index, n, device):
+    """The list of a listed query as a device tensor: (contiguous int32 tensor or None, n_list, its address -- 0 for None: every row)."""
+    if index is None:
+        return None, n, 0
+    import torch
+    index = torch.as_tensor(index).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+    return index, int(index.numel()), index.data_ptr() or 16   # (an empty list is a list: never dereferenced)
+
+
 class Context:
     """Resident device context (tor_context_* / tor_scene_upload / tor_render_device)."""
 
@@ -960,24 +1131,15 @@ class Context:
         g = _mask_words(np.asarray(groups).reshape(-1))
         _check(lib().tor_scene_groups(self._h, int(g.size), C.c_void_p(g.ctypes.data or 16)))
 
-    @staticmethod
-    def _mask_arg(who, mask, n, device=None):
-        """The mask operands of a masked entry: (what to keep alive, the address of the per-ray words or 0, the scalar word)."""
-        if isinstance(mask, (int, np.integer)):
-            return None, C.c_void_p(0), int(mask) & 0xFFFFFFFF
-        is_torch = type(mask).__module__.startswith("torch")
-        if device is not None:
-            import torch
-            if not is_torch:
-                mask = torch.from_numpy(_mask_words(np.asarray(mask).reshape(-1)).view(np.int32))
-            if mask.dtype not in (torch.int32, torch.uint32) or tuple(mask.shape) != (n,):
-                raise ValueError(f"Context.{who}: a per-ray mask must be an (n,) uint32 / int32 tensor or array")
-            mask = mask.to(device).contiguous()
-            return mask, C.c_void_p(mask.data_ptr() or 16), 0
-        words = _mask_words(mask.cpu().numpy() if is_torch else np.asarray(mask))
-        if words.shape != (n,):
-            raise ValueError(f"Context.{who}: a per-ray mask must be an (n,) uint32 / int32 tensor or array")
-        return words, C.c_void_p(words.ctypes.data or 16), 0
+    def _cuda(self):
+        """The context's torch device (the current one for a context on the library's default device)."""
+        import torch
+        return torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+
+    def _to_device(self, a, dtype=None):
+        """A numpy operand of a query that only the device answers: its contiguous copy on the context's device."""
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self._cuda())
 
     def hit(self, rays, t_range=None, time_range=None, mode="auto", mask=None) -> "HitResult":
         """Closest hits of a batch of rays against the uploaded scene: world.hit(r, t_min, t_max, rec) of the reference
@@ -990,55 +1152,14 @@ class Context:
         mask: None (every object), or an int / a per-ray (n,) uint32 or int32 tensor or array: ray i sees object j iff
         groups[j] & mask_i != 0 (set_groups) -- world.hit on the sub-list it sees, `object` the index in the full list."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
-                raise ValueError("Context.hit: rays must be an (n, 7) float64 CUDA tensor")
-            dev = getattr(self, "_device", None)
-            if dev is not None and rays.device.index != dev:
-                raise ValueError(f"Context.hit: the rays are on {rays.device}, the context on cuda:{dev}")
-            rays = rays.contiguous()
-            n = int(rays.shape[0])
-            if t_range is not None:
-                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
-                        or t_range.device != rays.device:
-                    raise ValueError("Context.hit: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
-                t_range = t_range.contiguous()
-            if time_range is None:
-                times = rays[:, 6]
-                times = times[torch.isfinite(times)]
-                time_range = (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
-            raw = torch.empty((n, 8), dtype=torch.float64, device=rays.device)
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
-            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0),
-                    float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream))
-            if mask is None:
-                _check(lib().tor_hit_device(*args))
-                return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range))
-            mk, p_mask, word = self._mask_arg("hit", mask, n, rays.device)
-            _check(lib().tor_hit_masked_device(*args, p_mask, word))
-            return HitResult(raw, raw.view(torch.int32), last_note(), keep=(rays, t_range, mk))
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.hit: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        if t_range is not None:
-            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
-            if t_range.shape != (n, 2):
-                raise ValueError("Context.hit: t_range must have shape (n, 2)")
-        if time_range is None:
-            times = rays[:, 6][np.isfinite(rays[:, 6])]
-            time_range = (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
-        raw = np.zeros((n, 8), dtype=np.float64)
-        args = (self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
-                float(time_range[0]), float(time_range[1]), m, C.c_void_p(raw.ctypes.data if n else 0))
-        if mask is None:
-            _check(lib().tor_hit_host(*args))
-        else:
-            _mk, p_mask, word = self._mask_arg("hit", mask, n)
-            _check(lib().tor_hit_masked_host(*args, p_mask, word))
-        return HitResult(raw, raw.view(np.int32), last_note())
-
+        ops = _operands(self, "hit", rays, "rays", 7)
+        rays = ops.lead
+        t_range = ops.rows(t_range, "t_range", 2)
+        tr = ops.times(6, time_range)
+        raw = ops.new(ops.n, 8, zero=False)
+        mk, masked = (None, None) if mask is None else ops.mask(mask)
+        ops.call(ops.ptr(rays), ops.ptr(t_range), tr[0], tr[1], m, ops.ptr(raw), masked=masked)
+        return HitResult(raw, ops.words(raw), last_note(), keep=ops.keep(rays, t_range, mk))
 
     def radiance(self, rays, rng, max_depth=50, time_range=None, mode="auto"):
         """radiance(ray, world, max_depth, rng) of the reference (render.nim:21-47), bit for bit, per ray, on the uploaded scene
@@ -1051,44 +1172,12 @@ class Context:
         time_range: (lo, hi) the block bounds are built for (a speed hint; the library adds 0); None = the rays' finite times.
         mode: "auto" | "brute" | "blocks"."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
-                raise ValueError("Context.radiance: rays must be an (n, 7) float64 CUDA tensor")
-            dev = getattr(self, "_device", None)
-            if dev is not None and rays.device.index != dev:
-                raise ValueError(f"Context.radiance: the rays are on {rays.device}, the context on cuda:{dev}")
-            n = int(rays.shape[0])
-            if not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (n, 4) \
-                    or rng.device != rays.device:
-                raise ValueError("Context.radiance: with tensor rays, rng must be an (n, 4) int64 tensor on the rays' device")
-            rays, rng = rays.contiguous(), rng.contiguous()
-            if time_range is None:
-                times = rays[:, 6]
-                times = times[torch.isfinite(times)]
-                time_range = (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
-            color = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(lib().tor_radiance_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), int(max_depth),
-                                             float(time_range[0]), float(time_range[1]), m, C.c_void_p(color.data_ptr()),
-                                             C.c_void_p(stream)))
-            return color, rng, _mode_of(last_note(), "radiance: ")
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.radiance: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        st = np.asarray(rng)
-        if st.shape != (n, 4) or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
-            raise ValueError("Context.radiance: rng must be an (n, 4) array of 64-bit integers")
-        st = np.ascontiguousarray(st).view(np.uint64).copy()
-        if time_range is None:
-            times = rays[:, 6][np.isfinite(rays[:, 6])]
-            time_range = (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
-        color = np.zeros((n, 3), dtype=np.float64)
-        _check(lib().tor_radiance_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(st.ctypes.data if n else 0),
-                                       int(max_depth), float(time_range[0]), float(time_range[1]), m,
-                                       C.c_void_p(color.ctypes.data if n else 0)))
-        return color, st, _mode_of(last_note(), "radiance: ")
+        ops = _operands(self, "radiance", rays, "rays", 7)
+        rng = ops.states(rng)
+        tr = ops.times(6, time_range)
+        color = ops.new(ops.n, 3, zero=False)
+        ops.call(ops.ptr(ops.lead), ops.ptr(rng), int(max_depth), tr[0], tr[1], m, ops.ptr(color))
+        return color, rng, _mode_of(last_note(), "radiance: ")
 
     def camera_rays(self, cam: Camera, nrows: int, ncols: int, first_sample: int = 0, n_samples: int = 1, seeding=SEED_SAMPLE,
                     pixels=None, rng=None):
@@ -1099,7 +1188,7 @@ class Context:
         e * n_samples + (s - first_sample).  SEED_PIXEL: n_samples = 1 and rng (n_pixels, 4) the states to draw from (rng_seed2,
         or what radiance() left), updated in place when it is a contiguous int64 CUDA tensor."""
         import torch
-        dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
+        dev = self._cuda()
         if pixels is not None:
             pixels = torch.as_tensor(pixels).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
             n_pix = int(pixels.numel())
@@ -1126,53 +1215,6 @@ class Context:
 
     # ---- path steps (tor_bounce_device and friends): the pieces of radiance()'s loop for hosts that write their own integrator ----
 
-    def _step_tensors(self, who, rays, rng):
-        """Torch operands of a step: (rays, rng, device, stream), contiguous (a contiguous tensor is the caller's own: updated in place)."""
-        import torch
-        if rays.dtype != torch.float64 or rays.dim() != 2 or rays.shape[1] != 7 or not rays.is_cuda:
-            raise ValueError(f"Context.{who}: rays must be an (n, 7) float64 CUDA tensor")
-        dev = getattr(self, "_device", None)
-        if dev is not None and rays.device.index != dev:
-            raise ValueError(f"Context.{who}: the rays are on {rays.device}, the context on cuda:{dev}")
-        n = int(rays.shape[0])
-        if rng is not None:
-            if not isinstance(rng, torch.Tensor) or rng.dtype not in (torch.int64, torch.uint64) or tuple(rng.shape) != (n, 4) \
-                    or rng.device != rays.device:
-                raise ValueError(f"Context.{who}: with tensor rays, rng must be an (n, 4) int64 tensor on the rays' device")
-            rng = rng.contiguous()
-        return rays.contiguous(), rng, rays.device, torch.cuda.current_stream(rays.device).cuda_stream
-
-    @staticmethod
-    def _step_index(index, n, device=None):
-        """The list of a step: (contiguous int32 tensor / array or None, n_list, its address -- 0 for None: every ray)."""
-        if index is None:
-            return None, n, C.c_void_p(0)
-        if device is not None:
-            import torch
-            index = torch.as_tensor(index).to(device=device, dtype=torch.int32).reshape(-1).contiguous()
-            return index, int(index.numel()), C.c_void_p(index.data_ptr() or 16)   # (an empty list is a list: never dereferenced)
-        index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
-        return index, int(index.size), C.c_void_p(index.ctypes.data or 16)
-
-    @staticmethod
-    def _time_range_of(rays, time_range):
-        if time_range is not None:
-            return float(time_range[0]), float(time_range[1])
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            times = rays[:, 6]
-            times = times[torch.isfinite(times)]
-            return (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
-        times = rays[:, 6][np.isfinite(rays[:, 6])]
-        return (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
-
-    @staticmethod
-    def _step_states(who, rng, n):
-        st = np.asarray(rng)
-        if st.shape != (n, 4) or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
-            raise ValueError(f"Context.{who}: rng must be an (n, 4) array of 64-bit integers")
-        return np.ascontiguousarray(st).view(np.uint64).copy()
-
     def bounce(self, rays, rng, index=None, time_range=None, mode="auto", out=None, mask=None) -> "BounceResult":
         """One iteration of radiance()'s loop (render.nim:26-38) for the listed rays, bit for bit (tor_bounce_device /
         tor_bounce_host): world.hit(ray, 0.001, +inf, rec), then rec.material.scatter(ray, rec, rng, attenuation, scattered).
@@ -1187,63 +1229,31 @@ class Context:
         mask: as for hit() (per-ray words are indexed by the ray): the closest VISIBLE object scatters; a ray that sees nothing
         misses, draws nothing and keeps its ray and state."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
-        if type(rays).__module__.startswith("torch"):
+        if mask is not None and not _is_tensor(rays):   # (the masked step has no blocking entry: through the device and back)
             import torch
-            rays, rng, dev, stream = self._step_tensors("bounce", rays, rng)
-            n = int(rays.shape[0])
-            index, n_list, p_list = self._step_index(index, n, dev)
-            tr = self._time_range_of(rays, time_range)
-            if out is not None and isinstance(out.raw, torch.Tensor) and int(out.raw.shape[0]) == n and out.raw.device == dev:
-                raw, att, status = out.raw, out.attenuation, out.status
-            else:
-                raw = torch.zeros((n, 8), dtype=torch.float64, device=dev)
-                raw.view(torch.int32)[:, 14] = -1
-                att = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-                status = torch.zeros((n,), dtype=torch.int32, device=dev)
-            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), p_list, n_list, tr[0], tr[1], m,
-                    C.c_void_p(raw.data_ptr()), C.c_void_p(att.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream))
-            mk = None
-            if mask is None:
-                _check(lib().tor_bounce_device(*args))
-            else:
-                mk, p_mask, word = self._mask_arg("bounce", mask, n, dev)
-                _check(lib().tor_bounce_masked_device(*args, p_mask, word))
-            note = last_note() if n and n_list else "bounce: nothing to do"
-            return BounceResult(raw, raw.view(torch.int32), note, att, status, rays, rng, keep=(index, mk))
-        if mask is not None:   # (the masked step has no blocking entry: through the device and back)
-            import torch
-            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
-
-            def to(a):
-                return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            r = to(np.array(rays, dtype=np.float64).reshape(-1, 7))
-            s = to(self._step_states("bounce", rng, int(r.shape[0])).view(np.int64))
+            host = _Arrays(self, "bounce", np.array(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
+            r, s = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
             if out is not None and isinstance(out.raw, np.ndarray):
-                raw = to(out.raw)
-                out = BounceResult(raw, raw.view(torch.int32), "", to(out.attenuation), to(out.status), None, None)
+                raw = self._to_device(out.raw)
+                out = BounceResult(raw, raw.view(torch.int32), "", self._to_device(out.attenuation), self._to_device(out.status), None, None)
             res = self.bounce(r, s, index, time_range, mode, out, mask)
-            torch.cuda.synchronize(dev)
+            torch.cuda.synchronize(r.device)
             raw = res.raw.cpu().numpy()
             return BounceResult(raw, raw.view(np.int32), "bounce: " + res.mode, res.attenuation.cpu().numpy(), res.status.cpu().numpy(),
                                 res.rays.cpu().numpy(), res.rng.cpu().numpy().view(np.uint64))
-        rays = np.array(rays, dtype=np.float64, order="C")
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.bounce: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        st = self._step_states("bounce", rng, n)
-        index, n_list, p_list = self._step_index(index, n)
-        tr = self._time_range_of(rays, time_range)
-        if out is not None and isinstance(out.raw, np.ndarray) and out.raw.shape[0] == n:
+        ops = _operands(self, "bounce", rays, "rays", 7, copy=True)
+        n, rays = ops.n, ops.lead
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        tr = ops.times(6, time_range)
+        if out is not None and ops.holds(out.raw):
             raw, att, status = out.raw, out.attenuation, out.status
         else:
-            raw = np.zeros((n, 8), dtype=np.float64)
-            raw.view(np.int32)[:, 14] = -1
-            att, status = np.zeros((n, 3), dtype=np.float64), np.zeros((n,), dtype=np.int32)
-        _check(lib().tor_bounce_host(self._h, n, C.c_void_p(rays.ctypes.data), C.c_void_p(st.ctypes.data), p_list, n_list,
-                                     tr[0], tr[1], m, C.c_void_p(raw.ctypes.data), C.c_void_p(att.ctypes.data),
-                                     C.c_void_p(status.ctypes.data)))
-        note = last_note() if n and n_list else "bounce: nothing to do"
-        return BounceResult(raw, raw.view(np.int32), note, att, status, rays, st)
+            raw, att, status = ops.new(n, 8, unused=14), ops.new(n, 3), ops.new(n, dtype="int32")
+        mk, masked = (None, None) if mask is None else ops.mask(mask)
+        ops.call(ops.ptr(rays), ops.ptr(rng), p_list, n_list, tr[0], tr[1], m, ops.ptr(raw), ops.ptr(att), ops.ptr(status),
+                 masked=masked)
+        return BounceResult(raw, ops.words(raw), ops.note(n_list), att, status, rays, rng, keep=ops.keep(index, mk))
 
     def scatter(self, rays, hits, rng, index=None, out=None) -> "BounceResult":
         """rec.material.scatter(r_in, rec, rng, attenuation, scattered) (materials.nim:21-96) for the caller's hit records, bit for
@@ -1251,58 +1261,35 @@ class Context:
         raw records -- the material of `object`, and p, normal, front_face as given (a host may have perturbed the normal); an
         object outside the scene counts as a miss.  rays, rng, index, out and the result as for bounce() (the result's hit
         fields are the caller's records); bounce() equals hit() followed by scatter()."""
-        raw = hits.raw if hasattr(hits, "raw") else hits
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            rays, rng, dev, stream = self._step_tensors("scatter", rays, rng)
-            n = int(rays.shape[0])
-            if not isinstance(raw, torch.Tensor) or raw.dtype != torch.float64 or tuple(raw.shape) != (n, 8) or raw.device != dev:
-                raise ValueError("Context.scatter: with tensor rays, hits must be (n, 8) float64 records on the rays' device")
-            raw = raw.contiguous()
-            index, n_list, p_list = self._step_index(index, n, dev)
-            if out is not None and isinstance(out.status, torch.Tensor) and int(out.status.shape[0]) == n and out.status.device == dev:
-                att, status = out.attenuation, out.status
-            else:
-                att = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-                status = torch.zeros((n,), dtype=torch.int32, device=dev)
-            _check(lib().tor_scatter_device(self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(raw.data_ptr()), C.c_void_p(rng.data_ptr()),
-                                            p_list, n_list, C.c_void_p(att.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(stream)))
-            return BounceResult(raw, raw.view(torch.int32), "scatter", att, status, rays, rng, keep=index)
-        rays = np.array(rays, dtype=np.float64, order="C")
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.scatter: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        raw = np.ascontiguousarray(raw, dtype=np.float64)
-        if raw.shape != (n, 8):
-            raise ValueError("Context.scatter: hits must be (n, 8) records")
-        st = self._step_states("scatter", rng, n)
-        index, n_list, p_list = self._step_index(index, n)
-        if out is not None and isinstance(out.status, np.ndarray) and out.status.shape[0] == n:
+        ops = _operands(self, "scatter", rays, "rays", 7, copy=True)
+        n, rays = ops.n, ops.lead
+        raw = ops.rows(hits.raw if hasattr(hits, "raw") else hits, "hits", 8)
+        if raw is None:
+            ops.bad("hits", "(n, 8) records")
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is not None and ops.holds(out.status):
             att, status = out.attenuation, out.status
         else:
-            att, status = np.zeros((n, 3), dtype=np.float64), np.zeros((n,), dtype=np.int32)
-        _check(lib().tor_scatter_host(self._h, n, C.c_void_p(rays.ctypes.data), C.c_void_p(raw.ctypes.data), C.c_void_p(st.ctypes.data),
-                                      p_list, n_list, C.c_void_p(att.ctypes.data), C.c_void_p(status.ctypes.data)))
-        return BounceResult(raw, raw.view(np.int32), "scatter", att, status, rays, st)
+            att, status = ops.new(n, 3), ops.new(n, dtype="int32")
+        ops.call(ops.ptr(rays), ops.ptr(raw), ops.ptr(rng), p_list, n_list, ops.ptr(att), ops.ptr(status))
+        return BounceResult(raw, ops.words(raw), "scatter", att, status, rays, rng, keep=ops.keep(index))
 
     def sky(self, rays, index=None, out=None):
         """The reference's sky (render.nim:41-44) without the attenuation for the listed rays (tor_sky_device): (n, 3) float64,
         (1 - t) * white + t * (0.5, 0.7, 1.0) with t = 0.5 * unit(direction).y + 1.0 (sic); rays that are not listed keep what
         `out` holds (a new array: 0).  CUDA tensors zero-copy on torch's current stream; numpy goes through the device and back."""
-        import torch
-        as_numpy = not type(rays).__module__.startswith("torch")
+        as_numpy = not _is_tensor(rays)
         if as_numpy:
-            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
-            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)).to(dev)
-            out = None if out is None else torch.from_numpy(np.ascontiguousarray(out, dtype=np.float64)).to(dev)
-        rays, _, dev, stream = self._step_tensors("sky", rays, None)
-        n = int(rays.shape[0])
-        index, n_list, p_list = self._step_index(index, n, dev)
+            rays = self._to_device(np.asarray(rays, dtype=np.float64).reshape(-1, 7))
+            out = None if out is None else self._to_device(out, np.float64)
+        ops = _Tensors(self, "sky", rays, "rays", 7)
+        index, n_list, p_list = ops.index(index)
         if out is None:
-            out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        elif out.dtype != torch.float64 or tuple(out.shape) != (n, 3) or out.device != dev or not out.is_contiguous():
-            raise ValueError("Context.sky: out must be a contiguous (n, 3) float64 tensor on the rays' device")
-        _check(lib().tor_sky_device(self._h, n, C.c_void_p(rays.data_ptr()), p_list, n_list, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            out = ops.new(ops.n, 3)
+        elif not ops.fits(out, ops.n, 3):
+            ops.bad("out", "a contiguous (n, 3) float64 tensor on the rays' device")
+        ops.call(ops.ptr(ops.lead), p_list, n_list, ops.ptr(out))
         return out.cpu().numpy() if as_numpy else out
 
     def bounce_select(self, status, index=None):
@@ -1314,11 +1301,11 @@ class Context:
                 or not status.is_contiguous():
             raise ValueError("Context.bounce_select: status must be a contiguous (n,) int32 CUDA tensor")
         n = int(status.shape[0])
-        index, n_in, p_list = self._step_index(index, n, status.device)
+        index, n_in, p_list = _tensor_list(index, n, status.device)
         lst = torch.empty((max(n_in, 1),), dtype=torch.int32, device=status.device)
         n_out = C.c_int64(0)
-        _check(lib().tor_bounce_select_device(self._h, n, C.c_void_p(status.data_ptr()), p_list, n_in, C.c_void_p(lst.data_ptr()),
-                                              C.byref(n_out), C.c_void_p(torch.cuda.current_stream(status.device).cuda_stream)))
+        _check(lib().tor_bounce_select_device(self._h, n, status.data_ptr(), p_list, n_in, lst.data_ptr(), C.byref(n_out),
+                                              torch.cuda.current_stream(status.device).cuda_stream))
         return lst[:int(n_out.value)]
 
     def occluded(self, rays, t_range=None, index=None, time_range=None, mode="auto", out=None, mask=None) -> "OccludedResult":
@@ -1335,55 +1322,18 @@ class Context:
         mask: as for hit() (per-ray words are indexed by the ray): only the objects a ray sees can occlude it."""
         m = HIT_MODES[mode] if isinstance(mode, str) else int(mode)
         raw = out.raw if hasattr(out, "raw") else out
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            rays, _, dev, stream = self._step_tensors("occluded", rays, None)
-            n = int(rays.shape[0])
-            if t_range is not None:
-                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
-                        or t_range.device != dev:
-                    raise ValueError("Context.occluded: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
-                t_range = t_range.contiguous()
-            index, n_list, p_list = self._step_index(index, n, dev)
-            tr = self._time_range_of(rays, time_range)
-            if raw is None:
-                raw = torch.zeros((n,), dtype=torch.int32, device=dev)
-            elif not isinstance(raw, torch.Tensor) or raw.dtype != torch.int32 or tuple(raw.shape) != (n,) or raw.device != dev \
-                    or not raw.is_contiguous():
-                raise ValueError("Context.occluded: with tensor rays, out must be a contiguous (n,) int32 tensor on the rays' device")
-            args = (self._h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list,
-                    tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(stream))
-            mk = None
-            if mask is None:
-                _check(lib().tor_occluded_device(*args))
-            else:
-                mk, p_mask, word = self._mask_arg("occluded", mask, n, dev)
-                _check(lib().tor_occluded_masked_device(*args, p_mask, word))
-            note = last_note() if n and n_list else "occluded: nothing to do"
-            return OccludedResult(raw, raw.view(torch.bool).view(n, 4)[:, 0], note, keep=(rays, t_range, index, mk))
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.occluded: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        if t_range is not None:
-            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
-            if t_range.shape != (n, 2):
-                raise ValueError("Context.occluded: t_range must have shape (n, 2)")
-        index, n_list, p_list = self._step_index(index, n)
-        tr = self._time_range_of(rays, time_range)
+        ops = _operands(self, "occluded", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        t_range = ops.rows(t_range, "t_range", 2)
+        index, n_list, p_list = ops.index(index)
+        tr = ops.times(6, time_range)
         if raw is None:
-            raw = np.zeros((n,), dtype=np.int32)
-        elif not isinstance(raw, np.ndarray) or raw.dtype != np.int32 or raw.shape != (n,) or not raw.flags.c_contiguous:
-            raise ValueError("Context.occluded: out must be a contiguous (n,) int32 array")
-        args = (self._h, n, C.c_void_p(rays.ctypes.data if n else 0), C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0),
-                p_list, n_list, tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0))
-        if mask is None:
-            _check(lib().tor_occluded_host(*args))
-        else:
-            _mk, p_mask, word = self._mask_arg("occluded", mask, n)
-            _check(lib().tor_occluded_masked_host(*args, p_mask, word))
-        note = last_note() if n and n_list else "occluded: nothing to do"
-        return OccludedResult(raw, raw.view(np.bool_).reshape(n, 4)[:, 0], note)
+            raw = ops.new(n, dtype="int32")
+        elif not ops.fits(raw, n, dtype="int32"):
+            ops.bad("out", "a contiguous (n,) int32 tensor or array, as the rays are")
+        mk, masked = (None, None) if mask is None else ops.mask(mask)
+        ops.call(ops.ptr(rays), ops.ptr(t_range), p_list, n_list, tr[0], tr[1], m, ops.ptr(raw), masked=masked)
+        return OccludedResult(raw, ops.as_bool(raw), ops.note(n_list), keep=ops.keep(rays, t_range, index, mk))
 
     def crossings(self, rays, k, t_range=None, index=None, time_range=None, mode="auto", mask=None, records=False,
                   out=None) -> "CrossingsResult":
@@ -1410,67 +1360,22 @@ class Context:
             raise ValueError(f"Context.crossings: k must be in 1 .. {CROSSINGS_MAX}")
         if out is not None and not isinstance(out, CrossingsResult):
             raise ValueError("Context.crossings: out must be a CrossingsResult")
-        if type(rays).__module__.startswith("torch"):
-            import torch
-            rays, _, dev, stream = self._step_tensors("crossings", rays, None)
-            n = int(rays.shape[0])
-            if t_range is not None:
-                if not isinstance(t_range, torch.Tensor) or t_range.dtype != torch.float64 or tuple(t_range.shape) != (n, 2) \
-                        or t_range.device != dev:
-                    raise ValueError("Context.crossings: with tensor rays, t_range must be an (n, 2) float64 tensor on the rays' device")
-                t_range = t_range.contiguous()
-            index, n_list, p_list = self._step_index(index, n, dev)
-            tr = self._time_range_of(rays, time_range)
-            if out is None:
-                raw = torch.zeros((n, k, 2), dtype=torch.float64, device=dev)
-                raw.view(torch.int32)[:, :, 2] = -1
-                count = torch.zeros((n,), dtype=torch.int32, device=dev)
-                hits = None
-                if records:
-                    hits = torch.zeros((n, k, 8), dtype=torch.float64, device=dev)
-                    hits.view(torch.int32)[:, :, 14] = -1
-            else:
-                raw, count, hits = out.raw, out.count, out.hits
-                if not isinstance(raw, torch.Tensor) or raw.device != dev or tuple(raw.shape) != (n, k, 2) or not raw.is_contiguous() \
-                        or tuple(count.shape) != (n,) or not count.is_contiguous() or (hits is not None) != bool(records):
-                    raise ValueError("Context.crossings: out must come from a call on the rays' device with the same n, k and records")
-            mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("crossings", mask, n, dev)
-            _check(lib().tor_crossings_device(self._h, n, C.c_void_p(rays.data_ptr()),
-                                              C.c_void_p(t_range.data_ptr() if t_range is not None else 0), p_list, n_list, k, p_mask, word,
-                                              tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(count.data_ptr()),
-                                              C.c_void_p(hits.data_ptr() if hits is not None else 0), C.c_void_p(stream)))
-            note = last_note() if n and n_list else "crossings: nothing to do"
-            return CrossingsResult(raw, raw.view(torch.int32), count, hits, note, keep=(rays, t_range, index, mk))
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 7:
-            raise ValueError("Context.crossings: rays must have shape (n, 7)")
-        n = int(rays.shape[0])
-        if t_range is not None:
-            t_range = np.ascontiguousarray(t_range, dtype=np.float64)
-            if t_range.shape != (n, 2):
-                raise ValueError("Context.crossings: t_range must have shape (n, 2)")
-        index, n_list, p_list = self._step_index(index, n)
-        tr = self._time_range_of(rays, time_range)
+        ops = _operands(self, "crossings", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        t_range = ops.rows(t_range, "t_range", 2)
+        index, n_list, p_list = ops.index(index)
+        tr = ops.times(6, time_range)
         if out is None:
-            raw = np.zeros((n, k, 2), dtype=np.float64)
-            raw.view(np.int32)[:, :, 2] = -1
-            count = np.zeros((n,), dtype=np.int32)
-            hits = None
-            if records:
-                hits = np.zeros((n, k, 8), dtype=np.float64)
-                hits.view(np.int32)[:, :, 14] = -1
+            raw, count = ops.new(n, k, 2, unused=2), ops.new(n, dtype="int32")
+            hits = ops.new(n, k, 8, unused=14) if records else None
         else:
             raw, count, hits = out.raw, out.count, out.hits
-            if not isinstance(raw, np.ndarray) or raw.shape != (n, k, 2) or not raw.flags.c_contiguous or count.shape != (n,) \
-                    or not count.flags.c_contiguous or (hits is not None) != bool(records):
-                raise ValueError("Context.crossings: out must come from a numpy call with the same n, k and records")
-        _mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("crossings", mask, n)
-        _check(lib().tor_crossings_host(self._h, n, C.c_void_p(rays.ctypes.data if n else 0),
-                                        C.c_void_p(t_range.ctypes.data if t_range is not None and n else 0), p_list, n_list, k, p_mask, word,
-                                        tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0), C.c_void_p(count.ctypes.data if n else 0),
-                                        C.c_void_p(hits.ctypes.data if hits is not None and n else 0)))
-        note = last_note() if n and n_list else "crossings: nothing to do"
-        return CrossingsResult(raw, raw.view(np.int32), count, hits, note)
+            if not ops.fits(raw, n, k, 2) or not ops.fits(count, n, dtype="int32") or (hits is not None) != bool(records):
+                ops.bad("out", "the result of a call with the same n, k and records, on tensors or arrays as the rays are")
+        mk, (p_mask, word) = (None, (0, 0xFFFFFFFF)) if mask is None else ops.mask(mask)
+        ops.call(ops.ptr(rays), ops.ptr(t_range), p_list, n_list, k, p_mask, word, tr[0], tr[1], m, ops.ptr(raw),
+                 ops.ptr(count), ops.ptr(hits))
+        return CrossingsResult(raw, ops.words(raw), count, hits, ops.note(n_list), keep=ops.keep(rays, t_range, index, mk))
 
     def nearest(self, points, k=1, max_distance=None, index=None, time_range=None, mode="auto", mask=None, out=None) -> "NearestResult":
         """Nearest-surface point query (tor_nearest_device / tor_nearest_host): per listed point the k objects whose surfaces lie
@@ -1495,69 +1400,21 @@ class Context:
             raise ValueError(f"Context.nearest: k must be in 1 .. {NEAREST_MAX}")
         if out is not None and not isinstance(out, NearestResult):
             raise ValueError("Context.nearest: out must be a NearestResult")
-        if type(points).__module__.startswith("torch"):
-            import torch
-            if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 4 or not points.is_cuda:
-                raise ValueError("Context.nearest: points must be an (n, 4) float64 CUDA tensor")
-            dev = points.device
-            if getattr(self, "_device", None) is not None and dev.index != self._device:
-                raise ValueError(f"Context.nearest: the points are on {dev}, the context on cuda:{self._device}")
-            points = points.contiguous()
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            n = int(points.shape[0])
-            if max_distance is not None:
-                if isinstance(max_distance, (int, float, np.floating, np.integer)):
-                    max_distance = torch.full((n,), float(max_distance), dtype=torch.float64, device=dev)
-                elif not isinstance(max_distance, torch.Tensor) or max_distance.dtype != torch.float64 or tuple(max_distance.shape) != (n,) \
-                        or max_distance.device != dev:
-                    raise ValueError("Context.nearest: with tensor points, max_distance must be a number or an (n,) float64 tensor on the points' device")
-                max_distance = max_distance.contiguous()
-            index, n_list, p_list = self._step_index(index, n, dev)
-            tr = self._point_times(points, time_range)
-            if out is None:
-                raw = torch.zeros((n, k, 2), dtype=torch.float64, device=dev)
-                raw.view(torch.int32)[:, :, 2] = -1
-                count = torch.zeros((n,), dtype=torch.int32, device=dev)
-            else:
-                raw, count = out.raw, out.count
-                if not isinstance(raw, torch.Tensor) or raw.device != dev or tuple(raw.shape) != (n, k, 2) or not raw.is_contiguous() \
-                        or tuple(count.shape) != (n,) or not count.is_contiguous():
-                    raise ValueError("Context.nearest: out must come from a call on the points' device with the same n and k")
-            mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("nearest", mask, n, dev)
-            _check(lib().tor_nearest_device(self._h, n, C.c_void_p(points.data_ptr()),
-                                            C.c_void_p(max_distance.data_ptr() if max_distance is not None else 0), p_list, n_list, k,
-                                            p_mask, word, tr[0], tr[1], m, C.c_void_p(raw.data_ptr()), C.c_void_p(count.data_ptr()),
-                                            C.c_void_p(stream)))
-            note = last_note() if n and n_list else "nearest: nothing to do"
-            return NearestResult(raw, raw.view(torch.int32), count, note, keep=(points, max_distance, index, mk))
-        points = np.ascontiguousarray(points, dtype=np.float64)
-        if points.ndim != 2 or points.shape[1] != 4:
-            raise ValueError("Context.nearest: points must have shape (n, 4)")
-        n = int(points.shape[0])
-        if max_distance is not None:
-            if np.ndim(max_distance) == 0:
-                max_distance = np.full((n,), float(max_distance), dtype=np.float64)
-            max_distance = np.ascontiguousarray(max_distance, dtype=np.float64)
-            if max_distance.shape != (n,):
-                raise ValueError("Context.nearest: max_distance must be a number or have shape (n,)")
-        index, n_list, p_list = self._step_index(index, n)
-        tr = self._point_times(points, time_range)
+        ops = _operands(self, "nearest", points, "points", 4)
+        n, points = ops.n, ops.lead
+        max_distance = ops.rows(max_distance, "max_distance", or_number=True)
+        index, n_list, p_list = ops.index(index)
+        tr = ops.times(3, time_range)
         if out is None:
-            raw = np.zeros((n, k, 2), dtype=np.float64)
-            raw.view(np.int32)[:, :, 2] = -1
-            count = np.zeros((n,), dtype=np.int32)
+            raw, count = ops.new(n, k, 2, unused=2), ops.new(n, dtype="int32")
         else:
             raw, count = out.raw, out.count
-            if not isinstance(raw, np.ndarray) or raw.shape != (n, k, 2) or not raw.flags.c_contiguous or count.shape != (n,) \
-                    or not count.flags.c_contiguous:
-                raise ValueError("Context.nearest: out must come from a numpy call with the same n and k")
-        _mk, p_mask, word = (None, C.c_void_p(0), 0xFFFFFFFF) if mask is None else self._mask_arg("nearest", mask, n)
-        _check(lib().tor_nearest_host(self._h, n, C.c_void_p(points.ctypes.data if n else 0),
-                                      C.c_void_p(max_distance.ctypes.data if max_distance is not None and n else 0), p_list, n_list, k,
-                                      p_mask, word, tr[0], tr[1], m, C.c_void_p(raw.ctypes.data if n else 0),
-                                      C.c_void_p(count.ctypes.data if n else 0)))
-        note = last_note() if n and n_list else "nearest: nothing to do"
-        return NearestResult(raw, raw.view(np.int32), count, note)
+            if not ops.fits(raw, n, k, 2) or not ops.fits(count, n, dtype="int32"):
+                ops.bad("out", "the result of a call with the same n and k, on tensors or arrays as the points are")
+        mk, (p_mask, word) = (None, (0, 0xFFFFFFFF)) if mask is None else ops.mask(mask)
+        ops.call(ops.ptr(points), ops.ptr(max_distance), p_list, n_list, k, p_mask, word, tr[0], tr[1], m, ops.ptr(raw),
+                 ops.ptr(count))
+        return NearestResult(raw, ops.words(raw), count, ops.note(n_list), keep=ops.keep(points, max_distance, index, mk))
 
     def deposit(self, colors, pixels, sums, moments=None, counts=None, index=None, max_value=1.0, rejected=None) -> None:
         """Exact sample deposit (tor_deposit_device): adds the samples (colors[i], pixels[i]) to the film buffers in the progressive
@@ -1574,15 +1431,11 @@ class Context:
         pixels in that layout; moments (None or like sums), counts (None or int32 with npix elements), rejected (None or one int64)
         on the same device, contiguous, all ADDED to.  Asynchronous on torch's current stream."""
         import torch
-        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float64 or colors.dim() != 2 or colors.shape[1] != 3 \
-                or not colors.is_cuda:
-            raise ValueError("Context.deposit: colors must be an (n, 3) float64 CUDA tensor")
-        dev = colors.device
-        if getattr(self, "_device", None) is not None and dev.index != self._device:
-            raise ValueError(f"Context.deposit: the colors are on {dev}, the context on cuda:{self._device}")
-        n = int(colors.shape[0])
-        if not isinstance(pixels, torch.Tensor) or pixels.dtype != torch.int32 or tuple(pixels.shape) != (n,) or pixels.device != dev:
-            raise ValueError("Context.deposit: pixels must be an (n,) int32 tensor on the colors' device")
+        ops = _Tensors(self, "deposit", colors, "colors", 3)
+        colors, n, dev = ops.lead, ops.n, ops.dev
+        pixels = ops.rows(pixels, "pixels", dtype="int32")
+        if pixels is None:
+            ops.bad("pixels", "an (n,) int32 tensor on the colors' device")
         if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.dim() < 1 or sums.shape[-1] != 3 \
                 or sums.device != dev or not sums.is_contiguous():
             raise ValueError("Context.deposit: sums must be a contiguous (..., 3) float64 tensor on the colors' device")
@@ -1596,33 +1449,15 @@ class Context:
         if rejected is not None and (not isinstance(rejected, torch.Tensor) or rejected.dtype != torch.int64 or int(rejected.numel()) != 1
                                      or rejected.device != dev):
             raise ValueError("Context.deposit: rejected must be one int64 on the sums' device")
-        colors, pixels = colors.contiguous(), pixels.contiguous()
-        index, n_list, p_list = self._step_index(index, n, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib().tor_deposit_device(self._h, n, C.c_void_p(colors.data_ptr()), C.c_void_p(pixels.data_ptr()), p_list,
-                                        n_list if index is not None else 0, float(max_value), npix, C.c_void_p(sums.data_ptr()),
-                                        C.c_void_p(moments.data_ptr() if moments is not None else 0),
-                                        C.c_void_p(counts.data_ptr() if counts is not None else 0),
-                                        C.c_void_p(rejected.data_ptr() if rejected is not None else 0), C.c_void_p(stream)))
-
-    @staticmethod
-    def _point_times(points, time_range):
-        """_time_range_of for (n, 4) points: the time is column 3."""
-        if time_range is not None:
-            return float(time_range[0]), float(time_range[1])
-        if type(points).__module__.startswith("torch"):
-            import torch
-            times = points[:, 3]
-            times = times[torch.isfinite(times)]
-            return (0.0, 0.0) if times.numel() == 0 else tuple(float(v) for v in torch.aminmax(times))
-        times = points[:, 3][np.isfinite(points[:, 3])]
-        return (0.0, 0.0) if times.size == 0 else (float(times.min()), float(times.max()))
+        index, n_list, p_list = ops.index(index)
+        ops.call(ops.ptr(colors), ops.ptr(pixels), p_list, n_list if index is not None else 0, float(max_value), npix,
+                 ops.ptr(sums), ops.ptr(moments), ops.ptr(counts), ops.ptr(rejected))
 
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
         `time` (a scalar or one per segment), (n, 2) ranges (t_min, 1.0)) -- torch tensors when p is one, else numpy arrays."""
-        if type(p).__module__.startswith("torch"):
+        if _is_tensor(p):
             import torch
             p = p.reshape(-1, 3)
             q = torch.as_tensor(q, dtype=p.dtype, device=p.device).reshape(-1, 3)
@@ -1668,14 +1503,14 @@ class Context:
         mask: as for bounce(), for every step; or a callable mask(step) -> int | per-ray words, so that step 0 (the camera's rays)
         sees other objects than the later steps."""
         import torch
-        as_numpy = not type(rays).__module__.startswith("torch")
+        as_numpy = not _is_tensor(rays)
         if as_numpy:
-            dev = torch.device("cuda", self._device if getattr(self, "_device", None) is not None else torch.cuda.current_device())
-            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)).to(dev)
-            rng = torch.from_numpy(self._step_states("trace", rng, int(rays.shape[0])).view(np.int64)).to(dev)
-        rays, rng, dev, _ = self._step_tensors("trace", rays, rng)
-        n = int(rays.shape[0])
-        tr = self._time_range_of(rays, time_range)
+            host = _Arrays(self, "trace", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
+            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
+        ops = _Tensors(self, "trace", rays, "rays", 7)
+        rays, n, dev = ops.lead, ops.n, ops.dev
+        rng = ops.states(rng)
+        tr = ops.times(6, time_range)
         work = rays.clone()
         color = torch.zeros((n, 3), dtype=torch.float64, device=dev)
         att = torch.ones((n, 3), dtype=torch.float64, device=dev)
