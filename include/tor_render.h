@@ -985,4 +985,10 @@ TOR_API const char* tor_version(void);
 }
 #endif
 
+/* ---- direct-light sampling queries: the shadow rays of next-event estimation --------------------------------------------------------
+ * tor_scene_lights, tor_light_sample_device / _host, tor_light_pdf_device / _host: per shading point one light of the context's
+ * light table, a direction inside the cone its sphere subtends, the shadow segment for tor_occluded_device and the solid-angle
+ * density -- defined operation by operation, in the query family's style, in tor_lights.h. */
+#include "tor_lights.h"
+
 #endif /* TOR_RENDER_H */

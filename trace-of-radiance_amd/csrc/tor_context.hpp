@@ -122,6 +122,9 @@ struct HitQueryState {
   double pt_reach2 = -1.0;          // squared distance from org within which a POINT may use the boxes (< 0: none may), cached per
   int64_t pt_scene = -1;            // (scene, time range) like the bounds
   uint64_t pt_lo = 0, pt_hi = 0;
+  // direct-light sampling queries (tor_lights.hip)
+  DeviceBuffer lights;              // the light table (tor_scene_lights): 16 float64 per light, packed when the table is set
+  int64_t n_lights = 0;             // 0: no table (the state after every upload that replaces the scene)
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

@@ -94,6 +94,7 @@ HitQueryState::~HitQueryState() {
   grp[1].release();
   absr[0].release();
   absr[1].release();
+  lights.release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 
