@@ -991,4 +991,10 @@ TOR_API const char* tor_version(void);
  * density -- defined operation by operation, in the query family's style, in tor_lights.h. */
 #include "tor_lights.h"
 
+/* ---- environment-light queries: the sky as an emitter ---------------------------------------------------------------------------------
+ * tor_scene_environment, tor_env_sample_device / _host, tor_env_eval_device / _host: a context-owned octahedral environment map,
+ * evaluated per ray direction, importance-sampled per shading point, with the solid-angle density of any direction -- defined
+ * operation by operation in tor_env.h. */
+#include "tor_env.h"
+
 #endif /* TOR_RENDER_H */

@@ -170,6 +170,9 @@ EXPORTED_SYMBOLS = [
 LIGHT_SYMBOLS = ["tor_scene_lights", "tor_light_sample_device", "tor_light_sample_host", "tor_light_pdf_device", "tor_light_pdf_host"]
 LIGHT_BY_WEIGHT, LIGHT_BY_SOLID_ANGLE = 0, 1   # TOR_LIGHT_BY_*: what Context.sample_lights picks a light by
 LIGHT_STRATEGIES = {"weight": LIGHT_BY_WEIGHT, "solid_angle": LIGHT_BY_SOLID_ANGLE}
+# the environment-light queries (include/tor_env.h), bound as the light entries are
+ENV_SYMBOLS = ["tor_scene_environment", "tor_env_sample_device", "tor_env_sample_host", "tor_env_eval_device", "tor_env_eval_host"]
+ENV_MAX_SIDE = 2048   # TOR_ENV_MAX_SIDE: the most texels per side of an environment map
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -236,6 +239,7 @@ def lib():
     L = C.CDLL(ab or LIB_PATH)
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
     _bind_lights(L, skip_missing=bool(ab))
+    _bind_env(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -383,6 +387,29 @@ def _bind_lights(L, skip_missing=False) -> None:
         if skip_missing and not hasattr(L, name):
             continue
         getattr(L, name).argtypes = _LIGHT_SIGNATURES[name]
+
+
+def _env_signatures() -> dict:
+    """The ctypes argtypes of the entries of include/tor_env.h (every one returns int)."""
+    v, i64 = C.c_void_p, C.c_int64
+    return {
+        "tor_scene_environment": [v, i64, v, v],
+        "tor_env_sample_device": [v, i64, v, v, v, i64, v, v, v, v, v],
+        "tor_env_sample_host": [v, i64, v, v, v, i64, v, v, v, v],
+        "tor_env_eval_device": [v, i64, v, v, i64, v, v, v, v],
+        "tor_env_eval_host": [v, i64, v, v, i64, v, v, v],
+    }
+
+
+_ENV_SIGNATURES = _env_signatures()
+
+
+def _bind_env(L, skip_missing=False) -> None:
+    """_bind for the entries of ENV_SYMBOLS."""
+    for name in ENV_SYMBOLS:
+        if skip_missing and not hasattr(L, name):
+            continue
+        getattr(L, name).argtypes = _ENV_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -1173,6 +1200,27 @@ class Context:
             raise ValueError("Context.set_lights: one weight per light")
         _check(lib().tor_scene_lights(self._h, int(o.size), C.c_void_p(o.ctypes.data or 16), C.c_void_p(w.ctypes.data or 16)))
 
+    def set_environment(self, rgb, importance=None):
+        """The environment map of the context (tor_scene_environment): `rgb` is (n, n, 3) float64, finite and >= 0, the texels of
+        an octahedral map in [row][col] order (environment_directions(n) gives the direction of every texel centre, so any sky
+        is baked with one call); `importance` (n, n), finite and >= 0, is what sample_environment picks a texel by -- None: the
+        texel's luminance times its solid angle.  None for `rgb` clears the map.  The map belongs to the context, not to the
+        scene: uploads leave it alone, and environment / sample_environment need no scene."""
+        if rgb is None:
+            _check(lib().tor_scene_environment(self._h, 0, C.c_void_p(0), C.c_void_p(0)))
+            return
+        c = np.ascontiguousarray(np.asarray(rgb, dtype=np.float64))
+        if c.ndim != 3 or c.shape[0] != c.shape[1] or c.shape[2] != 3 or c.shape[0] < 1:
+            raise ValueError("Context.set_environment: rgb must be (n, n, 3) with n >= 1")
+        n = int(c.shape[0])
+        if importance is None:
+            _check(lib().tor_scene_environment(self._h, n, C.c_void_p(c.ctypes.data), C.c_void_p(0)))
+            return
+        w = np.ascontiguousarray(np.asarray(importance, dtype=np.float64))
+        if w.shape != (n, n):
+            raise ValueError("Context.set_environment: importance must be (n, n), one value per texel")
+        _check(lib().tor_scene_environment(self._h, n, C.c_void_p(c.ctypes.data), C.c_void_p(w.ctypes.data)))
+
     def _cuda(self):
         """The context's torch device (the current one for a context on the library's default device)."""
         import torch
@@ -1645,6 +1693,162 @@ class Context:
             return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
         return color, rng, ran
 
+    # ---- environment-light queries (tor_env_eval_device, tor_env_sample_device): the sky as an emitter ----
+
+    def environment(self, rays, index=None, out=None, pdf=False):
+        """The environment map's colour in the direction of every listed ray (tor_env_eval_device / tor_env_eval_host): (n, 3)
+        float64, the RGB of the texel the direction encodes into -- the definition, operation by operation, is in
+        include/tor_env.h.  The direction need not be unit; one that is zero, NaN or infinite gives colour 0, pdf 0, texel -1.
+
+        rays: (n, 7) float64 -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream, no host
+        synchronisation) or anything numpy takes (copied, blocking).  index as for bounce().  out: an (n, 3) array of the rays'
+        kind (or an EnvEval of an earlier call with pdf=True), written again -- rays that are not listed keep what it holds;
+        otherwise new (colour and pdf 0, texel -1).  pdf=True: an EnvEval with color, pdf (n,) the solid-angle density
+        sample_environment gives that direction (what multiple importance sampling needs) and texel (n,) int32
+        row * n + col."""
+        ops = _operands(self, "env_eval", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        index, n_list, p_list = ops.index(index)
+        dens = texel = None
+        if isinstance(out, EnvEval):
+            color, dens, texel = out.color, out.pdf, out.texel
+        else:
+            color = out
+        if color is None:
+            color = ops.new(n, 3)
+        elif not ops.fits(color, n, 3):
+            ops.bad("out", "a contiguous (n, 3) float64 tensor or array, as the rays are")
+        if pdf:
+            if dens is None:
+                dens = ops.new(n)
+                texel = ops.new(n, dtype="int32", zero=False)
+                texel[...] = -1
+            elif not ops.fits(dens, n) or not ops.fits(texel, n, dtype="int32"):
+                ops.bad("out", "the result of a call with pdf=True on as many rays")
+        else:
+            dens = texel = None
+        ops.call(ops.ptr(rays), p_list, n_list, ops.ptr(color), ops.ptr(dens), ops.ptr(texel))
+        self._env_keep = ops.keep(rays, index)   # (alive while the query may still run)
+        return EnvEval(color, dens, texel, ops.note(n_list)) if pdf else color
+
+    def sample_environment(self, points, rng, index=None, out=None) -> "EnvSample":
+        """One direction per listed shading point, drawn in proportion to the environment map's importance
+        (tor_env_sample_device / tor_env_sample_host; include/tor_env.h): a texel by its importance, a uniform position inside
+        it, the octahedral decode.
+
+        points: (n, 4) float64 {x, y, z, time} -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or
+        anything numpy takes (copied, blocking).  rng: (n, 4) 64-bit states as for bounce(): every listed point draws exactly
+        four uniform01; a contiguous CUDA tensor is updated in place.  index as for bounce().  Returns an EnvSample: rays
+        (n, 7) {origin p, unit direction, time} -- they go into occluded() with the default range (0.001, +inf) --, pdf (n,)
+        per unit solid angle, texel (n,) int32 row * n + col, color (n, 3) the texel's RGB, rng and mode.  out: an EnvSample of
+        an earlier call on as many points, written again (points that are not listed keep what it holds); otherwise a new one
+        (texel -1, the rest 0)."""
+        if out is not None and not isinstance(out, EnvSample):
+            raise ValueError("Context.sample_environment: out must be an EnvSample")
+        ops = _operands(self, "env_sample", points, "points", 4)
+        n, points = ops.n, ops.lead
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            rays, pdf, color = ops.new(n, 7), ops.new(n), ops.new(n, 3)
+            texel = ops.new(n, dtype="int32", zero=False)
+            texel[...] = -1
+        else:
+            rays, pdf, texel, color = out.rays, out.pdf, out.texel, out.color
+            if not ops.fits(rays, n, 7) or not ops.fits(pdf, n) or not ops.fits(texel, n, dtype="int32") or not ops.fits(color, n, 3):
+                ops.bad("out", "the result of a call on as many points, on tensors or arrays as the points are")
+        ops.call(ops.ptr(points), ops.ptr(rng), p_list, n_list, ops.ptr(rays), ops.ptr(pdf), ops.ptr(texel), ops.ptr(color))
+        return EnvSample(rays, pdf, texel, color, rng, ops.note(n_list), keep=ops.keep(points, index))
+
+    def trace_environment(self, rays, rng, diffuse, max_depth=50, direct=True, mis=False, time_range=None, mode="auto"):
+        """trace()'s loop with the environment map (set_environment) as the sky, and next-event estimation towards it: a ray
+        that misses adds att * environment(ray) * w, and with `direct` every diffuse hit that goes on (except on the last of
+        the max_depth steps) draws a direction from the map (sample_environment), asks occluded() with range (0.001, +inf)
+        whether it is free, and adds att * color * (cos / pi / pdf * share) where it is.  w = 1 when `direct` is off or the
+        ray left the camera, a Metal or a Dielectric; otherwise 0, or with mis=True the balance share
+        p_bsdf / (p_bsdf + p_env) -- `share` is then p_env / (p_env + p_bsdf), else 1.  p_bsdf is the Lambertian density
+        cos / pi, p_env the map's density of the direction (environment(pdf=True)).
+
+        diffuse: (n_objects,) bool (diffuse_objects(scene)).  rays, rng, time_range, mode and the result (color, rng, mode) as
+        for trace().  No step builds a list of the misses, so none synchronises with the host on their count.
+
+        The environment draws come from a third state per path, derived from the path's entry state like trace_direct's light
+        states but with the constant 0xd1342543de82ef95 in place of the golden ratio's 0x9e3779b97f4a7c15: the bounces see
+        exactly the states trace() gives them.  So with direct=False the colours are those of
+        trace(sky=lambda rays, idx: ctx.environment(rays, idx)[idx.long()]), bit for bit, and the returned states are the path
+        states, as trace() returns them."""
+        import torch
+        as_numpy = not _is_tensor(rays)
+        if as_numpy:
+            host = _Arrays(self, "trace_environment", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
+            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
+        ops = _Tensors(self, "trace_environment", rays, "rays", 7)
+        rays, n, dev = ops.lead, ops.n, ops.dev
+        rng = ops.states(rng)
+        tr = ops.times(6, time_range)
+        f64 = torch.float64
+        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
+        work = rays.clone()
+        color = torch.zeros((n, 3), dtype=f64, device=dev)
+        att = torch.ones((n, 3), dtype=f64, device=dev)
+        erng = _derived_states(rng.view(torch.int64) if rng.dtype != torch.int64 else rng, _ENV_STREAM)
+        points = torch.zeros((n, 4), dtype=f64, device=dev)          # the shading point of every ray's last diffuse hit ...
+        p_bsdf = torch.zeros((n,), dtype=f64, device=dev)            # ... the Lambertian density of the direction it left in ...
+        specular = torch.ones((n,), dtype=torch.bool, device=dev)    # ... or: the ray left a camera, a Metal or a Dielectric
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        res, es, occ, ev, ran = None, None, None, None, None
+        for step in range(int(max_depth)):
+            if live.numel() == 0:
+                break
+            res = self.bounce(work, rng, live, tr, mode, out=res)
+            ran = ran or res.mode
+            idx = live.long()
+            st = res.status[idx]
+            # the map's colour (and density) of every stepped ray, kept where it missed: no list of the misses
+            if direct and mis:
+                ev = self.environment(work, live, out=ev, pdf=True)
+                sky, p_env = ev.color[idx], ev.pdf[idx]
+                share = p_bsdf[idx] / (p_bsdf[idx] + p_env)
+                wgt = torch.where(specular[idx], torch.ones_like(share), torch.where(torch.isfinite(share), share, torch.zeros_like(share)))
+                sky = sky * att[idx] * wgt[:, None]
+            else:
+                ev = self.environment(work, live, out=ev)
+                sky = ev[idx] * att[idx]
+                if direct:
+                    sky = sky * specular[idx].to(f64)[:, None]
+            color[idx] = torch.where((st == BOUNCE_MISS)[:, None], color[idx] + sky, color[idx])
+            live = self.bounce_select(res.status, live)
+            scat = live.long()
+            att[scat] = att[scat] * res.attenuation[scat]
+            if not direct:
+                continue
+            # next-event estimation at the diffuse hits that go on
+            sobj = res.object[scat].long()
+            isdiff = diffuse[sobj]
+            specular[scat] = ~isdiff
+            nee = scat[isdiff]
+            if nee.numel() == 0 or step == int(max_depth) - 1:   # (a sample after the last step would be one vertex more than trace() follows)
+                continue
+            points[nee, 0:3], points[nee, 3] = res.p[nee], work[nee, 6]
+            nrm = res.normal[nee]
+            d = work[nee, 3:6]
+            cos_out = (nrm * d).sum(1) / torch.sqrt((d * d).sum(1))
+            p_bsdf[nee] = torch.clamp(cos_out, min=0.0) / np.pi
+            lst = nee.int()
+            es = self.sample_environment(points, erng, lst, out=es)
+            occ = self.occluded(es.rays, None, lst, tr, mode, out=occ)
+            cos_l = (nrm * es.rays[nee, 3:6]).sum(1)              # (the sampled direction is unit)
+            pdf = es.pdf[nee]
+            ok = (~occ.occluded[nee]) & (pdf > 0) & torch.isfinite(pdf) & (cos_l > 0)
+            share = pdf / (pdf + cos_l / np.pi) if mis else torch.ones_like(pdf)
+            add = att[nee] * es.color[nee] * (cos_l / np.pi / pdf * share)[:, None]
+            color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
+        if ran is None:
+            ran = "nothing to do"
+        if as_numpy:
+            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
+        return color, rng, ran
+
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
@@ -1763,6 +1967,16 @@ def _light_states(rng):
     """The light-draw states of trace_direct: per path and word k the splitmix64 finaliser (rng.nim:31-36's mixing) of
     s_k xor rotl(s_(k+1), 23) + (k + 1) * golden, in wrapping int64 tensor arithmetic -- a second stream per path that shares no
     draw with the path's own."""
+    return _derived_states(rng, 0x9e3779b97f4a7c15)
+
+
+_ENV_STREAM = 0xd1342543de82ef95   # the odd constant of trace_environment's third stream (where _light_states has the golden ratio's)
+
+
+def _derived_states(rng, constant):
+    """A further stream per path: per path and word k the splitmix64 finaliser (rng.nim:31-36's mixing) of
+    s_k xor rotl(s_(k+1), 23) + (k + 1) * constant, in wrapping int64 tensor arithmetic.  Streams of different odd constants
+    share no draw with the path's own or with each other."""
     def lsr(z, k):
         return (z >> k) & ((1 << (64 - k)) - 1)
 
@@ -1773,11 +1987,29 @@ def _light_states(rng):
     out = rng.clone()
     for k in range(4):
         nxt = rng[:, (k + 1) % 4]
-        z = (rng[:, k] ^ ((nxt << 23) | lsr(nxt, 41))) + signed(((k + 1) * 0x9e3779b97f4a7c15) & ((1 << 64) - 1))
+        z = (rng[:, k] ^ ((nxt << 23) | lsr(nxt, 41))) + signed(((k + 1) * constant) & ((1 << 64) - 1))
         z = (z ^ lsr(z, 30)) * mix
         z = (z ^ lsr(z, 27)) * mix
         out[:, k] = z ^ lsr(z, 31)
     return out
+
+
+def environment_directions(n, a=0.5, b=0.5) -> np.ndarray:
+    """The (n, n, 3) float64 unit directions of the positions (a, b) in [0, 1) inside every texel of an n x n octahedral
+    environment map, [row][col] -- include/tor_env.h's decode, operation by operation in numpy; (0.5, 0.5) are the texel centres.
+    A host bakes any sky with it: set_environment(f(environment_directions(n)))."""
+    n = int(n)
+    if not 1 <= n <= ENV_MAX_SIDE:
+        raise ValueError(f"environment_directions: need 1 <= n <= {ENV_MAX_SIDE}")
+    h = 2.0 / float(n)
+    s = np.broadcast_to(((np.arange(n, dtype=np.float64) + float(a)) * h - 1.0)[None, :], (n, n))
+    t = np.broadcast_to(((np.arange(n, dtype=np.float64) + float(b)) * h - 1.0)[:, None], (n, n))
+    py = (1.0 - np.abs(s)) - np.abs(t)
+    up = py >= 0
+    px = np.where(up, s, np.copysign(1.0 - np.abs(t), s))
+    pz = np.where(up, t, np.copysign(1.0 - np.abs(s), t))
+    inv = 1.0 / np.sqrt(px * px + py * py + pz * pz)
+    return np.stack([px * inv, py * inv, pz * inv], axis=-1)
 
 
 def diffuse_objects(scene) -> np.ndarray:
@@ -1863,6 +2095,26 @@ class LightSample:
     def __init__(self, rays, pdf, light, dist, rng, note: str, keep=None):
         self.rays, self.pdf, self.light, self.dist, self.rng, self._keep = rays, pdf, light, dist, rng, keep
         self.mode = _mode_of(note, "light sample: ")
+
+
+class EnvSample:
+    """Environment samples of Context.sample_environment, one per point (include/tor_env.h): rays (n, 7) float64 {origin p, unit
+    direction, time}, pdf (n,) float64 per unit solid angle, texel (n,) int32 row * n + col (-1: never written), color (n, 3)
+    float64 the texel's RGB, rng (n, 4) the states after the four draws -- torch tensors or numpy arrays, as the points were.
+    `mode`: "env sample"."""
+
+    def __init__(self, rays, pdf, texel, color, rng, note: str, keep=None):
+        self.rays, self.pdf, self.texel, self.color, self.rng, self._keep = rays, pdf, texel, color, rng, keep
+        self.mode = note
+
+
+class EnvEval:
+    """Context.environment(pdf=True), one entry per ray (include/tor_env.h): color (n, 3) float64, pdf (n,) float64 the density
+    sample_environment gives the ray's direction, texel (n,) int32 row * n + col (-1: an unusable direction, or not listed).
+    `mode`: "env eval"."""
+
+    def __init__(self, color, pdf, texel, note: str):
+        self.color, self.pdf, self.texel, self.mode = color, pdf, texel, note
 
 
 class Progressive:

@@ -125,6 +125,11 @@ struct HitQueryState {
   // direct-light sampling queries (tor_lights.hip)
   DeviceBuffer lights;              // the light table (tor_scene_lights): 16 float64 per light, packed when the table is set
   int64_t n_lights = 0;             // 0: no table (the state after every upload that replaces the scene)
+  // environment-light queries (tor_env.hip): the map belongs to the context, not to the scene -- tor_scene_upload leaves it alone
+  DeviceBuffer env;                 // the map's tables (tor_scene_environment), one allocation laid out by env_n (tor_env.hip EnvLayout)
+  int64_t env_n = 0;                // texels per side, 0: no map
+  double env_total = 0.0;           // T, the sum of the importances as the header adds them
+  int32_t env_last_row = 0;         // the last row with S_r > 0 (the row search's fallback)
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

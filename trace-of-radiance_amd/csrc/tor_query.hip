@@ -95,6 +95,7 @@ HitQueryState::~HitQueryState() {
   absr[0].release();
   absr[1].release();
   lights.release();
+  env.release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 
