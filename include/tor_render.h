@@ -997,4 +997,10 @@ TOR_API const char* tor_version(void);
  * operation by operation in tor_env.h. */
 #include "tor_env.h"
 
+/* ---- light-tracing queries: emit from the lights, connect to the camera ---------------------------------------------------------------
+ * tor_light_emit_device / _host, tor_camera_connect_device / _host: a path started ON a lamp of the light table, and for a world
+ * point the pixel it lands in, the lens point and the measurement weight -- the splats of a light tracer, defined operation by
+ * operation in tor_camera.h. */
+#include "tor_camera.h"
+
 #endif /* TOR_RENDER_H */

@@ -173,6 +173,8 @@ LIGHT_STRATEGIES = {"weight": LIGHT_BY_WEIGHT, "solid_angle": LIGHT_BY_SOLID_ANG
 # the environment-light queries (include/tor_env.h), bound as the light entries are
 ENV_SYMBOLS = ["tor_scene_environment", "tor_env_sample_device", "tor_env_sample_host", "tor_env_eval_device", "tor_env_eval_host"]
 ENV_MAX_SIDE = 2048   # TOR_ENV_MAX_SIDE: the most texels per side of an environment map
+# the light-tracing queries (include/tor_camera.h), bound as the light entries are
+CAMERA_SYMBOLS = ["tor_camera_connect_device", "tor_camera_connect_host", "tor_light_emit_device", "tor_light_emit_host"]
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -240,6 +242,7 @@ def lib():
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
     _bind_lights(L, skip_missing=bool(ab))
     _bind_env(L, skip_missing=bool(ab))
+    _bind_camera(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -410,6 +413,28 @@ def _bind_env(L, skip_missing=False) -> None:
         if skip_missing and not hasattr(L, name):
             continue
         getattr(L, name).argtypes = _ENV_SIGNATURES[name]
+
+
+def _camera_signatures() -> dict:
+    """The ctypes argtypes of the entries of include/tor_camera.h (every one returns int)."""
+    v, i32, i64, d, cam = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER(Camera)
+    return {
+        "tor_camera_connect_device": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v, v],
+        "tor_camera_connect_host": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v],
+        "tor_light_emit_device": [v, i64, v, v, i64, d, d, v, v, v, v, v],
+        "tor_light_emit_host": [v, i64, v, v, i64, d, d, v, v, v, v],
+    }
+
+
+_CAMERA_SIGNATURES = _camera_signatures()
+
+
+def _bind_camera(L, skip_missing=False) -> None:
+    """_bind for the entries of CAMERA_SYMBOLS."""
+    for name in CAMERA_SYMBOLS:
+        if skip_missing and not hasattr(L, name):
+            continue
+        getattr(L, name).argtypes = _CAMERA_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -1693,6 +1718,180 @@ class Context:
             return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
         return color, rng, ran
 
+    # ---- light-tracing queries (tor_light_emit_device, tor_camera_connect_device): emit from the lights, connect to the camera ----
+
+    def connect_camera(self, cam: Camera, nrows: int, ncols: int, points, rng, index=None, out=None) -> "CameraConnection":
+        """For each listed world point the pixel it lands in, the lens point it is seen through and the measurement weight
+        (tor_camera_connect_device / tor_camera_connect_host) -- the inverse of camera_rays; the definition, operation by
+        operation in float64, is in include/tor_camera.h.  It reads no scene.
+
+        points: (n, 4) float64 {x, y, z, time} -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or
+        anything numpy takes (copied, blocking).  rng: (n, 4) 64-bit states as for bounce(): every listed point draws exactly two
+        uniform01 (the lens point), pinhole or not, connected or not; a contiguous CUDA tensor is updated in place.  index as for
+        bounce().  Returns a CameraConnection: rays (n, 7) {origin the point, direction to the lens point, time} -- parameter
+        1.0 is the lens point, so the rays go into occluded() with range (t_min, 1.0) --, pixel (n,) int32 row * ncols + col
+        (row 0 = bottom; -1: behind the lens plane, outside the frame or not finite, then factor = 0 and ray = 0), factor (n,):
+        a vertex with throughput beta, BSDF value f and cosine cos_y towards the lens point adds beta * f * cos_y * factor to
+        the pixel's radiance estimate when the segment is free, lens (n, 2) the lens point in the camera's (u, v), rng and mode.
+        out: a CameraConnection of an earlier call on as many points, written again (points that are not listed keep what it
+        holds); otherwise a new one (pixel -1, the rest 0)."""
+        if out is not None and not isinstance(out, CameraConnection):
+            raise ValueError("Context.connect_camera: out must be a CameraConnection")
+        ops = _operands(self, "camera_connect", points, "points", 4)
+        n, points = ops.n, ops.lead
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            rays, factor, lens = ops.new(n, 7), ops.new(n), ops.new(n, 2)
+            pixel = ops.new(n, dtype="int32", zero=False)
+            pixel[...] = -1
+        else:
+            rays, pixel, factor, lens = out.rays, out.pixel, out.factor, out.lens
+            if not ops.fits(rays, n, 7) or not ops.fits(pixel, n, dtype="int32") or not ops.fits(factor, n) or not ops.fits(lens, n, 2):
+                ops.bad("out", "the result of a call on as many points, on tensors or arrays as the points are")
+        _check(getattr(lib(), "tor_camera_connect" + ops.suffix)(
+            ops.h, C.byref(cam), int(nrows), int(ncols), n, ops.ptr(points), ops.ptr(rng), p_list, n_list, ops.ptr(rays), ops.ptr(pixel),
+            ops.ptr(factor), ops.ptr(lens), *ops.tail))
+        return CameraConnection(rays, pixel, factor, lens, rng, ops.note(n_list), keep=ops.keep(points, index))
+
+    def emit_lights(self, rng, time_range=(0.0, 0.0), index=None, out=None) -> "LightEmission":
+        """One path start per listed state on the lamps of the light table (tor_light_emit_device / tor_light_emit_host;
+        include/tor_camera.h): a time in time_range, a light by its weight, a uniform point of its sphere and a cosine-weighted
+        direction about the normal there.
+
+        rng: (n, 4) 64-bit states -- a torch CUDA tensor (int64 holding the u64 bits; zero-copy, asynchronous on torch's current
+        stream, a contiguous one is updated in place) or anything numpy takes (copied, blocking): every listed path draws
+        exactly six.  time_range: (lo, hi), finite, lo <= hi -- the camera's shutter interval.  index as for bounce().  Returns
+        a LightEmission: rays (n, 7) {origin on the lamp, unit direction, time}, normal (n, 3), light (n,) int32 the OBJECT
+        index, pdf_area (n,) per unit area with the pick included (+inf for a lamp of radius 0), pdf_dir (n,) = cos / pi per
+        unit solid angle, rng and mode.  A lamp of uniform radiance Le starts its path with beta = Le * pi / pdf_area.  out: a
+        LightEmission of an earlier call on as many states, written again; otherwise a new one (light -1, the rest 0)."""
+        if out is not None and not isinstance(out, LightEmission):
+            raise ValueError("Context.emit_lights: out must be a LightEmission")
+        if _is_tensor(rng):
+            import torch
+            if rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
+                raise ValueError("Context.emit_lights: rng must be an (n, 4) int64 CUDA tensor")
+            rng = rng.contiguous()
+            words = rng.view(torch.float64)
+        else:
+            rng = np.asarray(rng)
+            if rng.ndim != 2 or rng.shape[1] != 4 or rng.dtype.kind not in "iu" or rng.dtype.itemsize != 8:
+                raise ValueError("Context.emit_lights: rng must be an (n, 4) array of 64-bit integers")
+            words = np.ascontiguousarray(rng).view(np.float64)
+        ops = _operands(self, "light_emit", words, "rng", 4)   # (the leading operand of the one operand layer: the states' words)
+        n = ops.n
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            rays, normal, pdf = ops.new(n, 7), ops.new(n, 3), ops.new(n, 2)
+            light = ops.new(n, dtype="int32", zero=False)
+            light[...] = -1
+        else:
+            rays, normal, light, pdf = out.rays, out.normal, out.light, out.pdf
+            if not ops.fits(rays, n, 7) or not ops.fits(normal, n, 3) or not ops.fits(light, n, dtype="int32") or not ops.fits(pdf, n, 2):
+                ops.bad("out", "the result of a call on as many states, on tensors or arrays as the states are")
+        ops.call(ops.ptr(rng), p_list, n_list, float(time_range[0]), float(time_range[1]), ops.ptr(rays), ops.ptr(normal),
+                 ops.ptr(light), ops.ptr(pdf))
+        return LightEmission(rays, normal, light, pdf, rng, ops.note(n_list), keep=ops.keep(index))
+
+    def trace_light(self, cam: Camera, nrows: int, ncols: int, rng, emission, diffuse, max_depth=50, lamp_mask=None, time_range=None,
+                    mode="auto", splat=None):
+        """A light tracer on top of emit_lights, bounce, connect_camera and occluded: one path per state starts on a lamp of the
+        light table (set_lights) with beta = Le * pi / pdf_area, and every vertex the camera can see directly is splatted into
+        the pixel it lands in.  The emission vertex itself adds Le * cos_y * factor / pdf_area where cos_y > 0.  Per step the
+        live rays bounce; every hit on a `diffuse` object is connected (connect_camera), the segment to the lens point asked of
+        occluded() with range (0.001, 1.0), and where it is free and cos_y > 0 (the face normal the step returned against the
+        unit direction to the lens point) the vertex adds beta * albedo / pi * cos_y * factor; then beta *= attenuation for the
+        rays that scattered, which stay live, for at most max_depth steps.
+
+        Each batch goes to splat(pixels, colors, index): pixels (n,) int32 (-1 where nothing is added), colors (n, 3) float64
+        already divided by nrows * ncols, index the int32 list of the entries of this batch -- Film.deposit's signature; with
+        N paths in all, a pixel's radiance estimate is the sum of its splats times nrows * ncols / N.  splat None: nothing is
+        kept.  Returns (the number of splats offered, rng after the paths' last draws, the mode that ran).
+
+        emission: (n_objects, 3) float64, the radiance Le of every lamp.  diffuse: (n_objects,) bool (diffuse_objects(scene)).
+        lamp_mask: the occluded() mask of the connection segments (None: every group).  time_range: the emission's (lo, hi);
+        None: the camera's shutter interval.  rng: (n, 4) states, a contiguous CUDA tensor is updated in place; numpy states
+        go through the device and come back as numpy.  The connection draws come from a second state per path, derived from
+        the path's entry state (_derived_states with a constant of its own), so the bounces see the states they would see
+        without connections.
+
+        What a light tracer cannot see: surfaces the camera sees THROUGH a Metal or Dielectric vertex (a mirror image, the
+        far side of a glass ball) -- no connection reaches the lens by way of a specular vertex; those need trace / trace_direct
+        / trace_environment.  Mixing both estimators in one film counts the directly seen diffuse surfaces twice and is out of
+        scope, as are multiple importance sampling between them and the sky (an environment is no lamp of the table)."""
+        import torch
+        as_numpy = not _is_tensor(rng)
+        if as_numpy:
+            st = np.asarray(rng)
+            if st.ndim != 2 or st.shape[1] != 4 or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+                raise ValueError("Context.trace_light: rng must be an (n, 4) array of 64-bit integers")
+            rng = self._to_device(np.ascontiguousarray(st).view(np.int64))
+        elif rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
+            raise ValueError("Context.trace_light: rng must be an (n, 4) int64 CUDA tensor")
+        rng = rng.contiguous()
+        n, dev, f64 = int(rng.shape[0]), rng.device, torch.float64
+        tr = (float(cam.shutter_open), float(cam.shutter_close)) if time_range is None else (float(time_range[0]), float(time_range[1]))
+        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
+        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
+        inv_npix = 1.0 / float(int(nrows) * int(ncols))
+        crng = _derived_states(rng.view(torch.int64) if rng.dtype != torch.int64 else rng, _CAMERA_STREAM)
+        if n == 0:
+            return 0, (rng.cpu().numpy().view(np.uint64) if as_numpy else rng), "nothing to do"
+        em = self.emit_lights(rng, tr)
+        work, lamp = em.rays.clone(), em.light.long().clamp(min=0)
+        pdf_area = em.pdf_area
+        beta = emission[lamp] * (np.pi / pdf_area)[:, None]                   # (a lamp of radius 0 has no area: it emits nothing)
+        points = torch.zeros((n, 4), dtype=f64, device=dev)
+        t_range = torch.empty((n, 2), dtype=f64, device=dev)
+        t_range[:, 0], t_range[:, 1] = 0.001, 1.0
+        colors = torch.zeros((n, 3), dtype=f64, device=dev)
+        offered = 0
+
+        def connect(lst, nrm, weight, conn, occ):
+            """Connect the listed vertices (their points are set): splat weight * cos_y * factor / npix where visible."""
+            conn = self.connect_camera(cam, nrows, ncols, points, crng, lst, out=conn)
+            occ = self.occluded(conn.rays, t_range, lst, tr, mode, out=occ, mask=lamp_mask)
+            at = lst.long()
+            d = conn.rays[at, 3:6]
+            cos_y = (nrm * d).sum(1) / torch.sqrt((d * d).sum(1))
+            ok = (conn.pixel[at] >= 0) & (~occ.occluded[at]) & (cos_y > 0)
+            add = weight * (cos_y * conn.factor[at] * inv_npix)[:, None]
+            colors[at] = torch.where(ok[:, None] & torch.isfinite(add), add, torch.zeros_like(add))
+            pixels = torch.where(ok, conn.pixel[at], torch.full_like(conn.pixel[at], -1))
+            conn.pixel[at] = pixels
+            if splat is not None:
+                splat(conn.pixel, colors, lst)
+            return conn, occ, int(lst.numel())
+
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        points[:, 0:3], points[:, 3] = work[:, 0:3], work[:, 6]
+        conn, occ, k = connect(live, em.normal, emission[lamp] / pdf_area[:, None], None, None)
+        offered += k
+        res, ran = None, None
+        for step in range(int(max_depth)):
+            if live.numel() == 0:
+                break
+            res = self.bounce(work, rng, live, tr, mode, out=res)
+            ran = ran or res.mode
+            idx = live.long()
+            st = res.status[idx]
+            obj = res.object[idx].long().clamp(min=0)
+            at = idx[(st != BOUNCE_MISS) & diffuse[obj]]
+            if at.numel():
+                points[at, 0:3], points[at, 3] = res.p[at], work[at, 6]
+                conn, occ, k = connect(at.int(), res.normal[at], beta[at] * res.attenuation[at] / np.pi, conn, occ)
+                offered += k
+            live = self.bounce_select(res.status, live)
+            scat = live.long()
+            beta[scat] = beta[scat] * res.attenuation[scat]
+        if ran is None:
+            ran = "nothing to do"
+        if as_numpy:
+            return offered, rng.cpu().numpy().view(np.uint64), ran
+        return offered, rng, ran
+
     # ---- environment-light queries (tor_env_eval_device, tor_env_sample_device): the sky as an emitter ----
 
     def environment(self, rays, index=None, out=None, pdf=False):
@@ -1971,6 +2170,7 @@ def _light_states(rng):
 
 
 _ENV_STREAM = 0xd1342543de82ef95   # the odd constant of trace_environment's third stream (where _light_states has the golden ratio's)
+_CAMERA_STREAM = 0xf1357aea2e62a9c5   # the odd constant of trace_light's connection stream
 
 
 def _derived_states(rng, constant):
@@ -2106,6 +2306,29 @@ class EnvSample:
     def __init__(self, rays, pdf, texel, color, rng, note: str, keep=None):
         self.rays, self.pdf, self.texel, self.color, self.rng, self._keep = rays, pdf, texel, color, rng, keep
         self.mode = note
+
+
+class CameraConnection:
+    """Camera connections of Context.connect_camera, one per point (include/tor_camera.h): rays (n, 7) float64 {origin the point,
+    direction to the lens point (parameter 1.0), time}, pixel (n,) int32 row * ncols + col (-1: none), factor (n,) float64 the
+    measurement weight, lens (n, 2) float64 the lens point in the camera's (u, v), rng (n, 4) the states after the two draws --
+    torch tensors or numpy arrays, as the points were.  `mode`: "pinhole" | "thin lens"."""
+
+    def __init__(self, rays, pixel, factor, lens, rng, note: str, keep=None):
+        self.rays, self.pixel, self.factor, self.lens, self.rng, self._keep = rays, pixel, factor, lens, rng, keep
+        self.mode = _mode_of(note, "camera connect: ")
+
+
+class LightEmission:
+    """Path starts of Context.emit_lights, one per state (include/tor_camera.h): rays (n, 7) float64 {origin on the lamp, unit
+    direction, time}, normal (n, 3) float64, light (n,) int32 the picked light's OBJECT index (-1: never written), pdf (n, 2)
+    float64 whose columns are pdf_area (per unit area, the pick included) and pdf_dir (cos / pi per unit solid angle), rng
+    (n, 4) the states after the six draws -- torch tensors or numpy arrays, as the states were.  `mode`: "by weight"."""
+
+    def __init__(self, rays, normal, light, pdf, rng, note: str, keep=None):
+        self.rays, self.normal, self.light, self.pdf, self.rng, self._keep = rays, normal, light, pdf, rng, keep
+        self.pdf_area, self.pdf_dir = pdf[:, 0], pdf[:, 1]
+        self.mode = _mode_of(note, "light emit: ")
 
 
 class EnvEval:
@@ -2285,6 +2508,24 @@ class Film:
                 colors = colors[0]
             self.ctx.deposit(colors, chunk.repeat_interleave(k), self.sums, self.moments, self.counts, None, self.max_value,
                              self._rejected)
+        self.samples += k
+        return self
+
+    def add_light_pass(self, cam: Camera, k: int, emission, diffuse, chunk_paths: int = 1 << 20, **kw) -> "Film":
+        """A light-traced pass worth k samples per pixel: nrows * ncols * k light paths (Context.trace_light, kw its keywords),
+        in chunks of at most chunk_paths, path p of the pass on the state rng_seed2(samples, p) -- `samples` before the pass
+        numbers it --, every splat deposited (splat = self.deposit); then samples += k, so image() resolves sums / samples on a
+        film without counts.  A light tracer's splats are small and many: the clamp max_value applies to each splat."""
+        import torch
+        k = int(k)
+        if k < 1 or int(chunk_paths) < 1:
+            raise TorError(ERR_INVALID_ARGUMENT, "Film.add_light_pass: k and chunk_paths must be >= 1")
+        total = self.nrows * self.ncols * k
+        for a in range(0, total, int(chunk_paths)):
+            b = min(a + int(chunk_paths), total)
+            st = rng_seed2(np.full(b - a, self.samples, dtype=np.uint64), np.arange(a, b, dtype=np.uint64))
+            rng = torch.from_numpy(st.view(np.int64)).to(self.sums.device)
+            self.ctx.trace_light(cam, self.nrows, self.ncols, rng, emission, diffuse, splat=self.deposit, **kw)
         self.samples += k
         return self
 

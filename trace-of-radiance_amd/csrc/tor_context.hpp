@@ -125,6 +125,8 @@ struct HitQueryState {
   // direct-light sampling queries (tor_lights.hip)
   DeviceBuffer lights;              // the light table (tor_scene_lights): 16 float64 per light, packed when the table is set
   int64_t n_lights = 0;             // 0: no table (the state after every upload that replaces the scene)
+  double lights_total = 0.0;        // the table's total weight: the last light's running sum (tor_camera.hip: the emission's pick)
+  int64_t lights_last_pos = 0;      // the last light of weight > 0 (the pick's fallback)
   // environment-light queries (tor_env.hip): the map belongs to the context, not to the scene -- tor_scene_upload leaves it alone
   DeviceBuffer env;                 // the map's tables (tor_scene_environment), one allocation laid out by env_n (tor_env.hip EnvLayout)
   int64_t env_n = 0;                // texels per side, 0: no map

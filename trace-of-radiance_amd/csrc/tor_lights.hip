@@ -344,6 +344,8 @@ int tor_scene_lights(TorContext* ctx, int64_t n_lights, const int32_t* objects, 
   if (n_lights > 0 && !any) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": at least one weight must be > 0");
   // the records, from the scene's cold records (by original index) and the list's radii
   std::vector<double> recs((size_t)n_lights * tor::kLightWords, 0.0);
+  double run = 0.0;
+  int64_t last_pos = 0;
   if (n_lights > 0) {
     tor::HostLayout lay;
     std::string err;
@@ -357,7 +359,6 @@ int tor_scene_lights(TorContext* ctx, int64_t n_lights, const int32_t* objects, 
       if (orig >= 0 && orig < n) slot_of[(size_t)orig] = (int64_t)s;
     }
     const TorHittableVariant* objs = (const TorHittableVariant*)ctx->scene_bytes.data();
-    double run = 0.0;
     for (int64_t j = 0; j < n_lights; ++j) {
       const int64_t o = objects[j];
       if (slot_of[(size_t)o] < 0) return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the flat layout holds no record of object " + std::to_string(o));
@@ -376,6 +377,7 @@ int tor_scene_lights(TorContext* ctx, int64_t n_lights, const int32_t* objects, 
       r[11] = wt;
       run = run + wt;
       r[12] = run;
+      if (wt > 0.0) last_pos = j;
       std::memcpy(&r[13], &o, 8);
     }
   }
@@ -387,6 +389,8 @@ int tor_scene_lights(TorContext* ctx, int64_t n_lights, const int32_t* objects, 
     HIP_TRY(hipMemcpy(hq.lights.ptr, recs.data(), recs.size() * 8, hipMemcpyHostToDevice));
   }
   hq.n_lights = n_lights;
+  hq.lights_total = run;
+  hq.lights_last_pos = last_pos;
   return TOR_OK;
 }
 
