@@ -550,6 +550,24 @@ def test_accel_fuzz_short(tor):
     assert b"0 mismatches" in r.stdout
 
 
+def test_accel_fuzz_dense_oracle(tor):
+    """tools/fuzz_accel.py on a fixed count of scenes, so that what it covers does not depend on the box: six `dense` scenes (1-3
+    clusters of nearly coincident spheres, the worst case of the pooled lists and of every candidate queue), every one of them also
+    rendered by the CPU oracle in both stream modes -- 12 oracle checks -- and every accel mode, both knob contexts, the wave-per-pixel
+    kernel and the library's own choice of kernel against the brute force."""
+    import re
+    import subprocess
+    import sys as _sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([_sys.executable, os.path.join(root, "tools", "fuzz_accel.py"), "--scenes", "6", "2026", "dense", "--oracle", "1"],
+                       capture_output=True, timeout=300)
+    out = r.stdout.decode()
+    assert r.returncode == 0, out[-2000:] + r.stderr.decode()[-2000:]
+    assert "0 mismatches" in out and "heights: dense" in out
+    m = re.search(r"(\d+) scenes, (\d+) renders, (\d+) of them checked against the CPU oracle", out)
+    assert m and int(m.group(1)) == 6 and int(m.group(3)) == 12, out[-500:]
+
+
 def test_default_accel_from_environment(tor, monkeypatch):
     """tor_render() keeps the reference's signature (no options); TOR_DEFAULT_ACCEL opts it into the exact
     accelerations.  Same canvas, and explicit options are never overridden."""

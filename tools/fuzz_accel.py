@@ -4,6 +4,9 @@ discriminant for every object) and the brute force with stage one of the screen 
 table (TOR_PLANE=2: no gate) -- against the float64 brute-force canvas (default: the host's gate and the waves' votes decide per
 segment), bit for bit.
 Usage: python tools/fuzz_accel.py [seconds] [seed] [heights] [--oracle K] [--big K]
+       python tools/fuzz_accel.py --scenes N [seed] [heights] [--oracle K] [--big K]
+    --scenes N: exactly N scenes instead of a time budget (no `seconds` argument then): what a run covers does not depend on how fast
+             the box is that day
     heights: mixed (default: half of the scenes rest their spheres on 1-4 common heights; 15 % are dense, see below) | none (every sphere
              at its own height: no common-height segment anywhere -- the round-5 record) | dense (every scene: 1-3 clusters of nearly
              coincident spheres, the worst case of the pooled lists and of every candidate queue)
@@ -88,6 +91,14 @@ def main():
         k = argv.index("--oracle")
         oracle_every = int(argv[k + 1])
         del argv[k:k + 2]
+    scenes_wanted = 0
+    if "--scenes" in argv:   # a fixed count instead of a time budget: the positional arguments then start at the seed
+        k = argv.index("--scenes")
+        scenes_wanted = int(argv[k + 1])
+        del argv[k:k + 2]
+        if scenes_wanted < 1:
+            sys.exit("fuzz_accel.py: --scenes needs a count >= 1")
+        argv.insert(0, "inf")
     budget = float(argv[0]) if len(argv) > 0 else 120.0
     rng = np.random.default_rng(int(argv[1]) if len(argv) > 1 else 12345)
     global HEIGHTS
@@ -105,7 +116,7 @@ def main():
     os.environ.pop("TOR_PLANE", None)
     t0 = time.time()
     n_scenes = n_renders = bad = 0
-    while time.time() - t0 < budget:
+    while (n_scenes < scenes_wanted) if scenes_wanted else (time.time() - t0 < budget):
         recs, cam = random_scene(rng)
         scene = tor.Scene.from_records(recs)
         h, w = int(rng.choice([16, 24, 40])), int(rng.choice([26, 34, 64]))

@@ -323,7 +323,8 @@ __device__ __forceinline__ bool serve_chains(const KParams& p, bool dedicated) {
             const double cc = (ocx * ocx + ocy * ocy + ocz * ocz) - k15;  // spheres.nim:32
             const double disc = hb * hb - a * cc;                         // spheres.nim:33
             // both roots are <= 0 when half_b >= 0 and c >= 0: such an object can never be accepted (t_min = 0.001)
-            if (disc > 0.0 && (hb < 0.0 || cc < 0.0)) {
+            // (k15 >= 0: never a padding slot -- r^2 = -1 --, as in integrate_resolve_coop.inc)
+            if (disc > 0.0 && k15 >= 0.0 && (hb < 0.0 || cc < 0.0)) {
               const double root = __builtin_sqrt(disc);  // spheres.nim:35-48
               double sol = (-hb - root) / a;
               bool ok = (0.001 < sol) && (sol < __builtin_inf());

@@ -70,11 +70,15 @@ __device__ __forceinline__ void coop_pixel_body(const KParams& p) {
   // ---- stage the objects: cold record (16 float64) -> per trip of 64 slots, 10 arrays of 64 float64
   //      [trip][array][lane]: every ds_read of the object loop is `lane * 8 + trip base` + an immediate offset ----
   for (int k = threadIdx.x; k < n_pad; k += kThreads) {
-    double c[kCoopArrays] = {0, 0, 0, 0, 0, 0, 0, 1.0, -1.0, 0};  // padding: never hit (r^2 = -1 -> discriminant < 0)
+    // padding: never hit.  r^2 = -inf -> c = +inf and the discriminant is -inf or NaN for every ray.  (r^2 = -1 only gives
+    // discriminant <= -|d|^2 while |o|^2 + 1 != |o|^2: from 1e9 units away the 1 is rounded off, and the reference's own rounding
+    // then "hits" the padding sphere at the world origin -- a record behind the end of the list.)
+    double c[kCoopArrays] = {0, 0, 0, 0, 0, 0, 0, 1.0, -__builtin_inf(), 0};
     if (k < p.n_cold_slots) {
       const double* r = p.cold + (size_t)k * 16;
       c[0] = r[0]; c[1] = r[1]; c[2] = r[2]; c[3] = r[3]; c[4] = r[4]; c[5] = r[5];
-      c[6] = r[7]; c[7] = r[8]; c[8] = r[15]; c[9] = r[13];
+      c[6] = r[7]; c[7] = r[8]; c[9] = r[13];
+      c[8] = r[15] < 0.0 ? -__builtin_inf() : r[15];  // (the layout's own padding slots carry r^2 = -1: as above)
     }
     double* dst = soa + (size_t)(k >> 6) * (kCoopArrays * 64) + (k & 63);
 #pragma unroll

@@ -21,6 +21,14 @@
                 m = (m << 1) | ((t_in <= t_out) ? 1u : 0u);
               }
               rec += 8 * kBlock;
+              // a ray beyond the boxes' reach enters every box -- every REAL box: the padding entries of the super-box segment have
+              // no block boxes or records behind them (as integrate_loop_boxes32.inc does for a `wild` ray)
+              unsigned far = box_far;
+              if (seg_kind == 4) {
+                const int n_valid = p.n_super - i;  // bit (7 - j) <-> record i + j
+                far &= (n_valid >= kBlock) ? 0xffu : ((n_valid <= 0) ? 0u : ((0xff00u >> n_valid) & 0xffu));
+              }
+              m |= far;
               q[qn * 64] = ((seg_kind == 3) ? 0x80000000u : 0x40000000u) | ((unsigned)(seg_block0 + i / kBlock) << 8) | m;
               qn += (m != 0) ? 1u : 0u;
               if (ballot64(qn >= (unsigned)kQCap) != 0) { full = true; i += kBlock; break; }

@@ -45,7 +45,9 @@
               const double hb = ocx * sdx + ocy * sdy + ocz * sdz;
               const double cc = (ocx * ocx + ocy * ocy + ocz * ocz) - e15;
               const double disc = hb * hb - sa * cc;
-              if (disc > 0.0) {  // spheres.nim:35-48
+              // (e15 >= 0: never a padding slot -- centre 0, r^2 = -1 -- which a `wild` ray's survivors include and which the
+              // reference's rounding "hits" from origins where |o|^2 + 1 == |o|^2)
+              if (disc > 0.0 && e15 >= 0.0) {  // spheres.nim:35-48
                 const double root = __builtin_sqrt(disc);
                 sol = (-hb - root) / sa;
                 ok = (0.001 < sol) && (sol < __builtin_inf());

@@ -70,7 +70,10 @@
           const double hb = ocx * dx + ocy * dy + ocz * dz;
           const double cc = (ocx * ocx + ocy * ocy + ocz * ocz) - r2;
           const double disc = hb * hb - a * cc;
-          if (disc > 0.0) {
+          // (r2 >= 0: never a padding slot -- centre 0, r^2 = -1 --, which a `wild` ray of the float32 filter keeps and which the
+          // reference's rounding "hits" from origins where |o|^2 + 1 == |o|^2; the words of the screened brute force hold no padding
+          // bit for a ray that is not wild by its DIRECTION, and that one the test above rejects)
+          if (disc > 0.0 && (kWords || r2 >= 0.0)) {
             const double root = __builtin_sqrt(disc);
             double sol = (-hb - root) / a;
             bool ok = (0.001 < sol) && (sol < __builtin_inf());
@@ -133,7 +136,10 @@
                 auto test = [&](int j) {
                   double cx, cy, cz, f;
                   spatial_center(blk + hs * j, HS, cx, cy, cz, f);
-                  m8 = push_bit(m8, disc_filter(ox, oy, oz, dx, dy, dz, a, cx, cy, cz, blk[hs * j + 3]));
+                  // (& ~sign of r^2: a padding record -- centre 0, r^2 = -1 -- is never kept.  "discriminant <= -|d|^2" holds for it
+                  // only while |o|^2 + 1 != |o|^2; a ray beyond the boxes' reach, which enters every block, is far enough for the
+                  // reference's own rounding to "hit" the padding sphere at the world origin)
+                  m8 = push_bit(m8, disc_filter(ox, oy, oz, dx, dy, dz, a, cx, cy, cz, blk[hs * j + 3]) & ~hi32(blk[hs * j + 3]));
                 };
                 if constexpr (hs == 4) {  // 32-byte static records: all eight in flight
 #pragma unroll
@@ -184,6 +190,7 @@
                   mc = (mc << 1) | ((t_in <= t_out) ? 1u : 0u);
                 }
                 }
+                mc |= box_far;  // (beyond the boxes' reach: all 8 block boxes of a real super box exist, NaN padding included)
                 while (mc != 0) {
                   const int cbit = 31 - __builtin_clz(mc);
                   mc &= ~(1u << cbit);

@@ -660,6 +660,11 @@ static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nro
       q.spatial_base = (int)hacc.spatial_base;
       q.n_super = (int)(tor::accel_boxes_padded(hacc) / tor::kPad);
       q.two_level = hacc.two_level ? 1 : 0;
+      // (the float32 records carry their own guard, the `wild` ray of tor_filter32.hpp; only the float64 block loop reads these)
+      q.box_reach2 = -1.0;
+      q.box_amin = INFINITY;
+      for (int k = 0; k < 3; ++k) q.box_org[k] = 0.0;
+      if (!(v32 && hacc.sp32)) tor::block_reach(hacc, bnd_host, q.box_org, &q.box_reach2, &q.box_amin);
       q.shot = (const double*)ctx->d_accel[v32].hot.ptr;
       q.sgrp = (const double*)ctx->d_accel[v32].grp.ptr;
       q.shot_stride = hacc.hot_stride;

@@ -521,6 +521,15 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
       const bool boxes32 = F32 && BLOCKS && p.bnd32 != nullptr;
       if (boxes32) b32 = make_box_ray32(r32, p.sp_bmax, p.sp_hmin);
 
+      // TOR_ACCEL_BLOCKS on the float64 boxes: their inflation covers the reference's rounding only for origins within the reach
+      // (tor_scene.hpp block_reach: a camera 1e9 units away "hits" spheres its rays pass thousands of units from, and the brute force
+      // -- the reference -- says so); a ray outside it, or with a NaN origin, enters every box: 0xff
+      unsigned box_far = 0;
+      if (BLOCKS && !F32) {
+        const double ex = ox - p.box_org[0], ey = oy - p.box_org[1], ez = oz - p.box_org[2];
+        box_far = ((ex * ex + ey * ey + ez * ez <= p.box_reach2) && (a_strict >= p.box_amin)) ? 0u : 0xffu;
+      }
+
       // TOR_ACCEL_F32 block expansion: the spatial movers share one time group
       SegF32 sp32{};
       double f_sp = 0.0;  // moving_spheres.nim:42 for the spatial movers' (time0, time1)

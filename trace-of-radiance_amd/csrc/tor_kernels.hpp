@@ -64,6 +64,11 @@ struct KParams {
   int shot32_lds_floats;  // > 0: copy that many floats of shot32 into LDS per workgroup
   float sp_mc0max, sp_dcmax;
   int two_level;          // the culling layout has super boxes (selects the BLOCKS = 2 kernel variants)
+  // TOR_ACCEL_BLOCKS without the float32 records: where the float64 boxes' margin covers the reference's rounding (tor_scene.hpp
+  // block_reach) -- a ray whose origin is farther than sqrt(box_reach2) from box_org, or whose |d|^2 is below box_amin, enters every box
+  double box_org[3];
+  double box_reach2;      // < 0: no ray may be culled
+  double box_amin;
   const float* bnd32;     // float32 boxes (8 floats per record, same indices as bnd): {c.x h.x c.y h.y c.z h.z 0 0}, centre - org and half-extent
   float sp_bmax;          // max |box coordinate - org|
   float sp_hmin;          // smallest half-extent of a culling box (tor_filter32.hpp make_box_ray32)

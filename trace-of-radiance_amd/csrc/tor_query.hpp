@@ -266,37 +266,10 @@ int scene_args(const char* who, TorContext* ctx) {
   return TOR_OK;
 }
 
-// Where the boxes of `bnd` (compute_block_bounds for acc) hold for the reference's rounding (the head of tor_query.hip): a hit the reference
-// accepts on a spatial object of radius r from an origin at distance |oc| lies at most 6 eps (|oc|^2 + r^2) / r outside the sphere, and
-// every box is inflated by at least 1e-6.  With 16 eps (|oc|^2 + r_max^2) / r_min <= 1e-6 / 4, over 10x margin, the hit lies inside
-// its box.  |oc| <= |o - org| + half the diagonal of the boxes' union, so origins within `reach` of org qualify.  a_min keeps the
-// test's products clear of the subnormal range (an underflowed product's error is absolute, not relative): a * r_min^2 >= 2^-1000.
+// Where the boxes of `bnd` (compute_block_bounds for acc) hold for the reference's rounding (the head of tor_query.hip): tor_scene.hpp
+// block_reach, shared with the integrator's float64 block loop.
 void hit_reach(const tor::HostAccel& acc, const std::vector<double>& bnd, tor::HitQueryState& hq) {
-  hq.reach2 = -1.0;
-  hq.a_min = INFINITY;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (size_t b = 0; b < acc.n_boxes; ++b) {
-    const double* c = &bnd[8 * b];
-    if (c[0] != c[0]) continue;  // NaN: empty box
-    for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], c[k]); hi[k] = std::fmax(hi[k], c[3 + k]); }
-  }
-  double r_min = INFINITY, r_max = 0.0;
-  for (const tor::HostAccel::Obj& o : acc.spatial)
-    if (o.valid) { r_min = std::fmin(r_min, o.abs_r); r_max = std::fmax(r_max, o.abs_r); }
-  if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) || !(r_min > 0.0) || !std::isfinite(r_max)) return;
-  const double eps = 0x1p-53;
-  double half_diag = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    hq.org[k] = 0.5 * lo[k] + 0.5 * hi[k];
-    half_diag += (hi[k] - lo[k]) * (hi[k] - lo[k]);
-  }
-  half_diag = 0.5 * std::sqrt(half_diag) * (1.0 + 1e-9);
-  const double oc2 = 0.25e-6 * r_min / (16.0 * eps) - r_max * r_max;  // the largest |oc|^2 the margin covers
-  if (!(oc2 > 0.0) || !std::isfinite(oc2)) return;
-  const double reach = std::sqrt(oc2) * (1.0 - 1e-9) - half_diag;
-  if (!(reach > 0.0)) return;
-  hq.reach2 = reach * reach * (1.0 - 1e-9);  // (the kernel's |o - org|^2 carries a few roundings)
-  hq.a_min = 0x1p-1000 / (r_min * r_min);
+  tor::block_reach(acc, bnd, hq.org, &hq.reach2, &hq.a_min);
 }
 
 // The one-stream-per-context rule of a query launch on `stream` (tor_render.h): neither the context's last render launch nor its

@@ -894,6 +894,34 @@ bool compute_block_bounds(const HostAccel& acc, double t_lo, double t_hi, std::v
   return true;
 }
 
+void block_reach(const HostAccel& acc, const std::vector<double>& bnd, double org[3], double* reach2, double* a_min) {
+  *reach2 = -1.0;
+  *a_min = INFINITY;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t b = 0; b < acc.n_boxes; ++b) {
+    const double* c = &bnd[8 * b];
+    if (c[0] != c[0]) continue;  // NaN: empty box
+    for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], c[k]); hi[k] = std::fmax(hi[k], c[3 + k]); }
+  }
+  double r_min = INFINITY, r_max = 0.0;
+  for (const HostAccel::Obj& o : acc.spatial)
+    if (o.valid) { r_min = std::fmin(r_min, o.abs_r); r_max = std::fmax(r_max, o.abs_r); }
+  if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) || !(r_min > 0.0) || !std::isfinite(r_max)) return;
+  const double eps = 0x1p-53;
+  double half_diag = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    org[k] = 0.5 * lo[k] + 0.5 * hi[k];
+    half_diag += (hi[k] - lo[k]) * (hi[k] - lo[k]);
+  }
+  half_diag = 0.5 * std::sqrt(half_diag) * (1.0 + 1e-9);
+  const double oc2 = 0.25e-6 * r_min / (16.0 * eps) - r_max * r_max;  // the largest |oc|^2 the margin covers
+  if (!(oc2 > 0.0) || !std::isfinite(oc2)) return;
+  const double reach = std::sqrt(oc2) * (1.0 - 1e-9) - half_diag;
+  if (!(reach > 0.0)) return;
+  *reach2 = reach * reach * (1.0 - 1e-9);  // (the kernels' |o - org|^2 carries a few roundings)
+  *a_min = 0x1p-1000 / (r_min * r_min);
+}
+
 float block_bounds_f32(const std::vector<double>& bnd, const double origin[3], std::vector<float>& bnd32, float* hmin_out) {
   const size_t n = bnd.size() / 8;
   bnd32.assign(8 * n, 0.0f);

@@ -98,6 +98,16 @@ void build_accel(const TorHittableVariant* objs, int64_t n, HostAccel& out, cons
 bool compute_block_bounds(const HostAccel& acc, double t_lo, double t_hi, std::vector<double>& bnd);
 inline size_t accel_boxes_padded(const HostAccel& acc) { return (acc.n_boxes + 7) / 8 * 8; }  // records of the kind-3 segment
 
+// Where the boxes of `bnd` (compute_block_bounds for acc) hold for the reference's rounding: a hit the reference accepts on a spatial
+// object of radius r from an origin at distance |oc| lies at most 6 eps (|oc|^2 + r^2) / r outside the sphere, and every box is
+// inflated by at least 1e-6.  With 16 eps (|oc|^2 + r_max^2) / r_min <= 1e-6 / 4, over 10x margin, the hit lies inside its box.
+// |oc| <= |o - org| + half the diagonal of the boxes' union, so origins within sqrt(*reach2) of org qualify; *a_min keeps the test's
+// products clear of the subnormal range (an underflowed product's error is absolute, not relative): a * r_min^2 >= 2^-1000.
+// *reach2 = -1 and *a_min = +inf when no origin qualifies (no box, a radius of 0, radii too small for the margin).  A ray outside
+// either bound must not be culled by the float64 boxes: the ray queries walk it (tor_query.hpp), the integrator's float64 block
+// loop lets it enter every box (integrate_loop_boxes64.inc).
+void block_reach(const HostAccel& acc, const std::vector<double>& bnd, double org[3], double* reach2, double* a_min);
+
 // The same boxes for the float32 slab test (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32): one record of 8 float32 per box,
 // same record indices as `bnd`, {c.x, h.x, c.y, h.y, c.z, h.z, 0, 0} relative to `origin` -- centre and half-extent, the
 // half-extent rounded up so that the float32 box contains the float64 one (NaN records stay NaN).  Returns max |coordinate| over the
