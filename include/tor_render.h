@@ -1003,4 +1003,10 @@ TOR_API const char* tor_version(void);
  * operation in tor_camera.h. */
 #include "tor_camera.h"
 
+/* ---- BSDF queries: value and density of the reference's scatter ----------------------------------------------------------------------
+ * tor_bsdf_eval_device / _host: for an incoming direction, a hit record and an outgoing direction the solid-angle density
+ * Material.scatter gives that direction and the value albedo * density -- what next-event estimation and multiple importance
+ * sampling need at a Lambertian or a fuzzy Metal vertex -- defined operation by operation in tor_bsdf.h. */
+#include "tor_bsdf.h"
+
 #endif /* TOR_RENDER_H */

@@ -175,6 +175,9 @@ ENV_SYMBOLS = ["tor_scene_environment", "tor_env_sample_device", "tor_env_sample
 ENV_MAX_SIDE = 2048   # TOR_ENV_MAX_SIDE: the most texels per side of an environment map
 # the light-tracing queries (include/tor_camera.h), bound as the light entries are
 CAMERA_SYMBOLS = ["tor_camera_connect_device", "tor_camera_connect_host", "tor_light_emit_device", "tor_light_emit_host"]
+# the BSDF queries (include/tor_bsdf.h), bound as the light entries are
+BSDF_SYMBOLS = ["tor_bsdf_eval_device", "tor_bsdf_eval_host"]
+BSDF_NONE, BSDF_DENSITY, BSDF_DELTA = 0, 1, 2   # TOR_BSDF_*: the kind of a Context.bsdf answer
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -243,6 +246,7 @@ def lib():
     _bind_lights(L, skip_missing=bool(ab))
     _bind_env(L, skip_missing=bool(ab))
     _bind_camera(L, skip_missing=bool(ab))
+    _bind_bsdf(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -435,6 +439,26 @@ def _bind_camera(L, skip_missing=False) -> None:
         if skip_missing and not hasattr(L, name):
             continue
         getattr(L, name).argtypes = _CAMERA_SIGNATURES[name]
+
+
+def _bsdf_signatures() -> dict:
+    """The ctypes argtypes of the entries of include/tor_bsdf.h (every one returns int)."""
+    v, i64 = C.c_void_p, C.c_int64
+    return {
+        "tor_bsdf_eval_device": [v, i64, v, v, v, v, i64, v, v, v, v],
+        "tor_bsdf_eval_host": [v, i64, v, v, v, v, i64, v, v, v],
+    }
+
+
+_BSDF_SIGNATURES = _bsdf_signatures()
+
+
+def _bind_bsdf(L, skip_missing=False) -> None:
+    """_bind for the entries of BSDF_SYMBOLS."""
+    for name in BSDF_SYMBOLS:
+        if skip_missing and not hasattr(L, name):
+            continue
+        getattr(L, name).argtypes = _BSDF_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -1621,8 +1645,40 @@ class Context:
         self._light_keep = ops.keep(points, objects, index)   # (alive while the query may still run)
         return pdf
 
+    def bsdf(self, rays_in, hits, rays_out, index=None, out=None) -> "BsdfEval":
+        """Value and density of the reference's scatter (tor_bsdf_eval_device / tor_bsdf_eval_host): per listed item the
+        solid-angle density rec.material.scatter gives the direction of rays_out[i] for the incoming direction of rays_in[i] at
+        the record hits[i], and value = albedo * pdf (f_r cos) -- the definition, operation by operation in float64, is in
+        include/tor_bsdf.h.  Lambertian: cos / pi; Metal with fuzz != 0: the closed-form density of reflect + fuzz * ball, gated
+        by the scatter's own dot(out, n) > 0; both kind BSDF_DENSITY.  Dielectric and Metal with fuzz == 0: BSDF_DELTA, an
+        object outside the scene: BSDF_NONE, both with value and pdf 0.
+
+        rays_in (n, 7) float64: a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or anything numpy takes
+        (blocking); only the direction is read.  hits: a HitResult / BounceResult or its (n, 8) raw records, as for scatter();
+        normal and object are read as given.  rays_out (n, 7): any positive finite length -- the rays of sample_lights,
+        sample_environment and scatter / bounce go straight in.  index as for bounce().  Nothing is drawn.  Returns a BsdfEval;
+        out: one of an earlier call on as many items, written again (items that are not listed keep what it holds); otherwise a
+        new one (all 0)."""
+        if out is not None and not isinstance(out, BsdfEval):
+            raise ValueError("Context.bsdf: out must be a BsdfEval")
+        ops = _operands(self, "bsdf_eval", rays_in, "rays_in", 7)
+        n, rays_in = ops.n, ops.lead
+        raw = ops.rows(hits.raw if hasattr(hits, "raw") else hits, "hits", 8)
+        rays_out = ops.rows(rays_out, "rays_out", 7)
+        if raw is None or rays_out is None:
+            ops.bad("hits and rays_out", "(n, 8) records and (n, 7) rays, as rays_in is")
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            value, pdf, kind = ops.new(n, 3), ops.new(n), ops.new(n, dtype="int32")
+        else:
+            value, pdf, kind = out.value, out.pdf, out.kind
+            if not ops.fits(value, n, 3) or not ops.fits(pdf, n) or not ops.fits(kind, n, dtype="int32"):
+                ops.bad("out", "the result of a call on as many items, on tensors or arrays as rays_in is")
+        ops.call(ops.ptr(rays_in), ops.ptr(raw), ops.ptr(rays_out), p_list, n_list, ops.ptr(value), ops.ptr(pdf), ops.ptr(kind))
+        return BsdfEval(value, pdf, kind, ops.note(n_list), keep=ops.keep(rays_in, raw, rays_out, index))
+
     def trace_direct(self, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=False, lamp_mask=None, time_range=None,
-                     mode="auto", strategy="solid_angle"):
+                     mode="auto", strategy="solid_angle", glossy=None):
         """trace()'s loop with next-event estimation: after each bounce, the rays that hit a diffuse object sample one light of
         the table (sample_lights), ask occluded() whether the segment to the sampled surface point is free, and add
             att * albedo / pi * emission[light] * max(0, n . unit(dir)) / pdf
@@ -1635,6 +1691,13 @@ class Context:
         of the shadow segments; with one, their range is (0.001, 1.0) and the mask must leave the lamps' group out (set_groups);
         None: every group, and the range ends at 1 - 1e-9 instead, just short of the sampled surface.  rays, rng, sky,
         time_range, mode and the result (color, rng, mode) as for trace(); strategy as for sample_lights.
+
+        glossy: None (the code path above, unchanged in every bit), or (n_objects,) bool (glossy_objects(scene): Metal with
+        fuzz != 0).  With it the material is no longer restated here: a vertex on a diffuse OR a glossy object takes the light
+        sample -- also one whose scattered ray Metal absorbed -- and is no longer booked specular; one bsdf() call gives value
+        and density p_b of the sampled light direction, and the sample adds att * value * emission[light] / pdf where the
+        segment is free and p_b > 0; with mis=True a second bsdf() call gives the density of the direction the path left in,
+        the partner of light_pdf in the balance weights on both sides.
 
         The light draws come from a second state per path, derived from the path's entry state (splitmix64 finalisers over its
         words), not from the path state itself: the bounces see exactly the states trace() gives them.  So with an all-zero
@@ -1664,9 +1727,15 @@ class Context:
         t_range[:, 0], t_range[:, 1] = 0.001, (1.0 if lamp_mask is not None else 1.0 - 1e-9)
         live = torch.arange(n, dtype=torch.int32, device=dev)
         res, ls, occ, ran = None, None, None, None
+        nee_ok, win, ev, ev2 = None, None, None, None
+        if glossy is not None:   # the objects whose vertices take a light sample, and the incoming rays of the step (bsdf's rays_in)
+            glossy = torch.as_tensor(np.asarray(glossy.cpu() if _is_tensor(glossy) else glossy).astype(bool)).to(dev).reshape(-1)
+            nee_ok, win = diffuse | glossy, torch.empty_like(work)
         for step in range(int(max_depth)):
             if live.numel() == 0:
                 break
+            if nee_ok is not None:
+                win.copy_(work)
             res = self.bounce(work, rng, live, tr, mode, out=res)
             ran = ran or res.mode
             idx = live.long()
@@ -1687,11 +1756,34 @@ class Context:
                 share = p_bsdf[hit] / (p_bsdf[hit] + p_light)
                 wgt = torch.where(specular[hit], wgt, torch.where(torch.isfinite(share), share, torch.zeros_like(share)))
             color[hit] = color[hit] + att[hit] * emission[obj] * wgt[:, None]
+            if nee_ok is not None:   # (before the attenuation moves on: the light sample is weighted by att * value)
+                nee = hit[nee_ok[obj]]
+                att_nee = att[nee]
             live = self.bounce_select(res.status, live)
             scat = live.long()
             att[scat] = att[scat] * res.attenuation[scat]
-            # next-event estimation at the diffuse hits that go on
             sobj = res.object[scat].long()
+            if nee_ok is not None:
+                # next-event estimation at every diffuse or glossy vertex, through bsdf(): also where Metal absorbed the
+                # scattered ray -- the vertex reflects the lamp whatever became of the one direction the scatter drew
+                specular[scat] = ~nee_ok[sobj]
+                if nee.numel() == 0 or step == int(max_depth) - 1:
+                    continue
+                points[nee, 0:3], points[nee, 3] = res.p[nee], win[nee, 6]
+                lst = nee.int()
+                ls = self.sample_lights(points, lrng, lst, strategy, out=ls)
+                occ = self.occluded(ls.rays, t_range, lst, tr, mode, out=occ, mask=lamp_mask)
+                ev = self.bsdf(win, res, ls.rays, lst, out=ev)
+                p_b, pdf, lamp = ev.pdf[nee], ls.pdf[nee], ls.light[nee].long()
+                ok = (~occ.occluded[nee]) & (lamp >= 0) & (pdf > 0) & torch.isfinite(pdf) & (p_b > 0) & torch.isfinite(p_b)
+                share = pdf / (pdf + p_b) if mis else torch.ones_like(pdf)
+                add = att_nee * ev.value[nee] * emission[lamp.clamp(min=0)] * (share / pdf)[:, None]
+                color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
+                if mis:   # the density of the direction the path actually left in (0 for an absorbed ray: it found nothing)
+                    ev2 = self.bsdf(win, res, work, lst, out=ev2)
+                    p_bsdf[nee] = ev2.pdf[nee]
+                continue
+            # next-event estimation at the diffuse hits that go on
             isdiff = diffuse[sobj]
             specular[scat] = ~isdiff
             nee = scat[isdiff]
@@ -2219,6 +2311,13 @@ def diffuse_objects(scene) -> np.ndarray:
     return recs[:, 10].astype(np.int64) == MAT_LAMBERTIAN
 
 
+def glossy_objects(scene) -> np.ndarray:
+    """One bool per object of `scene` (a Scene or its (n, 16) records): is its material a Metal with fuzz != 0 -- a lobe with a
+    density (Context.bsdf answers BSDF_DENSITY), not a mirror: the `glossy` operand of Context.trace_direct."""
+    recs = scene.to_records() if hasattr(scene, "to_records") else np.asarray(scene, dtype=np.float64).reshape(-1, 16)
+    return (recs[:, 10].astype(np.int64) == MAT_METAL) & (recs[:, 14] != 0.0)
+
+
 def groups_by_material(scene) -> np.ndarray:
     """One group word per object of `scene` (a Scene or its (n, 16) records): 1 << material kind (MAT_LAMBERTIAN 0, MAT_METAL 1,
     MAT_DIELECTRIC 2), for Context.set_groups.  Shadow rays that skip glass: mask = ~(1 << MAT_DIELECTRIC) & 0xFFFFFFFF."""
@@ -2329,6 +2428,16 @@ class LightEmission:
         self.rays, self.normal, self.light, self.pdf, self.rng, self._keep = rays, normal, light, pdf, rng, keep
         self.pdf_area, self.pdf_dir = pdf[:, 0], pdf[:, 1]
         self.mode = _mode_of(note, "light emit: ")
+
+
+class BsdfEval:
+    """Answers of Context.bsdf, one per item (include/tor_bsdf.h): value (n, 3) float64 albedo * pdf (f_r cos), pdf (n,) the
+    solid-angle density Material.scatter gives the outgoing direction, kind (n,) int32 (BSDF_NONE / BSDF_DENSITY / BSDF_DELTA)
+    and note (tor_last_note)."""
+    __slots__ = ("value", "pdf", "kind", "note", "_keep")
+
+    def __init__(self, value, pdf, kind, note: str, keep=None):
+        self.value, self.pdf, self.kind, self.note, self._keep = value, pdf, kind, note, keep
 
 
 class EnvEval:
