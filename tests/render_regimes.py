@@ -221,7 +221,7 @@ def expected_variant(recs, layout, accel, seeding, screen=True):
       * both: the cooperative resolve on float32 block records, BLOCKS 1 single-level and 2 two-level -- but those records hold ONE
         time group and only objects the filter may take: with several groups among the blocks' movers, or one object out of the
         filter's range, the whole launch stays on the float64 layout and runs the float64 block expansion (0, 0, 1) whatever the
-        levels (tor_api.cpp configure(): v32 = 0; DESIGN: "The float32 block records need ONE time group")."""
+        levels (tor_api.cpp configure_layout(): v32 = 0; DESIGN: "The float32 block records need ONE time group")."""
     assert layout is not None
     ok32 = _f32_eligible(recs)
     slots = np.asarray(layout[0]).reshape(-1)

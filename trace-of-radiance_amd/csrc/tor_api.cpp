@@ -283,6 +283,15 @@ int ensure_layouts(TorContext* ctx, int accel) {
   return build_flat(v32);
 }
 
+int last_render_allows(TorContext* ctx, const void* stream, const char* who, const char* sentence) {
+  if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != stream) {
+    const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
+    if (q == hipErrorNotReady) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + sentence);
+    if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
+  }
+  return TOR_OK;
+}
+
 }  // namespace tor
 
 using tor::DeviceBuffer;
@@ -505,544 +514,631 @@ static hipError_t launch_integrate_recorded(TorContext* ctx, const tor::KParams&
   return e;
 }
 
-// tor_render_device, and -- acc != null -- one pass of tor_render_accumulate_device: samples [acc->first_sample, + spp) added to the
-// raw quantised sums in d_pixels (and, with acc->moments, their second moments), no clearing, no finalize
-static int render_device_impl(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
-                              int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
-                              double* d_pixels, void* hip_stream, const tor::AccumLaunch* acc) {
-  const bool listed = acc && acc->list;
-  const bool resume = acc && acc->rng;  // tor_render_resume_device: a pass on the pixel streams from / into caller-owned state
-  const bool rlist = resume && listed;  // tor_render_resume_list_device: ... over the listed pixels only
-  const std::string who = rlist ? "tor_render_resume_list_device" : resume ? "tor_render_resume_device" : (listed ? "tor_render_accumulate_list_device" : (acc ? "tor_render_accumulate_device" : "tor_render_device"));
-  if (!ctx || !cam || !d_pixels) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": NULL argument");
-  if (!ctx->scene_ready) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": no scene uploaded");
+#define TOR_TRY(expr) do { const int rc__ = (expr); if (rc__ != TOR_OK) return rc__; } while (0)
+
+// ---- one render launch, phase by phase ("The host side of a launch") ---------------------------------------------
+// One call of a render entry.  The entry fills the first ten members; decode_call derives the rest down to n_tiles,
+// claim_ring_slot the ring slot's part.
+struct RenderCall {
+  const char* who;  // the entry's name, for its refusals
+  const TorCamera* cam;
+  int32_t nrows, ncols, spp;
+  float gamma_correction;
+  int64_t max_depth;
+  double* d_pixels;
+  hipStream_t stream;
+  // not null: one pass of tor_render_accumulate_device -- samples [acc->first_sample, + spp) added to the raw quantised sums in
+  // d_pixels (and, with acc->moments, their second moments), no clearing, no finalize
+  const tor::AccumLaunch* acc;
+  bool listed;  // ... over a pixel list
+  bool resume;  // tor_render_resume_device: a pass on the pixel streams from / into caller-owned state
+  bool rlist;   // tor_render_resume_list_device: ... over the listed pixels only
+  TorOptions o;  // validated, defaults applied
+  int kseed;     // the kernel variant's SEEDING
+  int32_t local_rows;
+  long long npix, n_values;
+  long long work_pix;  // pixels this launch traces
+  long long n_tiles;
+  int slot;
+  unsigned long long* slot_counters;
+};
+
+static int refuse(const char* who, const std::string& what) { return fail(TOR_ERR_INVALID_ARGUMENT, who + what); }
+
+// Every refusal of a render entry that does not depend on the context's launches in flight, then what the phases below derive from
+// the arguments.
+static int decode_call(TorContext* ctx, const TorOptions* opt, RenderCall& c) {
+  const char* who = c.who;
+  const tor::AccumLaunch* acc = c.acc;
+  c.listed = acc && acc->list;
+  c.resume = acc && acc->rng;
+  c.rlist = c.resume && c.listed;
+  if (!ctx || !c.cam || !c.d_pixels) return refuse(who, ": NULL argument");
+  if (!ctx->scene_ready) return refuse(who, ": no scene uploaded");
   // The reference divides by (ncols-1) and (nrows-1) (render.nim:64-65) and by spp
   // (canvas.nim:49); degenerate sizes are rejected instead of producing inf/NaN canvases.
-  if (nrows < 2 || ncols < 2 || spp < 1)
-    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": need nrows >= 2, ncols >= 2, samples_per_pixel >= 1");
-  if (max_depth > 0x7fffffff) max_depth = 0x7fffffff;
-  TorOptions o;
-  if (!valid_options(opt, o, false)) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": bad TorOptions: " + tor::options_why());
-  if (o.device_count > 1) return fail(TOR_ERR_INVALID_ARGUMENT, who + ": one context renders on one device (device lists: tor_render_opt)");
-  if (resume && o.seeding != TOR_SEED_PIXEL)
-    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_PIXEL -- it continues the reference's per-pixel streams (render.nim:59-67) from per-pixel "
-                                                "generator states; passes of TOR_SEED_SAMPLE streams are tor_render_accumulate_device's");
-  if (acc && !resume && o.seeding != TOR_SEED_SAMPLE)
-    return fail(TOR_ERR_INVALID_ARGUMENT, who + ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
-                                                "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
+  if (c.nrows < 2 || c.ncols < 2 || c.spp < 1) return refuse(who, ": need nrows >= 2, ncols >= 2, samples_per_pixel >= 1");
+  if (c.max_depth > 0x7fffffff) c.max_depth = 0x7fffffff;
+  TorOptions& o = c.o;
+  if (!valid_options(opt, o, false)) return refuse(who, ": bad TorOptions: " + tor::options_why());
+  if (o.device_count > 1) return refuse(who, ": one context renders on one device (device lists: tor_render_opt)");
+  if (c.resume && o.seeding != TOR_SEED_PIXEL)
+    return refuse(who, ": needs TOR_SEED_PIXEL -- it continues the reference's per-pixel streams (render.nim:59-67) from per-pixel "
+                       "generator states; passes of TOR_SEED_SAMPLE streams are tor_render_accumulate_device's");
+  if (acc && !c.resume && o.seeding != TOR_SEED_SAMPLE)
+    return refuse(who, ": needs TOR_SEED_SAMPLE -- a TOR_SEED_PIXEL pixel is one sequential chain of "
+                       "samples on one generator (render.nim:59-67); resuming it would need per-pixel RNG state");
   // the kernel variant: SEED_SAMPLE with second moments (3) only for progressive launches that asked for them, over a pixel list (4)
   // for adaptive ones; resume passes on the pixel streams run 5, or 6 with second moments, or 7 over a pixel list (always with moments)
-  const int kseed = rlist ? 7 : resume ? (acc->moments ? 6 : 5) : (listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding));
-  hipStream_t stream = (hipStream_t)hip_stream;
+  c.kseed = c.rlist ? 7 : c.resume ? (acc->moments ? 6 : 5) : (c.listed ? 4 : ((acc && acc->moments) ? 3 : o.seeding));
   HIP_TRY(hipSetDevice(ctx->device));
 
-  const int32_t local_rows = tor_shard_rows(nrows, o.row_tile, o.shard_index, o.shard_count, nullptr);
-  const long long npix = (long long)local_rows * ncols;
-  const long long n_values = npix * 3;
-  const long long work_pix = listed ? (long long)acc->n_list : npix;  // pixels this launch traces
+  c.local_rows = tor_shard_rows(c.nrows, o.row_tile, o.shard_index, o.shard_count, nullptr);
+  c.npix = (long long)c.local_rows * c.ncols;
+  c.n_values = c.npix * 3;
+  c.work_pix = c.listed ? (long long)acc->n_list : c.npix;
+  c.n_tiles = (c.npix + tor::kTilePixelsHost - 1) / tor::kTilePixelsHost;
   ctx->timing_valid = false;
   ctx->last_samples = 0;
   ctx->last_migrate = false;
   ctx->last_split = false;
-  if (work_pix == 0) return TOR_OK;
+  return TOR_OK;
+}
 
-  // a ring slot (events, camera, bounds, counters, tile schedule) is reused every kRing launches: its previous
-  // launch must be done
-  const int slot = (int)(ctx->launches % TorContext::kRing);
-  if (ctx->launches >= TorContext::kRing) HIP_TRY(hipEventSynchronize(ctx->ev_stop[slot]));
+// A ring slot (events, camera, bounds, counters, tile schedule) is reused every kRing launches: its previous launch must be
+// done.  Then the stream rule, and the slot's counters start at zero.
+static int claim_ring_slot(TorContext* ctx, RenderCall& c) {
+  c.slot = (int)(ctx->launches % TorContext::kRing);
+  if (ctx->launches >= TorContext::kRing) HIP_TRY(hipEventSynchronize(ctx->ev_stop[c.slot]));
   // One stream per context while launches are in flight (tor_render.h): the per-launch state (work counters, tile
   // schedule, probe buffer, hand-off queue) is ordered by the stream.  A launch on ANOTHER stream is accepted only once
   // the previous launch of this context has finished.
-  if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != hip_stream) {
-    const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
-    if (q == hipErrorNotReady)
-      return fail(TOR_ERR_INVALID_ARGUMENT, who + ": the previous launch of this context is still running on a different stream -- "
-                                                  "launches of one context that may overlap must use ONE stream (or use one context per stream)");
-    if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
-  }
-  ctx->last_stream = hip_stream;
+  TOR_TRY(tor::last_render_allows(ctx, c.stream, c.who, ": the previous launch of this context is still running on a different stream -- "
+                                                        "launches of one context that may overlap must use ONE stream (or use one context per stream)"));
+  ctx->last_stream = c.stream;
   ctx->last_stream_valid = true;
-  unsigned long long* const slot_counters = (unsigned long long*)ctx->counters.ptr + (size_t)slot * TorContext::kSlotWords;
-  HIP_TRY(hipMemsetAsync(slot_counters, 0, TorContext::kSlotWords * sizeof(unsigned long long), stream));
-  // (a resume pass takes no shortcut: with max_depth <= 0 the reference still draws every sample's pixel jitter, lens and time
-  // samples -- render.nim:63-65, cameras.nim:47-57 -- and the states must advance exactly so; its kernels end such a sample black)
-  if (!resume && (max_depth <= 0 || ctx->n_objects < 0)) {
-    if (acc) return TOR_OK;  // every sample is black: the pass adds zeros, the sums (and moments) stay as they are
-    // render.nim:25: the bounce loop does not run -> every sample is black -> pow(0, g) = 0
-    HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
-    return TOR_OK;
-  }
-  if (o.seeding == TOR_SEED_SAMPLE && !acc) HIP_TRY(hipMemsetAsync(d_pixels, 0, (size_t)n_values * 8, stream));
+  c.slot_counters = (unsigned long long*)ctx->counters.ptr + (size_t)c.slot * TorContext::kSlotWords;
+  HIP_TRY(hipMemsetAsync(c.slot_counters, 0, TorContext::kSlotWords * sizeof(unsigned long long), c.stream));
+  return TOR_OK;
+}
 
-  tor::KParams p{};
-  // Small SEED_PIXEL frames: one wave per pixel (coop_pixel_kernel) -- the lane-per-pixel kernel would be bound by
-  // the latency of the longest pixel chain.  Same canvas bit for bit; needs only the float64 flat layout.
-  // Split fraction (measured: tools/split_sweep.py, with the tiles ordered by their longest chain): the wave-per-pixel
-  // kernel saturates at ~285 Msamples/s, the lane kernel (with both exact accelerations) is bound by its longest chains;
-  // the best share of the probed work for the wave kernel is ~20 000 / pixels, capped at 0.2 (C1 at 100 spp: 16-17 ms for
-  // anything in 0.15-0.35, at 1000 spp 130 ms at 0.15 against 163 ms at 0.45) and floored at 0.02 (only the glass-sphere
-  // tiles); from ~1.2 M pixels on the lane kernel keeps everything.
-  float split_frac = ctx->split_frac;
-  if (split_frac < 0.0f) {
-    split_frac = 0.0f;
-    if (o.accel == (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32) && npix <= 1200000) {
-      split_frac = 20000.0f / (float)npix;
-      if (split_frac > 0.2f) split_frac = 0.2f;
-      if (split_frac < 0.02f) split_frac = 0.02f;
+// Split fraction (measured: tools/split_sweep.py, with the tiles ordered by their longest chain): the wave-per-pixel
+// kernel saturates at ~285 Msamples/s, the lane kernel (with both exact accelerations) is bound by its longest chains;
+// the best share of the probed work for the wave kernel is ~20 000 / pixels, capped at 0.2 (C1 at 100 spp: 16-17 ms for
+// anything in 0.15-0.35, at 1000 spp 130 ms at 0.15 against 163 ms at 0.45) and floored at 0.02 (only the glass-sphere
+// tiles); from ~1.2 M pixels on the lane kernel keeps everything.
+static float split_fraction(const TorContext* ctx, const RenderCall& c) {
+  if (ctx->split_frac >= 0.0f) return ctx->split_frac;
+  if (c.o.accel != (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32) || c.npix > 1200000) return 0.0f;
+  const float f = 20000.0f / (float)c.npix;
+  return f > 0.2f ? 0.2f : (f < 0.02f ? 0.02f : f);
+}
+
+// the scene part of q that names the device arrays of one layout
+static void use_layout(tor::KParams& q, const tor::DeviceLayout& L, const TorContext* ctx, const RenderCall& c, int accel) {
+  q.stat = L.stat;
+  q.mov = L.mov;
+  q.movy = L.movy;
+  q.segs = L.segs;
+  q.cold = L.cold;
+  q.hot32 = L.has_f32 ? L.hot32 : nullptr;
+  q.xhdr = L.xhdr;
+  q.xrec = L.xrec;
+  q.xpl = ctx->plane_screen != 0 ? L.xpl : nullptr;
+  q.xpl32 = ctx->plane_screen != 0 ? L.xpl32 : nullptr;
+  q.plane_gate2 = ctx->plane_screen == 2 ? 0.0 : 4.0 * tor::kPlaneGate * tor::kPlaneGate;
+  // stage two of the plane-screened segments reads its records per lane: from LDS when the table fits beside the per-wave
+  // queues -- and, with sample streams, the camera-ray reservoirs -- at this launch's workgroups per CU (random_scene: 15.9 KB + 18.7 KB
+  // + 18.8 KB of 53.3 KB) and inside the 64 KB a launch may
+  // ask for without an opt-in, else through the vector cache.  Only the ARITH 2 variants stage it (brute-force layouts
+  // behind the screen: tor_kernels.hip dynamic_lds), so the room is only counted there.
+  q.xrec_lds_doubles = 0;
+  if (q.xpl != nullptr && ctx->screen && accel == 0) {
+    const size_t wgs = (size_t)std::max(1, ctx->max_blocks_per_cu[c.o.seeding][0]);
+    const size_t need = (size_t)L.n_xrec * 8 + (size_t)tor::integrate_fixed_lds_bytes(0, 0, c.kseed);
+    if (need <= (size_t)(160 * 1024) / wgs - 1024 && need <= (size_t)64 * 1024) q.xrec_lds_doubles = L.n_xrec;
+  }
+  q.n_segs = L.n_segs;
+}
+
+static bool fits_lds(size_t bytes, int wgs, size_t hard_cap, size_t fixed) {
+  return bytes <= hard_cap && bytes + fixed <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
+}
+
+// LDS staging of the block records next to the per-wave queues (10 KB per workgroup in these variants, 160 KB per CU): the
+// float32 pair records (TOR_ACCEL_F32; survivors are re-tested from the cold records -- staging the float64
+// records as well measured +2 % at best) or the float64 compact records.  It must fit at this mode's
+// workgroups/CU, else global loads (through L2).
+// `full` is that count; returns the workgroups per CU the launch may run with what was staged (0: nothing staged).
+static int stage_records_in_lds(tor::KParams& q, const tor::HostAccel& hacc, size_t bnd32_stage_floats, int full, int kseed) {
+  const size_t hot_bytes = q.shot32 ? hacc.hot32.size() * 4 : hacc.hot.size() * 8;
+  const char* st = tor::knob("TOR_STAGE_LDS");
+  const size_t hard_cap = st ? (size_t)std::atoll(st) : (size_t)1 << 30;
+  const size_t fixed = (size_t)tor::integrate_fixed_lds_bytes(1, q.shot32 != nullptr ? 1 : 0, kseed);
+  // Workgroups per CU come first: on the 1601-object animation frames 3 workgroups/CU reading the records through L2
+  // render 2339 Msamples/s, 2 workgroups/CU with the records in LDS 1914.  So the launch keeps its full workgroup count
+  // and stages what fits beside it: the block boxes of a two-level scene first (6.6 KB there; every lane reads 8 of
+  // them per super box it expands), then the block records if there is still room; only a launch whose mode runs at 2
+  // workgroups/CU anyway gets the bigger LDS share.
+  const bool stage_boxes = q.shot32 && bnd32_stage_floats > 0 && fits_lds(bnd32_stage_floats * 4, full, hard_cap, fixed);
+  const size_t box_bytes = stage_boxes ? bnd32_stage_floats * 4 : 0;
+  bool stage_hot = fits_lds(hot_bytes + box_bytes, full, hard_cap, fixed);
+  int wg = (stage_hot || stage_boxes) ? full : 0;
+  if (!q.shot32 && !stage_hot && full > 2 && fits_lds(hot_bytes, full - 1, hard_cap, fixed)) {
+    // (the float64 compact records of TOR_ACCEL_BLOCKS alone are read by every lane for every block it enters: there
+    // one workgroup fewer with the records in LDS wins, 1212 against 1140 Msamples/s on the same frames)
+    stage_hot = true;
+    wg = full - 1;
+  }
+  q.shot_lds_doubles = (stage_hot && !q.shot32) ? (int)hacc.hot.size() : 0;
+  q.shot32_lds_floats = (stage_hot && q.shot32) ? (int)hacc.hot32.size() : 0;
+  q.bnd32_lds_floats = stage_boxes ? (int)bnd32_stage_floats : 0;
+  return wg;
+}
+
+// what configure_layout chose beside the scene part of the KParams
+struct LayoutChoice {
+  bool use_accel = false;  // the launch walks the culling layout
+  int stage_wg = 0;        // > 0: compact records staged in LDS, at most this many workgroups per CU
+  const tor::HostAccel* hacc = nullptr;
+};
+
+// Layout configuration of a launch: which device arrays the kernel walks for `accel`, the per-call block bounds (into bnd_host /
+// bnd32_host) and the LDS staging decision.  Two launches of one call may use it: the frame's kernel with the caller's
+// accel bits and -- SEED_PIXEL -- the cost probe, which always runs with both exact accelerations when the scene has
+// them (it only COUNTS closest-hit queries per pixel; the count does not depend on how the hit is found).
+static int configure_layout(TorContext* ctx, const RenderCall& c, int accel, tor::KParams& q, std::vector<double>& bnd_host,
+                            std::vector<float>& bnd32_host, LayoutChoice& out) {
+  TOR_TRY(tor::ensure_layouts(ctx, accel));
+  // TOR_ACCEL_F32 layout variant; with TOR_ACCEL_BLOCKS it needs float32 block records (HostAccel::sp32),
+  // otherwise the whole launch stays on the float64 layout
+  int v32 = (accel & TOR_ACCEL_F32) ? 1 : 0;
+  if (v32 && (accel & TOR_ACCEL_BLOCKS) && ctx->accel[1].available && !ctx->accel[1].sp32) v32 = 0;
+  const bool blocks_avail = (accel & TOR_ACCEL_BLOCKS) && ctx->accel_built[v32] && ctx->accel[v32].available;
+  if (!blocks_avail) use_layout(q, ctx->flat[v32], ctx, c, accel);
+  for (int k = 0; k < 3; ++k) q.org[k] = ctx->f32.origin[k];
+  q.bnd = nullptr;
+  q.spatial_base = 0;
+  q.shot = nullptr;
+  q.sgrp = nullptr;
+  q.shot_lds_doubles = 0;
+  q.shot_stride = 8;
+  const tor::HostAccel& hacc = ctx->accel[v32];
+  out = LayoutChoice{false, 0, &hacc};
+  if (blocks_avail) {
+    // rays carry the camera's shutter times, or 0 after a metal / dielectric bounce (rays.nim:19)
+    const double t_lo = std::fmin(0.0, std::fmin(c.cam->shutter_open, c.cam->shutter_close));
+    const double t_hi = std::fmax(0.0, std::fmax(c.cam->shutter_open, c.cam->shutter_close));
+    out.use_accel = tor::compute_block_bounds(hacc, t_lo, t_hi, bnd_host);
+    if (!out.use_accel) {  // non-finite ray-time range: brute force over the flat layout
+      TOR_TRY(tor::ensure_layouts(ctx, accel & ~TOR_ACCEL_BLOCKS));
+      use_layout(q, ctx->flat[v32], ctx, c, accel);
     }
   }
-  // Layout configuration of a launch: which device arrays the kernel walks for `accel`, the per-call block bounds and the
-  // LDS staging decision.  A lambda because two launches of one call may use it: the frame's kernel with the caller's
-  // accel bits and -- SEED_PIXEL -- the cost probe, which always runs with both exact accelerations when the scene has
-  // them (it only COUNTS closest-hit queries per pixel; the count does not depend on how the hit is found).
-  auto configure = [&](tor::KParams& q, int accel, std::vector<double>& bnd_host, std::vector<float>& bnd32_host, bool& use_accel, int& stage_wg,
-                       const tor::HostAccel*& hacc_out) -> int {
-    {
-      const int rc = tor::ensure_layouts(ctx, accel);
-      if (rc != TOR_OK) return rc;
-    }
-    // TOR_ACCEL_F32 layout variant; with TOR_ACCEL_BLOCKS it needs float32 block records (HostAccel::sp32),
-    // otherwise the whole launch stays on the float64 layout
-    int v32 = (accel & TOR_ACCEL_F32) ? 1 : 0;
-    if (v32 && (accel & TOR_ACCEL_BLOCKS) && ctx->accel[1].available && !ctx->accel[1].sp32) v32 = 0;
-    auto use_layout = [&](const tor::DeviceLayout& L) {
-      q.stat = L.stat;
-      q.mov = L.mov;
-      q.movy = L.movy;
-      q.segs = L.segs;
-      q.cold = L.cold;
-      q.hot32 = L.has_f32 ? L.hot32 : nullptr;
-      q.xhdr = L.xhdr;
-      q.xrec = L.xrec;
-      q.xpl = ctx->plane_screen != 0 ? L.xpl : nullptr;
-      q.xpl32 = ctx->plane_screen != 0 ? L.xpl32 : nullptr;
-      q.plane_gate2 = ctx->plane_screen == 2 ? 0.0 : 4.0 * tor::kPlaneGate * tor::kPlaneGate;
-      // stage two of the plane-screened segments reads its records per lane: from LDS when the table fits beside the per-wave
-      // queues -- and, with sample streams, the camera-ray reservoirs -- at this launch's workgroups per CU (random_scene: 15.9 KB + 18.7 KB
-      // + 18.8 KB of 53.3 KB) and inside the 64 KB a launch may
-      // ask for without an opt-in, else through the vector cache.  Only the ARITH 2 variants stage it (brute-force layouts
-      // behind the screen: tor_kernels.hip dynamic_lds), so the room is only counted there.
-      q.xrec_lds_doubles = 0;
-      if (q.xpl != nullptr && ctx->screen && accel == 0) {
-        const size_t wgs = (size_t)std::max(1, ctx->max_blocks_per_cu[o.seeding][0]);
-        const size_t need = (size_t)L.n_xrec * 8 + (size_t)tor::integrate_fixed_lds_bytes(0, 0, kseed);
-        if (need <= (size_t)(160 * 1024) / wgs - 1024 && need <= (size_t)64 * 1024) q.xrec_lds_doubles = L.n_xrec;
-      }
-      q.n_segs = L.n_segs;
-    };
-    const bool blocks_avail = (accel & TOR_ACCEL_BLOCKS) && ctx->accel_built[v32] && ctx->accel[v32].available;
-    if (!blocks_avail) use_layout(ctx->flat[v32]);
-    for (int k = 0; k < 3; ++k) q.org[k] = ctx->f32.origin[k];
-    q.bnd = nullptr;
-    q.spatial_base = 0;
-    q.shot = nullptr;
-    q.sgrp = nullptr;
-    q.shot_lds_doubles = 0;
-    q.shot_stride = 8;
-    use_accel = false;
-    stage_wg = 0;  // > 0: compact records staged in LDS, at most this many workgroups per CU
-    const tor::HostAccel& hacc = ctx->accel[v32];
-    hacc_out = &hacc;
-    if (blocks_avail) {
-      // rays carry the camera's shutter times, or 0 after a metal / dielectric bounce (rays.nim:19)
-      const double t_lo = std::fmin(0.0, std::fmin(cam->shutter_open, cam->shutter_close));
-      const double t_hi = std::fmax(0.0, std::fmax(cam->shutter_open, cam->shutter_close));
-      use_accel = tor::compute_block_bounds(hacc, t_lo, t_hi, bnd_host);
-      if (!use_accel) {  // non-finite ray-time range: brute force over the flat layout
-        const int rc = tor::ensure_layouts(ctx, accel & ~TOR_ACCEL_BLOCKS);
-        if (rc != TOR_OK) return rc;
-        use_layout(ctx->flat[v32]);
-      }
-    }
-    if (use_accel) {
-      use_layout(ctx->d_accel[v32].always);
-      q.bnd = (const double*)((char*)ctx->bnd_ring.ptr + (size_t)slot * ctx->bnd_slot_bytes);  // filled below (async copy)
-      q.spatial_base = (int)hacc.spatial_base;
-      q.n_super = (int)(tor::accel_boxes_padded(hacc) / tor::kPad);
-      q.two_level = hacc.two_level ? 1 : 0;
-      // (the float32 records carry their own guard, the `wild` ray of tor_filter32.hpp; only the float64 block loop reads these)
-      q.box_reach2 = -1.0;
-      q.box_amin = INFINITY;
-      for (int k = 0; k < 3; ++k) q.box_org[k] = 0.0;
-      if (!(v32 && hacc.sp32)) tor::block_reach(hacc, bnd_host, q.box_org, &q.box_reach2, &q.box_amin);
-      q.shot = (const double*)ctx->d_accel[v32].hot.ptr;
-      q.sgrp = (const double*)ctx->d_accel[v32].grp.ptr;
-      q.shot_stride = hacc.hot_stride;
-      // LDS staging of the compact records next to the per-wave queues (18 KB per workgroup, 160 KB per
-      // CU): see the staging decision below.
-      q.shot32 = nullptr;
-      if (v32 && hacc.sp32) {
-        q.shot32 = (const float*)ctx->d_accel[v32].hot32.ptr;
-        q.shot32_stride = hacc.hot32_stride;
-        q.shot32_block_stride = hacc.hot32_block_stride;
-        q.sp_mc0max = hacc.sp_mc0max; q.sp_dcmax = hacc.sp_dcmax;
-        q.sp_t0 = hacc.sp_t0; q.sp_dt = hacc.sp_dt;
-      }
-      // LDS staging of the block records next to the per-wave queues (10 KB per workgroup in these variants, 160 KB per CU): the
-      // float32 pair records (TOR_ACCEL_F32; survivors are re-tested from the cold records -- staging the float64
-      // records as well measured +2 % at best) or the float64 compact records.  It must fit at this mode's
-      // workgroups/CU, else global loads (through L2).
-      size_t hot_bytes = q.shot32 ? hacc.hot32.size() * 4 : hacc.hot.size() * 8;
-      size_t bnd32_stage_floats = 0;
-      if (q.shot32) {
-        // float32 boxes for the slab tests; on two-level scenes the lanes read the block boxes themselves: stage them
-        q.sp_bmax = tor::block_bounds_f32(bnd_host, ctx->f32.origin, bnd32_host, &q.sp_hmin);
-        q.bnd32 = (const float*)((const char*)q.bnd + bnd_host.size() * 8);
-        if (hacc.two_level) bnd32_stage_floats = 8 * tor::accel_boxes_padded(hacc);
-      }
-      const char* st = tor::knob("TOR_STAGE_LDS");
-      const size_t hard_cap = st ? (size_t)std::atoll(st) : (size_t)1 << 30;
-      int& wg = stage_wg;
-      wg = 0;
-      auto fits = [&](size_t bytes, int wgs) {
-        return bytes <= hard_cap && bytes + (size_t)tor::integrate_fixed_lds_bytes(1, q.shot32 != nullptr ? 1 : 0, kseed) <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
-      };
-      // Workgroups per CU come first: on the 1601-object animation frames 3 workgroups/CU reading the records through L2
-      // render 2339 Msamples/s, 2 workgroups/CU with the records in LDS 1914.  So the launch keeps its full workgroup count
-      // and stages what fits beside it: the block boxes of a two-level scene first (6.6 KB there; every lane reads 8 of
-      // them per super box it expands), then the block records if there is still room; only a launch whose mode runs at 2
-      // workgroups/CU anyway gets the bigger LDS share.
-      const int full = ctx->max_blocks_per_cu[o.seeding][accel != 0];
-      const bool stage_boxes = q.shot32 && bnd32_stage_floats > 0 && fits(bnd32_stage_floats * 4, full);
-      const size_t box_bytes = stage_boxes ? bnd32_stage_floats * 4 : 0;
-      bool stage_hot = fits(hot_bytes + box_bytes, full);
-      wg = (stage_hot || stage_boxes) ? full : 0;
-      if (!q.shot32 && !stage_hot && full > 2 && fits(hot_bytes, full - 1)) {
-        // (the float64 compact records of TOR_ACCEL_BLOCKS alone are read by every lane for every block it enters: there
-        // one workgroup fewer with the records in LDS wins, 1212 against 1140 Msamples/s on the same frames)
-        stage_hot = true;
-        wg = full - 1;
-      }
-      q.shot_lds_doubles = (stage_hot && !q.shot32) ? (int)hacc.hot.size() : 0;
-      q.shot32_lds_floats = (stage_hot && q.shot32) ? (int)hacc.hot32.size() : 0;
-      q.bnd32_lds_floats = stage_boxes ? (int)bnd32_stage_floats : 0;
-    }
-    return TOR_OK;
-  };
-  // Launch configuration, shared by the hand-off decision below and the launch itself.
-  bool use_accel = false;
-  int stage_wg = 0;  // > 0: compact records staged in LDS, at most this many workgroups per CU
-  const tor::HostAccel* hacc_p = nullptr;
-  bool configured = false;
+  if (!out.use_accel) return TOR_OK;
+  use_layout(q, ctx->d_accel[v32].always, ctx, c, accel);
+  q.bnd = (const double*)((char*)ctx->bnd_ring.ptr + (size_t)c.slot * ctx->bnd_slot_bytes);  // filled by the caller (async copy)
+  q.spatial_base = (int)hacc.spatial_base;
+  q.n_super = (int)(tor::accel_boxes_padded(hacc) / tor::kPad);
+  q.two_level = hacc.two_level ? 1 : 0;
+  // (the float32 records carry their own guard, the `wild` ray of tor_filter32.hpp; only the float64 block loop reads these)
+  q.box_reach2 = -1.0;
+  q.box_amin = INFINITY;
+  for (int k = 0; k < 3; ++k) q.box_org[k] = 0.0;
+  if (!(v32 && hacc.sp32)) tor::block_reach(hacc, bnd_host, q.box_org, &q.box_reach2, &q.box_amin);
+  q.shot = (const double*)ctx->d_accel[v32].hot.ptr;
+  q.sgrp = (const double*)ctx->d_accel[v32].grp.ptr;
+  q.shot_stride = hacc.hot_stride;
+  q.shot32 = nullptr;
+  size_t bnd32_stage_floats = 0;
+  if (v32 && hacc.sp32) {
+    q.shot32 = (const float*)ctx->d_accel[v32].hot32.ptr;
+    q.shot32_stride = hacc.hot32_stride;
+    q.shot32_block_stride = hacc.hot32_block_stride;
+    q.sp_mc0max = hacc.sp_mc0max; q.sp_dcmax = hacc.sp_dcmax;
+    q.sp_t0 = hacc.sp_t0; q.sp_dt = hacc.sp_dt;
+    // float32 boxes for the slab tests; on two-level scenes the lanes read the block boxes themselves: stage them
+    q.sp_bmax = tor::block_bounds_f32(bnd_host, ctx->f32.origin, bnd32_host, &q.sp_hmin);
+    q.bnd32 = (const float*)((const char*)q.bnd + bnd_host.size() * 8);
+    if (hacc.two_level) bnd32_stage_floats = 8 * tor::accel_boxes_padded(hacc);
+  }
+  out.stage_wg = stage_records_in_lds(q, hacc, bnd32_stage_floats, ctx->max_blocks_per_cu[c.o.seeding][accel != 0], c.kseed);
+  return TOR_OK;
+}
+
+// Launch configuration of the frame's lane kernel, shared by the hand-off decision and the launch itself.
+struct FrameConfig {
+  tor::KParams p{};
+  LayoutChoice lay;
   // launch shape: workgroups per CU for this mode (fewer when the LDS staging needs the room); the
   // kernel variant's register budget follows it
-  int cap = 0, waves_per_simd = 0;
+  int waves_per_simd = 0;
   long long resident_waves = 0;
-  auto configure_frame = [&]() -> int {
-    if (configured) return TOR_OK;
-    const int rc = configure(p, o.accel, ctx->bnd_host[slot], ctx->bnd32_host[slot], use_accel, stage_wg, hacc_p);
-    if (rc != TOR_OK) return rc;
-    cap = ctx->max_blocks_per_cu[o.seeding][o.accel != 0];
-    if (cap < 1) cap = 4;
-    if (stage_wg > 0 && stage_wg < cap) cap = stage_wg;
-    waves_per_simd = ctx->waves_override > 0 ? ctx->waves_override : ((cap >= 2 && cap <= 4) ? cap : 4);
-    int bpc_eff = tor::integrate_blocks_per_cu(p, kseed, o.arith, waves_per_simd);
-    if (bpc_eff > cap) bpc_eff = cap;
-    resident_waves = (long long)ctx->num_cus * bpc_eff * (tor::kThreads / 64);
-    configured = true;
-    return TOR_OK;
-  };
-  const long long n_tiles = (npix + tor::kTilePixelsHost - 1) / tor::kTilePixelsHost;
-  // Chain hand-off (DESIGN 4.7 (HISTORY 4.10)): the lane kernel pushes its long chains to server waves inside the same launch -- it
-  // replaces both the whole-frame wave kernel and split mode wherever the launch's kernel variant carries the servers
-  // (both exact accelerations, single-level culling layout with float32 records, <= 128 block boxes) and the probe runs.
-  // Decided HERE, in full, before split mode and the wave-per-pixel kernel are ruled out: a frame whose hand-off cannot
-  // run after all (non-finite shutter range -> no culling, a variant without servers, a tiny machine) keeps those two
-  // (ADVICE r3).
-  bool migrate = false;
-  if (o.seeding == TOR_SEED_PIXEL && o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->mig_mode != 0 && o.accel == (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32) &&
-      ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && npix > tor::kTilePixelsHost && !ctx->collect_stats && ctx->n_objects > 0 &&
-      !resume) {  // (no hand-off for resume passes: a stalled launch would leave some pixels advanced in place and others not -- DESIGN 4.11)
-    const int rc = configure_frame();
-    if (rc != TOR_OK) return rc;
-    const tor::HostAccel& ha = ctx->accel[1];
-    migrate = ctx->accel_built[1] && ha.available && ha.sp32 && !ha.two_level && tor::accel_boxes_padded(ha) <= 128 &&
-              use_accel && n_tiles > 1 && tor::integrate_variant_serves_chains(p, o.seeding) && resident_waves >= 8;
-  }
-  const bool split_applies = !migrate && o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && split_frac > 0.0f && ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp &&
-                             npix >= ctx->split_min_pixels && npix <= ctx->split_max_pixels && !ctx->collect_stats && ctx->n_objects > 0 &&
-                             !rlist;  // (a listed pass has no tile schedule to split: no probe, no order -- see below)
+};
+
+static int configure_frame(TorContext* ctx, const RenderCall& c, FrameConfig& f) {
+  TOR_TRY(configure_layout(ctx, c, c.o.accel, f.p, ctx->bnd_host[c.slot], ctx->bnd32_host[c.slot], f.lay));
+  int cap = ctx->max_blocks_per_cu[c.o.seeding][c.o.accel != 0];
+  if (cap < 1) cap = 4;
+  if (f.lay.stage_wg > 0 && f.lay.stage_wg < cap) cap = f.lay.stage_wg;
+  f.waves_per_simd = ctx->waves_override > 0 ? ctx->waves_override : ((cap >= 2 && cap <= 4) ? cap : 4);
+  int bpc_eff = tor::integrate_blocks_per_cu(f.p, c.kseed, c.o.arith, f.waves_per_simd);
+  if (bpc_eff > cap) bpc_eff = cap;
+  f.resident_waves = (long long)ctx->num_cus * bpc_eff * (tor::kThreads / 64);
+  return TOR_OK;
+}
+
+// Chain hand-off (DESIGN 4.7 (HISTORY 4.10)): the lane kernel pushes its long chains to server waves inside the same launch -- it
+// replaces both the whole-frame wave kernel and split mode wherever the launch's kernel variant carries the servers
+// (both exact accelerations, single-level culling layout with float32 records, <= 128 block boxes) and the probe runs.
+// Decided in full -- handoff_candidate, then handoff_runs on the configured frame -- before split mode and the wave-per-pixel
+// kernel are ruled out: a frame whose hand-off cannot run after all (non-finite shutter range -> no culling, a variant without
+// servers, a tiny machine) keeps those two.
+static bool handoff_candidate(const TorContext* ctx, const RenderCall& c) {
+  return c.o.seeding == TOR_SEED_PIXEL && c.o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->mig_mode != 0 &&
+         c.o.accel == (TOR_ACCEL_BLOCKS | TOR_ACCEL_F32) && ctx->lpt_min_spp > 0 && c.spp >= ctx->lpt_min_spp &&
+         c.npix > tor::kTilePixelsHost && !ctx->collect_stats && ctx->n_objects > 0 &&
+         !c.resume;  // (no hand-off for resume passes: a stalled launch would leave some pixels advanced in place and others not -- DESIGN 4.11)
+}
+
+static bool handoff_runs(const TorContext* ctx, const RenderCall& c, const FrameConfig& f) {
+  const tor::HostAccel& ha = ctx->accel[1];
+  return ctx->accel_built[1] && ha.available && ha.sp32 && !ha.two_level && tor::accel_boxes_padded(ha) <= 128 && f.lay.use_accel &&
+         c.n_tiles > 1 && tor::integrate_variant_serves_chains(f.p, c.o.seeding) && f.resident_waves >= 8;
+}
+
+static bool split_applies(const TorContext* ctx, const RenderCall& c, float split_frac) {
+  return c.o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && split_frac > 0.0f && ctx->lpt_min_spp > 0 && c.spp >= ctx->lpt_min_spp &&
+         c.npix >= ctx->split_min_pixels && c.npix <= ctx->split_max_pixels && !ctx->collect_stats && ctx->n_objects > 0 &&
+         !c.rlist;  // (a listed pass has no tile schedule to split: no probe, no order -- see probe_and_schedule)
+}
+
+// `elsewhere`: split mode or the hand-off takes the frame
+static bool wave_kernel_wanted(const TorContext* ctx, const RenderCall& c, bool elsewhere) {
   // (a listed pass: the list's length stands in for the pixel count -- what decides is how many chains can run side by side -- against
   // three quarters of the threshold: measured at 1080p the two kernels cross at ~95 000 listed pixels, below the whole-frame rule's
   // 114 688, because a listed lane pass has no probe to pay for and no tile order to lose)
   const long long coop_max_listed = ctx->coop_max_pixels / 4 * 3;
-  const bool want_wave_kernel = o.pixel_kernel == TOR_PIXEL_KERNEL_WAVE ||
-                                (o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->coop_max_pixels > 0 && (rlist ? work_pix <= coop_max_listed : npix <= ctx->coop_max_pixels) && !split_applies && !migrate);
-  if (o.seeding == TOR_SEED_PIXEL && !ctx->collect_stats && want_wave_kernel && ctx->n_objects > 0) {
-    const int rc = tor::ensure_layouts(ctx, 0);
-    if (rc != TOR_OK) return rc;
-    const tor::DeviceLayout& L = ctx->flat[0];
-    tor::KParams wp{};
-    wp.cold = L.cold;
-    wp.n_cold_slots = L.n_sorted;
-    wp.coop_slots = (L.n_sorted + 63) / 64 * 64;
-    wp.coop_trips = L.coop_trips;
-    const int bpc = tor::coop_blocks_per_cu(wp, o.arith);
-    if (bpc > 0) {
-      wp.nrows = nrows; wp.ncols = ncols; wp.spp = spp; wp.max_depth = (int)max_depth;
-      wp.shard_index = o.shard_index; wp.shard_count = o.shard_count; wp.row_tile = o.row_tile;
-      wp.n_pixels = (unsigned)npix;
-      wp.work_counter = slot_counters;
-      wp.out = d_pixels;
-      if (resume) { wp.first_sample = acc->first_sample; wp.mom = acc->moments; wp.rstate = acc->rng; }
-      if (rlist) { wp.pixel_list = acc->list; wp.total_work = (unsigned long long)work_pix; }  // work item k = list slot k
-      ctx->cam_host[slot] = *cam;
-      wp.cam_dev = (const double*)((char*)ctx->cam_ring.ptr + (size_t)slot * sizeof(TorCamera));
-      HIP_TRY(hipMemcpyAsync((void*)wp.cam_dev, &ctx->cam_host[slot], sizeof(TorCamera), hipMemcpyHostToDevice, stream));
-      long long blocks = ((rlist ? work_pix : npix) + (tor::kThreads / 64) - 1) / (tor::kThreads / 64);
-      const long long resident = (long long)ctx->num_cus * bpc;
-      if (blocks > resident) blocks = resident;
-      HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-      HIP_TRY(tor::launch_coop(wp, o.arith, (int)blocks, stream));
-      HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-      ctx->launches += 1;
-      ctx->last_slot = slot;
-      ctx->timing_valid = true;
-      ctx->last_samples = (int64_t)(rlist ? work_pix : npix) * spp;
-      if (resume) return TOR_OK;  // raw sums: tor_resolve_device finalizes
-      HIP_TRY(tor::launch_finalize(d_pixels, n_values, 1.0 / (double)spp, 1.0 / (double)gamma_correction, stream));
-      return TOR_OK;
+  const bool want = c.o.pixel_kernel == TOR_PIXEL_KERNEL_WAVE ||
+                    (c.o.pixel_kernel == TOR_PIXEL_KERNEL_AUTO && ctx->coop_max_pixels > 0 &&
+                     (c.rlist ? c.work_pix <= coop_max_listed : c.npix <= ctx->coop_max_pixels) && !elsewhere);
+  return c.o.seeding == TOR_SEED_PIXEL && !ctx->collect_stats && want && ctx->n_objects > 0;
+}
+
+// the call's own part of a render kernel's KParams, the lane kernel's and the wave-per-pixel kernel's alike
+static void call_params(tor::KParams& q, const RenderCall& c) {
+  q.nrows = c.nrows; q.ncols = c.ncols; q.spp = c.spp; q.max_depth = (int)c.max_depth;
+  q.shard_index = c.o.shard_index; q.shard_count = c.o.shard_count; q.row_tile = c.o.row_tile;
+  q.n_pixels = (unsigned)c.npix;
+  q.work_counter = c.slot_counters;
+  q.out = c.d_pixels;
+  q.first_sample = c.acc ? c.acc->first_sample : 0;
+  q.mom = c.acc ? c.acc->moments : nullptr;
+  q.pixel_list = c.listed ? c.acc->list : nullptr;
+  q.rstate = c.resume ? c.acc->rng : nullptr;
+}
+
+// the wave-per-pixel kernel's view of the float64 flat layout
+static void coop_params(tor::KParams& q, const tor::DeviceLayout& L) {
+  q.cold = L.cold;
+  q.n_cold_slots = L.n_sorted;
+  q.coop_slots = (L.n_sorted + 63) / 64 * 64;
+  q.coop_trips = L.coop_trips;
+}
+
+// the camera travels in its own small device slot (one per in-flight launch)
+static int upload_camera(TorContext* ctx, const RenderCall& c, const double*& cam_dev) {
+  ctx->cam_host[c.slot] = *c.cam;
+  cam_dev = (const double*)((char*)ctx->cam_ring.ptr + (size_t)c.slot * sizeof(TorCamera));
+  HIP_TRY(hipMemcpyAsync((void*)cam_dev, &ctx->cam_host[c.slot], sizeof(TorCamera), hipMemcpyHostToDevice, c.stream));
+  return TOR_OK;
+}
+
+// One timed launch of a call, between the slot's ev_start and ev_stop: the wave-per-pixel kernel (`wave`), the lane kernel
+// (`lane`), or -- split mode, both -- the wave kernel on stream2 beside the lane kernel, joined before ev_stop.  `wave_blocks` is
+// the wave kernel's grid when it runs alone.
+static int launch_bracketed(TorContext* ctx, const RenderCall& c, const tor::KParams* wave, int wave_blocks, const tor::KParams* lane,
+                            int waves_per_simd, int lane_blocks) {
+  const int slot = c.slot;
+  const bool split = wave && lane;
+  if (split) {
+    if (!ctx->stream2) HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    if (!ctx->ev_fork[slot]) {
+      HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork[slot], hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join[slot], hipEventDisableTiming));
     }
   }
-  {
-    const int rc = configure_frame();
-    if (rc != TOR_OK) return rc;
+  HIP_TRY(hipEventRecord(ctx->ev_start[slot], c.stream));
+  if (split) {
+    HIP_TRY(hipEventRecord(ctx->ev_fork[slot], c.stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork[slot], 0));
   }
-  const tor::HostAccel& hacc = *hacc_p;
-  std::vector<double>& bnd_host = ctx->bnd_host[slot];
-  p.nrows = nrows; p.ncols = ncols; p.spp = spp; p.max_depth = (int)max_depth;
-  p.inv_spp = 1.0 / (double)spp; p.inv_ncols = 1.0 / (double)ncols; p.inv_row_tile = 1.0 / (double)(o.row_tile > 0 ? o.row_tile : 1);
-  p.shard_index = o.shard_index; p.shard_count = o.shard_count; p.row_tile = o.row_tile;
-  p.work_counter = slot_counters;
-  p.stats = ctx->collect_stats ? slot_counters + 1 : nullptr;
-  p.out = d_pixels;
-  p.first_sample = acc ? acc->first_sample : 0;
-  p.mom = acc ? acc->moments : nullptr;
-  p.pixel_list = listed ? acc->list : nullptr;
-  p.rstate = resume ? acc->rng : nullptr;
+  if (split) wave_blocks = ctx->num_cus * tor::coop_blocks_per_cu(*wave, c.o.arith);  // beside the lane kernel it takes what is resident
+  if (wave) HIP_TRY(tor::launch_coop(*wave, c.o.arith, wave_blocks, split ? ctx->stream2 : c.stream));
+  if (split) HIP_TRY(hipEventRecord(ctx->ev_join[slot], ctx->stream2));
+  if (lane) HIP_TRY(launch_integrate_recorded(ctx, *lane, c.kseed, c.o.arith, waves_per_simd, lane_blocks, c.stream));
+  if (split) HIP_TRY(hipStreamWaitEvent(c.stream, ctx->ev_join[slot], 0));
+  HIP_TRY(hipEventRecord(ctx->ev_stop[slot], c.stream));
+  ctx->launches += 1;
+  ctx->last_slot = slot;
+  ctx->last_split = split;
+  ctx->timing_valid = true;
+  ctx->last_samples = (int64_t)c.work_pix * c.spp;
+  return TOR_OK;
+}
+
+// Small SEED_PIXEL frames: one wave per pixel (coop_pixel_kernel) -- the lane-per-pixel kernel would be bound by
+// the latency of the longest pixel chain.  Same canvas bit for bit; needs only the float64 flat layout.
+// `launched` stays false when the objects do not fit LDS: the lane kernel takes the frame.
+// (work_pix: on the pixel streams a listed pass is a resume pass -- decode_call -- so it is the list's length exactly when rlist)
+static int launch_wave_frame(TorContext* ctx, const RenderCall& c, bool& launched) {
+  launched = false;
+  TOR_TRY(tor::ensure_layouts(ctx, 0));
+  tor::KParams wp{};
+  coop_params(wp, ctx->flat[0]);
+  const int bpc = tor::coop_blocks_per_cu(wp, c.o.arith);
+  if (bpc <= 0) return TOR_OK;
+  call_params(wp, c);
+  if (c.rlist) wp.total_work = (unsigned long long)c.work_pix;  // work item k = list slot k
+  TOR_TRY(upload_camera(ctx, c, wp.cam_dev));
+  long long blocks = (c.work_pix + (tor::kThreads / 64) - 1) / (tor::kThreads / 64);
+  const long long resident = (long long)ctx->num_cus * bpc;
+  if (blocks > resident) blocks = resident;
+  TOR_TRY(launch_bracketed(ctx, c, &wp, (int)blocks, nullptr, 0, 0));
+  launched = true;
+  return TOR_OK;
+}
+
+// The call's part of the lane kernel's KParams, its grid (`blocks`), and the uploads the launch reads: camera and block bounds.
+static int prepare_lane_launch(TorContext* ctx, const RenderCall& c, FrameConfig& f, bool migrate, int& blocks) {
+  tor::KParams& p = f.p;
+  const TorOptions& o = c.o;
+  call_params(p, c);
+  p.inv_spp = 1.0 / (double)c.spp; p.inv_ncols = 1.0 / (double)c.ncols; p.inv_row_tile = 1.0 / (double)(o.row_tile > 0 ? o.row_tile : 1);
+  p.stats = ctx->collect_stats ? c.slot_counters + 1 : nullptr;
 
   long long waves;
-  p.n_pixels = (unsigned)npix;
   p.order = nullptr;
   p.pixel_cost = nullptr;
   ctx->last_probe_pixels = 0;
   p.sched = nullptr;
-  if (rlist) {
-    p.total_work = (unsigned long long)work_pix;  // list slots, in tiles of 64 consecutive ones (the last may be partial)
+  if (c.rlist) {
+    p.total_work = (unsigned long long)c.work_pix;  // list slots, in tiles of 64 consecutive ones (the last may be partial)
     p.chunk = tor::kTilePixelsHost;
-    waves = (work_pix + tor::kTilePixelsHost - 1) / tor::kTilePixelsHost;
+    waves = (c.work_pix + tor::kTilePixelsHost - 1) / tor::kTilePixelsHost;
   } else if (o.seeding == TOR_SEED_PIXEL) {
-    p.total_work = (unsigned long long)n_tiles * tor::kTilePixelsHost;  // tiles of 64 pixels
+    p.total_work = (unsigned long long)c.n_tiles * tor::kTilePixelsHost;  // tiles of 64 pixels
     p.chunk = tor::kTilePixelsHost;
-    waves = n_tiles;
+    waves = c.n_tiles;
   } else {
-    p.total_work = (unsigned long long)work_pix * (unsigned long long)spp;
-    long long c = (long long)(p.total_work / (unsigned long long)(resident_waves * 16));
+    p.total_work = (unsigned long long)c.work_pix * (unsigned long long)c.spp;
+    long long ch = (long long)(p.total_work / (unsigned long long)(f.resident_waves * 16));
     // largest chunk of the guided schedule: up to 1024 samples, or one whole pixel when a pixel has more (<= 4096)
-    const long long cap_c = (spp > 1024) ? (spp < 4096 ? spp : 4096) : 1024;
-    if (c < 64) c = 64;
-    if (c > cap_c) c = cap_c;
-    p.chunk = (unsigned)((c >= spp) ? c : c / 64 * 64);
+    const long long cap_c = (c.spp > 1024) ? (c.spp < 4096 ? c.spp : 4096) : 1024;
+    if (ch < 64) ch = 64;
+    if (ch > cap_c) ch = cap_c;
+    p.chunk = (unsigned)((ch >= c.spp) ? ch : ch / 64 * 64);
     waves = (long long)((p.total_work + 63) / 64);
   }
-  if (waves > resident_waves) waves = resident_waves;
-  int blocks = (int)((waves + (tor::kThreads / 64) - 1) / (tor::kThreads / 64));
+  if (waves > f.resident_waves) waves = f.resident_waves;
+  blocks = (int)((waves + (tor::kThreads / 64) - 1) / (tor::kThreads / 64));
   if (blocks < 1) blocks = 1;
   p.screen = ctx->screen ? 1 : 0;
-  p.n_boxes = use_accel ? (int)tor::accel_boxes_padded(hacc) : 0;
+  p.n_boxes = f.lay.use_accel ? (int)tor::accel_boxes_padded(*f.lay.hacc) : 0;
   p.mig = nullptr;
-  if (migrate) blocks = (int)(resident_waves / (tor::kThreads / 64));  // the whole machine: waves without a tile are servers at once
+  if (migrate) blocks = (int)(f.resident_waves / (tor::kThreads / 64));  // the whole machine: waves without a tile are servers at once
   p.n_waves = (unsigned)(blocks * (tor::kThreads / 64));
   p.wave_log = nullptr;
   if (ctx->collect_stats) {
     HIP_TRY(ctx->wave_log.ensure((size_t)p.n_waves * 64));
-    HIP_TRY(hipMemsetAsync(ctx->wave_log.ptr, 0, (size_t)p.n_waves * 64, stream));
+    HIP_TRY(hipMemsetAsync(ctx->wave_log.ptr, 0, (size_t)p.n_waves * 64, c.stream));
     p.wave_log = (unsigned long long*)ctx->wave_log.ptr;
     ctx->last_n_waves = (int64_t)p.n_waves;
   }
-
-  // the camera travels in its own small device slot (one per in-flight launch)
-  ctx->cam_host[slot] = *cam;
-  p.cam_dev = (const double*)((char*)ctx->cam_ring.ptr + (size_t)slot * sizeof(TorCamera));
-  HIP_TRY(hipMemcpyAsync((void*)p.cam_dev, &ctx->cam_host[slot], sizeof(TorCamera), hipMemcpyHostToDevice, stream));
-  if (use_accel) {
-    HIP_TRY(hipMemcpyAsync((void*)p.bnd, bnd_host.data(), bnd_host.size() * 8, hipMemcpyHostToDevice, stream));
+  TOR_TRY(upload_camera(ctx, c, p.cam_dev));
+  if (f.lay.use_accel) {
+    const std::vector<double>& bnd_host = ctx->bnd_host[c.slot];
+    HIP_TRY(hipMemcpyAsync((void*)p.bnd, bnd_host.data(), bnd_host.size() * 8, hipMemcpyHostToDevice, c.stream));
     if (p.bnd32)
-      HIP_TRY(hipMemcpyAsync((void*)p.bnd32, ctx->bnd32_host[slot].data(), ctx->bnd32_host[slot].size() * 4, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpyAsync((void*)p.bnd32, ctx->bnd32_host[c.slot].data(), ctx->bnd32_host[c.slot].size() * 4, hipMemcpyHostToDevice, c.stream));
   }
+  return TOR_OK;
+}
+
+// The cost probe: a 2-spp launch on per-sample streams that only counts closest-hit queries per pixel (into tile_cost; it
+// never touches the canvas).
+static int launch_cost_probe(TorContext* ctx, const RenderCall& c, const tor::KParams& p, DeviceBuffer& tile_cost) {
+  const int slot = c.slot;
+  tor::KParams pp = p;
+  if (ctx->probe_accel && (c.o.accel & TOR_ACCEL_BLOCKS) == 0) {
+    // The probe only counts closest-hit queries per pixel -- the count does not depend on how a hit is found -- so a launch
+    // without the block culling (whose ring slot of block bounds is free) still probes with both exact accelerations when
+    // the scene has them: 2.5 ms instead of 7.7 ms in front of a float64 brute-force 1080p frame.
+    tor::KParams pa = p;
+    LayoutChoice pl;
+    TOR_TRY(configure_layout(ctx, c, TOR_ACCEL_BLOCKS | TOR_ACCEL_F32, pa, ctx->probe_bnd_host[slot], ctx->probe_bnd32_host[slot], pl));
+    if (pl.use_accel && pa.shot32 != nullptr && pa.bnd32 != nullptr) {
+      HIP_TRY(hipMemcpyAsync((void*)pa.bnd, ctx->probe_bnd_host[slot].data(), ctx->probe_bnd_host[slot].size() * 8, hipMemcpyHostToDevice, c.stream));
+      HIP_TRY(hipMemcpyAsync((void*)pa.bnd32, ctx->probe_bnd32_host[slot].data(), ctx->probe_bnd32_host[slot].size() * 4, hipMemcpyHostToDevice, c.stream));
+      pp = pa;
+    }
+  }
+  pp.spp = ctx->probe_spp;
+  pp.inv_spp = 1.0 / (double)ctx->probe_spp;
+  pp.total_work = (unsigned long long)c.npix * (unsigned long long)ctx->probe_spp;
+  ctx->last_probe_pixels = c.npix;
+  pp.chunk = 256;
+  pp.work_counter = c.slot_counters + 5;
+  pp.stats = nullptr;
+  pp.wave_log = nullptr;
+  pp.out = nullptr;
+  pp.pixel_cost = (unsigned*)tile_cost.ptr;
+  long long pw = (long long)((pp.total_work + 63) / 64);
+  const long long pres = (long long)ctx->num_cus * 3 * (tor::kThreads / 64);
+  if (pw > pres) pw = pres;
+  const int pblocks = (int)((pw + (tor::kThreads / 64) - 1) / (tor::kThreads / 64));
+  pp.n_waves = (unsigned)(pblocks * (tor::kThreads / 64));
+  HIP_TRY(tor::launch_probe(pp, pblocks, c.stream));
+  return TOR_OK;
+}
+
+// The hand-off's queue of handed-over chains: 64-byte records + ready flags (zeroed per launch), control words in the ring slot;
+// and the part of the tile schedule that sets its thresholds.
+static int setup_handoff_queue(TorContext* ctx, const RenderCall& c, tor::KParams& p, tor::MigSchedule& ms, int blocks) {
+  const size_t cap = (size_t)(c.npix < (1ll << 20) ? c.npix : (1ll << 20));
+  HIP_TRY(ctx->mig_rec.ensure(cap * 64));
+  HIP_TRY(ctx->mig_flag.ensure(cap * 4));
+  HIP_TRY(hipMemsetAsync(ctx->mig_flag.ptr, 0, cap * 4, c.stream));
+  p.mig = c.slot_counters + TorContext::kMigWord0;
+  p.mig_rec = (unsigned long long*)ctx->mig_rec.ptr;
+  p.mig_flag = (unsigned*)ctx->mig_flag.ptr;
+  p.mig_cap = (unsigned)cap;
+  p.mig_tail_lanes = ctx->mig_tail_lanes;
+  p.mig_flags = ctx->mig_flags;
+  p.mig_patience = (unsigned)(ctx->srv_patience_us > 0 ? ctx->srv_patience_us : 0) * 100u;
+  p.mig_tail_rest = ctx->mig_tail_rest;
+  // (read per launch, not per context: the drop-in's cached contexts outlive any one caller's settings)
+  double stall_s = ctx->mig_stall_s;
+  if (const char* s = tor::knob("TOR_SRV_STALL_S")) stall_s = std::atof(s);
+  p.mig_stall_ticks = stall_s > 0.0 ? (unsigned long long)(stall_s * 1e8) + 2ull : (stall_s < 0.0 ? 1ull : 0ull);  // (< 0, a test setting: every waiting server gives up at its first look)
+  ms.mig = p.mig;
+  ms.lavg_scale = (float)c.spp / (float)ctx->probe_spp / ((float)blocks * (float)tor::kThreads);
+  ms.srv_frac = ctx->srv_frac;
+  ms.srv_min_frac = ctx->srv_min_frac;
+  ms.push_theta = ctx->push_theta;
+  ms.chain_scale = (float)c.spp / (float)ctx->probe_spp / (float)c.npix;
+  ms.chain_theta = ctx->chain_theta;
+  ms.floor_theta = ctx->floor_theta;
+  ms.blocks = blocks;
+  ms.spp = c.spp;
+  ms.max_depth = (int)c.max_depth;
+  return TOR_OK;
+}
+
+// Cost-ordered schedule of a SEED_PIXEL frame: a 2-spp probe + a counting sort; ~2/spp of extra work.  With `split_ok` it also
+// decides split mode -- `split` says whether it applies, `wk` is then the wave kernel's KParams -- and with `migrate` it sets up
+// the hand-off queue.
+static int probe_and_schedule(TorContext* ctx, const RenderCall& c, FrameConfig& f, int blocks, bool migrate, bool split_ok, float split_frac,
+                              tor::KParams& wk, bool& split) {
+  split = false;
   // (a listed pass runs no probe and no tile order: the probe costs 2 samples of EVERY pixel of the shard -- more than a pass of 16 over a
   // list of a few per cent of them -- and its tiles are tiles of pixels, not of list slots)
-  if (o.seeding == TOR_SEED_PIXEL && ctx->lpt_min_spp > 0 && spp >= ctx->lpt_min_spp && n_tiles > 1 && !rlist) {
-    // Cost-ordered schedule: a 2-spp probe (per-sample streams; it only counts closest-hit queries
-    // per tile, it never touches the canvas) + a counting sort; ~2/spp of extra work.
-    // (one buffer per context, not per ring slot: only the probe and the two sort kernels touch it, and the launches of a
-    // context are ordered on one stream)
-    DeviceBuffer& tile_cost = ctx->probe_buf;
-    DeviceBuffer& tile_order = ctx->tile_order[slot];
-    // per-pixel query counts of the probe, then per tile: sort key, probed work
-    HIP_TRY(tile_cost.ensure(((size_t)npix + 2 * (size_t)n_tiles) * 4 + tor::kTileSortScratchBytes));
-    HIP_TRY(tile_order.ensure((size_t)n_tiles * 4));
-    HIP_TRY(hipMemsetAsync(tile_cost.ptr, 0, (size_t)npix * 4, stream));
-    tor::KParams pp = p;
-    if (ctx->probe_accel && (o.accel & TOR_ACCEL_BLOCKS) == 0) {
-      // The probe only counts closest-hit queries per pixel -- the count does not depend on how a hit is found -- so a launch
-      // without the block culling (whose ring slot of block bounds is free) still probes with both exact accelerations when
-      // the scene has them: 2.5 ms instead of 7.7 ms in front of a float64 brute-force 1080p frame.
-      tor::KParams pa = p;
-      bool pa_accel = false;
-      int pa_stage = 0;
-      const tor::HostAccel* pa_h = nullptr;
-      const int rc = configure(pa, TOR_ACCEL_BLOCKS | TOR_ACCEL_F32, ctx->probe_bnd_host[slot], ctx->probe_bnd32_host[slot], pa_accel, pa_stage, pa_h);
-      if (rc != TOR_OK) return rc;
-      if (pa_accel && pa.shot32 != nullptr && pa.bnd32 != nullptr) {
-        HIP_TRY(hipMemcpyAsync((void*)pa.bnd, ctx->probe_bnd_host[slot].data(), ctx->probe_bnd_host[slot].size() * 8, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync((void*)pa.bnd32, ctx->probe_bnd32_host[slot].data(), ctx->probe_bnd32_host[slot].size() * 4, hipMemcpyHostToDevice, stream));
-        pp = pa;
-      }
-    }
-    pp.spp = ctx->probe_spp;
-    pp.inv_spp = 1.0 / (double)ctx->probe_spp;
-    pp.total_work = (unsigned long long)npix * (unsigned long long)ctx->probe_spp;
-    ctx->last_probe_pixels = npix;
-    pp.chunk = 256;
-    pp.work_counter = slot_counters + 5;
-    pp.stats = nullptr;
-    pp.wave_log = nullptr;
-    pp.out = nullptr;
-    pp.pixel_cost = (unsigned*)tile_cost.ptr;
-    long long pw = (long long)((pp.total_work + 63) / 64);
-    const long long pres = (long long)ctx->num_cus * 3 * (tor::kThreads / 64);
-    if (pw > pres) pw = pres;
-    const int pblocks = (int)((pw + (tor::kThreads / 64) - 1) / (tor::kThreads / 64));
-    pp.n_waves = (unsigned)(pblocks * (tor::kThreads / 64));
-    HIP_TRY(tor::launch_probe(pp, pblocks, stream));
-    // Split mode (mid-size frames): the lane kernel is bound by its longest pixel chains, the wave-per-pixel kernel by
-    // its throughput -- so the most expensive tiles (split_frac of the probed cost) go to the wave kernel on a second
-    // stream while the lane kernel renders the rest.  Disjoint pixels, same arithmetic: same canvas.
-    tor::KParams wk{};
-    bool split = false;
-    if (split_applies) {
-      const int rc = tor::ensure_layouts(ctx, 0);
-      if (rc != TOR_OK) return rc;
-      const tor::DeviceLayout& L = ctx->flat[0];
-      wk = p;
-      wk.cold = L.cold;
-      wk.n_cold_slots = L.n_sorted;
-      wk.coop_slots = (L.n_sorted + 63) / 64 * 64;
-      wk.coop_trips = L.coop_trips;
-      wk.order = (const unsigned*)tile_order.ptr;
-      wk.split = slot_counters + 6;
-      wk.work_counter = slot_counters + 7;
-      wk.stats = nullptr;
-      wk.wave_log = nullptr;
-      split = tor::coop_blocks_per_cu(wk, o.arith) > 0;
-    }
-    unsigned* const tile_key = (unsigned*)tile_cost.ptr + npix;
-    // schedule of the lane kernel (tor_kernels.hip): the hot chains -- a pixel chain is hot when it needs more than hot_frac of the
-    // iterations an average wave runs in this frame
-    //   average = total probed queries * spp / probe_spp / lanes
-    p.prio_shift = ctx->prio_shift;
-    p.sched = slot_counters + 8;
-    tor::MigSchedule ms;
-    ms.key_mode = ctx->key_mode;
-    ms.probe_spp = ctx->probe_spp;
-    if (migrate) {
-      // queue of handed-over chains: 64-byte records + ready flags (zeroed per launch), control words in the ring slot
-      const size_t cap = (size_t)(npix < (1ll << 20) ? npix : (1ll << 20));
-      HIP_TRY(ctx->mig_rec.ensure(cap * 64));
-      HIP_TRY(ctx->mig_flag.ensure(cap * 4));
-      HIP_TRY(hipMemsetAsync(ctx->mig_flag.ptr, 0, cap * 4, stream));
-      p.mig = slot_counters + TorContext::kMigWord0;
-      p.mig_rec = (unsigned long long*)ctx->mig_rec.ptr;
-      p.mig_flag = (unsigned*)ctx->mig_flag.ptr;
-      p.mig_cap = (unsigned)cap;
-      p.mig_tail_lanes = ctx->mig_tail_lanes;
-      p.mig_flags = ctx->mig_flags;
-      p.mig_patience = (unsigned)(ctx->srv_patience_us > 0 ? ctx->srv_patience_us : 0) * 100u;
-      p.mig_tail_rest = ctx->mig_tail_rest;
-      // (read per launch, not per context: the drop-in's cached contexts outlive any one caller's settings)
-      double stall_s = ctx->mig_stall_s;
-      if (const char* c = tor::knob("TOR_SRV_STALL_S")) stall_s = std::atof(c);
-      p.mig_stall_ticks = stall_s > 0.0 ? (unsigned long long)(stall_s * 1e8) + 2ull : (stall_s < 0.0 ? 1ull : 0ull);  // (< 0, a test setting: every waiting server gives up at its first look)
-      ms.mig = p.mig;
-      ms.lavg_scale = (float)spp / (float)ctx->probe_spp / ((float)blocks * (float)tor::kThreads);
-      ms.srv_frac = ctx->srv_frac;
-      ms.srv_min_frac = ctx->srv_min_frac;
-      ms.push_theta = ctx->push_theta;
-      ms.chain_scale = (float)spp / (float)ctx->probe_spp / (float)npix;
-      ms.chain_theta = ctx->chain_theta;
-      ms.floor_theta = ctx->floor_theta;
-      ms.blocks = blocks;
-      ms.spp = spp;
-      ms.max_depth = (int)max_depth;
-    }
-    HIP_TRY(tor::launch_tile_order((const unsigned*)tile_cost.ptr, (unsigned)npix, tile_key, tile_key + n_tiles, (unsigned*)tile_order.ptr,
-                                   (int)n_tiles, split ? split_frac : 0.0f, split ? slot_counters + 6 : nullptr,
-                                   split ? slot_counters : nullptr,
-                                   ctx->hot_frac > 0.0f ? ctx->hot_frac * (float)spp / (float)ctx->probe_spp / (float)(resident_waves * 64) : -1.0f,
-                                   p.sched, ms, stream));
-    p.order = (const unsigned*)tile_order.ptr;
-    if (split) {
-      if (!ctx->stream2) HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-      if (!ctx->ev_fork[slot]) {
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork[slot], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join[slot], hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-      HIP_TRY(hipEventRecord(ctx->ev_fork[slot], stream));
-      HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork[slot], 0));
-      const long long wave_blocks = (long long)ctx->num_cus * tor::coop_blocks_per_cu(wk, o.arith);
-      HIP_TRY(tor::launch_coop(wk, o.arith, (int)wave_blocks, ctx->stream2));
-      HIP_TRY(hipEventRecord(ctx->ev_join[slot], ctx->stream2));
-      HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
-      HIP_TRY(hipStreamWaitEvent(stream, ctx->ev_join[slot], 0));
-      HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-      ctx->launches += 1;
-      ctx->last_slot = slot;
-      ctx->last_split = true;
-      ctx->timing_valid = true;
-      ctx->last_samples = (int64_t)npix * spp;
-      if (resume) return TOR_OK;  // raw sums: tor_resolve_device finalizes
-      HIP_TRY(tor::launch_finalize(d_pixels, n_values, 1.0 / (double)spp, 1.0 / (double)gamma_correction, stream));
-      return TOR_OK;
-    }
+  if (!(c.o.seeding == TOR_SEED_PIXEL && ctx->lpt_min_spp > 0 && c.spp >= ctx->lpt_min_spp && c.n_tiles > 1 && !c.rlist)) return TOR_OK;
+  tor::KParams& p = f.p;
+  const long long npix = c.npix, n_tiles = c.n_tiles;
+  // (one buffer per context, not per ring slot: only the probe and the two sort kernels touch it, and the launches of a
+  // context are ordered on one stream)
+  DeviceBuffer& tile_cost = ctx->probe_buf;
+  DeviceBuffer& tile_order = ctx->tile_order[c.slot];
+  // per-pixel query counts of the probe, then per tile: sort key, probed work
+  HIP_TRY(tile_cost.ensure(((size_t)npix + 2 * (size_t)n_tiles) * 4 + tor::kTileSortScratchBytes));
+  HIP_TRY(tile_order.ensure((size_t)n_tiles * 4));
+  HIP_TRY(hipMemsetAsync(tile_cost.ptr, 0, (size_t)npix * 4, c.stream));
+  TOR_TRY(launch_cost_probe(ctx, c, p, tile_cost));
+  // Split mode (mid-size frames): the lane kernel is bound by its longest pixel chains, the wave-per-pixel kernel by
+  // its throughput -- so the most expensive tiles (split_frac of the probed cost) go to the wave kernel on a second
+  // stream while the lane kernel renders the rest.  Disjoint pixels, same arithmetic: same canvas.
+  if (split_ok) {
+    TOR_TRY(tor::ensure_layouts(ctx, 0));
+    wk = p;
+    coop_params(wk, ctx->flat[0]);
+    wk.order = (const unsigned*)tile_order.ptr;
+    wk.split = c.slot_counters + 6;
+    wk.work_counter = c.slot_counters + 7;
+    wk.stats = nullptr;
+    wk.wave_log = nullptr;
+    split = tor::coop_blocks_per_cu(wk, c.o.arith) > 0;
   }
-  ctx->last_migrate = migrate && p.mig != nullptr;
-  if (ctx->last_migrate) {
-    // A hand-off launch covers the whole machine and its waves WAIT for each other (servers for lane waves): two of them
-    // interleaved on one GPU -- two contexts on one device, e.g. a device list that repeats an ordinal -- would each hold part
-    // of the machine and wait for workgroups that can never start.  So hand-off launches of this process are chained per
-    // device: each waits (on the device, not the host) for the previous one's end event.  Kernels without
-    // inter-workgroup waits may still overlap it; they end on their own.
-    std::lock_guard<std::mutex> lock(g_handoff_mutex);
-    hipEvent_t& ev = g_handoff_event[ctx->device];
-    if (ev) HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
-    else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-    HIP_TRY(hipEventRecord(ev, stream));
-  } else {
-    HIP_TRY(hipEventRecord(ctx->ev_start[slot], stream));
-    HIP_TRY(launch_integrate_recorded(ctx, p, kseed, o.arith, waves_per_simd, blocks, stream));
-    HIP_TRY(hipEventRecord(ctx->ev_stop[slot], stream));
-  }
-  ctx->launches += 1;
-  ctx->last_slot = slot;
-  ctx->timing_valid = true;
-  ctx->last_samples = (int64_t)work_pix * spp;
-  if (acc) return TOR_OK;  // raw sums: tor_resolve_device finalizes
-  // canvas.nim:47-54
-  const double scale = 1.0 / (double)spp;
-  const double gamma = 1.0 / (double)gamma_correction;
-  HIP_TRY(tor::launch_finalize(d_pixels, n_values, scale, gamma, stream));
+  unsigned* const tile_key = (unsigned*)tile_cost.ptr + npix;
+  // schedule of the lane kernel (tor_kernels.hip): the hot chains -- a pixel chain is hot when it needs more than hot_frac of the
+  // iterations an average wave runs in this frame
+  //   average = total probed queries * spp / probe_spp / lanes
+  p.prio_shift = ctx->prio_shift;
+  p.sched = c.slot_counters + 8;
+  tor::MigSchedule ms;
+  ms.key_mode = ctx->key_mode;
+  ms.probe_spp = ctx->probe_spp;
+  if (migrate) TOR_TRY(setup_handoff_queue(ctx, c, p, ms, blocks));
+  HIP_TRY(tor::launch_tile_order((const unsigned*)tile_cost.ptr, (unsigned)npix, tile_key, tile_key + n_tiles, (unsigned*)tile_order.ptr,
+                                 (int)n_tiles, split ? split_frac : 0.0f, split ? c.slot_counters + 6 : nullptr,
+                                 split ? c.slot_counters : nullptr,
+                                 ctx->hot_frac > 0.0f ? ctx->hot_frac * (float)c.spp / (float)ctx->probe_spp / (float)(f.resident_waves * 64) : -1.0f,
+                                 p.sched, ms, c.stream));
+  p.order = (const unsigned*)tile_order.ptr;
   return TOR_OK;
+}
+
+// A hand-off launch covers the whole machine and its waves WAIT for each other (servers for lane waves): two of them
+// interleaved on one GPU -- two contexts on one device, e.g. a device list that repeats an ordinal -- would each hold part
+// of the machine and wait for workgroups that can never start.  So hand-off launches of this process are chained per
+// device: each waits (on the device, not the host) for the previous one's end event.  Kernels without
+// inter-workgroup waits may still overlap it; they end on their own.
+static int launch_handoff(TorContext* ctx, const RenderCall& c, const FrameConfig& f, int blocks) {
+  std::lock_guard<std::mutex> lock(g_handoff_mutex);
+  hipEvent_t& ev = g_handoff_event[ctx->device];
+  if (ev) HIP_TRY(hipStreamWaitEvent(c.stream, ev, 0));
+  else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  TOR_TRY(launch_bracketed(ctx, c, nullptr, 0, &f.p, f.waves_per_simd, blocks));
+  HIP_TRY(hipEventRecord(ev, c.stream));
+  return TOR_OK;
+}
+
+// A pass (acc) leaves raw sums: tor_resolve_device finalizes.  One condition for all three launches: the wave kernel and split
+// mode run on TOR_SEED_PIXEL only, where decode_call admits no pass but a resume pass -- there `acc` is `resume`.
+static int finish_call(const RenderCall& c) {
+  if (c.acc) return TOR_OK;
+  // canvas.nim:47-54
+  HIP_TRY(tor::launch_finalize(c.d_pixels, c.n_values, 1.0 / (double)c.spp, 1.0 / (double)c.gamma_correction, c.stream));
+  return TOR_OK;
+}
+
+// All five render entries: the phases above, in order.
+static int render_device_impl(TorContext* ctx, const TorOptions* opt, RenderCall& c) {
+  TOR_TRY(decode_call(ctx, opt, c));
+  if (c.work_pix == 0) return TOR_OK;
+  TOR_TRY(claim_ring_slot(ctx, c));
+  // (a resume pass takes no shortcut: with max_depth <= 0 the reference still draws every sample's pixel jitter, lens and time
+  // samples -- render.nim:63-65, cameras.nim:47-57 -- and the states must advance exactly so; its kernels end such a sample black)
+  if (!c.resume && (c.max_depth <= 0 || ctx->n_objects < 0)) {
+    if (c.acc) return TOR_OK;  // every sample is black: the pass adds zeros, the sums (and moments) stay as they are
+    // render.nim:25: the bounce loop does not run -> every sample is black -> pow(0, g) = 0
+    HIP_TRY(hipMemsetAsync(c.d_pixels, 0, (size_t)c.n_values * 8, c.stream));
+    return TOR_OK;
+  }
+  if (c.o.seeding == TOR_SEED_SAMPLE && !c.acc) HIP_TRY(hipMemsetAsync(c.d_pixels, 0, (size_t)c.n_values * 8, c.stream));
+
+  // The frame is configured (layouts built, block bounds computed) where it was always configured: before the hand-off decision
+  // for its candidates, else only once the wave-per-pixel kernel -- which needs the float64 flat layout alone -- has not taken it.
+  FrameConfig f;
+  const float split_frac = split_fraction(ctx, c);
+  const bool candidate = handoff_candidate(ctx, c);
+  if (candidate) TOR_TRY(configure_frame(ctx, c, f));
+  const bool migrate = candidate && handoff_runs(ctx, c, f);
+  const bool split_ok = !migrate && split_applies(ctx, c, split_frac);
+  if (wave_kernel_wanted(ctx, c, split_ok || migrate)) {
+    bool launched = false;
+    TOR_TRY(launch_wave_frame(ctx, c, launched));
+    if (launched) return finish_call(c);
+  }
+  if (!candidate) TOR_TRY(configure_frame(ctx, c, f));
+
+  int blocks = 0;
+  bool split = false;
+  tor::KParams wk{};
+  TOR_TRY(prepare_lane_launch(ctx, c, f, migrate, blocks));
+  TOR_TRY(probe_and_schedule(ctx, c, f, blocks, migrate, split_ok, split_frac, wk, split));
+  ctx->last_migrate = migrate && f.p.mig != nullptr;
+  if (split) TOR_TRY(launch_bracketed(ctx, c, &wk, 0, &f.p, f.waves_per_simd, blocks));
+  else if (ctx->last_migrate) TOR_TRY(launch_handoff(ctx, c, f, blocks));
+  else TOR_TRY(launch_bracketed(ctx, c, nullptr, 0, &f.p, f.waves_per_simd, blocks));
+  return finish_call(c);
 }
 
 int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                       int32_t spp, float gamma_correction, int64_t max_depth, const TorOptions* opt,
                       double* d_pixels, void* hip_stream) {
-  return render_device_impl(ctx, cam, nrows, ncols, spp, gamma_correction, max_depth, opt, d_pixels, hip_stream, nullptr);
+  RenderCall c{"tor_render_device", cam, nrows, ncols, spp, gamma_correction, max_depth, d_pixels, (hipStream_t)hip_stream, nullptr};
+  return render_device_impl(ctx, opt, c);
 }
 
 // ---- progressive rendering (TOR_SEED_SAMPLE): passes of samples into raw sums, resolve, noise -------------------------
@@ -1061,7 +1157,8 @@ int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t 
                                           "<= 2^17 (131072): beyond that the 2^-36-granular float64 sums are no longer exact");
   if (!ctx || !cam || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_accumulate_device: NULL argument");
   const tor::AccumLaunch acc{first_sample, d_moments};
-  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+  RenderCall c{"tor_render_accumulate_device", cam, nrows, ncols, n_samples, 2.2f, max_depth, d_sums, (hipStream_t)hip_stream, &acc};
+  return render_device_impl(ctx, opt, c);
 }
 
 // ---- resumable rendering on the reference's per-pixel streams (TOR_SEED_PIXEL) -----------------------------------------
@@ -1077,7 +1174,8 @@ int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int32_t nrow
   if (!ctx || !cam || !d_rng || !d_sums) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_render_resume_device: NULL argument");
   tor::AccumLaunch acc{first_sample, d_moments};
   acc.rng = (unsigned long long*)d_rng;
-  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+  RenderCall c{"tor_render_resume_device", cam, nrows, ncols, n_samples, 2.2f, max_depth, d_sums, (hipStream_t)hip_stream, &acc};
+  return render_device_impl(ctx, opt, c);
 }
 
 // ... over a pixel list: adaptive sampling on the reference's streams.  The list rules are tor_render_accumulate_list_device's; the pass
@@ -1105,7 +1203,8 @@ int tor_render_resume_list_device(TorContext* ctx, const TorCamera* cam, int32_t
   static const int32_t empty_list[1] = {0};
   tor::AccumLaunch acc{first_sample, d_moments, n_list > 0 ? d_list : empty_list, n_list};
   acc.rng = (unsigned long long*)d_rng;
-  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+  RenderCall c{"tor_render_resume_list_device", cam, nrows, ncols, n_samples, 2.2f, max_depth, d_sums, (hipStream_t)hip_stream, &acc};
+  return render_device_impl(ctx, opt, c);
 }
 
 int tor_resolve_device(TorContext* ctx, const double* d_sums, int64_t n_values, int64_t total_samples, float gamma_correction,
@@ -1158,7 +1257,8 @@ int tor_render_accumulate_list_device(TorContext* ctx, const TorCamera* cam, int
   }
   if (!ctx || !cam || !d_list || !d_sums || !d_moments) return fail(TOR_ERR_INVALID_ARGUMENT, std::string(who) + ": NULL argument (sums and moments are both required)");
   const tor::AccumLaunch acc{first_sample, d_moments, d_list, n_list};
-  return render_device_impl(ctx, cam, nrows, ncols, n_samples, 2.2f, max_depth, opt, d_sums, hip_stream, &acc);
+  RenderCall c{"tor_render_accumulate_list_device", cam, nrows, ncols, n_samples, 2.2f, max_depth, d_sums, (hipStream_t)hip_stream, &acc};
+  return render_device_impl(ctx, opt, c);
 }
 
 int tor_adaptive_select_device(TorContext* ctx, const double* d_sums, const double* d_moments, const int32_t* d_list_in, int32_t n_in,

@@ -272,6 +272,10 @@ const std::string& options_why();  // why the last valid_options() call on this 
 // Makes sure the layouts a launch with (accel bits) needs exist on the device (built from scene_bytes).
 int ensure_layouts(TorContext* ctx, int accel);
 
+// The render half of the one-stream-per-context rule (tor_render.h): a launch or query on `stream` is accepted when the context's last
+// render launch ran on that stream or has finished; else it is refused with the caller's name and `sentence`.
+int last_render_allows(TorContext* ctx, const void* stream, const char* who, const char* sentence);
+
 // Copies n_rows compact rows of row_bytes from device memory (on ctx's device, ready on `stream`) into host
 // memory: row k lands at dst + rows[k] * row_bytes (rows == nullptr: k * row_bytes).  D2H in chunks into the
 // context's pinned staging, worker threads move the chunks on while later chunks are still in flight.  Blocking.

@@ -279,12 +279,10 @@ int query_stream_rule(const char* who, TorContext* ctx, hipStream_t stream) {
   using tor::fail_hip;
   const std::string w = who;
   tor::HitQueryState& hq = ctx->hitq;
-  if (ctx->launches > 0 && ctx->last_stream_valid && ctx->last_stream != (void*)stream) {
-    const hipError_t q = hipEventQuery(ctx->ev_stop[ctx->last_slot]);
-    if (q == hipErrorNotReady)
-      return fail(TOR_ERR_INVALID_ARGUMENT, w + ": the context's last render launch is still running on a different stream -- launches "
-                                                "of one context that may overlap must use ONE stream (or use one context per stream)");
-    if (q != hipSuccess) return fail_hip(q, "hipEventQuery");
+  {
+    const int rc = tor::last_render_allows(ctx, (void*)stream, who, ": the context's last render launch is still running on a different stream -- launches "
+                                                                    "of one context that may overlap must use ONE stream (or use one context per stream)");
+    if (rc != TOR_OK) return rc;
   }
   if (hq.launched && hq.stream != (void*)stream) {
     const hipError_t q = hipEventQuery(hq.ev_done);
