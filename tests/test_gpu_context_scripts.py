@@ -1,0 +1,246 @@
+"""One long-lived context per script on the MI355X (tests/context_scripts.py): uploads, tables, queries of every family, renders and
+two open accumulations interleaved on one stream, with no host synchronisation between the steps other than what the library and
+its Python layer force themselves: a numpy operand (the blocking _host twins), a refusal, a replacing upload (tor_scene_upload
+waits for the device before it overwrites the scene), and a block query on device tensors with time_range=None, whose range the
+Python layer reads back from the tensor's times (torch.aminmax, a download).  The test adds none: every device operand is uploaded
+before the first step, every device output is kept and downloaded after the last.
+
+Arbiter: every answer is compared bit for bit with the family's restatement under the MODEL's state (context_scripts.Model: which
+records, words, table and map the step must see), NaNs as the families' own tests compare them (a NaN on both sides of a float
+field is equal, every other bit counts); renders and the accumulations with oracle.render / oracle.accumulate (PORTABLE math), the
+film with deposit_restatement.  No fresh context answers for another.  What ran (res.mode / tor.last_note()) is asserted where the
+per-family tests fix it: `brute` is the brute force, and odd_objects falls back and says why.  At the end
+ctx.scene_counters()[:2] is the model's count of uploads and cache hits.  tests/test_context_scripts.py shows on the CPU that a
+stale cache behind any of the steps would change a quarter of its rows; profiles/context_script_mutants.txt what the same_size
+script fails on when a cache key is broken.
+
+Measured wall time on an MI355X, restatements and oracle renders included: the whole module 15.2 s for 5 tests -- same_size
+(290 steps) 5.7 s, same_size_g9 (290 steps) 0.3 s, sizes (384 steps) 6.6 s, seeded_1 (123 steps) 0.4 s, seeded_2 (123 steps)
+0.1 s; nearly all of it is the restatements on the CPU (bounce, scatter and radiance loop in Python), the library's share of a
+script is tens of milliseconds."""
+import numpy as np
+import pytest
+import torch
+
+import context_scripts as S
+import deposit_restatement as D
+import render_regimes as R
+
+pytestmark = pytest.mark.gpu
+_scenes = {}
+
+
+def _scene(tor, name, bad=False):
+    """The Scene of a named list, built once and kept alive (the library keeps a byte copy, the test keeps the caller's); `bad`: the
+    same list with an unknown kind in its middle."""
+    key = (name, bad)
+    if key not in _scenes:
+        sc = tor.Scene.from_records(np.asarray(S.records(name)))
+        if bad:
+            sc.objects[len(sc) // 2].kind = 7
+        _scenes[key] = sc
+    return _scenes[key]
+
+
+def _dev(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint64:
+        a = a.view(np.int64)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    return torch.from_numpy(a).cuda()
+
+
+def _host(t):
+    """A kept output as numpy (after the last step): 64-bit and 32-bit integers by their bits, as the restatements hold them."""
+    a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.int64 else a
+
+
+def _records_as_fields(outs):
+    """Keys that end in `raw` hold TorHit records: their fields, as context_scripts.answer names them."""
+    done = {}
+    for k, v in outs.items():
+        if k.endswith("raw"):
+            done.update(S._hit_fields(_host(v), k[:-3]))
+        else:
+            done[k] = _host(v)
+    return done
+
+
+def _call(tor, ctx, step, op, env):
+    """One query, render or pass: returns (the kept outputs, what ran or None).  `op(name)`: the operand as the step wants it -- a
+    device tensor uploaded before the script began, or the numpy array itself (the blocking twin)."""
+    f, b = step["family"], S.base(step["family"])
+    mask = {"mask": op("masks")} if f in S.MASKED else {}
+    tr, mode = step.get("time_range"), step.get("mode")
+    if b == "hit":
+        res = ctx.hit(op("rays"), op("t_range"), tr, mode, **mask)
+        return {"raw": res.raw}, res.mode
+    if b == "occluded":
+        res = ctx.occluded(op("rays"), op("t_range"), None, tr, mode, **mask)
+        return {"occluded": res.raw}, res.mode
+    if b == "crossings":
+        res = ctx.crossings(op("rays"), step["k"], op("t_range"), None, tr, mode, mask.get("mask"), bool(step.get("records")))
+        out = {"t": res.t, "object": res.object, "which": res.which, "count": res.count}
+        if step.get("records"):
+            out["hits_raw"] = res.hits
+        return out, res.mode
+    if b == "nearest":
+        res = ctx.nearest(op("points"), step["k"], op("dmax"), None, tr, mode, mask.get("mask"))
+        return {"distance": res.distance, "object": res.object, "inside": res.inside, "count": res.count}, res.mode
+    if b == "bounce":
+        res = ctx.bounce(op("rays"), op("states"), None, tr, mode, **mask)
+        return {"raw": res.raw, "status": res.status, "attenuation": res.attenuation, "rays": res.rays, "states": res.rng}, res.mode
+    if f == "scatter":
+        res = ctx.scatter(op("rays"), op("hits"), op("states"))
+        return {"status": res.status, "attenuation": res.attenuation, "rays": res.rays, "states": res.rng}, None
+    if f == "radiance":
+        color, rng, ran = ctx.radiance(op("rays"), op("states"), S.RADIANCE_DEPTH, tr, mode)
+        return {"color": color, "states": rng}, ran
+    if f == "bsdf":
+        ev = ctx.bsdf(op("rays_in"), op("hits"), op("rays_out"))
+        return {"value": ev.value, "pdf": ev.pdf, "kind": ev.kind}, None
+    if f == "sample_lights":
+        ls = ctx.sample_lights(op("points"), op("states"))
+        return {"rays": ls.rays, "pdf": ls.pdf, "light": ls.light, "dist": ls.dist, "states": ls.rng}, None
+    if f == "light_pdf":
+        return {"pdf": ctx.light_pdf(op("points"), op("objects"))}, None
+    if f == "emit_lights":
+        em = ctx.emit_lights(op("states"), step["shutter"])
+        return {"rays": em.rays, "normal": em.normal, "light": em.light, "pdf": em.pdf, "states": em.rng}, None
+    if f == "connect_camera":
+        import camera_inputs as CI
+        cc = ctx.connect_camera(CI.camera_struct(tor, env["x"]["cam24"]), *env["x"]["frame"], op("points"), op("states"))
+        return {"rays": cc.rays, "pixel": cc.pixel, "factor": cc.factor, "lens": cc.lens, "states": cc.rng}, None
+    if f == "environment":
+        ev = ctx.environment(op("rays"), pdf=True)
+        return {"color": ev.color, "pdf": ev.pdf, "texel": ev.texel}, None
+    if f == "sample_environment":
+        es = ctx.sample_environment(op("points"), op("states"))
+        return {"rays": es.rays, "pdf": es.pdf, "texel": es.texel, "color": es.color, "states": es.rng}, None
+    if f == "deposit":
+        env["film"].deposit(env["dev"]["pixels"], env["dev"]["colors"])
+        return {}, None
+    cam = tor.camera(**env["x"]["camera"])
+    stream = torch.cuda.current_stream().cuda_stream
+    if f == "render":
+        buf = torch.zeros((R.H, R.W, 3), dtype=torch.float64, device="cuda")
+        ctx.render_device(cam, R.H, R.W, R.SPP, 2.2, R.DEPTH, tor.make_options(seeding=step["seeding"], accel=step["accel"]),
+                          buf.data_ptr(), stream)
+        return {"pixels": buf.view(-1, 3)}, None
+    if f not in env["open"]:                              # an accumulation is opened at its first pass and stays open
+        make = tor.Progressive if f == "progressive" else tor.PixelProgressive
+        seeding = tor.SEED_SAMPLE if f == "progressive" else tor.SEED_PIXEL
+        env["open"][f] = make(ctx, cam, R.H, R.W, R.DEPTH, tor.make_options(seeding=seeding, accel=3))
+    assert env["open"][f].samples == step["first"]
+    env["open"][f].add(3)
+    return {}, None
+
+
+def _check_what_ran(tor, step, state, ran, model_range):
+    f = step["family"]
+    if not S.takes_mode(f) or ran is None:
+        return
+    if step["mode"] == "brute":
+        assert ran == "brute force", (step, ran)
+    elif state.scene == "odd_objects":                   # radii for which the boxes' margin holds for no origin: the blocks fall back
+        assert ran.startswith("brute force ("), (step, ran)
+        if S.base(f) != "nearest" and model_range == (0.0, 1.0):
+            assert ran == f"brute force ({S.WHY_RADII})", (step, ran)
+    elif S.has_blocks(state.scene):                      # dense, dense2, tiny, noground and the edited copy: the blocks run, in every
+        # range (a silent fallback would take `bnd` and `grp` out of the script); nearest's `auto` may choose the brute force, and says so
+        auto_nearest = S.base(f) == "nearest" and step["mode"] == "auto" and ran.startswith("brute force (auto: ")
+        assert ran == "blocks" or auto_nearest, (step, state.key(), ran)
+    else:                                                # nine objects: no culling layout
+        assert ran.startswith("brute force ("), (step, state.key(), ran)
+
+
+def _run(tor, oracle, name):
+    steps = S.script(name)
+    model = S.Model()
+    expects = model.replay(steps, oracle)
+    asks = [e.step["op"] in ("query", "render", "pass") for e in expects]
+    xs = [S.inputs(oracle, e.step, e.state) if a else None for e, a in zip(expects, asks)]
+    devs = [{k: _dev(v) for k, v in x.items() if isinstance(v, np.ndarray)} if x is not None else None for x in xs]
+    torch.cuda.synchronize()                              # the operands are on the device; from here on nothing waits
+
+    ctx = tor.Context(0)
+    env = {"open": {}, "film": tor.Film(ctx, *S.FILM, moments=True, counts=True)}
+    kept, ranges = {}, {}
+    try:
+        for i, e in enumerate(expects):
+            step, op = e.step, e.step["op"]
+            call = None
+            if op == "upload":
+                call = lambda: ctx.upload(_scene(tor, step["scene"], bool(step.get("bad"))).list())
+            elif op == "set_groups":
+                n = len(S.records(e.state.scene))
+                call = lambda: ctx.set_groups(S.words(step["words"], n))
+            elif op == "set_lights":
+                call = lambda: ctx.set_lights(*S.light_table(step["table"])) if step["table"] else ctx.set_lights([])
+            elif op == "set_environment":
+                call = lambda: ctx.set_environment(*S.env_map(step["map"])[:2]) if step["map"] else ctx.set_environment(None)
+            else:
+                host = bool(step.get("host")) and step["family"] != "deposit" and op == "query"
+                env["x"], env["dev"] = xs[i], devs[i]
+                operand = lambda k: (xs[i].get(k) if host else devs[i].get(k))
+                call = lambda: _call(tor, ctx, step, operand, env)
+            where = f"{name}: step {i} {step} under {e.state.key()}"
+            try:
+                got = call()
+            except tor.TorError as err:
+                assert e.refuse is not None, f"{where} raised {err}"
+                assert err.code == e.refuse[0] and e.refuse[1] in str(err), f"{where} was refused with {err}"
+                continue
+            assert e.refuse is None, f"{where} was not refused {e.refuse}"
+            if asks[i]:
+                kept[i] = got[0]
+                times = xs[i].get("points", xs[i].get("rays"))[:, -1] if S.takes_mode(step["family"]) else None
+                _check_what_ran(tor, step, e.state, got[1], S.Model().effective_range(step, times) if times is not None else None)
+        assert tuple(ctx.scene_counters()[:2]) == (model.n_uploads, model.n_cache_hits)
+        torch.cuda.synchronize()
+
+        bad = []
+        film, sums = D.deposit(np.zeros((0, 3)), np.zeros(0, dtype=np.int32), S.FILM[0] * S.FILM[1]), np.zeros((R.H * R.W, 3))
+        for i, e in enumerate(expects):
+            if i not in kept:
+                continue
+            want = S.answer(oracle, e.step, xs[i], e.state)
+            f = e.step["family"]
+            if f == "deposit":                            # the film stays open: every deposit so far, in any order
+                film = D.deposit(xs[i]["colors"], xs[i]["pixels"], S.FILM[0] * S.FILM[1], 1.0, None, film)
+                continue
+            if f == "progressive":
+                sums = sums + want["sums"]               # (multiples of 2^-36 far below 2^17: the sum is exact)
+                continue
+            if f == "pixel_progressive":
+                last_canvas = want["pixels"]
+                continue
+            got = _records_as_fields(kept[i])
+            rows = S.differing_rows(want, {k: got[k].reshape(np.asarray(want[k]).shape) for k in want})
+            if rows.any():
+                bad.append((i, f, f"{int(rows.sum())} of {rows.size} rows", {k: v for k, v in e.step.items() if k != "op"}, e.state.key()))
+        fl = env["film"]
+        got_film = {"sums": _host(fl.sums).reshape(-1, 3), "moments": _host(fl.moments).reshape(-1, 3), "counts": _host(fl.counts).reshape(-1),
+                    "rejected": int(fl.rejected())}
+        if D.mismatches(got_film, film):
+            bad.append(("film", D.mismatches(got_film, film)))
+        pg, pp = env["open"]["progressive"], env["open"]["pixel_progressive"]
+        assert pg.samples == pp.samples == 6
+        if S.differing_rows({"sums": sums}, {"sums": _host(pg.sums).reshape(-1, 3)}).any():
+            bad.append(("progressive", "the sums of the two passes are not the oracle's"))
+        if S.differing_rows({"pixels": last_canvas}, {"pixels": _host(pp.image(2.2)).reshape(-1, 3)}).any():
+            bad.append(("pixel_progressive", "the canvas after two passes is not the oracle's"))
+        assert not bad, f"{name}: {len(bad)} steps differ from their restatements: {[b[:3] for b in bad]}; the first in full: {bad[:4]}"
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("name", S.SCRIPTS)
+def test_script_against_the_restatements(tor, oracle, name):
+    import time
+    t = time.perf_counter()
+    _run(tor, oracle, name)
+    print(f"{name}: {len(S.script(name))} steps, {time.perf_counter() - t:.2f} s")
