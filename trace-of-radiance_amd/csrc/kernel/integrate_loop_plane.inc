@@ -3,7 +3,8 @@
 // tor_kernels.hip).
 //   STAGE ONE, wave-uniform: every object through the PLANE screen (tor_screen.hpp: plane_word / plane_word_mov) -- the distance
 //     of its centre's ground projection from the ray's ground track, from {cx', cz'} alone (float32 offsets from the segment's
-//     origin, 8 bytes through the scalar data path, one ahead; plane_word32: 2 v_fma_f32 + 1 v_sub_f32 + the v_alignbit per object)
+//     origin, 8 bytes through the scalar data path -- the whole words' requests by hand, a group of 8 ahead, the blocks' one record
+//     ahead; plane_word32: 2 v_fma_f32 + 1 v_sub_f32 + the v_alignbit per object)
 //     for statics and movers along y at ANY height, from
 //     {c0x, c0z, dcx, dcz} (32 bytes, 5 + 1 instructions) for movers whose centre travels in x or z.  Keeps the spheres within R of
 //     the ground track: ~9 of random_scene's 481 per query.  Whole words (32 slots) run without the per-block bookkeeping.
@@ -98,6 +99,67 @@
                   nw = nw < kQCap - w_count ? nw : kQCap - w_count;
                   unsigned m = 0;
                   int w = 0;
+                  if constexpr (PW == 2 && kPlaneAhead == 1) {
+                    // The float32 records by hand: one s_load_dwordx16 per group of 8 objects, requested a whole group ahead of
+                    // the wait that needs it (two 16-dword buffers in turn; left to the compiler the request sits one object
+                    // ahead, and the first one of a trip right in front of its wait).  A request is in flight only inside
+                    // straight-line code: every trip begins and ends with `ra` landed, so no register the scalar cache still
+                    // writes crosses a branch, where the compiler may copy it.  The running mask goes through every statement: the
+                    // v_alignbit chain pins a group's objects between its two statements.  The last request of a segment reads
+                    // the group behind it: the next segment's records or the table's slack (kPlaneSlackFloats), used by nobody.
+                    if (nw > 0) {
+                      typedef float __attribute__((ext_vector_type(16))) f16v;
+                      f16v ra, rb;
+#define TOR_FEED_REQ(nxt, off) asm volatile("s_load_dwordx16 %0, %3, %4" : "=&s"(nxt), "+v"(m), "+v"(mp) : "s"(rec), "i"(off))
+#define TOR_FEED_WAIT(cur) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(cur), "+v"(m), "+v"(mp))
+#define TOR_FEED_WAIT_REQ(cur, nxt, off) \
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %1, %4, %5" : "+s"(cur), "=&s"(nxt), "+v"(m), "+v"(mp) : "s"(rec), "i"(off))
+                      auto grp = [&](const f16v& b) {
+#pragma unroll
+                        for (int j = 0; j < kBlock; ++j) m = push_bit(m, plane_word32(ps32, b[2 * j], b[2 * j + 1]));
+                      };
+                      // (a finished word is stored BEHIND the next wait, not in front of it: the wait counts LDS writes too)
+                      unsigned mp = 0;
+                      auto store = [&]() {
+                        q[(unsigned)(w_count + w) * 64] = mp;
+                        nz = push_cond(nz, mp != 0u);
+                        w += 1;
+                      };
+                      TOR_FEED_REQ(ra, 0);
+                      TOR_FEED_WAIT(ra);
+#pragma unroll 1
+                      while (w + 2 <= nw) {
+                        m = 0;
+                        TOR_FEED_REQ(rb, 64); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 128); grp(rb);
+                        TOR_FEED_WAIT_REQ(ra, rb, 192); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 256); grp(rb);
+                        mp = m;
+                        m = 0;
+                        TOR_FEED_WAIT_REQ(ra, rb, 320); store(); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 384); grp(rb);
+                        TOR_FEED_WAIT_REQ(ra, rb, 448); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 512); grp(rb);
+                        mp = m;
+                        TOR_FEED_WAIT(ra); store();
+                        rec += PW * 8 * kBlock;
+                      }
+                      if (w < nw) {
+                        m = 0;
+                        TOR_FEED_REQ(rb, 64); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 128); grp(rb);
+                        TOR_FEED_WAIT_REQ(ra, rb, 192); grp(ra);
+                        TOR_FEED_WAIT_REQ(rb, ra, 256); grp(rb);
+                        mp = m;
+                        TOR_FEED_WAIT(ra); store();
+                        rec += PW * 4 * kBlock;
+                      }
+#undef TOR_FEED_REQ
+#undef TOR_FEED_WAIT
+#undef TOR_FEED_WAIT_REQ
+                      n0 = ra[0]; n1 = ra[1];  // the first record behind the words, for the blocks that follow
+                    }
+                  } else {
                   auto word = [&]() {
                     m = 0;
 #pragma unroll
@@ -111,6 +173,7 @@
 #pragma unroll 1
                   while (w + 2 <= nw) { word(); word(); }
                   if (w < nw) word();
+                  }
                   mw = m;
                   i += nw * 4 * kBlock;
                   gb += 4 * nw;

@@ -325,7 +325,7 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
   out.movy.assign(6 * n_movy_p + 8, 0.0);
   out.xrec.assign(n_xrec + 8, 0.0);
   out.xpl.assign(n_xpl + 8, 1e300);  // padding: far from every ground track (a ray that keeps everything keeps it too: the second form drops it)
-  out.xpl32.assign(n_xpl + 16, kPlane32PadX);  // (the same, float32: tor_screen.hpp plane_seg32)
+  out.xpl32.assign(n_xpl + kPlaneSlackFloats, kPlane32PadX);  // (the same, float32: tor_screen.hpp plane_seg32; the slack: stage one's read-ahead)
   for (size_t k = 1; k < out.xpl32.size(); k += 2) out.xpl32[k] = kPlane32PadZ;
   out.xpl32seg.clear();
   out.hot32.assign(n32_floats + 32, 0.0f);

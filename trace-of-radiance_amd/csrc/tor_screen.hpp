@@ -340,6 +340,19 @@ TOR_HD int plane_word_mov(const PlaneSeg& s, double c0x, double c0z, double dcx,
 // xkind 13 (movers in x / z) keeps the float64 chain plane_word_mov.
 // (TOR_SCREEN_MUTATE == 3: the mutation check of this proof -- T = sqrt(thr) rounded to nearest, every margin above dropped; the
 // superset test of tests/test_plane32.py must then FAIL.  Never defined in a product build.)
+// Stage one's whole-word loop requests its float32 records kPlaneAhead groups of 8 objects (one s_load_dwordx16, 16 floats) ahead
+// of the wait that needs them (kernel/integrate_loop_plane.inc), so it reads that far behind a segment's last record: the host
+// keeps kPlaneSlackFloats of padding behind the table (tor_scene.cpp).  0: the compiler's own requests, one record ahead.
+// (-DTOR_PLANE_AHEAD=0: A/B builds only)
+#ifdef TOR_PLANE_AHEAD
+constexpr int kPlaneAhead = TOR_PLANE_AHEAD;
+#else
+constexpr int kPlaneAhead = 1;
+#endif
+static_assert(kPlaneAhead == 0 || kPlaneAhead == 1, "two groups ahead would need scalar loads to return in order");
+constexpr int kPlaneGroupFloats = 16;
+constexpr int kPlaneSlackFloats = 16;
+static_assert(kPlaneSlackFloats >= kPlaneAhead * kPlaneGroupFloats && kPlaneSlackFloats >= 2, "the plane table's slack must cover stage one's read-ahead");
 constexpr float kPlane32PadX = 0x1p100f, kPlane32PadZ = 0x1.3c6ef3p99f;
 constexpr double kPlane32Clamp = 0x1p100;
 struct PlaneSeg32 {  // per ray and segment
