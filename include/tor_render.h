@@ -1009,4 +1009,10 @@ TOR_API const char* tor_version(void);
  * sampling need at a Lambertian or a fuzzy Metal vertex -- defined operation by operation in tor_bsdf.h. */
 #include "tor_bsdf.h"
 
+/* ---- photon-map queries: build a hashed grid, gather by radius, exactly --------------------------------------------------------------
+ * tor_photons_build_device / _host, tor_photons_gather_device / _host, tor_photons_info: light-path vertices stored as photons in a
+ * context-owned map, and per query point the exact sum of the powers of the photons within a radius -- density estimation for
+ * caustics seen through specular vertices -- defined by brute force, operation by operation, in tor_photons.h. */
+#include "tor_photons.h"
+
 #endif /* TOR_RENDER_H */

@@ -18,6 +18,7 @@ GPU is missing.  (The package directory name contains a hyphen; import it with
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 import sys
@@ -178,6 +179,10 @@ CAMERA_SYMBOLS = ["tor_camera_connect_device", "tor_camera_connect_host", "tor_l
 # the BSDF queries (include/tor_bsdf.h), bound as the light entries are
 BSDF_SYMBOLS = ["tor_bsdf_eval_device", "tor_bsdf_eval_host"]
 BSDF_NONE, BSDF_DENSITY, BSDF_DELTA = 0, 1, 2   # TOR_BSDF_*: the kind of a Context.bsdf answer
+# the photon-map queries (include/tor_photons.h), bound as the light entries are
+PHOTON_SYMBOLS = ["tor_photons_build_device", "tor_photons_build_host", "tor_photons_gather_device", "tor_photons_gather_host",
+                  "tor_photons_info"]
+PHOTON_KERNELS = {"constant": 0, "epanechnikov": 1}   # TOR_PHOTON_KERNEL_*: the weight of a photon inside the gather radius
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -247,6 +252,7 @@ def lib():
     _bind_env(L, skip_missing=bool(ab))
     _bind_camera(L, skip_missing=bool(ab))
     _bind_bsdf(L, skip_missing=bool(ab))
+    _bind_photons(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -459,6 +465,29 @@ def _bind_bsdf(L, skip_missing=False) -> None:
         if skip_missing and not hasattr(L, name):
             continue
         getattr(L, name).argtypes = _BSDF_SIGNATURES[name]
+
+
+def _photon_signatures() -> dict:
+    """The ctypes argtypes of the entries of include/tor_photons.h (every one returns int)."""
+    v, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+    return {
+        "tor_photons_build_device": [v, i64, v, v, v, v, i64, f64, v],
+        "tor_photons_build_host": [v, i64, v, v, v, v, i64, f64],
+        "tor_photons_gather_device": [v, i64, v, v, v, v, i64, i32, f64, v, v, v],
+        "tor_photons_gather_host": [v, i64, v, v, v, v, i64, i32, f64, v, v],
+        "tor_photons_info": [v, v],
+    }
+
+
+_PHOTON_SIGNATURES = _photon_signatures()
+
+
+def _bind_photons(L, skip_missing=False) -> None:
+    """_bind for the entries of PHOTON_SYMBOLS."""
+    for name in PHOTON_SYMBOLS:
+        if skip_missing and not hasattr(L, name):
+            continue
+        getattr(L, name).argtypes = _PHOTON_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -1984,6 +2013,207 @@ class Context:
             return offered, rng.cpu().numpy().view(np.uint64), ran
         return offered, rng, ran
 
+    # ---- photon-map queries (tor_photons_build_device, tor_photons_gather_device): density estimation in world space ----
+
+    def build_photons(self, positions, powers, directions=None, radius=None, index=None) -> "PhotonMap":
+        """Build the context's photon map (tor_photons_build_device / tor_photons_build_host; include/tor_photons.h): the listed
+        photons {position, power, incoming direction} are copied into a hashed uniform grid of cell size radius * (1 + 2^-20)
+        that the context owns; it replaces the previous map and survives upload(), set_lights() and set_environment().  A photon
+        with a non-finite position or direction, a NaN, infinite or negative power channel (-0.0 passes) or a cell beyond
+        +-2^30 is dropped and counted.  No scene is needed.
+
+        positions, powers (n, 3) float64, directions (n, 3) or None -- torch CUDA tensors (zero-copy, asynchronous on torch's
+        current stream; the arrays may go once the stream has passed the call) or anything numpy takes (blocking).  radius: the
+        map's gather radius R, finite and > 0.  index: as for deposit() -- None every photon, entries outside [0, n) skipped, a
+        repeated entry stored again.
+
+        The powers are stored times a power of two chosen so that the largest finite channel lies in (1/2, 1] -- exact, short
+        of underflow for channels 2^-1000 below the largest -- which puts them in the range the gather's max_value clamp and
+        2^-36 quantum are made for; PhotonGather.irradiance divides it out again.  (Finding the largest channel of a tensor
+        waits for it.)  Returns a PhotonMap: scale, radius, note and info(), which reads the counts back when it is asked."""
+        if radius is None:
+            raise ValueError("Context.build_photons: radius is required")
+        ops = _operands(self, "photons_build", positions, "positions", 3)
+        n, positions, xp = ops.n, ops.lead, ops.xp
+        powers = ops.rows(powers, "powers", 3)
+        if powers is None:
+            ops.bad("powers", "an (n, 3) float64 array of the positions' kind")
+        directions = ops.rows(directions, "directions", 3)
+        index, n_list, p_list = ops.index(index)
+        top = float(xp.where(xp.isfinite(powers), powers, xp.zeros_like(powers)).max()) if n else 0.0
+        scale = 1.0
+        if top > 0.0:
+            mant, e = math.frexp(top)   # top = mant * 2^e, mant in [1/2, 1)
+            scale = math.ldexp(1.0, -max(min(e - 1 if mant == 0.5 else e, 1000), -1000))
+        scaled = powers * scale
+        ops.call(ops.ptr(positions), ops.ptr(scaled), ops.ptr(directions), p_list, n_list, float(radius))
+        self._photon_scale, self._photon_radius = scale, float(radius)
+        self._photon_keep = ops.keep(positions, scaled, directions, index)   # (alive while the build may still run)
+        return PhotonMap(self, scale, float(radius), last_note())
+
+    def photons_info(self) -> dict:
+        """tor_photons_info: {stored, dropped, n_buckets, largest_bucket} of the context's photon map.  Blocking."""
+        out = (C.c_int64 * 4)()
+        _check(lib().tor_photons_info(self._h, out))
+        return {"stored": int(out[0]), "dropped": int(out[1]), "n_buckets": int(out[2]), "largest_bucket": int(out[3])}
+
+    def gather_photons(self, points, normals=None, radius=None, index=None, kernel="epanechnikov", max_value=1.0, out=None) -> "PhotonGather":
+        """Gather the photon map around points (tor_photons_gather_device / tor_photons_gather_host; include/tor_photons.h): per
+        listed point x, over the stored photons j with d2 = |p_j - x|^2 < r^2 and, with normals, dir_j . n < 0 (strict, NaN
+        fails), sums += quantize36(min(power_j * w, max_value)) per channel and count += 1, w = 1 (kernel "constant") or
+        1 - d2 / r^2 ("epanechnikov").  The answer is the brute-force sum over every stored photon, bit for bit, while
+        count * max_value < 2^17 (PhotonGather.check_budget); the grid only makes it fast.
+
+        points (n, 3) float64, normals (n, 3) or None -- torch CUDA tensors (zero-copy, asynchronous on torch's current stream)
+        or anything numpy takes (blocking).  radius: None (the map's R), a number or one float64 per point; min(radius, R) is
+        used, a negative or NaN radius accepts nothing.  index as for bounce().  0 < max_value <= DEPOSIT_MAX_VALUE, in units of
+        the scaled powers (build_photons).  out: a PhotonGather of an earlier call on as many points, written again (points
+        that are not listed keep what it holds); otherwise a new one (zeros).  Returns a PhotonGather: sums (n, 3), count (n,)
+        int32, and irradiance(paths) / check_budget()."""
+        k = PHOTON_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+        if out is not None and not isinstance(out, PhotonGather):
+            raise ValueError("Context.gather_photons: out must be a PhotonGather")
+        ops = _operands(self, "photons_gather", points, "points", 3)
+        n, points, xp = ops.n, ops.lead, ops.xp
+        normals = ops.rows(normals, "normals", 3)
+        rad = ops.rows(radius, "radius", or_number=True)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            sums, count = ops.new(n, 3), ops.new(n, dtype="int32")
+        else:
+            sums, count = out.sums, out.count
+            if not ops.fits(sums, n, 3) or not ops.fits(count, n, dtype="int32"):
+                ops.bad("out", "the result of a call on as many points, on tensors or arrays as the points are")
+        ops.call(ops.ptr(points), ops.ptr(normals), ops.ptr(rad), p_list, n_list, k, float(max_value), ops.ptr(sums), ops.ptr(count))
+        big = getattr(self, "_photon_radius", None)
+        used = big if rad is None else xp.where(rad < big, rad, xp.full_like(rad, big))   # min(radius, R) as the library takes it
+        return PhotonGather(sums, count, getattr(self, "_photon_scale", 1.0), used, k, float(max_value), ops.note(n_list),
+                            keep=ops.keep(points, normals, rad, index))
+
+    def trace_photons(self, rng, emission, diffuse, max_depth=50, caustic_only=False, lamp_mask=None, time_range=None, mode="auto") -> "Photons":
+        """trace_light's loop without the connections: one light path per state starts on a lamp of the light table
+        (set_lights, emit_lights) with beta = Le * pi / pdf_area; per step the live rays bounce, and every hit on a `diffuse`
+        object stores a photon {p, beta as it ARRIVES (before the surface's albedo), the incoming ray's direction (not
+        normalised: a gather uses only its sign against the normal)}; then beta *= attenuation for the rays that scattered,
+        which stay live, for at most max_depth steps.
+
+        caustic_only: keep a photon only if its path has taken at least one specular step (a hit on an object that is not
+        `diffuse`) and no diffuse one; the path stops at its first diffuse hit.  emission, diffuse, time_range ((lo, hi) of the
+        emission; None: (0, 0)), mode and rng as for trace_light; lamp_mask is accepted for symmetry and unused (there are no
+        connection segments).  Returns Photons(position (m, 3), power (m, 3), direction (m, 3), paths = n, rng, mode): the
+        operands of build_photons.  The powers are NOT divided by the path count: PhotonGather.irradiance(paths) does that, so
+        the photons of several calls concatenate."""
+        import torch
+        as_numpy = not _is_tensor(rng)
+        if as_numpy:
+            st = np.asarray(rng)
+            if st.ndim != 2 or st.shape[1] != 4 or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+                raise ValueError("Context.trace_photons: rng must be an (n, 4) array of 64-bit integers")
+            rng = self._to_device(np.ascontiguousarray(st).view(np.int64))
+        elif rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
+            raise ValueError("Context.trace_photons: rng must be an (n, 4) int64 CUDA tensor")
+        rng = rng.contiguous()
+        n, dev, f64 = int(rng.shape[0]), rng.device, torch.float64
+        tr = (0.0, 0.0) if time_range is None else (float(time_range[0]), float(time_range[1]))
+        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
+        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
+        pos, pw, dr = [], [], []
+        ran = None
+        if n:
+            em = self.emit_lights(rng, tr)
+            work, lamp = em.rays.clone(), em.light.long().clamp(min=0)
+            beta = emission[lamp] * (np.pi / em.pdf_area)[:, None]   # (a lamp of radius 0 has no area: it emits nothing)
+            beta = torch.where((em.light >= 0)[:, None], beta, torch.zeros_like(beta))
+            specular = torch.zeros(n, dtype=torch.bool, device=dev)   # the path has taken a specular step
+            live = torch.arange(n, dtype=torch.int32, device=dev)
+            win, res = torch.empty_like(work), None
+            for step in range(int(max_depth)):
+                if live.numel() == 0:
+                    break
+                win.copy_(work)   # the incoming rays of the step: bounce() writes the scattered ones over `work`
+                res = self.bounce(work, rng, live, tr, mode, out=res)
+                ran = ran or res.mode
+                idx = live.long()
+                st = res.status[idx]
+                obj = res.object[idx].long().clamp(min=0)
+                hit = st != BOUNCE_MISS
+                on_diffuse = hit & diffuse[obj]
+                at = idx[on_diffuse & specular[idx]] if caustic_only else idx[on_diffuse]
+                if at.numel():
+                    pos.append(res.p[at].clone()), pw.append(beta[at].clone()), dr.append(win[at, 3:6].clone())
+                specular[idx[hit & ~diffuse[obj]]] = True
+                live = self.bounce_select(res.status, live)
+                if caustic_only:   # the path stops at its first diffuse hit
+                    live = live[~diffuse[res.object[live.long()].long().clamp(min=0)]]
+                scat = live.long()
+                beta[scat] = beta[scat] * res.attenuation[scat]
+        cat = (lambda parts: torch.cat(parts) if parts else torch.zeros((0, 3), dtype=f64, device=dev))
+        position, power, direction = cat(pos), cat(pw), cat(dr)
+        if as_numpy:
+            return Photons(position.cpu().numpy(), power.cpu().numpy(), direction.cpu().numpy(), n, rng.cpu().numpy().view(np.uint64),
+                           ran or "nothing to do")
+        return Photons(position, power, direction, n, rng, ran or "nothing to do")
+
+    def trace_photon_map(self, rays, rng, emission, diffuse, paths, radius=None, kernel="epanechnikov", max_depth=50, time_range=None,
+                         mode="auto"):
+        """Direct visualisation of the context's photon map (build_photons from trace_photons' photons of `paths` light paths in
+        all, caustic_only=False): every camera ray is followed through its specular steps, with trace()'s bookkeeping, to its
+        first hit on a `diffuse` object, where the map is gathered (gather_photons with the face normal the step returned); the
+        colour is
+            sum over the hits on the way of att * emission[object]  +  att * albedo / pi * irradiance estimate
+        with att the product of the attenuations of the steps before, and albedo the attenuation of the diffuse step.  A ray
+        that misses is black: the sky is no source here (an environment is no lamp of the light table), and neither is it in
+        trace_photons.  The estimator is complete on its own: emission is seen directly or through specular vertices only,
+        every other light path of the scene is in the map once, so nothing is counted twice.  The path ends at that diffuse
+        hit (the albedo is the step's attenuation; a step the material absorbed reflects nothing).  Mixing it with trace_direct
+        is out of scope.
+
+        rays, rng, time_range, mode, max_depth as for trace(); radius, kernel as for gather_photons.  Returns (color (n, 3),
+        rng, the mode that ran)."""
+        import torch
+        as_numpy = not _is_tensor(rays)
+        if as_numpy:
+            host = _Arrays(self, "trace_photon_map", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
+            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
+        ops = _Tensors(self, "trace_photon_map", rays, "rays", 7)
+        rays, n, dev = ops.lead, ops.n, ops.dev
+        rng = ops.states(rng)
+        tr = ops.times(6, time_range)
+        f64 = torch.float64
+        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
+        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
+        work = rays.clone()
+        color = torch.zeros((n, 3), dtype=f64, device=dev)
+        att = torch.ones((n, 3), dtype=f64, device=dev)
+        points, normals = torch.zeros((n, 3), dtype=f64, device=dev), torch.zeros((n, 3), dtype=f64, device=dev)
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        res, ran, gat = None, None, None
+        for step in range(int(max_depth)):
+            if live.numel() == 0:
+                break
+            res = self.bounce(work, rng, live, tr, mode, out=res)
+            ran = ran or res.mode
+            idx = live.long()
+            st = res.status[idx]
+            hit = idx[st != BOUNCE_MISS]
+            obj = res.object[hit].long()
+            color[hit] = color[hit] + att[hit] * emission[obj]
+            at = hit[diffuse[obj]]
+            if at.numel():
+                points[at], normals[at] = res.p[at], res.normal[at]
+                gat = self.gather_photons(points, normals, radius, at.int(), kernel, out=gat)
+                albedo = torch.where((res.status[at] == BOUNCE_SCATTERED)[:, None], res.attenuation[at], torch.zeros_like(att[at]))
+                color[at] = color[at] + att[at] * albedo / np.pi * gat.irradiance(paths)[at]
+            live = self.bounce_select(res.status, live)
+            live = live[~diffuse[res.object[live.long()].long().clamp(min=0)]]
+            scat = live.long()
+            att[scat] = att[scat] * res.attenuation[scat]
+        if ran is None:
+            ran = "nothing to do"
+        if as_numpy:
+            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
+        return color, rng, ran
+
     # ---- environment-light queries (tor_env_eval_device, tor_env_sample_device): the sky as an emitter ----
 
     def environment(self, rays, index=None, out=None, pdf=False):
@@ -2438,6 +2668,67 @@ class BsdfEval:
 
     def __init__(self, value, pdf, kind, note: str, keep=None):
         self.value, self.pdf, self.kind, self.note, self._keep = value, pdf, kind, note, keep
+
+
+class PhotonMap:
+    """What Context.build_photons returns: scale (the power of two the stored powers were multiplied by), radius (the map's R),
+    note (tor_last_note) and info() -- {stored, dropped, n_buckets, largest_bucket}, read back (blocking) when first asked for.
+    The map itself lives in the context; this names the one that was current when it was built."""
+    __slots__ = ("ctx", "scale", "radius", "note", "_info")
+
+    def __init__(self, ctx, scale: float, radius: float, note: str):
+        self.ctx, self.scale, self.radius, self.note, self._info = ctx, scale, radius, note, None
+
+    def info(self) -> dict:
+        if self._info is None:
+            self._info = self.ctx.photons_info()
+        return self._info
+
+
+class Photons:
+    """Context.trace_photons' photons, the operands of Context.build_photons: position, power, direction (m, 3) float64, paths
+    (the number of light paths that were started -- what PhotonGather.irradiance divides by), rng (the states after the paths'
+    last draws) and mode."""
+    __slots__ = ("position", "power", "direction", "paths", "rng", "mode")
+
+    def __init__(self, position, power, direction, paths: int, rng=None, mode: str = ""):
+        self.position, self.power, self.direction, self.paths, self.rng, self.mode = position, power, direction, int(paths), rng, mode
+
+
+class PhotonGather:
+    """Answers of Context.gather_photons, one per point (include/tor_photons.h): sums (n, 3) float64 the clamped, quantised
+    weighted powers (in the map's scaled units), count (n,) int32 the accepted photons; scale, radius (min(radius, R): a number
+    or one per point), kernel (0 constant, 1 Epanechnikov), max_value and note."""
+    __slots__ = ("sums", "count", "scale", "radius", "kernel", "max_value", "note", "_keep")
+
+    def __init__(self, sums, count, scale: float, radius, kernel: int, max_value: float, note: str, keep=None):
+        self.sums, self.count, self.scale, self.radius, self.kernel, self.max_value = sums, count, scale, radius, kernel, max_value
+        self.note, self._keep = note, keep
+
+    def irradiance(self, paths):
+        """The density estimate (n, 3): sums / scale, times the kernel's normalisation -- 1 / (pi r^2) for the constant disc,
+        2 / (pi r^2) for Epanechnikov -- divided by `paths`, the number of light paths behind the map.  0 where nothing was
+        accepted (a radius of 0, negative or NaN among them)."""
+        c = (2.0 if self.kernel == 1 else 1.0) / (math.pi * float(paths) * self.scale)
+        r = self.radius
+        if isinstance(r, (int, float)):
+            return self.sums * (c / (r * r)) if r > 0 else self.sums * 0.0
+        xp = sys.modules["torch"] if _is_tensor(r) else np
+        f = xp.where(self.count > 0, c / (r * r), xp.zeros_like(r))
+        return self.sums * f[:, None]
+
+    def budget(self) -> int:
+        """The most photons a point may accept with exact sums: count * max_value < 2^17."""
+        return int(math.ceil(MAX_ACCUM_SAMPLES / self.max_value)) - 1
+
+    def check_budget(self) -> int:
+        """Raises when a point accepted more photons than budget(), i.e. its sums may have stopped being exact and may depend on
+        the order inside the buckets.  Returns the largest count.  Blocking."""
+        n = int(self.count.max()) if len(self.count) else 0
+        if n > self.budget():
+            raise TorError(ERR_INVALID_ARGUMENT, f"PhotonGather.check_budget: {n} photons at one point, above the exactness bound "
+                                                 f"{self.budget()} of max_value = {self.max_value:g}")
+        return n
 
 
 class EnvEval:

@@ -132,6 +132,15 @@ struct HitQueryState {
   int64_t env_n = 0;                // texels per side, 0: no map
   double env_total = 0.0;           // T, the sum of the importances as the header adds them
   int32_t env_last_row = 0;         // the last row with S_r > 0 (the row search's fallback)
+  // photon-map queries (tor_photons.hip): the map belongs to the context too and survives uploads
+  DeviceBuffer ph_cell;             // per stored photon {cx, cy, cz, 0} int32, in bucket order
+  DeviceBuffer ph_rec;              // per stored photon 9 float64 {position, power, direction}, in bucket order
+  DeviceBuffer ph_start;            // n_buckets + 1 uint32: where each bucket starts; [n_buckets] = the stored count; then 4 int64 of info
+  DeviceBuffer ph_tmp;              // the build's scratch: per list entry its bucket, per bucket a counter, the scan's block sums
+  bool ph_built = false;            // a map exists (an empty one is a map)
+  bool ph_has_dir = false;          // it was built with directions
+  double ph_radius = 0.0, ph_h = 0.0;  // R and the cell size h = R + R * 2^-20
+  int64_t ph_buckets = 0;           // n_buckets, a power of two
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

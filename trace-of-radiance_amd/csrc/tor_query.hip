@@ -96,6 +96,10 @@ HitQueryState::~HitQueryState() {
   absr[1].release();
   lights.release();
   env.release();
+  ph_cell.release();
+  ph_rec.release();
+  ph_start.release();
+  ph_tmp.release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 
