@@ -1015,4 +1015,11 @@ TOR_API const char* tor_version(void);
  * caustics seen through specular vertices -- defined by brute force, operation by operation, in tor_photons.h. */
 #include "tor_photons.h"
 
+/* ---- participating-media queries: optical-depth march, isotropic scatter -------------------------------------------------------------
+ * tor_scene_media, tor_media_march_device / _host, tor_media_scatter_device / _host, tor_rng_uniform_device / _host: where along a
+ * ray the optical depth through a table of homogeneous spherical media reaches a budget, the isotropic scatter at that collision,
+ * and plain uniforms from a path's stream -- fog, smoke and haze for host-written integrators, defined operation by operation in
+ * tor_media.h. */
+#include "tor_media.h"
+
 #endif /* TOR_RENDER_H */

@@ -183,6 +183,12 @@ BSDF_NONE, BSDF_DENSITY, BSDF_DELTA = 0, 1, 2   # TOR_BSDF_*: the kind of a Cont
 PHOTON_SYMBOLS = ["tor_photons_build_device", "tor_photons_build_host", "tor_photons_gather_device", "tor_photons_gather_host",
                   "tor_photons_info"]
 PHOTON_KERNELS = {"constant": 0, "epanechnikov": 1}   # TOR_PHOTON_KERNEL_*: the weight of a photon inside the gather radius
+# the participating-media queries (include/tor_media.h), bound as the light entries are
+MEDIA_SYMBOLS = ["tor_scene_media", "tor_media_march_device", "tor_media_march_host", "tor_media_scatter_device",
+                 "tor_media_scatter_host", "tor_rng_uniform_device", "tor_rng_uniform_host"]
+MEDIA_MAX = 64            # TOR_MEDIA_MAX: the most media of a table (the active set of a march is one 64-bit word)
+UNIFORM_MAX_DRAWS = 16    # TOR_UNIFORM_MAX_DRAWS: the most uniforms per state of one Context.uniform call
+MEDIA_REFUSED, MEDIA_ESCAPED, MEDIA_COLLIDED = -1, 0, 1   # the status of a Context.march_media answer
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -253,6 +259,7 @@ def lib():
     _bind_camera(L, skip_missing=bool(ab))
     _bind_bsdf(L, skip_missing=bool(ab))
     _bind_photons(L, skip_missing=bool(ab))
+    _bind_media(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -488,6 +495,31 @@ def _bind_photons(L, skip_missing=False) -> None:
         if skip_missing and not hasattr(L, name):
             continue
         getattr(L, name).argtypes = _PHOTON_SIGNATURES[name]
+
+
+def _media_signatures() -> dict:
+    """The ctypes argtypes of the entries of include/tor_media.h (every one returns int)."""
+    v, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
+    return {
+        "tor_scene_media": [v, i64, v, v, v],
+        "tor_media_march_device": [v, i64, v, v, v, v, i64, v, v, v, v, v, v],
+        "tor_media_march_host": [v, i64, v, v, v, v, i64, v, v, v, v, v],
+        "tor_media_scatter_device": [v, i64, v, v, v, v, v, i64, v, v, v],
+        "tor_media_scatter_host": [v, i64, v, v, v, v, v, i64, v, v],
+        "tor_rng_uniform_device": [v, i64, v, v, i64, i32, v, v],
+        "tor_rng_uniform_host": [v, i64, v, v, i64, i32, v],
+    }
+
+
+_MEDIA_SIGNATURES = _media_signatures()
+
+
+def _bind_media(L, skip_missing=False) -> None:
+    """_bind for the entries of MEDIA_SYMBOLS."""
+    for name in MEDIA_SYMBOLS:
+        if skip_missing and not hasattr(L, name):
+            continue
+        getattr(L, name).argtypes = _MEDIA_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -2370,6 +2402,207 @@ class Context:
             return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
         return color, rng, ran
 
+    # ---- participating media (tor_scene_media, tor_media_march_device, tor_media_scatter_device, tor_rng_uniform_device) ----
+
+    def set_media(self, objects, sigma, albedo=None):
+        """The media table of the uploaded scene (tor_scene_media): `objects` are the indices of the boundary spheres in the
+        uploaded list (unique, at most MEDIA_MAX) -- ordinary scene objects, which a host hides from the surface queries with
+        visibility groups --, `sigma` one extinction per unit length per medium (finite, >= 0), `albedo` None (1, 1, 1) or
+        (n, 3), finite and >= 0.  march_media / scatter_media / transmittance / trace_media read it.  An empty `objects` clears
+        the table, and so does every upload that replaces the scene."""
+        o = np.ascontiguousarray(np.asarray(objects).reshape(-1), dtype=np.int32)
+        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if s.size != o.size:
+            raise ValueError("Context.set_media: one sigma per medium")
+        p_albedo = 0
+        if albedo is not None:
+            a = np.ascontiguousarray(np.asarray(albedo, dtype=np.float64).reshape(-1, 3))
+            if a.shape[0] != o.size:
+                raise ValueError("Context.set_media: albedo must be (n, 3), one colour per medium")
+            p_albedo = a.ctypes.data or 16
+        _check(lib().tor_scene_media(self._h, int(o.size), C.c_void_p(o.ctypes.data or 16), C.c_void_p(s.ctypes.data or 16),
+                                     C.c_void_p(p_albedo)))
+
+    def march_media(self, rays, tau, t_range=None, index=None, out=None) -> "MediaMarch":
+        """The optical-depth march (tor_media_march_device / tor_media_march_host): per listed ray, where along it the accumulated
+        sigma * length through the media of the table (set_media) reaches the budget `tau` -- a collision --, or, if it never
+        does, how much depth the range holds.  The definition, operation by operation in float64, is in include/tor_media.h;
+        overlapping media add their densities in table order.
+
+        rays: (n, 7) float64 -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or anything numpy takes
+        (copied, blocking).  tau: a number or (n,) float64 of the rays' kind; the library takes no logarithm: free-flight sampling
+        passes -log1p(-u) of a uniform (Context.uniform), and tau = inf asks for the depth of the whole range, whose
+        transmittance is exp(-depth).  t_range: None -- (0.0, +inf), NOT the (0.001, +inf) of the surface queries: a scattered
+        ray starts inside the medium -- or (n, 2).  index as for bounce().  Returns a MediaMarch: status (n,) int32
+        (MEDIA_COLLIDED: t is the collision, depth = tau, active the bit set of the media there, rho their summed sigma;
+        MEDIA_ESCAPED: t = t_max, depth what was accumulated; MEDIA_REFUSED: tau not >= 0 or an empty range), t, depth, rho (n,)
+        float64 and active (n,) int64 holding the 64 bits.  out: a MediaMarch of an earlier call on as many rays, written again
+        (rays that are not listed keep what it holds); otherwise a new one (0)."""
+        if out is not None and not isinstance(out, MediaMarch):
+            raise ValueError("Context.march_media: out must be a MediaMarch")
+        ops = _operands(self, "media_march", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        tau = ops.rows(tau, "tau", or_number=True)
+        if tau is None:
+            ops.bad("tau", "a number or an (n,) float64 tensor or array, as the rays are")
+        t_range = ops.rows(t_range, "t_range", 2)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            status, t, depth, active, rho = ops.new(n, dtype="int32"), ops.new(n), ops.new(n), ops.new(n, dtype="int64"), ops.new(n)
+        else:
+            status, t, depth, active, rho = out.status, out.t, out.depth, out.active, out.rho
+            if not ops.fits(status, n, dtype="int32") or not ops.fits(t, n) or not ops.fits(depth, n) \
+                    or not ops.fits(active, n, dtype="int64") or not ops.fits(rho, n):
+                ops.bad("out", "the result of a call on as many rays, on tensors or arrays as the rays are")
+        ops.call(ops.ptr(rays), ops.ptr(t_range), ops.ptr(tau), p_list, n_list, ops.ptr(status), ops.ptr(t), ops.ptr(depth),
+                 ops.ptr(active), ops.ptr(rho))
+        return MediaMarch(status, t, depth, active, rho, ops.note(n_list), keep=ops.keep(rays, t_range, tau, index))
+
+    def scatter_media(self, rays, march, rng, index=None, out=None) -> "MediaScatter":
+        """The isotropic scatter at a collision (tor_media_scatter_device / tor_media_scatter_host): per listed ray the new ray
+        {origin + t * direction, random_unit_vector(rng) (sampling.nim:51-55), time} and the albedo of the mixture there, sum of
+        sigma * albedo over the active media divided by the sum of sigma, in table order.
+
+        rays as for march_media; march: its MediaMarch, or a pair (t, active); rng: (n, 4) 64-bit states as for bounce() -- every
+        listed ray draws exactly two outputs, sampled or not; a contiguous CUDA tensor is updated in place.  index as for
+        bounce(): list the rays whose status is MEDIA_COLLIDED (an entry with no active medium gets attenuation 0 and a zero
+        ray).  Returns a MediaScatter, which unpacks as (rays, attenuation) -- (n, 7) and (n, 3) -- and carries rng and mode.
+        out: a MediaScatter (or a pair) of an earlier call on as many rays, written again; `rays` itself may be passed as out[0]."""
+        ops = _operands(self, "media_scatter", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        t, active = (march.t, march.active) if isinstance(march, MediaMarch) else march
+        t, active = ops.rows(t, "march.t"), ops.rows(active, "march.active", dtype="int64")
+        if t is None or active is None:
+            ops.bad("march", "a MediaMarch or a pair (t, active)")
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            rays_out, att = ops.new(n, 7), ops.new(n, 3)
+        else:
+            rays_out, att = out
+            if not ops.fits(rays_out, n, 7) or not ops.fits(att, n, 3):
+                ops.bad("out", "a pair of contiguous (n, 7) and (n, 3) float64 tensors or arrays, as the rays are")
+        ops.call(ops.ptr(rays), ops.ptr(t), ops.ptr(active), ops.ptr(rng), p_list, n_list, ops.ptr(rays_out), ops.ptr(att))
+        return MediaScatter(rays_out, att, rng, ops.note(n_list), keep=ops.keep(rays, t, active, index))
+
+    def uniform(self, rng, n=1, index=None, out=None):
+        """Plain uniforms from a path's stream (tor_rng_uniform_device / tor_rng_uniform_host): u[i, k] = uniform01(rng[i])
+        (support/rng.nim:129-133) for k = 0 .. n - 1, for every listed state -- what free-flight sampling and Russian roulette
+        draw, without running a sampler that consumes the uniform for a purpose of its own.  It needs no scene.
+
+        rng: (m, 4) 64-bit states -- a CUDA int64 tensor (a contiguous one is advanced in place, asynchronous on torch's current
+        stream) or an array of 64-bit integers (copied, blocking).  1 <= n <= UNIFORM_MAX_DRAWS.  index as for bounce().  out: an
+        (m, n) float64 buffer of the states' kind, written again (states that are not listed keep what it holds); otherwise a
+        new one (0).  Returns a Uniforms, which unpacks as (u, rng): the uniforms and the advanced states."""
+        n = int(n)
+        if not 1 <= n <= UNIFORM_MAX_DRAWS:
+            raise ValueError(f"Context.uniform: n must be in 1 .. {UNIFORM_MAX_DRAWS}")
+        if _is_tensor(rng):
+            import torch
+            if rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
+                raise ValueError("Context.uniform: rng must be an (m, 4) int64 CUDA tensor")
+            st = rng.contiguous()
+            ops = _Tensors(self, "rng_uniform", st.view(torch.float64), "rng", 4)
+        else:
+            st = np.asarray(rng)
+            if st.ndim != 2 or st.shape[1] != 4 or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
+                raise ValueError("Context.uniform: rng must be an (m, 4) array of 64-bit integers")
+            st = np.ascontiguousarray(st).view(np.uint64).copy()
+            ops = _Arrays(self, "rng_uniform", st.view(np.float64), "rng", 4)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            out = ops.new(ops.n, n)
+        elif not ops.fits(out, ops.n, n):
+            ops.bad("out", "a contiguous (m, n) float64 tensor or array, as the states are")
+        ops.call(ops.ptr(ops.lead), p_list, n_list, n, ops.ptr(out))
+        return Uniforms(out, st, ops.note(n_list), keep=ops.keep(index))
+
+    def transmittance(self, p, q, time=0.0, mask=None):
+        """The transmittance of the segments p -> q through the media of the table: exp(-depth) of march_media on the rays
+        p -> q - p with range (0, 1) and tau = inf -- the exp is torch's or numpy's, as p is; the library computes the depth
+        alone.  mask: None, or what may stand in the way as for visible(): the result is then multiplied by visible(p, q, time,
+        mask=mask).  One value per segment, a tensor or an array as p is."""
+        rays, tr = self.shadow_segments(p, q, time, 0.0)
+        depth = self.march_media(rays, float("inf"), tr).depth
+        if _is_tensor(depth):
+            import torch
+            tm = torch.exp(-depth)
+        else:
+            tm = np.exp(-depth)
+        if mask is not None:
+            tm = tm * self.visible(p, q, time, mask=mask)
+        return tm
+
+    def trace_media(self, rays, rng, max_depth=50, sky=None, mask=None, free_flight=None):
+        """The volumetric twin of trace(): a wavefront path tracer through the surfaces of the scene and the media of the table.
+        att = 1; per iteration, for the live rays, in this order: hit() with `mask` (the surfaces a ray sees; the media's
+        boundary spheres belong to a group the mask leaves out); ONE uniform01 per live ray (uniform()); tau = free_flight(u),
+        default -log1p(-u) (torch's: the library takes no logarithm); march_media() with range (0, the hit's t or +inf).  A ray
+        that collided scatters isotropically (scatter_media(): two more outputs of its stream) and att *= the mixture's albedo;
+        one that reached its surface scatters as the reference's material does (scatter(): that material's draws), att *= its
+        attenuation, and an absorbed ray ends black; one that reached nothing ends with sky * att.  Rays still live after
+        max_depth iterations are black.  So the draw order of a path is, per iteration, the free-flight uniform first, then
+        the draws of whichever scatter it met.  Returns (color (n, 3), rng (n, 4) after the path's last draw).
+
+        sky: None (Context.sky) or sky(rays, index) -> (len(index), 3), as for trace().  mask: as for hit(), or a callable
+        mask(step).  free_flight: a callable on the (n,) tensor of uniforms giving tau (every entry is evaluated, the live ones
+        are used).  hit() takes no list, so every iteration's closest-hit launch runs on all n rays and the hits of the rays
+        that have ended are not read; uniform, march_media and the two scatters run on the live list.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the
+        device and come back as numpy."""
+        import torch
+        as_numpy = not _is_tensor(rays)
+        if as_numpy:
+            host = _Arrays(self, "trace_media", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
+            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
+        ops = _Tensors(self, "trace_media", rays, "rays", 7)
+        rays, n, dev = ops.lead, ops.n, ops.dev
+        rng = ops.states(rng)
+        tr = ops.times(6, None)
+        work = rays.clone()
+        color = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        att = torch.ones((n, 3), dtype=torch.float64, device=dev)
+        inf = torch.full((n,), float("inf"), dtype=torch.float64, device=dev)
+        t_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+        u = torch.zeros((n, 1), dtype=torch.float64, device=dev)
+        live = torch.arange(n, dtype=torch.int32, device=dev)
+        march, nxt = None, None
+        for step in range(int(max_depth)):
+            if live.numel() == 0:
+                break
+            hit = self.hit(work, time_range=tr, mask=mask(step) if callable(mask) else mask)
+            u, rng = self.uniform(rng, 1, index=live, out=u)
+            tau = -torch.log1p(-u[:, 0]) if free_flight is None else \
+                torch.as_tensor(free_flight(u[:, 0]), dtype=torch.float64).to(dev).reshape(n)
+            t_range[:, 1] = torch.where(hit.object >= 0, hit.t, inf)
+            march = self.march_media(work, tau, t_range, index=live, out=march)
+            idx = live.long()
+            st, obj = march.status[idx], hit.object[idx]
+            collided = live[st == MEDIA_COLLIDED]
+            surface = live[(st == MEDIA_ESCAPED) & (obj >= 0)]
+            missed = live[(st == MEDIA_ESCAPED) & (obj < 0)]
+            alive = torch.zeros((n,), dtype=torch.bool, device=dev)
+            if missed.numel():
+                mi = missed.long()
+                c = self.sky(work, missed)[mi] if sky is None else \
+                    torch.as_tensor(sky(work, missed), dtype=torch.float64).to(dev).reshape(-1, 3)
+                color[mi] = c * att[mi]
+            if surface.numel():
+                res = self.scatter(work, hit, rng, index=surface)
+                si = surface.long()
+                sc = si[res.status[si] == BOUNCE_SCATTERED]
+                att[sc] = att[sc] * res.attenuation[sc]
+                alive[sc] = True
+            if collided.numel():
+                nxt = self.scatter_media(work, march, rng, index=collided, out=nxt)
+                ci = collided.long()
+                work[ci] = nxt.rays[ci]
+                att[ci] = att[ci] * nxt.attenuation[ci]
+                alive[ci] = True
+            live = torch.nonzero(alive).reshape(-1).int()
+        if as_numpy:
+            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64)
+        return color, rng
+
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
@@ -2729,6 +2962,38 @@ class PhotonGather:
             raise TorError(ERR_INVALID_ARGUMENT, f"PhotonGather.check_budget: {n} photons at one point, above the exactness bound "
                                                  f"{self.budget()} of max_value = {self.max_value:g}")
         return n
+
+
+class MediaMarch:
+    """The answers of Context.march_media, one per ray (include/tor_media.h): status (n,) int32 (MEDIA_COLLIDED / MEDIA_ESCAPED /
+    MEDIA_REFUSED), t, depth and rho (n,) float64, active (n,) int64 holding the 64 bits of the active set -- torch tensors or numpy
+    arrays, as the rays were; rays that were not listed keep what `out` held.  `mode` is the library's note ("5 media")."""
+
+    def __init__(self, status, t, depth, active, rho, note: str, keep=None):
+        self.status, self.t, self.depth, self.active, self.rho, self._keep = status, t, depth, active, rho, keep
+        self.mode = _mode_of(note, "media march: ")
+
+
+class MediaScatter(tuple):
+    """The answers of Context.scatter_media: the pair (rays (n, 7), attenuation (n, 3)), which also carries them by name with rng
+    ((n, 4), the states as the scatter left them) and `mode`, the library's note."""
+
+    def __new__(cls, rays, attenuation, rng, note: str, keep=None):
+        self = super().__new__(cls, (rays, attenuation))
+        self.rays, self.attenuation, self.rng, self._keep = rays, attenuation, rng, keep
+        self.mode = _mode_of(note, "media scatter: ")
+        return self
+
+
+class Uniforms(tuple):
+    """The answers of Context.uniform: the pair (u (m, n) float64, rng (m, 4), the states as the draws left them), which also carries
+    them by name with `mode`, the library's note."""
+
+    def __new__(cls, u, rng, note: str, keep=None):
+        self = super().__new__(cls, (u, rng))
+        self.u, self.rng, self._keep = u, rng, keep   # (keep: the list stays alive while the query may run)
+        self.mode = _mode_of(note, "rng uniform: ")
+        return self
 
 
 class EnvEval:

@@ -487,6 +487,7 @@ int tor_scene_upload(TorContext* ctx, TorHittableList world) {
   ctx->hitq.groups.clear();  // a new scene: every object in every group (tor_scene_groups)
   ctx->hitq.groups_gen += 1;
   ctx->hitq.n_lights = 0;    // ... and no light table (tor_scene_lights)
+  ctx->hitq.n_media = 0;     // ... and no media table (tor_scene_media)
   ctx->scene_ready = true;
   return TOR_OK;
 }

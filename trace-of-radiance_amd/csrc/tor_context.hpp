@@ -141,6 +141,9 @@ struct HitQueryState {
   bool ph_has_dir = false;          // it was built with directions
   double ph_radius = 0.0, ph_h = 0.0;  // R and the cell size h = R + R * 2^-20
   int64_t ph_buckets = 0;           // n_buckets, a power of two
+  // participating-media queries (tor_media.hip)
+  DeviceBuffer media;               // the media table (tor_scene_media): 16 float64 per medium, packed when the table is set
+  int64_t n_media = 0;              // 0: no table (the state after every upload that replaces the scene)
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

@@ -95,6 +95,7 @@ HitQueryState::~HitQueryState() {
   absr[0].release();
   absr[1].release();
   lights.release();
+  media.release();
   env.release();
   ph_cell.release();
   ph_rec.release();
