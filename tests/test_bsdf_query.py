@@ -285,7 +285,7 @@ def test_g_the_entries_are_declared_bound_and_exported(tor):
     assert tor.BSDF_SYMBOLS == ["tor_bsdf_eval_device", "tor_bsdf_eval_host"]
     for name in tor.BSDF_SYMBOLS:
         assert re.search(r"TOR_API\s+int\s+" + name + r"\s*\(", src), f"{name} is not declared in tor_bsdf.h"
-        assert hasattr(L, name) and getattr(L, name).argtypes == tor._bsdf_signatures()[name]
+        assert hasattr(L, name) and getattr(L, name).argtypes == tor._signatures()[name]
     assert sorted(tor.BSDF_SYMBOLS) == sorted(set(re.findall(r"TOR_API\s+int\s+(tor_\w+)\s*\(", src)))
     assert (tor.BSDF_NONE, tor.BSDF_DENSITY, tor.BSDF_DELTA) == (R.NONE, R.DENSITY, R.DELTA) == (0, 1, 2)
     assert re.search(r"TOR_BSDF_NONE = 0, TOR_BSDF_DENSITY = 1, TOR_BSDF_DELTA = 2", src)

@@ -159,7 +159,7 @@ def test_e_the_entries_are_declared_bound_and_built(tor):
                                  "tor_media_scatter_host", "tor_rng_uniform_device", "tor_rng_uniform_host"]
     for name in tor.MEDIA_SYMBOLS:
         assert re.search(r"TOR_API\s+int\s+" + name + r"\s*\(", src), f"{name} is not declared in tor_media.h"
-        assert hasattr(L, name) and getattr(L, name).argtypes == tor._media_signatures()[name]
+        assert hasattr(L, name) and getattr(L, name).argtypes == tor._signatures()[name]
         assert name not in tor.EXPORTED_SYMBOLS
     assert sorted(tor.MEDIA_SYMBOLS) == sorted(set(re.findall(r"TOR_API\s+int\s+(tor_\w+)\s*\(", src)))
     assert re.search(r"#define TOR_MEDIA_MAX 64\b", src) and tor.MEDIA_MAX == R.MEDIA_MAX == 64

@@ -168,7 +168,7 @@ def test_e_the_entries_are_declared_bound_and_exported(tor):
                                   "tor_photons_gather_host", "tor_photons_info"]
     for name in tor.PHOTON_SYMBOLS:
         assert re.search(r"TOR_API\s+int\s+" + name + r"\s*\(", src), f"{name} is not declared in tor_photons.h"
-        assert hasattr(L, name) and getattr(L, name).argtypes == tor._photon_signatures()[name]
+        assert hasattr(L, name) and getattr(L, name).argtypes == tor._signatures()[name]
         assert name not in tor.EXPORTED_SYMBOLS
     assert sorted(tor.PHOTON_SYMBOLS) == sorted(set(re.findall(r"TOR_API\s+int\s+(tor_\w+)\s*\(", src)))
     assert tor.PHOTON_KERNELS == R.KERNELS == {"constant": 0, "epanechnikov": 1}

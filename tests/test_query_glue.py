@@ -406,7 +406,8 @@ def test_refused_calls_raise_before_any_entry(glue, tor):
     glue.refused(ValueError, "scatter", r, np.zeros((4, 8)), np.zeros((5, 4), dtype=np.uint64))
 
 
-# the ctypes signature of every exported symbol: "argtypes" ("-": none set) and restype; *x is POINTER(x)
+# the ctypes signature of every exported symbol, of tor_render.h and of the six later headers: "argtypes" ("-": none set) and
+# restype; *x is POINTER(x)
 SIGNATURES = {
     "tor_render": ("*CanvasStruct *Camera HittableList i64", "i32"),
     "tor_render_opt": ("*CanvasStruct *Camera HittableList i64 *Options", "i32"),
@@ -498,6 +499,41 @@ SIGNATURES = {
     "tor_nearest_device": ("v i64 v v v i64 i32 v u32 d d i32 v v v", "i32"),
     "tor_nearest_host": ("v i64 v v v i64 i32 v u32 d d i32 v v", "i32"),
     "tor_deposit_device": ("v i64 v v v i64 d i64 v v v v v", "i32"),
+    # the later headers' entries, from their declarations (every pointer but the camera's is passed as an address)
+    # include/tor_lights.h
+    "tor_scene_lights": ("v i64 v v", "i32"),
+    "tor_light_sample_device": ("v i64 v v v i64 i32 v v v v v", "i32"),
+    "tor_light_sample_host": ("v i64 v v v i64 i32 v v v v", "i32"),
+    "tor_light_pdf_device": ("v i64 v v v i64 i32 v v", "i32"),
+    "tor_light_pdf_host": ("v i64 v v v i64 i32 v", "i32"),
+    # include/tor_env.h
+    "tor_scene_environment": ("v i64 v v", "i32"),
+    "tor_env_sample_device": ("v i64 v v v i64 v v v v v", "i32"),
+    "tor_env_sample_host": ("v i64 v v v i64 v v v v", "i32"),
+    "tor_env_eval_device": ("v i64 v v i64 v v v v", "i32"),
+    "tor_env_eval_host": ("v i64 v v i64 v v v", "i32"),
+    # include/tor_camera.h
+    "tor_camera_connect_device": ("v *Camera i32 i32 i64 v v v i64 v v v v v", "i32"),
+    "tor_camera_connect_host": ("v *Camera i32 i32 i64 v v v i64 v v v v", "i32"),
+    "tor_light_emit_device": ("v i64 v v i64 d d v v v v v", "i32"),
+    "tor_light_emit_host": ("v i64 v v i64 d d v v v v", "i32"),
+    # include/tor_bsdf.h
+    "tor_bsdf_eval_device": ("v i64 v v v v i64 v v v v", "i32"),
+    "tor_bsdf_eval_host": ("v i64 v v v v i64 v v v", "i32"),
+    # include/tor_photons.h
+    "tor_photons_build_device": ("v i64 v v v v i64 d v", "i32"),
+    "tor_photons_build_host": ("v i64 v v v v i64 d", "i32"),
+    "tor_photons_gather_device": ("v i64 v v v v i64 i32 d v v v", "i32"),
+    "tor_photons_gather_host": ("v i64 v v v v i64 i32 d v v", "i32"),
+    "tor_photons_info": ("v v", "i32"),
+    # include/tor_media.h
+    "tor_scene_media": ("v i64 v v v", "i32"),
+    "tor_media_march_device": ("v i64 v v v v i64 v v v v v v", "i32"),
+    "tor_media_march_host": ("v i64 v v v v i64 v v v v v", "i32"),
+    "tor_media_scatter_device": ("v i64 v v v v v i64 v v v", "i32"),
+    "tor_media_scatter_host": ("v i64 v v v v v i64 v v", "i32"),
+    "tor_rng_uniform_device": ("v i64 v v i64 i32 v v", "i32"),
+    "tor_rng_uniform_host": ("v i64 v v i64 i32 v", "i32"),
 }
 
 
@@ -510,8 +546,11 @@ def test_every_exported_symbol_keeps_its_signature(tor):
             return C.POINTER(of(token[1:]))
         return simple[token] if token in simple else getattr(tor, token)
 
-    assert sorted(SIGNATURES) == sorted(set(tor.EXPORTED_SYMBOLS))
-    L = types.SimpleNamespace(**{name: types.SimpleNamespace(argtypes=None, restype=C.c_int) for name in tor.EXPORTED_SYMBOLS})
+    every = (tor.EXPORTED_SYMBOLS + tor.LIGHT_SYMBOLS + tor.ENV_SYMBOLS + tor.CAMERA_SYMBOLS + tor.BSDF_SYMBOLS + tor.PHOTON_SYMBOLS
+             + tor.MEDIA_SYMBOLS)
+    assert len(set(every)) == len(set(tor.EXPORTED_SYMBOLS)) + 28          # (the six later lists share no name with any other)
+    assert sorted(SIGNATURES) == sorted(set(every))
+    L = types.SimpleNamespace(**{name: types.SimpleNamespace(argtypes=None, restype=C.c_int) for name in every})
     tor._bind(L)
     for name, (argtypes, restype) in SIGNATURES.items():
         fn = getattr(L, name)

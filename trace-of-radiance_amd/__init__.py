@@ -254,12 +254,6 @@ def lib():
         print(f"trace-of-radiance_amd: TOR_AB_LIB set -- loading {ab} instead of the in-tree library", file=sys.stderr, flush=True)
     L = C.CDLL(ab or LIB_PATH)
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
-    _bind_lights(L, skip_missing=bool(ab))
-    _bind_env(L, skip_missing=bool(ab))
-    _bind_camera(L, skip_missing=bool(ab))
-    _bind_bsdf(L, skip_missing=bool(ab))
-    _bind_photons(L, skip_missing=bool(ab))
-    _bind_media(L, skip_missing=bool(ab))
     _lib = L
     return L
 
@@ -365,6 +359,40 @@ def _signatures() -> dict:
         "tor_nearest_device": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v, v],
         "tor_nearest_host": [v, i64, v, v, v, i64, i32, v, u32, d, d, i32, v, v],
         "tor_deposit_device": [v, i64, v, v, v, i64, d, i64, v, v, v, v, v],
+        # include/tor_lights.h
+        "tor_scene_lights": [v, i64, v, v],
+        "tor_light_sample_device": [v, i64, v, v, v, i64, i32, v, v, v, v, v],
+        "tor_light_sample_host": [v, i64, v, v, v, i64, i32, v, v, v, v],
+        "tor_light_pdf_device": [v, i64, v, v, v, i64, i32, v, v],
+        "tor_light_pdf_host": [v, i64, v, v, v, i64, i32, v],
+        # include/tor_env.h
+        "tor_scene_environment": [v, i64, v, v],
+        "tor_env_sample_device": [v, i64, v, v, v, i64, v, v, v, v, v],
+        "tor_env_sample_host": [v, i64, v, v, v, i64, v, v, v, v],
+        "tor_env_eval_device": [v, i64, v, v, i64, v, v, v, v],
+        "tor_env_eval_host": [v, i64, v, v, i64, v, v, v],
+        # include/tor_camera.h
+        "tor_camera_connect_device": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v, v],
+        "tor_camera_connect_host": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v],
+        "tor_light_emit_device": [v, i64, v, v, i64, d, d, v, v, v, v, v],
+        "tor_light_emit_host": [v, i64, v, v, i64, d, d, v, v, v, v],
+        # include/tor_bsdf.h
+        "tor_bsdf_eval_device": [v, i64, v, v, v, v, i64, v, v, v, v],
+        "tor_bsdf_eval_host": [v, i64, v, v, v, v, i64, v, v, v],
+        # include/tor_photons.h
+        "tor_photons_build_device": [v, i64, v, v, v, v, i64, d, v],
+        "tor_photons_build_host": [v, i64, v, v, v, v, i64, d],
+        "tor_photons_gather_device": [v, i64, v, v, v, v, i64, i32, d, v, v, v],
+        "tor_photons_gather_host": [v, i64, v, v, v, v, i64, i32, d, v, v],
+        "tor_photons_info": [v, v],
+        # include/tor_media.h
+        "tor_scene_media": [v, i64, v, v, v],
+        "tor_media_march_device": [v, i64, v, v, v, v, i64, v, v, v, v, v, v],
+        "tor_media_march_host": [v, i64, v, v, v, v, i64, v, v, v, v, v],
+        "tor_media_scatter_device": [v, i64, v, v, v, v, v, i64, v, v, v],
+        "tor_media_scatter_host": [v, i64, v, v, v, v, v, i64, v, v],
+        "tor_rng_uniform_device": [v, i64, v, v, i64, i32, v, v],
+        "tor_rng_uniform_host": [v, i64, v, v, i64, i32, v],
     }
 
 
@@ -384,142 +412,6 @@ def _bind(L, names=None, skip_missing=False) -> None:
             fn.argtypes = argtypes
         if restype:
             fn.restype = restype[0]
-
-
-def _light_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_lights.h (every one returns int)."""
-    v, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    return {
-        "tor_scene_lights": [v, i64, v, v],
-        "tor_light_sample_device": [v, i64, v, v, v, i64, i32, v, v, v, v, v],
-        "tor_light_sample_host": [v, i64, v, v, v, i64, i32, v, v, v, v],
-        "tor_light_pdf_device": [v, i64, v, v, v, i64, i32, v, v],
-        "tor_light_pdf_host": [v, i64, v, v, v, i64, i32, v],
-    }
-
-
-_LIGHT_SIGNATURES = _light_signatures()
-
-
-def _bind_lights(L, skip_missing=False) -> None:
-    """_bind for the entries of LIGHT_SYMBOLS."""
-    for name in LIGHT_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _LIGHT_SIGNATURES[name]
-
-
-def _env_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_env.h (every one returns int)."""
-    v, i64 = C.c_void_p, C.c_int64
-    return {
-        "tor_scene_environment": [v, i64, v, v],
-        "tor_env_sample_device": [v, i64, v, v, v, i64, v, v, v, v, v],
-        "tor_env_sample_host": [v, i64, v, v, v, i64, v, v, v, v],
-        "tor_env_eval_device": [v, i64, v, v, i64, v, v, v, v],
-        "tor_env_eval_host": [v, i64, v, v, i64, v, v, v],
-    }
-
-
-_ENV_SIGNATURES = _env_signatures()
-
-
-def _bind_env(L, skip_missing=False) -> None:
-    """_bind for the entries of ENV_SYMBOLS."""
-    for name in ENV_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _ENV_SIGNATURES[name]
-
-
-def _camera_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_camera.h (every one returns int)."""
-    v, i32, i64, d, cam = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER(Camera)
-    return {
-        "tor_camera_connect_device": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v, v],
-        "tor_camera_connect_host": [v, cam, i32, i32, i64, v, v, v, i64, v, v, v, v],
-        "tor_light_emit_device": [v, i64, v, v, i64, d, d, v, v, v, v, v],
-        "tor_light_emit_host": [v, i64, v, v, i64, d, d, v, v, v, v],
-    }
-
-
-_CAMERA_SIGNATURES = _camera_signatures()
-
-
-def _bind_camera(L, skip_missing=False) -> None:
-    """_bind for the entries of CAMERA_SYMBOLS."""
-    for name in CAMERA_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _CAMERA_SIGNATURES[name]
-
-
-def _bsdf_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_bsdf.h (every one returns int)."""
-    v, i64 = C.c_void_p, C.c_int64
-    return {
-        "tor_bsdf_eval_device": [v, i64, v, v, v, v, i64, v, v, v, v],
-        "tor_bsdf_eval_host": [v, i64, v, v, v, v, i64, v, v, v],
-    }
-
-
-_BSDF_SIGNATURES = _bsdf_signatures()
-
-
-def _bind_bsdf(L, skip_missing=False) -> None:
-    """_bind for the entries of BSDF_SYMBOLS."""
-    for name in BSDF_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _BSDF_SIGNATURES[name]
-
-
-def _photon_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_photons.h (every one returns int)."""
-    v, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
-    return {
-        "tor_photons_build_device": [v, i64, v, v, v, v, i64, f64, v],
-        "tor_photons_build_host": [v, i64, v, v, v, v, i64, f64],
-        "tor_photons_gather_device": [v, i64, v, v, v, v, i64, i32, f64, v, v, v],
-        "tor_photons_gather_host": [v, i64, v, v, v, v, i64, i32, f64, v, v],
-        "tor_photons_info": [v, v],
-    }
-
-
-_PHOTON_SIGNATURES = _photon_signatures()
-
-
-def _bind_photons(L, skip_missing=False) -> None:
-    """_bind for the entries of PHOTON_SYMBOLS."""
-    for name in PHOTON_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _PHOTON_SIGNATURES[name]
-
-
-def _media_signatures() -> dict:
-    """The ctypes argtypes of the entries of include/tor_media.h (every one returns int)."""
-    v, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-    return {
-        "tor_scene_media": [v, i64, v, v, v],
-        "tor_media_march_device": [v, i64, v, v, v, v, i64, v, v, v, v, v, v],
-        "tor_media_march_host": [v, i64, v, v, v, v, i64, v, v, v, v, v],
-        "tor_media_scatter_device": [v, i64, v, v, v, v, v, i64, v, v, v],
-        "tor_media_scatter_host": [v, i64, v, v, v, v, v, i64, v, v],
-        "tor_rng_uniform_device": [v, i64, v, v, i64, i32, v, v],
-        "tor_rng_uniform_host": [v, i64, v, v, i64, i32, v],
-    }
-
-
-_MEDIA_SIGNATURES = _media_signatures()
-
-
-def _bind_media(L, skip_missing=False) -> None:
-    """_bind for the entries of MEDIA_SYMBOLS."""
-    for name in MEDIA_SYMBOLS:
-        if skip_missing and not hasattr(L, name):
-            continue
-        getattr(L, name).argtypes = _MEDIA_SIGNATURES[name]
 
 
 def _check(rc: int) -> None:
@@ -1738,139 +1630,6 @@ class Context:
         ops.call(ops.ptr(rays_in), ops.ptr(raw), ops.ptr(rays_out), p_list, n_list, ops.ptr(value), ops.ptr(pdf), ops.ptr(kind))
         return BsdfEval(value, pdf, kind, ops.note(n_list), keep=ops.keep(rays_in, raw, rays_out, index))
 
-    def trace_direct(self, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=False, lamp_mask=None, time_range=None,
-                     mode="auto", strategy="solid_angle", glossy=None):
-        """trace()'s loop with next-event estimation: after each bounce, the rays that hit a diffuse object sample one light of
-        the table (sample_lights), ask occluded() whether the segment to the sampled surface point is free, and add
-            att * albedo / pi * emission[light] * max(0, n . unit(dir)) / pdf
-        where it is.  Emission FOUND by hitting an object counts only at step 0 or after a Metal / Dielectric bounce -- or, with
-        mis=True, everywhere with balance-heuristic weights: light_pdf against the Lambertian density cos / pi, on both sides.
-        Every emitter that diffuse surfaces are to see must be in the light table (set_lights).  The last of the max_depth steps
-        samples no light, so both ways of finding a lamp follow paths of the same lengths, trace()'s.
-
-        emission: (n_objects, 3) float64.  diffuse: (n_objects,) bool (diffuse_objects(scene)).  lamp_mask: the occluded() mask
-        of the shadow segments; with one, their range is (0.001, 1.0) and the mask must leave the lamps' group out (set_groups);
-        None: every group, and the range ends at 1 - 1e-9 instead, just short of the sampled surface.  rays, rng, sky,
-        time_range, mode and the result (color, rng, mode) as for trace(); strategy as for sample_lights.
-
-        glossy: None (the code path above, unchanged in every bit), or (n_objects,) bool (glossy_objects(scene): Metal with
-        fuzz != 0).  With it the material is no longer restated here: a vertex on a diffuse OR a glossy object takes the light
-        sample -- also one whose scattered ray Metal absorbed -- and is no longer booked specular; one bsdf() call gives value
-        and density p_b of the sampled light direction, and the sample adds att * value * emission[light] / pdf where the
-        segment is free and p_b > 0; with mis=True a second bsdf() call gives the density of the direction the path left in,
-        the partner of light_pdf in the balance weights on both sides.
-
-        The light draws come from a second state per path, derived from the path's entry state (splitmix64 finalisers over its
-        words), not from the path state itself: the bounces see exactly the states trace() gives them.  So with an all-zero
-        emission the colours are trace()'s, bit for bit, and the returned states are the path states, as trace() returns
-        them."""
-        import torch
-        as_numpy = not _is_tensor(rays)
-        if as_numpy:
-            host = _Arrays(self, "trace_direct", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
-            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
-        ops = _Tensors(self, "trace_direct", rays, "rays", 7)
-        rays, n, dev = ops.lead, ops.n, ops.dev
-        rng = ops.states(rng)
-        tr = ops.times(6, time_range)
-        f64 = torch.float64
-        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
-        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
-        work = rays.clone()
-        color = torch.zeros((n, 3), dtype=f64, device=dev)
-        att = torch.ones((n, 3), dtype=f64, device=dev)
-        skybuf = torch.zeros((n, 3), dtype=f64, device=dev) if sky is None else None
-        lrng = _light_states(rng.view(torch.int64) if rng.dtype != torch.int64 else rng)
-        points = torch.zeros((n, 4), dtype=f64, device=dev)          # the shading point of every ray's last diffuse hit ...
-        p_bsdf = torch.zeros((n,), dtype=f64, device=dev)            # ... the Lambertian density of the direction it left in ...
-        specular = torch.ones((n,), dtype=torch.bool, device=dev)    # ... or: the ray left a camera, a Metal or a Dielectric
-        t_range = torch.empty((n, 2), dtype=f64, device=dev)
-        t_range[:, 0], t_range[:, 1] = 0.001, (1.0 if lamp_mask is not None else 1.0 - 1e-9)
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        res, ls, occ, ran = None, None, None, None
-        nee_ok, win, ev, ev2 = None, None, None, None
-        if glossy is not None:   # the objects whose vertices take a light sample, and the incoming rays of the step (bsdf's rays_in)
-            glossy = torch.as_tensor(np.asarray(glossy.cpu() if _is_tensor(glossy) else glossy).astype(bool)).to(dev).reshape(-1)
-            nee_ok, win = diffuse | glossy, torch.empty_like(work)
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            if nee_ok is not None:
-                win.copy_(work)
-            res = self.bounce(work, rng, live, tr, mode, out=res)
-            ran = ran or res.mode
-            idx = live.long()
-            st = res.status[idx]
-            if sky is None:
-                self.sky(work, live, out=skybuf)
-                color[idx] = torch.where((st == BOUNCE_MISS)[:, None], skybuf[idx] * att[idx], color[idx])
-            else:
-                miss = idx[st == BOUNCE_MISS]
-                if miss.numel():
-                    color[miss] = torch.as_tensor(sky(work, miss.int()), dtype=f64).to(dev).reshape(-1, 3) * att[miss]
-            hit = idx[st != BOUNCE_MISS]
-            obj = res.object[hit].long()
-            # emission found by hitting it: the whole of it after a specular vertex; after a diffuse one nothing, or its MIS share
-            wgt = specular[hit].to(f64)
-            if mis and hit.numel():
-                p_light = self.light_pdf(points, res.object, hit.int(), strategy)[hit]
-                share = p_bsdf[hit] / (p_bsdf[hit] + p_light)
-                wgt = torch.where(specular[hit], wgt, torch.where(torch.isfinite(share), share, torch.zeros_like(share)))
-            color[hit] = color[hit] + att[hit] * emission[obj] * wgt[:, None]
-            if nee_ok is not None:   # (before the attenuation moves on: the light sample is weighted by att * value)
-                nee = hit[nee_ok[obj]]
-                att_nee = att[nee]
-            live = self.bounce_select(res.status, live)
-            scat = live.long()
-            att[scat] = att[scat] * res.attenuation[scat]
-            sobj = res.object[scat].long()
-            if nee_ok is not None:
-                # next-event estimation at every diffuse or glossy vertex, through bsdf(): also where Metal absorbed the
-                # scattered ray -- the vertex reflects the lamp whatever became of the one direction the scatter drew
-                specular[scat] = ~nee_ok[sobj]
-                if nee.numel() == 0 or step == int(max_depth) - 1:
-                    continue
-                points[nee, 0:3], points[nee, 3] = res.p[nee], win[nee, 6]
-                lst = nee.int()
-                ls = self.sample_lights(points, lrng, lst, strategy, out=ls)
-                occ = self.occluded(ls.rays, t_range, lst, tr, mode, out=occ, mask=lamp_mask)
-                ev = self.bsdf(win, res, ls.rays, lst, out=ev)
-                p_b, pdf, lamp = ev.pdf[nee], ls.pdf[nee], ls.light[nee].long()
-                ok = (~occ.occluded[nee]) & (lamp >= 0) & (pdf > 0) & torch.isfinite(pdf) & (p_b > 0) & torch.isfinite(p_b)
-                share = pdf / (pdf + p_b) if mis else torch.ones_like(pdf)
-                add = att_nee * ev.value[nee] * emission[lamp.clamp(min=0)] * (share / pdf)[:, None]
-                color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
-                if mis:   # the density of the direction the path actually left in (0 for an absorbed ray: it found nothing)
-                    ev2 = self.bsdf(win, res, work, lst, out=ev2)
-                    p_bsdf[nee] = ev2.pdf[nee]
-                continue
-            # next-event estimation at the diffuse hits that go on
-            isdiff = diffuse[sobj]
-            specular[scat] = ~isdiff
-            nee = scat[isdiff]
-            if nee.numel() == 0 or step == int(max_depth) - 1:   # (a light sample after the last step would be one vertex more than trace() follows)
-                continue
-            points[nee, 0:3], points[nee, 3] = res.p[nee], work[nee, 6]
-            nrm = res.normal[nee]
-            d = work[nee, 3:6]
-            cos_out = (nrm * d).sum(1) / torch.sqrt((d * d).sum(1))
-            p_bsdf[nee] = torch.clamp(cos_out, min=0.0) / np.pi
-            lst = nee.int()
-            ls = self.sample_lights(points, lrng, lst, strategy, out=ls)
-            occ = self.occluded(ls.rays, t_range, lst, tr, mode, out=occ, mask=lamp_mask)
-            sd = ls.rays[nee, 3:6]
-            cos_l = (nrm * sd).sum(1) / torch.sqrt((sd * sd).sum(1))
-            pdf, lamp = ls.pdf[nee], ls.light[nee].long()
-            ok = (~occ.occluded[nee]) & (lamp >= 0) & (pdf > 0) & torch.isfinite(pdf) & (cos_l > 0)
-            share = pdf / (pdf + cos_l / np.pi) if mis else torch.ones_like(pdf)
-            add = att[nee] * emission[lamp.clamp(min=0)] * (cos_l / np.pi / pdf * share)[:, None]
-            color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
-        if ran is None:
-            ran = "nothing to do"
-        if as_numpy:
-            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
-        return color, rng, ran
-
     # ---- light-tracing queries (tor_light_emit_device, tor_camera_connect_device): emit from the lights, connect to the camera ----
 
     def connect_camera(self, cam: Camera, nrows: int, ncols: int, points, rng, index=None, out=None) -> "CameraConnection":
@@ -1947,103 +1706,6 @@ class Context:
         ops.call(ops.ptr(rng), p_list, n_list, float(time_range[0]), float(time_range[1]), ops.ptr(rays), ops.ptr(normal),
                  ops.ptr(light), ops.ptr(pdf))
         return LightEmission(rays, normal, light, pdf, rng, ops.note(n_list), keep=ops.keep(index))
-
-    def trace_light(self, cam: Camera, nrows: int, ncols: int, rng, emission, diffuse, max_depth=50, lamp_mask=None, time_range=None,
-                    mode="auto", splat=None):
-        """A light tracer on top of emit_lights, bounce, connect_camera and occluded: one path per state starts on a lamp of the
-        light table (set_lights) with beta = Le * pi / pdf_area, and every vertex the camera can see directly is splatted into
-        the pixel it lands in.  The emission vertex itself adds Le * cos_y * factor / pdf_area where cos_y > 0.  Per step the
-        live rays bounce; every hit on a `diffuse` object is connected (connect_camera), the segment to the lens point asked of
-        occluded() with range (0.001, 1.0), and where it is free and cos_y > 0 (the face normal the step returned against the
-        unit direction to the lens point) the vertex adds beta * albedo / pi * cos_y * factor; then beta *= attenuation for the
-        rays that scattered, which stay live, for at most max_depth steps.
-
-        Each batch goes to splat(pixels, colors, index): pixels (n,) int32 (-1 where nothing is added), colors (n, 3) float64
-        already divided by nrows * ncols, index the int32 list of the entries of this batch -- Film.deposit's signature; with
-        N paths in all, a pixel's radiance estimate is the sum of its splats times nrows * ncols / N.  splat None: nothing is
-        kept.  Returns (the number of splats offered, rng after the paths' last draws, the mode that ran).
-
-        emission: (n_objects, 3) float64, the radiance Le of every lamp.  diffuse: (n_objects,) bool (diffuse_objects(scene)).
-        lamp_mask: the occluded() mask of the connection segments (None: every group).  time_range: the emission's (lo, hi);
-        None: the camera's shutter interval.  rng: (n, 4) states, a contiguous CUDA tensor is updated in place; numpy states
-        go through the device and come back as numpy.  The connection draws come from a second state per path, derived from
-        the path's entry state (_derived_states with a constant of its own), so the bounces see the states they would see
-        without connections.
-
-        What a light tracer cannot see: surfaces the camera sees THROUGH a Metal or Dielectric vertex (a mirror image, the
-        far side of a glass ball) -- no connection reaches the lens by way of a specular vertex; those need trace / trace_direct
-        / trace_environment.  Mixing both estimators in one film counts the directly seen diffuse surfaces twice and is out of
-        scope, as are multiple importance sampling between them and the sky (an environment is no lamp of the table)."""
-        import torch
-        as_numpy = not _is_tensor(rng)
-        if as_numpy:
-            st = np.asarray(rng)
-            if st.ndim != 2 or st.shape[1] != 4 or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
-                raise ValueError("Context.trace_light: rng must be an (n, 4) array of 64-bit integers")
-            rng = self._to_device(np.ascontiguousarray(st).view(np.int64))
-        elif rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
-            raise ValueError("Context.trace_light: rng must be an (n, 4) int64 CUDA tensor")
-        rng = rng.contiguous()
-        n, dev, f64 = int(rng.shape[0]), rng.device, torch.float64
-        tr = (float(cam.shutter_open), float(cam.shutter_close)) if time_range is None else (float(time_range[0]), float(time_range[1]))
-        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
-        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
-        inv_npix = 1.0 / float(int(nrows) * int(ncols))
-        crng = _derived_states(rng.view(torch.int64) if rng.dtype != torch.int64 else rng, _CAMERA_STREAM)
-        if n == 0:
-            return 0, (rng.cpu().numpy().view(np.uint64) if as_numpy else rng), "nothing to do"
-        em = self.emit_lights(rng, tr)
-        work, lamp = em.rays.clone(), em.light.long().clamp(min=0)
-        pdf_area = em.pdf_area
-        beta = emission[lamp] * (np.pi / pdf_area)[:, None]                   # (a lamp of radius 0 has no area: it emits nothing)
-        points = torch.zeros((n, 4), dtype=f64, device=dev)
-        t_range = torch.empty((n, 2), dtype=f64, device=dev)
-        t_range[:, 0], t_range[:, 1] = 0.001, 1.0
-        colors = torch.zeros((n, 3), dtype=f64, device=dev)
-        offered = 0
-
-        def connect(lst, nrm, weight, conn, occ):
-            """Connect the listed vertices (their points are set): splat weight * cos_y * factor / npix where visible."""
-            conn = self.connect_camera(cam, nrows, ncols, points, crng, lst, out=conn)
-            occ = self.occluded(conn.rays, t_range, lst, tr, mode, out=occ, mask=lamp_mask)
-            at = lst.long()
-            d = conn.rays[at, 3:6]
-            cos_y = (nrm * d).sum(1) / torch.sqrt((d * d).sum(1))
-            ok = (conn.pixel[at] >= 0) & (~occ.occluded[at]) & (cos_y > 0)
-            add = weight * (cos_y * conn.factor[at] * inv_npix)[:, None]
-            colors[at] = torch.where(ok[:, None] & torch.isfinite(add), add, torch.zeros_like(add))
-            pixels = torch.where(ok, conn.pixel[at], torch.full_like(conn.pixel[at], -1))
-            conn.pixel[at] = pixels
-            if splat is not None:
-                splat(conn.pixel, colors, lst)
-            return conn, occ, int(lst.numel())
-
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        points[:, 0:3], points[:, 3] = work[:, 0:3], work[:, 6]
-        conn, occ, k = connect(live, em.normal, emission[lamp] / pdf_area[:, None], None, None)
-        offered += k
-        res, ran = None, None
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            res = self.bounce(work, rng, live, tr, mode, out=res)
-            ran = ran or res.mode
-            idx = live.long()
-            st = res.status[idx]
-            obj = res.object[idx].long().clamp(min=0)
-            at = idx[(st != BOUNCE_MISS) & diffuse[obj]]
-            if at.numel():
-                points[at, 0:3], points[at, 3] = res.p[at], work[at, 6]
-                conn, occ, k = connect(at.int(), res.normal[at], beta[at] * res.attenuation[at] / np.pi, conn, occ)
-                offered += k
-            live = self.bounce_select(res.status, live)
-            scat = live.long()
-            beta[scat] = beta[scat] * res.attenuation[scat]
-        if ran is None:
-            ran = "nothing to do"
-        if as_numpy:
-            return offered, rng.cpu().numpy().view(np.uint64), ran
-        return offered, rng, ran
 
     # ---- photon-map queries (tor_photons_build_device, tor_photons_gather_device): density estimation in world space ----
 
@@ -2122,130 +1784,6 @@ class Context:
         return PhotonGather(sums, count, getattr(self, "_photon_scale", 1.0), used, k, float(max_value), ops.note(n_list),
                             keep=ops.keep(points, normals, rad, index))
 
-    def trace_photons(self, rng, emission, diffuse, max_depth=50, caustic_only=False, lamp_mask=None, time_range=None, mode="auto") -> "Photons":
-        """trace_light's loop without the connections: one light path per state starts on a lamp of the light table
-        (set_lights, emit_lights) with beta = Le * pi / pdf_area; per step the live rays bounce, and every hit on a `diffuse`
-        object stores a photon {p, beta as it ARRIVES (before the surface's albedo), the incoming ray's direction (not
-        normalised: a gather uses only its sign against the normal)}; then beta *= attenuation for the rays that scattered,
-        which stay live, for at most max_depth steps.
-
-        caustic_only: keep a photon only if its path has taken at least one specular step (a hit on an object that is not
-        `diffuse`) and no diffuse one; the path stops at its first diffuse hit.  emission, diffuse, time_range ((lo, hi) of the
-        emission; None: (0, 0)), mode and rng as for trace_light; lamp_mask is accepted for symmetry and unused (there are no
-        connection segments).  Returns Photons(position (m, 3), power (m, 3), direction (m, 3), paths = n, rng, mode): the
-        operands of build_photons.  The powers are NOT divided by the path count: PhotonGather.irradiance(paths) does that, so
-        the photons of several calls concatenate."""
-        import torch
-        as_numpy = not _is_tensor(rng)
-        if as_numpy:
-            st = np.asarray(rng)
-            if st.ndim != 2 or st.shape[1] != 4 or st.dtype.kind not in "iu" or st.dtype.itemsize != 8:
-                raise ValueError("Context.trace_photons: rng must be an (n, 4) array of 64-bit integers")
-            rng = self._to_device(np.ascontiguousarray(st).view(np.int64))
-        elif rng.dtype not in (torch.int64, torch.uint64) or rng.dim() != 2 or rng.shape[1] != 4 or not rng.is_cuda:
-            raise ValueError("Context.trace_photons: rng must be an (n, 4) int64 CUDA tensor")
-        rng = rng.contiguous()
-        n, dev, f64 = int(rng.shape[0]), rng.device, torch.float64
-        tr = (0.0, 0.0) if time_range is None else (float(time_range[0]), float(time_range[1]))
-        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
-        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
-        pos, pw, dr = [], [], []
-        ran = None
-        if n:
-            em = self.emit_lights(rng, tr)
-            work, lamp = em.rays.clone(), em.light.long().clamp(min=0)
-            beta = emission[lamp] * (np.pi / em.pdf_area)[:, None]   # (a lamp of radius 0 has no area: it emits nothing)
-            beta = torch.where((em.light >= 0)[:, None], beta, torch.zeros_like(beta))
-            specular = torch.zeros(n, dtype=torch.bool, device=dev)   # the path has taken a specular step
-            live = torch.arange(n, dtype=torch.int32, device=dev)
-            win, res = torch.empty_like(work), None
-            for step in range(int(max_depth)):
-                if live.numel() == 0:
-                    break
-                win.copy_(work)   # the incoming rays of the step: bounce() writes the scattered ones over `work`
-                res = self.bounce(work, rng, live, tr, mode, out=res)
-                ran = ran or res.mode
-                idx = live.long()
-                st = res.status[idx]
-                obj = res.object[idx].long().clamp(min=0)
-                hit = st != BOUNCE_MISS
-                on_diffuse = hit & diffuse[obj]
-                at = idx[on_diffuse & specular[idx]] if caustic_only else idx[on_diffuse]
-                if at.numel():
-                    pos.append(res.p[at].clone()), pw.append(beta[at].clone()), dr.append(win[at, 3:6].clone())
-                specular[idx[hit & ~diffuse[obj]]] = True
-                live = self.bounce_select(res.status, live)
-                if caustic_only:   # the path stops at its first diffuse hit
-                    live = live[~diffuse[res.object[live.long()].long().clamp(min=0)]]
-                scat = live.long()
-                beta[scat] = beta[scat] * res.attenuation[scat]
-        cat = (lambda parts: torch.cat(parts) if parts else torch.zeros((0, 3), dtype=f64, device=dev))
-        position, power, direction = cat(pos), cat(pw), cat(dr)
-        if as_numpy:
-            return Photons(position.cpu().numpy(), power.cpu().numpy(), direction.cpu().numpy(), n, rng.cpu().numpy().view(np.uint64),
-                           ran or "nothing to do")
-        return Photons(position, power, direction, n, rng, ran or "nothing to do")
-
-    def trace_photon_map(self, rays, rng, emission, diffuse, paths, radius=None, kernel="epanechnikov", max_depth=50, time_range=None,
-                         mode="auto"):
-        """Direct visualisation of the context's photon map (build_photons from trace_photons' photons of `paths` light paths in
-        all, caustic_only=False): every camera ray is followed through its specular steps, with trace()'s bookkeeping, to its
-        first hit on a `diffuse` object, where the map is gathered (gather_photons with the face normal the step returned); the
-        colour is
-            sum over the hits on the way of att * emission[object]  +  att * albedo / pi * irradiance estimate
-        with att the product of the attenuations of the steps before, and albedo the attenuation of the diffuse step.  A ray
-        that misses is black: the sky is no source here (an environment is no lamp of the light table), and neither is it in
-        trace_photons.  The estimator is complete on its own: emission is seen directly or through specular vertices only,
-        every other light path of the scene is in the map once, so nothing is counted twice.  The path ends at that diffuse
-        hit (the albedo is the step's attenuation; a step the material absorbed reflects nothing).  Mixing it with trace_direct
-        is out of scope.
-
-        rays, rng, time_range, mode, max_depth as for trace(); radius, kernel as for gather_photons.  Returns (color (n, 3),
-        rng, the mode that ran)."""
-        import torch
-        as_numpy = not _is_tensor(rays)
-        if as_numpy:
-            host = _Arrays(self, "trace_photon_map", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
-            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
-        ops = _Tensors(self, "trace_photon_map", rays, "rays", 7)
-        rays, n, dev = ops.lead, ops.n, ops.dev
-        rng = ops.states(rng)
-        tr = ops.times(6, time_range)
-        f64 = torch.float64
-        emission = torch.as_tensor(emission, dtype=f64).to(dev).reshape(-1, 3)
-        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
-        work = rays.clone()
-        color = torch.zeros((n, 3), dtype=f64, device=dev)
-        att = torch.ones((n, 3), dtype=f64, device=dev)
-        points, normals = torch.zeros((n, 3), dtype=f64, device=dev), torch.zeros((n, 3), dtype=f64, device=dev)
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        res, ran, gat = None, None, None
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            res = self.bounce(work, rng, live, tr, mode, out=res)
-            ran = ran or res.mode
-            idx = live.long()
-            st = res.status[idx]
-            hit = idx[st != BOUNCE_MISS]
-            obj = res.object[hit].long()
-            color[hit] = color[hit] + att[hit] * emission[obj]
-            at = hit[diffuse[obj]]
-            if at.numel():
-                points[at], normals[at] = res.p[at], res.normal[at]
-                gat = self.gather_photons(points, normals, radius, at.int(), kernel, out=gat)
-                albedo = torch.where((res.status[at] == BOUNCE_SCATTERED)[:, None], res.attenuation[at], torch.zeros_like(att[at]))
-                color[at] = color[at] + att[at] * albedo / np.pi * gat.irradiance(paths)[at]
-            live = self.bounce_select(res.status, live)
-            live = live[~diffuse[res.object[live.long()].long().clamp(min=0)]]
-            scat = live.long()
-            att[scat] = att[scat] * res.attenuation[scat]
-        if ran is None:
-            ran = "nothing to do"
-        if as_numpy:
-            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
-        return color, rng, ran
-
     # ---- environment-light queries (tor_env_eval_device, tor_env_sample_device): the sky as an emitter ----
 
     def environment(self, rays, index=None, out=None, pdf=False):
@@ -2312,95 +1850,6 @@ class Context:
                 ops.bad("out", "the result of a call on as many points, on tensors or arrays as the points are")
         ops.call(ops.ptr(points), ops.ptr(rng), p_list, n_list, ops.ptr(rays), ops.ptr(pdf), ops.ptr(texel), ops.ptr(color))
         return EnvSample(rays, pdf, texel, color, rng, ops.note(n_list), keep=ops.keep(points, index))
-
-    def trace_environment(self, rays, rng, diffuse, max_depth=50, direct=True, mis=False, time_range=None, mode="auto"):
-        """trace()'s loop with the environment map (set_environment) as the sky, and next-event estimation towards it: a ray
-        that misses adds att * environment(ray) * w, and with `direct` every diffuse hit that goes on (except on the last of
-        the max_depth steps) draws a direction from the map (sample_environment), asks occluded() with range (0.001, +inf)
-        whether it is free, and adds att * color * (cos / pi / pdf * share) where it is.  w = 1 when `direct` is off or the
-        ray left the camera, a Metal or a Dielectric; otherwise 0, or with mis=True the balance share
-        p_bsdf / (p_bsdf + p_env) -- `share` is then p_env / (p_env + p_bsdf), else 1.  p_bsdf is the Lambertian density
-        cos / pi, p_env the map's density of the direction (environment(pdf=True)).
-
-        diffuse: (n_objects,) bool (diffuse_objects(scene)).  rays, rng, time_range, mode and the result (color, rng, mode) as
-        for trace().  No step builds a list of the misses, so none synchronises with the host on their count.
-
-        The environment draws come from a third state per path, derived from the path's entry state like trace_direct's light
-        states but with the constant 0xd1342543de82ef95 in place of the golden ratio's 0x9e3779b97f4a7c15: the bounces see
-        exactly the states trace() gives them.  So with direct=False the colours are those of
-        trace(sky=lambda rays, idx: ctx.environment(rays, idx)[idx.long()]), bit for bit, and the returned states are the path
-        states, as trace() returns them."""
-        import torch
-        as_numpy = not _is_tensor(rays)
-        if as_numpy:
-            host = _Arrays(self, "trace_environment", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
-            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
-        ops = _Tensors(self, "trace_environment", rays, "rays", 7)
-        rays, n, dev = ops.lead, ops.n, ops.dev
-        rng = ops.states(rng)
-        tr = ops.times(6, time_range)
-        f64 = torch.float64
-        diffuse = torch.as_tensor(np.asarray(diffuse.cpu() if _is_tensor(diffuse) else diffuse).astype(bool)).to(dev).reshape(-1)
-        work = rays.clone()
-        color = torch.zeros((n, 3), dtype=f64, device=dev)
-        att = torch.ones((n, 3), dtype=f64, device=dev)
-        erng = _derived_states(rng.view(torch.int64) if rng.dtype != torch.int64 else rng, _ENV_STREAM)
-        points = torch.zeros((n, 4), dtype=f64, device=dev)          # the shading point of every ray's last diffuse hit ...
-        p_bsdf = torch.zeros((n,), dtype=f64, device=dev)            # ... the Lambertian density of the direction it left in ...
-        specular = torch.ones((n,), dtype=torch.bool, device=dev)    # ... or: the ray left a camera, a Metal or a Dielectric
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        res, es, occ, ev, ran = None, None, None, None, None
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            res = self.bounce(work, rng, live, tr, mode, out=res)
-            ran = ran or res.mode
-            idx = live.long()
-            st = res.status[idx]
-            # the map's colour (and density) of every stepped ray, kept where it missed: no list of the misses
-            if direct and mis:
-                ev = self.environment(work, live, out=ev, pdf=True)
-                sky, p_env = ev.color[idx], ev.pdf[idx]
-                share = p_bsdf[idx] / (p_bsdf[idx] + p_env)
-                wgt = torch.where(specular[idx], torch.ones_like(share), torch.where(torch.isfinite(share), share, torch.zeros_like(share)))
-                sky = sky * att[idx] * wgt[:, None]
-            else:
-                ev = self.environment(work, live, out=ev)
-                sky = ev[idx] * att[idx]
-                if direct:
-                    sky = sky * specular[idx].to(f64)[:, None]
-            color[idx] = torch.where((st == BOUNCE_MISS)[:, None], color[idx] + sky, color[idx])
-            live = self.bounce_select(res.status, live)
-            scat = live.long()
-            att[scat] = att[scat] * res.attenuation[scat]
-            if not direct:
-                continue
-            # next-event estimation at the diffuse hits that go on
-            sobj = res.object[scat].long()
-            isdiff = diffuse[sobj]
-            specular[scat] = ~isdiff
-            nee = scat[isdiff]
-            if nee.numel() == 0 or step == int(max_depth) - 1:   # (a sample after the last step would be one vertex more than trace() follows)
-                continue
-            points[nee, 0:3], points[nee, 3] = res.p[nee], work[nee, 6]
-            nrm = res.normal[nee]
-            d = work[nee, 3:6]
-            cos_out = (nrm * d).sum(1) / torch.sqrt((d * d).sum(1))
-            p_bsdf[nee] = torch.clamp(cos_out, min=0.0) / np.pi
-            lst = nee.int()
-            es = self.sample_environment(points, erng, lst, out=es)
-            occ = self.occluded(es.rays, None, lst, tr, mode, out=occ)
-            cos_l = (nrm * es.rays[nee, 3:6]).sum(1)              # (the sampled direction is unit)
-            pdf = es.pdf[nee]
-            ok = (~occ.occluded[nee]) & (pdf > 0) & torch.isfinite(pdf) & (cos_l > 0)
-            share = pdf / (pdf + cos_l / np.pi) if mis else torch.ones_like(pdf)
-            add = att[nee] * es.color[nee] * (cos_l / np.pi / pdf * share)[:, None]
-            color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
-        if ran is None:
-            ran = "nothing to do"
-        if as_numpy:
-            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
-        return color, rng, ran
 
     # ---- participating media (tor_scene_media, tor_media_march_device, tor_media_scatter_device, tor_rng_uniform_device) ----
 
@@ -2533,76 +1982,6 @@ class Context:
             tm = tm * self.visible(p, q, time, mask=mask)
         return tm
 
-    def trace_media(self, rays, rng, max_depth=50, sky=None, mask=None, free_flight=None):
-        """The volumetric twin of trace(): a wavefront path tracer through the surfaces of the scene and the media of the table.
-        att = 1; per iteration, for the live rays, in this order: hit() with `mask` (the surfaces a ray sees; the media's
-        boundary spheres belong to a group the mask leaves out); ONE uniform01 per live ray (uniform()); tau = free_flight(u),
-        default -log1p(-u) (torch's: the library takes no logarithm); march_media() with range (0, the hit's t or +inf).  A ray
-        that collided scatters isotropically (scatter_media(): two more outputs of its stream) and att *= the mixture's albedo;
-        one that reached its surface scatters as the reference's material does (scatter(): that material's draws), att *= its
-        attenuation, and an absorbed ray ends black; one that reached nothing ends with sky * att.  Rays still live after
-        max_depth iterations are black.  So the draw order of a path is, per iteration, the free-flight uniform first, then
-        the draws of whichever scatter it met.  Returns (color (n, 3), rng (n, 4) after the path's last draw).
-
-        sky: None (Context.sky) or sky(rays, index) -> (len(index), 3), as for trace().  mask: as for hit(), or a callable
-        mask(step).  free_flight: a callable on the (n,) tensor of uniforms giving tau (every entry is evaluated, the live ones
-        are used).  hit() takes no list, so every iteration's closest-hit launch runs on all n rays and the hits of the rays
-        that have ended are not read; uniform, march_media and the two scatters run on the live list.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the
-        device and come back as numpy."""
-        import torch
-        as_numpy = not _is_tensor(rays)
-        if as_numpy:
-            host = _Arrays(self, "trace_media", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
-            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
-        ops = _Tensors(self, "trace_media", rays, "rays", 7)
-        rays, n, dev = ops.lead, ops.n, ops.dev
-        rng = ops.states(rng)
-        tr = ops.times(6, None)
-        work = rays.clone()
-        color = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        att = torch.ones((n, 3), dtype=torch.float64, device=dev)
-        inf = torch.full((n,), float("inf"), dtype=torch.float64, device=dev)
-        t_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
-        u = torch.zeros((n, 1), dtype=torch.float64, device=dev)
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        march, nxt = None, None
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            hit = self.hit(work, time_range=tr, mask=mask(step) if callable(mask) else mask)
-            u, rng = self.uniform(rng, 1, index=live, out=u)
-            tau = -torch.log1p(-u[:, 0]) if free_flight is None else \
-                torch.as_tensor(free_flight(u[:, 0]), dtype=torch.float64).to(dev).reshape(n)
-            t_range[:, 1] = torch.where(hit.object >= 0, hit.t, inf)
-            march = self.march_media(work, tau, t_range, index=live, out=march)
-            idx = live.long()
-            st, obj = march.status[idx], hit.object[idx]
-            collided = live[st == MEDIA_COLLIDED]
-            surface = live[(st == MEDIA_ESCAPED) & (obj >= 0)]
-            missed = live[(st == MEDIA_ESCAPED) & (obj < 0)]
-            alive = torch.zeros((n,), dtype=torch.bool, device=dev)
-            if missed.numel():
-                mi = missed.long()
-                c = self.sky(work, missed)[mi] if sky is None else \
-                    torch.as_tensor(sky(work, missed), dtype=torch.float64).to(dev).reshape(-1, 3)
-                color[mi] = c * att[mi]
-            if surface.numel():
-                res = self.scatter(work, hit, rng, index=surface)
-                si = surface.long()
-                sc = si[res.status[si] == BOUNCE_SCATTERED]
-                att[sc] = att[sc] * res.attenuation[sc]
-                alive[sc] = True
-            if collided.numel():
-                nxt = self.scatter_media(work, march, rng, index=collided, out=nxt)
-                ci = collided.long()
-                work[ci] = nxt.rays[ci]
-                att[ci] = att[ci] * nxt.attenuation[ci]
-                alive[ci] = True
-            live = torch.nonzero(alive).reshape(-1).int()
-        if as_numpy:
-            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64)
-        return color, rng
-
     @staticmethod
     def shadow_segments(p, q, time=0.0, t_min=0.001):
         """The rays and ranges of the segments p -> q (what visible() queries): ((n, 7) rays with origin p, direction q - p and
@@ -2637,65 +2016,8 @@ class Context:
             kw["mask"] = mask
         return ~self.occluded(rays, tr, **kw).occluded
 
-    def trace(self, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None, mask=None):
-        """A wavefront path tracer on top of bounce(): radiance()'s loop (render.nim:21-47) one step per launch, open where the
-        reference is closed.  att = 1; per step: bounce the live rays; a miss ends with sky * att; with `emission` every hit adds
-        att * emission[object] (before the attenuation is updated); att *= attenuation for the rays that scattered, which stay
-        live, in order; rays still live after max_depth steps are black.  Returns (color (n, 3), rng (n, 4) after the path's last
-        draw, the mode that ran).  With sky, emission and on_bounce all None this is Context.radiance: colours and states, bit
-        for bit.
-
-        sky: None (Context.sky, the reference's gradient) or sky(rays, index) -> (len(index), 3) colours of the listed rays.
-        emission: (n_objects, 3) float64.  on_bounce(step, index, result): called after every step with the list that was
-        stepped (int32 tensor) and its BounceResult (result.rays are the scattered rays) -- the hook for feature buffers.
-        rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the device and come
-        back as numpy.  One time range for all steps: time_range, or the rays' finite times (the library adds 0).
-        mask: as for bounce(), for every step; or a callable mask(step) -> int | per-ray words, so that step 0 (the camera's rays)
-        sees other objects than the later steps."""
-        import torch
-        as_numpy = not _is_tensor(rays)
-        if as_numpy:
-            host = _Arrays(self, "trace", np.asarray(rays, dtype=np.float64).reshape(-1, 7), "rays", 7)
-            rays, rng = self._to_device(host.lead), self._to_device(host.states(rng).view(np.int64))
-        ops = _Tensors(self, "trace", rays, "rays", 7)
-        rays, n, dev = ops.lead, ops.n, ops.dev
-        rng = ops.states(rng)
-        tr = ops.times(6, time_range)
-        work = rays.clone()
-        color = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        att = torch.ones((n, 3), dtype=torch.float64, device=dev)
-        if emission is not None:
-            emission = torch.as_tensor(emission, dtype=torch.float64).to(dev).reshape(-1, 3)
-        skybuf = torch.zeros((n, 3), dtype=torch.float64, device=dev) if sky is None else None
-        live = torch.arange(n, dtype=torch.int32, device=dev)
-        res, ran = None, None
-        for step in range(int(max_depth)):
-            if live.numel() == 0:
-                break
-            res = self.bounce(work, rng, live, tr, mode, out=res, mask=mask(step) if callable(mask) else mask)
-            ran = ran or res.mode
-            idx = live.long()
-            st = res.status[idx]
-            if sky is None:   # the sky of every stepped ray, kept where it missed: no list of the misses, so no host synchronisation
-                self.sky(work, live, out=skybuf)
-                color[idx] = torch.where((st == BOUNCE_MISS)[:, None], skybuf[idx] * att[idx], color[idx])   # render.nim:45
-            else:
-                miss = idx[st == BOUNCE_MISS]
-                if miss.numel():
-                    color[miss] = torch.as_tensor(sky(work, miss.int()), dtype=torch.float64).to(dev).reshape(-1, 3) * att[miss]
-            if emission is not None:
-                hit = idx[st != BOUNCE_MISS]
-                color[hit] = color[hit] + att[hit] * emission[res.object[hit].long()]
-            if on_bounce is not None:
-                on_bounce(step, live, res)
-            live = self.bounce_select(res.status, live)
-            scat = live.long()
-            att[scat] = att[scat] * res.attenuation[scat]                 # render.nim:35
-        if ran is None:
-            ran = "nothing to do"
-        if as_numpy:
-            return color.cpu().numpy(), rng.cpu().numpy().view(np.uint64), ran
-        return color, rng, ran
+    # (trace, trace_direct, trace_light, trace_photons, trace_photon_map, trace_environment and trace_media are the functions of
+    # integrators.py, given to this class at the end of the module)
 
 
 def _mode_of(note: str, prefix: str) -> str:
@@ -2715,38 +2037,6 @@ def _mask_words(a: np.ndarray) -> np.ndarray:
     if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) > 0xFFFFFFFF):
         raise ValueError("group and mask words must fit 32 bits")
     return np.ascontiguousarray((a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32))
-
-
-def _light_states(rng):
-    """The light-draw states of trace_direct: per path and word k the splitmix64 finaliser (rng.nim:31-36's mixing) of
-    s_k xor rotl(s_(k+1), 23) + (k + 1) * golden, in wrapping int64 tensor arithmetic -- a second stream per path that shares no
-    draw with the path's own."""
-    return _derived_states(rng, 0x9e3779b97f4a7c15)
-
-
-_ENV_STREAM = 0xd1342543de82ef95   # the odd constant of trace_environment's third stream (where _light_states has the golden ratio's)
-_CAMERA_STREAM = 0xf1357aea2e62a9c5   # the odd constant of trace_light's connection stream
-
-
-def _derived_states(rng, constant):
-    """A further stream per path: per path and word k the splitmix64 finaliser (rng.nim:31-36's mixing) of
-    s_k xor rotl(s_(k+1), 23) + (k + 1) * constant, in wrapping int64 tensor arithmetic.  Streams of different odd constants
-    share no draw with the path's own or with each other."""
-    def lsr(z, k):
-        return (z >> k) & ((1 << (64 - k)) - 1)
-
-    def signed(c):
-        return c - (1 << 64) if c >= (1 << 63) else c
-
-    mix = signed(0xbf58476d1ce4e5b9)
-    out = rng.clone()
-    for k in range(4):
-        nxt = rng[:, (k + 1) % 4]
-        z = (rng[:, k] ^ ((nxt << 23) | lsr(nxt, 41))) + signed(((k + 1) * constant) & ((1 << 64) - 1))
-        z = (z ^ lsr(z, 30)) * mix
-        z = (z ^ lsr(z, 27)) * mix
-        out[:, k] = z ^ lsr(z, 31)
-    return out
 
 
 def environment_directions(n, a=0.5, b=0.5) -> np.ndarray:
@@ -3716,3 +3006,10 @@ def selftest_rng(mode: int, a: int, b: int = 0, c: int = 0, n: int = 4):
     draws = (C.c_uint64 * max(n, 1))()
     _check(lib().tor_selftest_rng_host(mode, a, b, c, state, draws, n))
     return [int(v) for v in state], [int(v) for v in draws[:n]]
+
+
+# Context.trace .. Context.trace_media: the functions of integrators.py as methods (last: that module imports this one's names)
+from . import integrators   # noqa: E402
+
+for _name in integrators.INTEGRATORS:
+    setattr(Context, _name, getattr(integrators, _name))
