@@ -1022,4 +1022,10 @@ TOR_API const char* tor_version(void);
  * tor_media.h. */
 #include "tor_media.h"
 
+/* ---- phase-function queries: Henyey-Greenstein sample, value, density ------------------------------------------------------------------
+ * tor_scene_media_phase, tor_phase_sample_device / _host, tor_phase_eval_device / _host: an asymmetry per medium of the media table, a
+ * direction drawn from the Henyey-Greenstein mixture of the media active at a collision, and value and density of a direction that
+ * was not drawn -- what lets a lamp of the light table light the fog --, defined operation by operation in tor_phase.h. */
+#include "tor_phase.h"
+
 #endif /* TOR_RENDER_H */

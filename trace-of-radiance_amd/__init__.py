@@ -189,6 +189,11 @@ MEDIA_SYMBOLS = ["tor_scene_media", "tor_media_march_device", "tor_media_march_h
 MEDIA_MAX = 64            # TOR_MEDIA_MAX: the most media of a table (the active set of a march is one 64-bit word)
 UNIFORM_MAX_DRAWS = 16    # TOR_UNIFORM_MAX_DRAWS: the most uniforms per state of one Context.uniform call
 MEDIA_REFUSED, MEDIA_ESCAPED, MEDIA_COLLIDED = -1, 0, 1   # the status of a Context.march_media answer
+# the phase-function queries (include/tor_phase.h): bound in a second step of lib(), after the table _bind gives every library
+PHASE_SYMBOLS = ["tor_scene_media_phase", "tor_phase_eval_device", "tor_phase_eval_host", "tor_phase_sample_device",
+                 "tor_phase_sample_host"]
+PHASE_G_MAX = 0.99          # TOR_PHASE_G_MAX: the largest |g| of Context.set_media_phase
+PHASE_G_MIN = 2.0 ** -20    # TOR_PHASE_G_MIN: the smallest |g| that is not 0
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
 HIT_MODES = {"auto": HIT_AUTO, "brute": HIT_BRUTE, "blocks": HIT_BLOCKS}
 BOUNCE_MISS, BOUNCE_SCATTERED, BOUNCE_ABSORBED = 0, 1, 2
@@ -254,6 +259,7 @@ def lib():
         print(f"trace-of-radiance_amd: TOR_AB_LIB set -- loading {ab} instead of the in-tree library", file=sys.stderr, flush=True)
     L = C.CDLL(ab or LIB_PATH)
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
+    _bind(L, PHASE_SYMBOLS, skip_missing=bool(ab), table=_PHASE_SIGNATURES)
     _lib = L
     return L
 
@@ -399,13 +405,29 @@ def _signatures() -> dict:
 _SIGNATURES = _signatures()
 
 
-def _bind(L, names=None, skip_missing=False) -> None:
+def _phase_signatures() -> dict:
+    """The entries of include/tor_phase.h, in a table of their own: lib() binds them after _signatures()'s."""
+    v, i64 = C.c_void_p, C.c_int64
+    return {
+        "tor_scene_media_phase": [v, i64, v],
+        "tor_phase_eval_device": [v, i64, v, v, v, v, i64, v, v, v],
+        "tor_phase_eval_host": [v, i64, v, v, v, v, i64, v, v],
+        "tor_phase_sample_device": [v, i64, v, v, v, v, v, i64, v, v, v, v],
+        "tor_phase_sample_host": [v, i64, v, v, v, v, v, i64, v, v, v],
+    }
+
+
+_PHASE_SIGNATURES = _phase_signatures()
+
+
+def _bind(L, names=None, skip_missing=False, table=None) -> None:
     """Give the named entries of the CDLL `L` (default: every entry of the table) their signatures.  A symbol `L` lacks raises,
-    unless skip_missing (another build of the library, which may be older than the entry)."""
-    for name in _SIGNATURES if names is None else names:
+    unless skip_missing (another build of the library, which may be older than the entry).  table: _SIGNATURES, or another."""
+    table = _SIGNATURES if table is None else table
+    for name in table if names is None else names:
         if skip_missing and not hasattr(L, name):
             continue
-        sig = _SIGNATURES[name]
+        sig = table[name]
         argtypes, *restype = sig if isinstance(sig, tuple) else (sig,)
         fn = getattr(L, name)
         if argtypes is not None:
@@ -1871,6 +1893,7 @@ class Context:
             p_albedo = a.ctypes.data or 16
         _check(lib().tor_scene_media(self._h, int(o.size), C.c_void_p(o.ctypes.data or 16), C.c_void_p(s.ctypes.data or 16),
                                      C.c_void_p(p_albedo)))
+        self._n_media = int(o.size)   # (what set_media_phase(None) passes as the table's count)
 
     def march_media(self, rays, tau, t_range=None, index=None, out=None) -> "MediaMarch":
         """The optical-depth march (tor_media_march_device / tor_media_march_host): per listed ray, where along it the accumulated
@@ -1933,6 +1956,76 @@ class Context:
                 ops.bad("out", "a pair of contiguous (n, 7) and (n, 3) float64 tensors or arrays, as the rays are")
         ops.call(ops.ptr(rays), ops.ptr(t), ops.ptr(active), ops.ptr(rng), p_list, n_list, ops.ptr(rays_out), ops.ptr(att))
         return MediaScatter(rays_out, att, rng, ops.note(n_list), keep=ops.keep(rays, t, active, index))
+
+    # ---- phase functions (tor_scene_media_phase, tor_phase_sample_device, tor_phase_eval_device) ----
+
+    def set_media_phase(self, g=None):
+        """The Henyey-Greenstein asymmetry of every medium of the table (tor_scene_media_phase): `g` one value per medium, each 0
+        (isotropic; what set_media leaves) or PHASE_G_MIN <= |g| <= PHASE_G_MAX; None: every medium 0.  sample_phase / phase /
+        trace_media(phase=True) / trace_media_direct read it.  set_media resets it; a replacing upload clears the table."""
+        if g is None:   # (the count set_media gave the table: the library refuses another)
+            _check(lib().tor_scene_media_phase(self._h, int(getattr(self, "_n_media", 0)), None))
+            return
+        a = np.ascontiguousarray(np.asarray(g, dtype=np.float64).reshape(-1))
+        _check(lib().tor_scene_media_phase(self._h, int(a.size), C.c_void_p(a.ctypes.data or 16)))
+
+    def sample_phase(self, rays, march, rng, index=None, out=None) -> "PhaseSample":
+        """The Henyey-Greenstein scatter at a collision (tor_phase_sample_device / tor_phase_sample_host): per listed ray one of
+        the active media is chosen in proportion to sigma, the cosine to the incoming direction is drawn by inverting its
+        phase function, the azimuth is uniform, and attenuation and pdf are those of the MIXTURE of the active media at that
+        cosine -- the definition, operation by operation in float64, is in include/tor_phase.h.
+
+        The operands of scatter_media: rays (n, 7); march: a MediaMarch or a pair (t, active); rng: (n, 4) 64-bit states --
+        every listed ray draws exactly three outputs, sampled or not; a contiguous CUDA tensor is updated in place.  index as
+        for bounce().  Returns a PhaseSample, which unpacks as (rays, attenuation) like a MediaScatter and carries pdf (n,), rng
+        and mode.  out: a PhaseSample of an earlier call on as many rays, written again; `rays` itself may be passed as its
+        rays."""
+        if out is not None and not isinstance(out, PhaseSample):
+            raise ValueError("Context.sample_phase: out must be a PhaseSample")
+        ops = _operands(self, "phase_sample", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        t, active = (march.t, march.active) if isinstance(march, MediaMarch) else march
+        t, active = ops.rows(t, "march.t"), ops.rows(active, "march.active", dtype="int64")
+        if t is None or active is None:
+            ops.bad("march", "a MediaMarch or a pair (t, active)")
+        rng = ops.states(rng)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            rays_out, att, pdf = ops.new(n, 7), ops.new(n, 3), ops.new(n)
+        else:
+            rays_out, att, pdf = out.rays, out.attenuation, out.pdf
+            if not ops.fits(rays_out, n, 7) or not ops.fits(att, n, 3) or not ops.fits(pdf, n):
+                ops.bad("out", "the result of a call on as many rays, on tensors or arrays as the rays are")
+        ops.call(ops.ptr(rays), ops.ptr(t), ops.ptr(active), ops.ptr(rng), p_list, n_list, ops.ptr(rays_out), ops.ptr(att),
+                 ops.ptr(pdf))
+        return PhaseSample(rays_out, att, pdf, rng, ops.note(n_list), keep=ops.keep(rays, t, active, index))
+
+    def phase(self, rays_in, march_or_active, rays_out, index=None, out=None) -> "PhaseEval":
+        """Value and density of the media's phase function (tor_phase_eval_device / tor_phase_eval_host), the twin of bsdf(): per
+        listed item the solid-angle density with which sample_phase draws the direction of rays_out[i] for a path that was
+        travelling along rays_in[i] through the media of the active word, and value = the single-scattering albedo of the
+        mixture times that phase function, per channel.  Nothing is drawn.
+
+        rays_in, rays_out (n, 7) float64, any positive finite length (the rays of sample_lights go straight in); only the
+        directions are read.  march_or_active: a MediaMarch, or (n,) int64 active words.  index as for bounce().  Returns a
+        PhaseEval(value (n, 3), pdf (n,), mode); out: one of an earlier call on as many items, written again."""
+        if out is not None and not isinstance(out, PhaseEval):
+            raise ValueError("Context.phase: out must be a PhaseEval")
+        ops = _operands(self, "phase_eval", rays_in, "rays_in", 7)
+        n, rays_in = ops.n, ops.lead
+        active = ops.rows(march_or_active.active if isinstance(march_or_active, MediaMarch) else march_or_active, "active", dtype="int64")
+        rays_out = ops.rows(rays_out, "rays_out", 7)
+        if active is None or rays_out is None:
+            ops.bad("active and rays_out", "(n,) int64 words and (n, 7) rays, as rays_in is")
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            value, pdf = ops.new(n, 3), ops.new(n)
+        else:
+            value, pdf = out.value, out.pdf
+            if not ops.fits(value, n, 3) or not ops.fits(pdf, n):
+                ops.bad("out", "the result of a call on as many items, on tensors or arrays as rays_in is")
+        ops.call(ops.ptr(rays_in), ops.ptr(active), ops.ptr(rays_out), p_list, n_list, ops.ptr(value), ops.ptr(pdf))
+        return PhaseEval(value, pdf, ops.note(n_list), keep=ops.keep(rays_in, active, rays_out, index))
 
     def uniform(self, rng, n=1, index=None, out=None):
         """Plain uniforms from a path's stream (tor_rng_uniform_device / tor_rng_uniform_host): u[i, k] = uniform01(rng[i])
@@ -2273,6 +2366,28 @@ class MediaScatter(tuple):
         self.rays, self.attenuation, self.rng, self._keep = rays, attenuation, rng, keep
         self.mode = _mode_of(note, "media scatter: ")
         return self
+
+
+class PhaseSample(tuple):
+    """The answers of Context.sample_phase: the pair (rays (n, 7), attenuation (n, 3)) as a MediaScatter is, which also carries
+    them by name with pdf (n,) -- the solid-angle density of the drawn direction --, rng ((n, 4), the states as the draws left
+    them) and `mode`, the library's note."""
+
+    def __new__(cls, rays, attenuation, pdf, rng, note: str, keep=None):
+        self = super().__new__(cls, (rays, attenuation))
+        self.rays, self.attenuation, self.pdf, self.rng, self._keep = rays, attenuation, pdf, rng, keep
+        self.mode = _mode_of(note, "phase sample: ")
+        return self
+
+
+class PhaseEval:
+    """The answers of Context.phase, one per item (include/tor_phase.h): value (n, 3) float64 the mixture's albedo times its
+    phase function, pdf (n,) the density sample_phase gives the outgoing direction, `mode` the library's note."""
+    __slots__ = ("value", "pdf", "mode", "_keep")
+
+    def __init__(self, value, pdf, note: str, keep=None):
+        self.value, self.pdf, self._keep = value, pdf, keep
+        self.mode = _mode_of(note, "phase eval: ")
 
 
 class Uniforms(tuple):

@@ -6,7 +6,8 @@
 //
 // The media table (tor_scene_media) is one device record of 16 float64 per medium, packed when the table is set:
 //     [0..2] center / center0   [3..5] center1 - center0   [6] time0   [7] time1 - time0   [8] 1.0 for a MovingSphere, else 0.0
-//     [9] radius * radius   [10] sigma   [11..13] albedo   [14] the object's index in the uploaded list (int64 bits)   [15] unused
+//     [9] radius * radius   [10] sigma   [11..13] albedo   [14] the object's index in the uploaded list (int64 bits)   [15] g: 0.0 here;
+//     tor_scene_media_phase (tor_phase.hip) sets the asymmetry of the phase function
 // -- the centre data and radius * radius are the scene's cold record's (tor_kernels.hpp), so the roots are roots_of's
 // (tor_crossings.hip) operation for operation.  Medium m is read at a wave-uniform address through the scalar-load view.
 //

@@ -1,5 +1,5 @@
-"""The host integrators of Context: trace, trace_direct, trace_light, trace_photons, trace_photon_map, trace_environment and
-trace_media -- wavefront loops over the path-step queries (bounce, bounce_select, sky, occluded, the samplers).  What the loops
+"""The host integrators of Context: trace, trace_direct, trace_light, trace_photons, trace_photon_map, trace_environment,
+trace_media and trace_media_direct -- wavefront loops over the path-step queries (bounce, bounce_select, sky, occluded, the samplers).  What the loops
 share is written once here: the entry and exit for numpy and torch operands, the step's head and tail (_Paths), the sky on a miss,
 the Lambertian next-event bookkeeping (_LambertianNee) and the conversion of the per-object operands.  Each integrator keeps a body
 of its own for what is its own.  The package's __init__ gives the functions named in INTEGRATORS to Context as methods; their first
@@ -10,7 +10,8 @@ import numpy as np
 
 from . import BOUNCE_MISS, BOUNCE_SCATTERED, MEDIA_COLLIDED, MEDIA_ESCAPED, Camera, Photons, _Arrays, _Tensors, _is_tensor
 
-INTEGRATORS = ("trace", "trace_direct", "trace_light", "trace_photons", "trace_photon_map", "trace_environment", "trace_media")
+INTEGRATORS = ("trace", "trace_direct", "trace_light", "trace_photons", "trace_photon_map", "trace_environment", "trace_media",
+               "trace_media_direct")
 
 
 def _flags(x, dev):
@@ -543,7 +544,7 @@ def trace_environment(ctx, rays, rng, diffuse, max_depth=50, direct=True, mis=Fa
     return p.finish(color)
 
 
-def trace_media(ctx, rays, rng, max_depth=50, sky=None, mask=None, free_flight=None):
+def trace_media(ctx, rays, rng, max_depth=50, sky=None, mask=None, free_flight=None, phase=False):
     """The volumetric twin of trace(): a wavefront path tracer through the surfaces of the scene and the media of the table.
     att = 1; per iteration, for the live rays, in this order: hit() with `mask` (the surfaces a ray sees; the media's
     boundary spheres belong to a group the mask leaves out); ONE uniform01 per live ray (uniform()); tau = free_flight(u),
@@ -554,18 +555,63 @@ def trace_media(ctx, rays, rng, max_depth=50, sky=None, mask=None, free_flight=N
     max_depth iterations are black.  So the draw order of a path is, per iteration, the free-flight uniform first, then
     the draws of whichever scatter it met.  Returns (color (n, 3), rng (n, 4) after the path's last draw).
 
+    phase: False -- the isotropic scatter above; True -- a collision scatters by the media's Henyey-Greenstein phase functions
+    (set_media_phase; sample_phase(): three outputs of the stream where scatter_media draws two, at the same place of the
+    draw order) and att *= its attenuation.
+
     sky: None (Context.sky) or sky(rays, index) -> (len(index), 3), as for trace().  mask: as for hit(), or a callable
     mask(step).  free_flight: a callable on the (n,) tensor of uniforms giving tau (every entry is evaluated, the live ones
     are used).  hit() takes no list, so every iteration's closest-hit launch runs on all n rays and the hits of the rays
     that have ended are not read; uniform, march_media and the two scatters run on the live list.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the
     device and come back as numpy."""
+    return _media_loop(ctx, "trace_media", rays, rng, max_depth, sky, mask, free_flight, phase, None)
+
+
+def trace_media_direct(ctx, rays, rng, emission, lamp_mask, max_depth=50, sky=None, mask=None, free_flight=None, transmit=None,
+                       strategy="solid_angle"):
+    """trace_media(phase=True) plus lamps: the lamps of the light table (set_lights) light the fog.  Emission found by hitting
+    an object adds att * emission[object] -- unless the path's previous vertex was a medium collision, where the light sample
+    has already counted it.  At every collision that is not on the last of the max_depth steps, with the point the scattered
+    ray's origin and time: sample_lights gives a segment to a lamp; occluded(segment, (0.001, 1.0), mask=lamp_mask) its
+    visibility; march_media(segment, inf, (0.0, 1.0)) its optical depth; T = transmit(depth), default torch's exp(-depth) (a
+    callable lets a test use defined bits, as free_flight does); phase(the incoming rays, the collision's active word, the
+    segment) the value; and the collision adds
+        att_before * value * emission[lamp] * (T / pdf)
+    where the segment is free, lamp >= 0 and the light's pdf is finite and > 0.  lamp_mask is required (ValueError for
+    None): without one the media's own boundary spheres would shadow every segment.
+
+    The light draws come from _light_states of the paths' entry states, so path states and draw order are those of
+    trace_media(phase=True), as trace_direct relates to trace: with an all-zero emission the colours and states are its,
+    bit for bit.  emission: (n_objects, 3) float64; strategy as for sample_lights; the rest as for trace_media.  Out of
+    scope: light samples at surfaces through fog, MIS between phase and light sampling, chromatic extinction, phase
+    functions other than Henyey-Greenstein."""
+    if lamp_mask is None:
+        raise ValueError("Context.trace_media_direct: lamp_mask is required (the media's boundary spheres would shadow every segment)")
+    return _media_loop(ctx, "trace_media_direct", rays, rng, max_depth, sky, mask, free_flight, True,
+                       (emission, lamp_mask, transmit, strategy))
+
+
+def _media_loop(ctx, who, rays, rng, max_depth, sky, mask, free_flight, phase, direct):
+    """The loop of trace_media and trace_media_direct; direct: None, or (emission, lamp_mask, transmit, strategy).  Without
+    `phase` and `direct` every launch and every bit is trace_media's as it was before either existed."""
     import torch
-    p = _Paths.from_rays(ctx, "trace_media", rays, rng, None)
+    p = _Paths.from_rays(ctx, who, rays, rng, None)
     n, dev, work, color, att = p.n, p.dev, p.work, p.color, p.att
     inf = torch.full((n,), float("inf"), dtype=torch.float64, device=dev)
     t_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
     u = torch.zeros((n, 1), dtype=torch.float64, device=dev)
     march, nxt = None, None
+    if direct is not None:
+        emission, lamp_mask, transmit, strategy = direct
+        emission = _colours(emission, dev)
+        lrng = _light_states(p.entry())
+        points = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+        shadow_range = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        shadow_range[:, 0], shadow_range[:, 1] = 0.001, 1.0
+        seg_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+        seg_range[:, 1] = 1.0
+        after_collision = torch.zeros((n,), dtype=torch.bool, device=dev)   # the path's previous vertex was a medium collision
+        ls, occ, seg, ev = None, None, None, None
     for step in p.steps(max_depth):
         live = p.live
         hit = ctx.hit(work, time_range=p.tr, mask=mask(step) if callable(mask) else mask)
@@ -580,19 +626,43 @@ def trace_media(ctx, rays, rng, max_depth=50, sky=None, mask=None, free_flight=N
         surface = live[(st == MEDIA_ESCAPED) & (obj >= 0)]
         missed = idx[(st == MEDIA_ESCAPED) & (obj < 0)]
         alive = torch.zeros((n,), dtype=torch.bool, device=dev)
+        lit = color[missed].clone() if direct is not None and missed.numel() else None   # what the light samples have added
         if sky is not None:
             p.caller_sky(sky, missed)
         elif missed.numel():   # (Context.sky on the list of the misses, not on every stepped ray as trace() asks it)
             color[missed] = ctx.sky(work, missed.int())[missed] * att[missed]
+        if lit is not None:    # (a path's sky is its only colour without lamps, and is assigned; with them it is added)
+            color[missed] = lit + color[missed]
         if surface.numel():
+            if direct is not None:   # emission found by hitting it, unless the light sample at a collision has counted it
+                si = surface.long()
+                found = att[si] * emission[hit.object[si].long()]
+                color[si] = color[si] + torch.where(after_collision[si][:, None], torch.zeros_like(found), found)
             res = ctx.scatter(work, hit, p.rng, index=surface)
             si = surface.long()
             sc = si[res.status[si] == BOUNCE_SCATTERED]
             att[sc] = att[sc] * res.attenuation[sc]
             alive[sc] = True
+            if direct is not None:
+                after_collision[sc] = False
         if collided.numel():
-            nxt = ctx.scatter_media(work, march, p.rng, index=collided, out=nxt)
+            nxt = (ctx.sample_phase if phase else ctx.scatter_media)(work, march, p.rng, index=collided, out=nxt)
             ci = collided.long()
+            if direct is not None:
+                after_collision[ci] = True
+                if step != int(max_depth) - 1:   # the light sample at the collision; `work` still holds the incoming rays
+                    points[ci, 0:3], points[ci, 3] = nxt.rays[ci, 0:3], nxt.rays[ci, 6]
+                    ls = ctx.sample_lights(points, lrng, collided, strategy, out=ls)
+                    occ = ctx.occluded(ls.rays, shadow_range, collided, p.tr, "auto", out=occ, mask=lamp_mask)
+                    seg = ctx.march_media(ls.rays, inf, seg_range, index=collided, out=seg)
+                    depth = seg.depth[ci]
+                    T = torch.exp(-depth) if transmit is None else \
+                        torch.as_tensor(transmit(depth), dtype=torch.float64).to(dev).reshape(-1)
+                    ev = ctx.phase(work, march.active, ls.rays, collided, out=ev)
+                    pdf, lamp = ls.pdf[ci], ls.light[ci].long()
+                    ok = (~occ.occluded[ci]) & (lamp >= 0) & (pdf > 0) & torch.isfinite(pdf)
+                    add = att[ci] * ev.value[ci] * emission[lamp.clamp(min=0)] * (T / pdf)[:, None]
+                    color[ci] = color[ci] + torch.where(ok[:, None], add, torch.zeros_like(add))
             work[ci] = nxt.rays[ci]
             att[ci] = att[ci] * nxt.attenuation[ci]
             alive[ci] = True
