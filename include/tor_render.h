@@ -308,7 +308,8 @@ TOR_API int tor_render_device(TorContext* ctx, const TorCamera* cam, int32_t nro
  * tor_accum_noise_device: from sums S, moments M of total_samples = N >= 2 samples, each channel's standard error of the
  * mean sqrt(max(0, (M - S*S/N) / (N - 1)) / N) in linear (pre-gamma) units; d_err (nullable, npix float64) receives the
  * per-pixel maximum over the three channels, out[0] / out[1] the frame's mean / maximum of it, reduced in a fixed order
- * (repeated calls return the same bits).  Blocking: returns when out is filled.  (The formula needs S, M and N only: the
+ * (repeated calls return the same bits).  A channel whose sum is NaN or infinite reports 0 (max(0, .) takes a NaN variance to
+ * 0), an infinite moment beside a finite sum inf; no NaN is reported.  Blocking: returns when out is filled.  (The formula needs S, M and N only: the
  * raw moments of tor_render_resume_device and tor_render_resume_list_device are served as they are.) */
 TOR_API int tor_render_accumulate_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                                          int32_t first_sample, int32_t n_samples, int64_t max_depth,
@@ -376,12 +377,16 @@ TOR_API int tor_render_resume_device(TorContext* ctx, const TorCamera* cam, int3
  * each operation one IEEE float64 rounding, nothing fused; the pixel has converged iff se_c <= abs_tol + rel_tol * mean_c for
  * all three channels.  d_counts[p] = n for every listed p (npix int32, the sample map), the unconverged pixels to d_list_out in
  * input order (an ordered compaction: d_list_out must not alias d_list_in), their number to *n_out.  Every entry must be a pixel
- * of d_sums.  abs_tol, rel_tol >= 0, not NaN.  n_in == 0 gives *n_out = 0.  Blocking: returns when *n_out is known.  It reads
+ * of d_sums.  abs_tol, rel_tol >= 0, not NaN.  A channel whose sum is NaN or infinite has se_c = 0 there: the pixel never
+ * converges when that makes the right-hand side NaN or -inf (a NaN sum; -inf; +inf with rel_tol = 0), and a sum of +inf with
+ * rel_tol > 0 counts as converged.  n_in == 0 gives *n_out = 0.  Blocking: returns when *n_out is known.  It reads
  * S, M and n only, so it serves the raw sums and moments of tor_render_resume_list_device (TOR_SEED_PIXEL) as it is.
  *
  * tor_resolve_counts_device: d_pixels[i] = pow(d_sums[i] / counts[i / 3], 1 / gamma_correction) for npix pixels, computed as
  * (1.0 / counts) * sum -- tor_resolve_device's operations with total_samples = counts[i / 3], so the same bits.  Every count
- * must lie in [1, 2^17].  d_pixels == d_sums resolves in place.  Asynchronous on hip_stream.  On the raw sums of
+ * must lie in [1, 2^17]; the counts live on the device, so one outside is not rejected and gives what the arithmetic gives: a
+ * count of 0 (scale inf) inf for a positive sum and NaN for a sum of 0, a negative count NaN for a positive sum and 0 for a
+ * sum of 0.  d_pixels == d_sums resolves in place.  Asynchronous on hip_stream.  On the raw sums of
  * tor_render_resume_list_device it gives, per pixel, the reference's pixel at counts[p] samples per pixel. */
 TOR_API int tor_render_accumulate_list_device(TorContext* ctx, const TorCamera* cam, int32_t nrows, int32_t ncols,
                                               const int32_t* d_list, int32_t n_list, int32_t first_sample, int32_t n_samples,
@@ -775,7 +780,8 @@ TOR_API int tor_context_handoff_stalled(TorContext* ctx, int32_t* stalled_out, i
 TOR_API int tor_context_scene_counters(TorContext* ctx, int64_t out[3]);
 
 /* Device-side output stage (io/ppm.nim:15-16 quantiser int(256*clamp(c,0,0.999))):
- * d_pixels (n_rows*ncols*3 float64) -> d_rgb8 (n_rows*ncols*3 bytes), same row order. */
+ * d_pixels (n_rows*ncols*3 float64) -> d_rgb8 (n_rows*ncols*3 bytes), same row order.  A NaN channel gives byte 0 (black):
+ * the reference's int(256 * clamp(NaN)) is undefined, and here no NaN reaches the conversion. */
 TOR_API int tor_quantize_rgb8_device(TorContext* ctx, const double* d_pixels, int64_t n_values,
                                      uint8_t* d_rgb8, void* hip_stream);
 
@@ -789,7 +795,8 @@ TOR_API int tor_quantize_rgb8_device(TorContext* ctx, const double* d_pixels, in
  *                            SPS announces ceil(size/16) macroblocks, its flushFrame writes floor(size/16).)
  *   tor_encode_frame_device: d_pixels = finished canvas (nrows*ncols*3 float64, row 0 = bottom);
  *                            d_slice receives tor_h264_frame_bytes() bytes; d_y/d_cb/d_cr (nullable)
- *                            receive the planes (H264Encoder.getFrameBuffers, h264.nim:206-224).
+ *                            receive the planes (H264Encoder.getFrameBuffers, h264.nim:206-224).  A NaN
+ *                            channel enters the colour conversion as byte 0, as in tor_quantize_rgb8_device.
  * Concatenating header + slices gives the Annex-B .264 file of main_animation_mp4;
  * tor_mp4_mux_file wraps it into the .mp4 (host side). */
 TOR_API int tor_h264_stream_header(int32_t width, int32_t height, uint8_t* out, int32_t cap);

@@ -98,6 +98,7 @@ def lib(variant: str | None = None):
     L.oracle_libm_pow.argtypes = [dp, C.c_double, dp, C.c_int64]
     L.oracle_quantize36.argtypes = [C.c_double]
     L.oracle_quantize36.restype = C.c_double
+    L.oracle_unit_vector_probe.argtypes = [dp, dp, dp, dp, C.c_int64]
     L.oracle_quantize_ppm.argtypes = [dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
     L.oracle_num_threads.restype = C.c_int
     u8p = C.POINTER(C.c_uint8)
@@ -203,6 +204,16 @@ def port_pow(x: np.ndarray, y: float, variant=None) -> np.ndarray:
     out = np.empty_like(x)
     lib(variant).oracle_port_pow(_dp(x), float(y), _dp(out), x.size)
     return out
+
+
+def unit_vector_probe(x: np.ndarray, y: np.ndarray):
+    """u = unit_vector((x, y, 0.5)) of vec3s.nim:106-107, element-wise -> (u . (1, 2, 3), u.x): the product's math self-test op 6."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    assert x.shape == y.shape
+    dot, ux = np.empty_like(x), np.empty_like(x)
+    lib().oracle_unit_vector_probe(_dp(x), _dp(y), _dp(dot), _dp(ux), x.size)
+    return dot, ux
 
 
 def quantize_ppm(pixels: np.ndarray) -> np.ndarray:

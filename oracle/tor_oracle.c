@@ -398,11 +398,17 @@ static double port_pow5(double x) {
 static inline double bits_to_double(uint64_t b) { double d; memcpy(&d, &b, 8); return d; }
 static inline uint64_t double_to_bits(double d) { uint64_t b; memcpy(&b, &d, 8); return b; }
 
-/* pow(x, y) for finite x >= 0 and finite y > 0 (the gamma curve, canvas.nim:52-54).
- * Other arguments fall back to libm (never produced by the path). */
+/* pow(x, y) for finite 0 <= x <= 2^1000 and finite 0 < y <= 2^20 (the gamma curve, canvas.nim:52-54): csrc/tor_math.hpp pow_pos,
+ * the same operations in the same order, on every argument.  Outside that domain, the same exits in the same order: NaN for
+ * !(x >= 0) or !(y > 0) (a NaN, a negative base, y <= 0), 0 for x == 0, inf for x > 2^1000; then, on the binary exponent n of
+ * the result while it is still a double, inf for n > 2000, 0 for n < -1100 (below half the smallest subnormal: a subnormal
+ * squared gets there inside the domain) and NaN for a NaN (y = inf beside x = 1), so that n is converted to int and the two scale
+ * factors are built only from exponents of normal doubles.  libm is not consulted: the reference never produces such arguments,
+ * the product's kernels can. */
 static double port_pow(double x, double y) {
-  if (!(x >= 0.0) || !(y > 0.0) || x > 0x1p+1000 || y > 0x1p+20) return pow(x, y);
+  if (!(x >= 0.0) || !(y > 0.0)) return __builtin_nan("");
   if (x == 0.0) return 0.0;
+  if (x > 0x1p+1000) return __builtin_inf();
   int e = 0;
   if (x < 0x1p-1022) { x *= 0x1p+54; e = -54; } /* subnormal */
   uint64_t b = double_to_bits(x);
@@ -427,9 +433,12 @@ static double port_pow(double x, double y) {
   dd ex = INV_FACT[16];
   for (int i = 15; i >= 0; --i) ex = dd_add(INV_FACT[i], dd_mul(r, ex));
   ex = dd_mul(ex, ex); ex = dd_mul(ex, ex); ex = dd_mul(ex, ex);
+  if (fn > 2000.0) return __builtin_inf();
+  if (fn < -1100.0) return 0.0;
+  if (fn != fn) return __builtin_nan("");
   int n = (int)fn;
   double res = ex.hi;
-  /* scale by 2^n in two exact steps (n is within [-1100, 1100] here) */
+  /* scale by 2^n in two steps, each factor a normal double: n1, n2 within [-550, 1000] after the exits above */
   int n1 = n / 2, n2 = n - n1;
   res *= bits_to_double((uint64_t)(n1 + 1023) << 52);
   res *= bits_to_double((uint64_t)(n2 + 1023) << 52);
@@ -945,15 +954,20 @@ EXPORT void oracle_port_pow(const double* x, double e, double* y, int64_t n) { f
 EXPORT void oracle_libm_sincos(const double* a, double* s, double* c, int64_t n) { for (int64_t i = 0; i < n; ++i) { s[i] = sin(a[i]); c[i] = cos(a[i]); } }
 EXPORT void oracle_libm_pow(const double* x, double e, double* y, int64_t n) { for (int64_t i = 0; i < n; ++i) y[i] = pow(x[i], e); }
 EXPORT double oracle_quantize36(double x) { return quantize36(x); }
+/* the twin of the product's math self-test op 6: u = vunit((x, y, 0.5)) -> dot[i] = u . (1, 2, 3), ux[i] = u.x */
+EXPORT void oracle_unit_vector_probe(const double* x, const double* y, double* dot, double* ux, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) { V3 u = vunit(v3(x[i], y[i], 0.5)); dot[i] = vdot(u, v3(1.0, 2.0, 3.0)); ux[i] = u.x; }
+}
 
-/* io/ppm.nim:15-16 quantiser: int(256 * clamp(c, 0.0, 0.999)); rows bottom-up like :20.
+/* io/ppm.nim:15-16 quantiser: int(256 * clamp(c, 0.0, 0.999)); rows bottom-up like :20.  A NaN channel is 0 (the reference's
+ * int(256 * clamp(NaN)) is undefined): `c > 0.0` is tested first, as in the product's three copies.
  * out: nrows*ncols*3 bytes, first row = TOP scanline (row nrows-1 of the canvas). */
 EXPORT void oracle_quantize_ppm(const double* pixels, int32_t nrows, int32_t ncols, uint8_t* out) {
   for (int32_t i = nrows - 1, k = 0; i >= 0; --i, ++k)
     for (int32_t j = 0; j < ncols; ++j)
       for (int ch = 0; ch < 3; ++ch) {
         double c = pixels[((size_t)i * ncols + j) * 3 + ch];
-        double cl = c < 0.0 ? 0.0 : (c > 0.999 ? 0.999 : c); /* safe_math.nim:10-14 */
+        double cl = c > 0.0 ? (c > 0.999 ? 0.999 : c) : 0.0; /* safe_math.nim:10-14; a NaN is 0 and never converted */
         out[((size_t)k * ncols + j) * 3 + ch] = (uint8_t)(int)(256 * cl);
       }
 }
@@ -1088,7 +1102,7 @@ EXPORT void oracle_to_rgb_raw(const double* pixels, int32_t nrows, int32_t ncols
     for (int32_t j = 0; j < ncols; ++j)
       for (int ch = 0; ch < 3; ++ch) {
         double c = pixels[((size_t)(nrows - 1 - i) * ncols + j) * 3 + ch];
-        double cl = c < 0.0 ? 0.0 : (c > 0.999 ? 0.999 : c);
+        double cl = c > 0.0 ? (c > 0.999 ? 0.999 : c) : 0.0; /* a NaN is 0 and never converted */
         out[((size_t)i * ncols + j) * 3 + ch] = (uint8_t)(256 * cl);
       }
 }

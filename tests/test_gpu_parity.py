@@ -61,10 +61,14 @@ def test_device_math_is_bit_identical_to_oracle(tor, oracle):
     r, _ = tor.selftest_math(4, num, den)
     assert np.array_equal(r, num / den)
     q, _ = tor.selftest_math(5, x)
-    assert np.array_equal(q, np.array([L.oracle_quantize36(float(v)) for v in x[:2000]]).tolist() + q[2000:].tolist())
-    u, _ = tor.selftest_math(6, x, x[::-1].copy())
-    uh, _ = tor.selftest_math(6, x, x[::-1].copy(), where="host")
-    assert np.array_equal(u, uh)
+    assert np.array_equal(q[:2000], np.array([L.oracle_quantize36(float(v)) for v in x[:2000]]))
+    from output_restatement import quantize36
+    assert np.array_equal(q, quantize36(x))                   # all 400 000 against the restatement (held to the rational statement on the CPU)
+    u, ux = tor.selftest_math(6, x, x[::-1].copy())
+    uh, uxh = tor.selftest_math(6, x, x[::-1].copy(), where="host")
+    assert np.array_equal(u, uh) and np.array_equal(ux, uxh)
+    uo, uxo = oracle.unit_vector_probe(x, x[::-1].copy())      # ... and against the oracle's unit vector (vec3s.nim:106-107)
+    assert np.array_equal(u, uo) and np.array_equal(ux, uxo)
 
 
 @pytest.mark.parametrize("arith", [0])   # (round 5: TOR_ARITH_FUSED removed)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import hit_restatement as H
+from output_restatement import noise as _numpy_noise      # tor_accum_noise_device restated, in the kernels' fixed order
 
 pytestmark = pytest.mark.gpu
 
@@ -239,38 +240,6 @@ def test_checkpoint(tor, cases):
     assert torch.equal(again.image().cpu(), full.image().cpu())
     other.close()
     ctx.close()
-
-
-def _numpy_noise(S, M, n):
-    """tor_accum_noise_device restated: the per-pixel error, and its sum in the kernels' fixed order (strided per thread, a tree per
-    block of 256, then the blocks the same way)"""
-    n = float(n)
-    var = (M - S * S / n) / (n - 1.0)
-    var = np.where(var > 0.0, var, 0.0)
-    e = np.sqrt(var / n).max(axis=-1).reshape(-1)
-    npix = e.size
-    blocks = min((npix + 255) // 256, 1024)
-
-    def tree(v):
-        v = v.copy()
-        w = 128
-        while w > 0:
-            v[:w] = v[:w] + v[w:2 * w]
-            w >>= 1
-        return v[0]
-
-    partial = np.zeros(blocks)
-    for b in range(blocks):
-        acc = np.zeros(256)
-        for i0 in range(b * 256, npix, blocks * 256):
-            chunk = e[i0:i0 + 256]
-            acc[:chunk.size] = acc[:chunk.size] + chunk
-        partial[b] = tree(acc)
-    acc = np.zeros(256)
-    for b0 in range(0, blocks, 256):
-        chunk = partial[b0:b0 + 256]
-        acc[:chunk.size] = acc[:chunk.size] + chunk
-    return e, tree(acc) / npix, float(e.max())
 
 
 def test_noise(tor, cases):

@@ -26,6 +26,8 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double* sums, double
 // Progressive rendering (tor_accum_noise_device): per pixel, the largest over the channels of the standard error of the mean,
 // sqrt(max(0, (M - S*S/n) / (n - 1)) / n), linear units; err nullable.  Block b sums / maxes pixels b*256 + t + k*gridDim*256
 // in a fixed order and a fixed tree: partials[2b] = sum, partials[2b + 1] = max.
+// Outside the finite: `var > 0.0 ? var : 0.0` takes a NaN variance to 0, so a channel whose sum is NaN or infinite (S * S / n = inf,
+// M - inf = -inf or NaN) reports noise 0; only an infinite moment beside a finite sum reports inf.  No NaN leaves this kernel.
 __global__ __launch_bounds__(256) void accum_noise_kernel(const double* sums, const double* moments, long long npix, double n,
                                                            double* err, double* partials) {
   __shared__ double s_sum[256], s_max[256];
@@ -89,6 +91,10 @@ __global__ __launch_bounds__(256) void accum_noise_finish_kernel(const double* p
 // Convergence of a pixel with sums S, moments M of n samples: per channel, mean = S / n, se = sqrt(max(0, (M - S*S/n) / (n-1)) / n)
 // (accum_noise_kernel's operations), converged iff se <= abs_tol + rel_tol * mean in all three channels.  Every operation is one IEEE
 // float64 rounding, nothing fused, so a host restatement in float64 reproduces the keep set bit for bit.
+// Outside the finite: a channel whose sum is NaN or infinite has se = 0 (as in accum_noise_kernel) and mean = NaN or +-inf.  A NaN
+// mean, or rel_tol = 0 beside an infinite one (0 * inf), makes the right-hand side NaN, and a mean of -inf makes it -inf: `<=` is
+// false and the pixel never converges.  A sum of +inf with rel_tol > 0 converges (0 <= inf), as does anything under abs_tol = inf
+// whose right-hand side is not NaN.
 __device__ __forceinline__ bool adaptive_still_active(const double* sums, const double* moments, unsigned pix, double n, double abs_tol,
                                                       double rel_tol) {
 #pragma clang fp contract(off)
@@ -187,19 +193,22 @@ __global__ __launch_bounds__(256) void resolve_counts_kernel(const double* sums,
   if (i < n_values) pixels[i] = pow_pos((1.0 / (double)counts[i / 3]) * sums[i], gamma);
 }
 
-// io/ppm.nim:15-16 ; safe_math.nim:10-14
+// io/ppm.nim:15-16 ; safe_math.nim:10-14: int(256 * clamp(c, 0, 0.999)).  A NaN channel is black: `c > 0.0` is tested first, so that
+// no NaN reaches the float-to-int conversion (undefined in C++; the reference's int(256 * clamp(NaN)) is undefined too).  The same
+// text stands in encode_ipcm_kernel below, in tor_canvas_to_rgb8 (tor_host.cpp) and in the oracle's two quantisers.
+__device__ __forceinline__ int quantize_channel(double c) {
+  const double cl = (c > 0.0) ? ((c > 0.999) ? 0.999 : c) : 0.0;
+  return (int)(256 * cl);
+}
+
 __global__ __launch_bounds__(256) void quantize_kernel(const double* pixels, long long n_values, uint8_t* out) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_values) {
-    double c = pixels[i];
-    double cl = (c < 0.0) ? 0.0 : ((c > 0.999) ? 0.999 : c);
-    out[i] = (uint8_t)(int)(256 * cl);
-  }
+  if (i < n_values) out[i] = (uint8_t)quantize_channel(pixels[i]);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Per-frame output stage of the animation driver (trace_of_radiance_animation.nim:186-196), fused:
-//   Canvas -> RGB8        io/rgb.nim:17-31   uint8(256 * clamp(c, 0, 0.999)), top scanline first.
+//   Canvas -> RGB8        io/rgb.nim:17-31   uint8(256 * clamp(c, 0, 0.999)), top scanline first; a NaN channel is 0.
 //                         (rgb.nim:29-31 indexes canvas[nrows - i, j], one row past the end for
 //                         i = 0; the intended flip canvas[nrows - 1 - i, j] is implemented here.)
 //   RGB8 -> Y'CbCr 4:2:0  io/color_conversions.nim:180-252, BT.601 fixed point:
@@ -222,11 +231,7 @@ __global__ __launch_bounds__(256) void encode_ipcm_kernel(const double* pixels, 
   const double* px = pixels + ((size_t)(nrows - 1 - sr) * ncols + sc) * 3;
   int rgb[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double v = px[c];
-    const double cl = (v < 0.0) ? 0.0 : ((v > 0.999) ? 0.999 : v);  // safe_math.nim:10-14
-    rgb[c] = (int)(uint8_t)(int)(256 * cl);
-  }
+  for (int c = 0; c < 3; ++c) rgb[c] = quantize_channel(px[c]);  // safe_math.nim:10-14; in [0, 255], a NaN channel 0
   const int tY = (77 * rgb[0] + 150 * rgb[1] + 29 * rgb[2]) >> 8;     // color_conversions.nim:218-220
   const uint8_t Y = (uint8_t)(((tY * 110) >> 7) + 16);                // :223
   s_u[threadIdx.x] = (short)(rgb[2] - tY);                            // :221

@@ -141,7 +141,8 @@ int64_t tor_random_scene(uint64_t seed, TorHittableVariant* out, int64_t cap) {
   return n;
 }
 
-// io/ppm.nim:14-27: rows from nrows-1 down to 0, int(256 * clamp(c, 0.0, 0.999))
+// io/ppm.nim:14-27: rows from nrows-1 down to 0, int(256 * clamp(c, 0.0, 0.999)).  A NaN channel is 0: `c > 0.0` is tested first,
+// so that no NaN reaches the float-to-int conversion (quantize_kernel's text).
 int tor_canvas_to_rgb8(const TorCanvas* canvas, uint8_t* out) {
   if (!canvas || !canvas->pixels || !out) return TOR_ERR_INVALID_ARGUMENT;
   const int32_t nrows = canvas->nrows, ncols = canvas->ncols;
@@ -151,7 +152,7 @@ int tor_canvas_to_rgb8(const TorCanvas* canvas, uint8_t* out) {
       const TorVec3& px = canvas->pixels[(size_t)i * ncols + j];
       const double ch[3] = {px.x, px.y, px.z};
       for (int c = 0; c < 3; ++c) {
-        const double cl = ch[c] < 0.0 ? 0.0 : (ch[c] > 0.999 ? 0.999 : ch[c]);  // safe_math.nim:10-14
+        const double cl = ch[c] > 0.0 ? (ch[c] > 0.999 ? 0.999 : ch[c]) : 0.0;  // safe_math.nim:10-14
         out[k++] = (uint8_t)(int)(256 * cl);
       }
     }
