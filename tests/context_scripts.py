@@ -1,17 +1,19 @@
 """Scripts over ONE long-lived context, and a model of the context's documented state (tests/test_context_scripts.py on the CPU,
 tests/test_gpu_context_scripts.py on the MI355X).
 
-A script is a list of steps -- setters (upload, set_groups, set_lights, set_environment), queries of every family, renders and the
-passes of two open accumulations -- as a host that keeps one context alive for a whole animation issues them.  script(name) returns
+A script is a list of steps -- setters (upload, set_groups, set_lights, set_environment, set_media, set_media_phase,
+build_photons), queries of every family, renders and the passes of two open accumulations -- as a host that keeps one context alive for a whole animation issues them.  script(name) returns
 the steps; Model replays them and says, per step, EITHER the state the answer depends on (records, group words or none, light table
-or none, environment map or none) OR that the step must be refused (code, a word of the message).  The model restates
-include/tor_render.h, tor_lights.h, tor_env.h and the Python docstrings (what an upload resets and what it keeps); inputs() draws a
+or none, environment map or none, media table with its g or none, photon map or none) OR that the step must be refused (code, a
+word of the message).  The model restates include/tor_render.h, tor_lights.h, tor_env.h, tor_media.h, tor_phase.h, tor_photons.h
+and the Python docstrings (what an upload resets and what it keeps); inputs() draws a
 step's operands and answer() hands them to the family's restatement under a given state.  Nothing here judges an answer.
 
 The inputs are shaped so that a stale cache shows: the edited copy of a scene changes the ground sphere's radius and material and
 the centre of object 3, so `probe` rows (segments that end between the two grounds, points a little above the ground, hits and BSDF
 items on the ground, lamps that include object 3) answer differently under the old records; `movers` rows are aimed at movers at
-times at the far end of the new time range.  numpy only (the restatements of bounce, scatter, radiance and the samplers draw
+times at the far end of the new time range; media rows are aimed at the boundary objects of the media tables, object 3 first
+among them; gather points come from the point sets of the current photon map and of the one before it.  numpy only (the restatements of bounce, scatter, radiance and the samplers draw
 through the oracle's exported generator, which the caller hands in)."""
 import copy
 
@@ -31,8 +33,13 @@ import hit_restatement as H
 import light_inputs as LI
 import light_restatement as LR
 import masked_restatement as M
+import media_inputs as MI
+import media_restatement as MR
 import nearest_inputs as NI
 import nearest_restatement as N
+import phase_restatement as PR
+import photon_inputs as PI
+import photon_restatement as PH
 import query_regimes as Q
 import radiance_restatement as RR
 import render_regimes as R
@@ -137,17 +144,102 @@ def env_map(key):
     return _envs[key]
 
 
+# ---- media tables, asymmetries, photon maps ------------------------------------------------------------------------------------------------
+# A media table lists boundary objects of the uploaded scene: boundaries(scene) = [MOVED, a mover where the scene has one, the two
+# objects nearest to MOVED] (in the dense scenes they overlap it: several media at once).  name: (which of the four, in table
+# order; sigma x the scene's scale; albedo).  B lists three of A's four in another order with other sigma and albedo: a stale
+# table shows, and so does a table packed from the previous records (the edit moves MOVED); the counts differ, so the note does too.
+MEDIA = {"A": ((0, 1, 2, 3), (2.0, 0.7, 3.0, 1.3), ((0.9, 0.1, 0.5), (0.2, 0.8, 1.0), (0.6, 0.6, 0.3), (1.0, 0.5, 0.25))),
+         "B": ((2, 0, 1), (1.1, 2.5, 0.9), ((0.3, 0.6, 0.9), (0.7, 0.7, 0.1), (0.05, 0.4, 0.8)))}
+BAD_MEDIA = {"twice": "listed twice", "negative": "sigma"}      # refused tables: an index listed twice, a negative sigma
+G = {"P": (0.6, -0.4, 0.0, 0.85), "Q": (-0.7, 0.3, -0.2, 0.0)}   # per medium, cut to the table's count: every sign changes, each has a 0
+# name: (the case of tests/photon_inputs.py, directions?, radius, what the powers are multiplied by -- the Python layer's scale
+# differs by 2^52 between L and S --, how many of the case's points are near photons)
+PHOTON_MAPS = {"L": ("sparse", True, PI.R, 2.0 ** 12, 192), "S": ("dense257", False, 0.2, 2.0 ** -40, 96), "E": ("dense0", True, PI.R, 1.0, 96)}
+PATHS = 1000.0                                          # what PhotonGather.irradiance divides by
+_boundaries, _maps = {}, {}
+
+
+def boundaries(name):
+    """The four boundary objects of a scene's media tables (see MEDIA)."""
+    if name not in _boundaries:
+        recs = records(name)
+        ok = placeable(recs) & (np.abs(recs[:, 9]) > 0)
+        assert ok[MOVED]
+        ok[MOVED] = False
+        movers = np.flatnonzero(ok & (recs[:, 0] == 1))
+        m = int(movers[0]) if movers.size else int(np.flatnonzero(ok)[0])
+        ok[m] = False
+        rest = np.flatnonzero(ok)
+        gap = np.linalg.norm(recs[rest, 1:4] - recs[MOVED, 1:4], axis=1) - np.abs(recs[rest, 9]) - abs(recs[MOVED, 9])
+        near = rest[np.argsort(gap, kind="stable")[:2]]
+        _boundaries[name] = (MOVED, m, int(near[0]), int(near[1]))
+    return _boundaries[name]
+
+
+def media_table(key, name, bad=None):
+    """(objects int32, sigma, albedo (n, 3)) of the named table on the named scene; bad: one of BAD_MEDIA."""
+    which, c, albedo = MEDIA[key]
+    objects = np.array([boundaries(name)[k] for k in which], dtype=np.int32)
+    sigma = np.array(c, dtype=np.float64) / scale(name)
+    if bad == "twice":
+        objects[-1] = objects[0]
+    if bad == "negative":
+        sigma[1] = -sigma[1]
+    return objects, sigma, np.array(albedo, dtype=np.float64)
+
+
+def g_vector(key, n):
+    """The asymmetries of `key` for a table of n media; None: every medium 0."""
+    return np.zeros(n) if key is None else np.array(G[key][:n], dtype=np.float64)
+
+
+def power_scale(powers):
+    """Context.build_photons' docstring: the power of two that puts the largest finite channel in (1/2, 1]."""
+    p = np.asarray(powers, dtype=np.float64)
+    top = float(np.where(np.isfinite(p), p, 0.0).max()) if p.size else 0.0
+    if not top > 0.0:
+        return 1.0
+    s = 2.0 ** -np.ceil(np.log2(top))
+    assert 0.5 < top * s <= 1.0
+    return float(s)
+
+
+def photon_map(key, listed=False):
+    """The named map: position, power, direction (or None), radius, index (the build's list or None: `listed` keeps every other photon
+    in another order, one of them twice, with two entries outside), scale (the Python layer's) and stored, the
+    restatement's map of the scaled powers.  points: the case's query points that lie near photons."""
+    if (key, listed) not in _maps:
+        case, dirs, radius, factor, n_near = PHOTON_MAPS[key]
+        c = PI.BY_NAME[case]
+        n = len(c["position"])
+        index = None
+        if listed and n:
+            perm = np.random.default_rng(n).permutation(n)
+            index = np.concatenate([perm[:n - n // 2], [-1, n, perm[0]]]).astype(np.int32)
+        power = c["power"] * factor
+        s = power_scale(power)
+        m = dict(position=c["position"], power=power, direction=c["direction"] if dirs else None, radius=radius, index=index, scale=s,
+                 has_dir=dirs, points=c["points"][:n_near])
+        m["stored"] = PH.store(m["position"], power * s, m["direction"], radius, index)
+        _maps[(key, listed)] = m
+    return _maps[(key, listed)]
+
+
 # ---- families ---------------------------------------------------------------------------------------------------------------------------
 RAY_FAMILIES = ("hit", "occluded", "crossings", "bounce", "radiance")
 BLOCK_FAMILIES = RAY_FAMILIES + ("nearest",)            # they take a mode and a time range: `bnd` and what hangs on it
 MASKED = tuple(f + "_m" for f in ("hit", "occluded", "crossings", "nearest", "bounce"))
 LIGHT_FAMILIES = ("sample_lights", "light_pdf", "emit_lights")
 ENV_FAMILIES = ("environment", "sample_environment")
-SCENE_FREE = ENV_FAMILIES + ("connect_camera", "deposit")   # they read no scene: no upload can change their answer
-QUERY_FAMILIES = BLOCK_FAMILIES + ("scatter", "bsdf") + MASKED + LIGHT_FAMILIES + ENV_FAMILIES + ("connect_camera", "deposit")
+MEDIA_FAMILIES = ("march_media", "scatter_media", "sample_phase", "phase")   # they read the media table
+PHASE_FAMILIES = ("sample_phase", "phase")              # ... and word 15 of it
+NEW_FAMILIES = ("gather_photons",) + MEDIA_FAMILIES + ("uniform",)
+SCENE_FREE = ENV_FAMILIES + ("connect_camera", "deposit", "gather_photons", "uniform")   # they read no scene: no upload can change their answer
+QUERY_FAMILIES = BLOCK_FAMILIES + ("scatter", "bsdf") + MASKED + LIGHT_FAMILIES + ENV_FAMILIES + ("connect_camera", "deposit") + NEW_FAMILIES
 FAMILIES = QUERY_FAMILIES + ("render",)
 ACCUMULATIONS = ("progressive", "pixel_progressive")
-SLOW = ("bounce", "bounce_m", "scatter", "radiance")    # their restatements loop in Python: 64 rays
+SLOW = ("bounce", "bounce_m", "scatter", "radiance", "sample_phase")    # their restatements loop in Python: 64 rays
 BATCHES = (1, 63, 64, 65, 257)
 MODES = ("auto", "brute", "blocks")
 TIME_RANGES = ((0.0, 1.0), (0.5, 0.5), (-3.0, 0.5), None)
@@ -164,16 +256,26 @@ def takes_mode(family):
 
 
 EVENTS = UPLOAD_EVENTS + ("time", "words")
+# which setter writes the table a family reads (the `setter` / `behind_queued_work` pair)
+SETTER_OF = dict([(f, ("set_lights",)) for f in LIGHT_FAMILIES] + [(f, ("set_environment",)) for f in ENV_FAMILIES]
+                 + [(f, ("set_media", "set_media_phase") if f in PHASE_FAMILIES else ("set_media",)) for f in MEDIA_FAMILIES]
+                 + [("gather_photons", ("build_photons",))])
 
 
 def transition_table():
     """The committed table: the cross product of every query and render family with the five events -- a replacing, a cache-hit
     and a refused upload, the time range changed since the last block query (`bnd` rebuilt), the group words changed since the last
-    masked query (`grp` rebuilt) -- and the four pairs.  The two accumulations have two passes per script and stand in the table as
-    the last pair."""
+    masked query (`grp` rebuilt) -- and the four pairs; then what the media table, its phase word and the photon map add (below).
+    The two accumulations have two passes per script and stand in the table as a pair."""
     t = [(f, e) for f in FAMILIES for e in EVENTS]
     t += [(f, "lights_after_upload") for f in LIGHT_FAMILIES] + [(f, "map_kept") for f in ENV_FAMILIES]
     t += [("host_twin", "smaller_after_device"), ("accumulation", "ten_foreign_steps")]
+    # media_table / phase_g / photon_map: another table, g or map since the family last ran; media_after_upload: set_media after a
+    # replacing upload copies the NEW records; map_kept: a gather behind a replacing upload; a host twin of the new families behind a
+    # larger device call of another family; a setter behind a render and a query of the table it writes, no host step between
+    t += [(f, "media_table") for f in MEDIA_FAMILIES] + [(f, "phase_g") for f in PHASE_FAMILIES] + [("gather_photons", "photon_map")]
+    t += [(f, "media_after_upload") for f in MEDIA_FAMILIES] + [("gather_photons", "map_kept")]
+    t += [("new_host_twin", "smaller_after_device"), ("setter", "behind_queued_work")]
     return t
 
 
@@ -181,8 +283,10 @@ def transition_table():
 class State:
     """What an answer can depend on: names and keys, resolved by records(), words(), light_table(), env_map()."""
 
-    def __init__(self, scene=None, groups=None, lights=None, env=None):
+    def __init__(self, scene=None, groups=None, lights=None, env=None, media=None, phase=None, photons=None):
         self.scene, self.groups, self.lights, self.env = scene, groups, lights, env
+        self.media, self.phase, self.photons = media, phase, photons   # a key of MEDIA, a key of G, (a key of PHOTON_MAPS, listed?)
+        self.packed = None                                # alternatives() alone: the scene whose records a stale table was packed from
 
     def but(self, **kw):
         s = copy.copy(self)
@@ -191,7 +295,7 @@ class State:
         return s
 
     def key(self):
-        return (self.scene, self.groups, self.lights, self.env)
+        return (self.scene, self.groups, self.lights, self.env, self.media, self.phase, self.photons)
 
 
 REFUSED = "refused"
@@ -212,7 +316,16 @@ class Model:
     an unknown kind is refused (TOR_ERR_INVALID_ARGUMENT, "unknown") and changes nothing; any other list replaces the scene, resets
     the group words (every object 0xFFFFFFFF) and clears the light table.  The environment map belongs to the context and
     survives every upload.  A light query without a table and an environment query without a map are refused (code -1, "light
-    table" / "environment map").  Renders and unmasked queries read no words; the time range of a block query is a speed hint."""
+    table" / "environment map").  Renders and unmasked queries read no words; the time range of a block query is a speed hint.
+
+    tor_scene_media (include/tor_media.h): the table is packed from the scene's records at the call; an empty one clears it, and
+    so does every replacing upload (a byte-identical or refused one keeps it); an index listed twice and a negative sigma are
+    refused and change nothing; every table starts with g = 0.  tor_scene_media_phase (tor_phase.h): refused without a table
+    ("media table") and with another count ("n_media").  The march, the scatter, the phase sampler and its evaluation are refused
+    before the first upload ("no scene") and without a table ("media table").  tor_photons_build_device (tor_photons.h): the map
+    belongs to the context and survives every upload, a build replaces it and needs no scene; a gather before any build is refused
+    ("no photon map"), one with normals on a map built without directions too ("without directions"; a build of no photons holds
+    nothing that normals could miss).  tor_rng_uniform_device needs nothing."""
 
     def __init__(self):
         self.state = State()
@@ -252,7 +365,30 @@ class Model:
             for ev in self.since.values():               # (what an earlier upload left pending is superseded)
                 ev.pop("cache_hit", None), ev.pop("refused", None)
             self._note("replace", s.scene)
-            self.state = State(step["scene"], None, None, s.env)
+            self.state = State(step["scene"], None, None, s.env, None, None, s.photons)
+            return Expect(step, self.state, None, {})
+        if op == "set_media":
+            if s.scene is None:
+                return Expect(step, s, (-1, "no scene"), {})
+            if step.get("bad"):
+                return Expect(step, s, (-1, BAD_MEDIA[step["bad"]]), {})
+            self._note("media_table", s.media, MEDIA_FAMILIES)
+            self._note("phase_g", s.phase, PHASE_FAMILIES)   # (every table starts isotropic)
+            self.state = s.but(media=step["table"], phase=None)
+            return Expect(step, self.state, None, {})
+        if op == "set_media_phase":
+            if s.scene is None:
+                return Expect(step, s, (-1, "no scene"), {})
+            if s.media is None:
+                return Expect(step, s, (-1, "media table"), {})
+            if step.get("wrong_count"):
+                return Expect(step, s, (-1, "n_media"), {})
+            self._note("phase_g", s.phase, PHASE_FAMILIES)
+            self.state = s.but(phase=step["g"])
+            return Expect(step, self.state, None, {})
+        if op == "build_photons":
+            self._note("photon_map", s.photons, ("gather_photons",))
+            self.state = s.but(photons=(step["map"], bool(step["listed"])))
             return Expect(step, self.state, None, {})
         if op == "set_groups":
             self.state = s.but(groups=step["words"])
@@ -278,6 +414,12 @@ class Model:
             return Expect(step, s, (-1, "light table"), events)
         if family in ENV_FAMILIES and s.env is None:
             return Expect(step, s, (-1, "environment map"), events)
+        if family in MEDIA_FAMILIES and (s.scene is None or s.media is None):
+            return Expect(step, s, (-1, "no scene" if s.scene is None else "media table"), events)
+        if family == "gather_photons" and s.photons is None:
+            return Expect(step, s, (-1, "no photon map"), events)
+        if family == "gather_photons" and step.get("normals") and not photon_map(*s.photons)["has_dir"]:
+            return Expect(step, s, (-1, "without directions"), events)
         if takes_mode(family) and step["mode"] != "brute":
             now = self.effective_range(step, times)
             if self.block_range is not None and now != self.block_range:
@@ -313,11 +455,46 @@ def alternatives(e):
     had they become the scene.  words / table / map: the previous words, table, map.  The families of SCENE_FREE read no scene and
     are exempt from every upload event; `time` at a block query is judged by time_rows().  `time` and `words` reach every other
     family too (the bounds or the words were rebuilt since it last ran, in buffers that lie beside its own): no restatement of
-    theirs can depend on either, so nothing is asked of their inputs, and the GPU test holds their answers all the same."""
+    theirs can depend on either, so nothing is asked of their inputs, and the GPU test holds their answers all the same.
+
+    The media families: replace with the table gone -- the previous table would answer (REFUSED against an answer); replace with
+    the table set again -- the march under a table packed from the PREVIOUS records (the scatter, the sampler and the evaluation
+    read sigma, albedo and g alone); cache_hit / refused -- REFUSED, had the upload cleared the table; media_table / phase_g /
+    photon_map -- the previous table, g, map (REFUSED where there was none, or where the previous map would refuse the normals).
+    `uniform` reads nothing and is exempt from everything; `gather_photons` reads no scene and is exempt from the upload events."""
     f, s, out = e.step["family"], e.state, []
     for event, old in e.events.items():
         if event in UPLOAD_EVENTS and f in SCENE_FREE:
             out.append((event, None, "reads no scene"))
+        elif f == "uniform":
+            out.append((event, None, "reads nothing"))
+        elif event in UPLOAD_EVENTS and f in MEDIA_FAMILIES:
+            if event == "replace" and s.media is None:   # the table should be gone: the previous one would answer
+                out.append((event, REFUSED if e.refuse is None else s.but(media="A"), ""))
+            elif event == "replace":                     # set again since: packed from the previous records?
+                fits = old is not None and len(records(old)) > int(media_table(s.media, s.scene)[0].max())
+                if f != "march_media":
+                    out.append((event, None, "reads sigma, albedo and g of the table, no boundary"))
+                else:
+                    out.append((event, s.but(packed=old) if fits else None, "the previous list does not hold these objects"))
+            else:                                        # a cache hit or a refusal taken for a replacing upload clears the table
+                out.append((event, REFUSED if s.media is not None else None, "no table either way"))
+        elif event == "media_table":
+            if f not in MEDIA_FAMILIES or old == s.media:
+                out.append((event, None, "set again to what it was"))
+            else:
+                out.append((event, REFUSED if old is None or s.media is None else s.but(media=old), ""))
+        elif event == "phase_g":
+            if f not in PHASE_FAMILIES or s.media is None or old == s.phase:
+                out.append((event, None, "set again to what it was, or no table"))
+            else:
+                out.append((event, s.but(phase=old), ""))
+        elif event == "photon_map":
+            if f != "gather_photons" or old == s.photons:
+                out.append((event, None, "built again as it was"))
+            else:
+                no_dirs = old is not None and e.step.get("normals") and not photon_map(*old)["has_dir"]
+                out.append((event, REFUSED if old is None or s.photons is None or no_dirs else s.but(photons=old), ""))
         elif event == "replace":
             if f in LIGHT_FAMILIES and s.lights is None:
                 out.append((event, REFUSED if e.refuse is None else s.but(lights="A"), ""))
@@ -501,6 +678,75 @@ def point_inputs(step, name):
     return np.ascontiguousarray(pts)
 
 
+def _unit(rng, n):
+    u = rng.normal(size=(n, 3))
+    return u / np.linalg.norm(u, axis=1, keepdims=True)
+
+
+def _media_of(state):
+    """(records, objects, sigma, albedo, g) a media query reads under `state` (a table packed from state.packed's records)."""
+    objects, sigma, albedo = media_table(state.media, state.scene)
+    return records(state.packed or state.scene), objects, sigma, albedo, g_vector(state.phase, len(objects))
+
+
+def media_rays(step, name):
+    """rays (n, 7) aimed at the boundary objects of the scene's media tables, as the lamp rows are aimed at lamps: every other row
+    at MOVED, every fourth at the mover, the rest at the two others; every fourth origin lies inside its object, the others two
+    to three radii out; directions of any length; times in [0, 1].  Without a scene: media_inputs' rays."""
+    n, rng = int(step["n"]), _rng(step, 3)
+    if name is None:
+        return np.ascontiguousarray(MI._rays(int(step["seed"]), n))
+    recs, b = records(name), boundaries(name)
+    i = np.arange(n)
+    chosen = recs[np.where(i % 2 == 0, b[0], np.where(i % 4 == 1, b[1], np.where(i % 8 == 3, b[2], b[3])))]
+    t = rng.uniform(0.0, 1.0, n)
+    c, r = _centres(chosen, t), np.abs(chosen[:, 9])
+    o = c + _unit(rng, n) * (r * np.where(i % 4 == 2, rng.uniform(0.0, 0.8, n), rng.uniform(2.0, 3.0, n)))[:, None]
+    d = (c + _unit(rng, n) * (0.3 * r)[:, None]) - o
+    d = d / np.linalg.norm(d, axis=1, keepdims=True) * (r * rng.uniform(0.3, 3.0, n))[:, None]
+    return np.ascontiguousarray(np.concatenate([o, d, t[:, None]], axis=1))
+
+
+def _media_inputs(step, state, x):
+    """The operands of a media query: rays and tau (media_inputs._taus); for the scatter, the sampler and the evaluation t and
+    active of the restated march under the step's state (their infinite budgets made small: more rows collide), 0 where the
+    model refuses the step."""
+    f, n, seed = step["family"], int(step["n"]), int(step["seed"])
+    rays, tau = media_rays(step, state.scene), MI._taus(seed, n)
+    if f == "march_media":
+        x["rays"], x["tau"] = rays, tau
+        return
+    t, active = np.zeros(n), np.zeros(n, dtype=np.int64)
+    if state.scene is not None and state.media is not None:
+        recs, objects, sigma, _, _ = _media_of(state)
+        m = MR.march(recs, objects, sigma, rays, np.where(np.isinf(tau), 0.05, tau))
+        t, active = m["t"], np.ascontiguousarray(m["active"]).view(np.int64)
+    x["active"] = active
+    if f == "phase":
+        rng = _rng(step, 4)
+        out = rays.copy()
+        out[:, 3:6] = _unit(rng, n) * rng.uniform(0.3, 3.0, n)[:, None]
+        x["rays_in"], x["rays_out"] = rays, out
+    else:
+        x["rays"], x["t"], x["states"] = rays, np.ascontiguousarray(t), _states(n, seed)
+
+
+def _gather_inputs(step, x):
+    """points (n, 3) drawn by turns from the point sets of the step's maps (those that lie near photons), per-point radii about the
+    maps' radius and unit normals where the step asks for them."""
+    n, rng = int(step["n"]), _rng(step, 5)
+    pools = [photon_map(k)["points"] for k in step["pools"]]
+    pts = np.empty((n, 3))
+    for k, pool in enumerate(pools):
+        rows = np.arange(k, n, len(pools))
+        pts[rows] = pool[rng.integers(0, len(pool), rows.size)]
+    x["points"] = pts
+    if step.get("normals"):
+        x["normals"] = _unit(rng, n)
+    if step.get("radius"):
+        x["radius"] = rng.uniform(0.1, 0.375, n)          # (0.4 .. 1.5 of the larger R: some are clamped to the map's)
+
+
 def inputs(oracle, step, state):
     """The operands of a query, render or pass step under `state`, as numpy arrays: drawn from the step's seed, the scene's
     records and (scatter, bsdf) the restatement's own hits."""
@@ -544,6 +790,12 @@ def inputs(oracle, step, state):
     elif f == "deposit":
         c, p = DI.case(DI.CASES[seed % len(DI.CASES)], 1.0, seed)
         x["colors"], x["pixels"] = np.ascontiguousarray(c[:n]), np.ascontiguousarray(p[:n])
+    elif f in MEDIA_FAMILIES:
+        _media_inputs(step, state, x)
+    elif f == "gather_photons":
+        _gather_inputs(step, x)
+    elif f == "uniform":
+        x["states"] = _states(n, seed)
     elif f in ("render",) + ACCUMULATIONS:
         recs = records(name)                            # (the camera looks at the objects: a ground sphere does not stretch its box)
         x["camera"] = R.camera(regime(name), "outside", recs[1:] if ground(recs) == 0 else recs)
@@ -617,6 +869,30 @@ def answer(oracle, step, x, state):
     if f == "deposit":
         w = D.deposit(x["colors"], x["pixels"], FILM[0] * FILM[1], 1.0)
         return {q: w[q] for q in ("sums", "moments", "counts")}
+    if f in MEDIA_FAMILIES:
+        mrecs, objects, sigma, albedo, gs = _media_of(state)
+        if f == "march_media":
+            w = MR.march(mrecs, objects, sigma, x["rays"], x["tau"])
+            return {q: w[q] for q in ("status", "t", "depth", "rho", "active")}
+        if f == "scatter_media":
+            w = MR.scatter(oracle, sigma, albedo, x["rays"], x["t"], x["active"], x["states"])
+            return {q: w[q] for q in ("rays", "attenuation", "states")}
+        if f == "sample_phase":
+            w = PR.sample(oracle, sigma, albedo, gs, x["rays"], x["t"], x["active"], x["states"])
+            return {q: w[q] for q in ("rays", "attenuation", "pdf", "states")}
+        return PR.evaluate(sigma, albedo, gs, x["rays_in"], x["active"], x["rays_out"])
+    if f == "uniform":
+        u, st = MR.uniforms(oracle, x["states"], int(step["draws"]))
+        return {"u": u, "states": st}
+    if f == "gather_photons":
+        m = photon_map(*state.photons)
+        w = PH.gather(m["stored"], x["points"], x.get("normals"), x.get("radius"), step["kernel"], 1.0)
+        # PhotonGather.irradiance: sums / scale times the kernel's normalisation over paths, with r = min(radius, R); 0 where
+        # nothing was accepted
+        r = np.minimum(x["radius"], m["radius"]) if "radius" in x else np.full(len(x["points"]), m["radius"])
+        c = (2.0 if step["kernel"] == "epanechnikov" else 1.0) / (np.pi * PATHS * m["scale"])
+        w["irradiance"] = w["sums"] * np.where(w["count"] > 0, c / (r * r), 0.0)[:, None]
+        return w
     ocam = R.oracle_camera(oracle, x["camera"])
     if f == "render":
         px = oracle.render(R.H, R.W, R.SPP, ocam, recs, max_depth=R.DEPTH, seeding=int(step["seeding"]), math=oracle.MATH_PORTABLE,
@@ -670,7 +946,7 @@ def time_rows(step, x, want, state, old_range):
 
 # ---- scripts -----------------------------------------------------------------------------------------------------------------------------
 class _Builder:
-    """Appends steps.  Mode, K and max_distance are drawn independently from the builder's generator, and the
+    """Appends steps (a gather's normals, per-point radius and kernel, a build's operand kind and list go by turns too).  Mode, K and max_distance are drawn independently from the builder's generator, and the
     operand kind (device tensors or numpy arrays) and the batch size go by turns per family; the operands' mix follows from what the model says happened since the family last
     ran."""
 
@@ -698,6 +974,19 @@ class _Builder:
 
     def environment(self, key):
         self.add(op="set_environment", map=key)
+
+    def media(self, key, bad=None):
+        """set_media: a named table, None (the empty one), or a refused one (bad: a key of BAD_MEDIA)."""
+        self.add(op="set_media", table=key, bad=bad)
+
+    def phase(self, key, wrong_count=False):
+        """set_media_phase: a named g vector or None; wrong_count: one value too few."""
+        self.add(op="set_media_phase", g=key, wrong_count=wrong_count)
+
+    def photons(self, key):
+        """build_photons: from numpy or device tensors by turns, with a list every other pair of turns."""
+        t = self.turns["build_photons"] = self.turns.get("build_photons", 0) + 1
+        self.add(op="build_photons", map=key, host=bool(t % 2), listed=bool((t // 2) % 2))
 
     def _draw(self, values):
         return values[int(self.rng.integers(len(values)))]
@@ -730,6 +1019,16 @@ class _Builder:
             step["dmax"] = bool(self.rng.random() < 0.4) and not pending and "time_range" not in kw
         if family == "emit_lights":
             step["shutter"] = self._draw(CI.TIME_RANGES)
+        if family == "uniform":
+            step["draws"] = self._draw((1, 3, 16))
+        if family == "gather_photons":                   # by turns: normals, a per-point radius, the kernel
+            t, cur, old = self.turns[family], m.state.photons, pending.get("photon_map")
+            pools = tuple(dict.fromkeys(k[0] for k in (cur, old) if k is not None and k[0] != "E"))
+            step["pools"] = pools or ("L", "S")          # the points of the map and of the one before it (the empty one has none)
+            has_dir = cur is None or photon_map(*cur)["has_dir"]
+            relisted = cur is not None and old is not None and cur[0] == old[0]   # (the same photons through a list: half are gone)
+            step["normals"] = bool((t // 2) % 2) and (has_dir or not pending) and not relisted   # (a refusal settles nothing pending)
+            step["radius"], step["kernel"] = t % 3 == 0, ("constant", "epanechnikov")[(t // 4) % 2]
         step.update(kw)
         if base(family) == "crossings":
             step["records"] = step["k"] == 4
@@ -803,9 +1102,57 @@ class _Builder:
             self.query(f)
 
 
+    def new_media(self):
+        """Every media family under another table than it last saw; the phase families under another g: set where it was 0, reset
+        by set_media, and one vector after the other."""
+        other = lambda: "B" if self.model.state.media == "A" else "A"
+        for f in MEDIA_FAMILIES:
+            self.media(other())
+            self.query(f)
+        for f in PHASE_FAMILIES:
+            self.phase("P")
+            self.query(f)
+            self.media(other())                          # g is 0 again
+            self.query(f)
+            self.phase("Q")
+            self.query(f)
+            self.phase("P")
+            self.query(f)
+
+    def new_map(self):
+        """A gather behind every rebuild: the large map, the smaller one without directions (a gather with normals is refused),
+        the empty one, the large one again."""
+        for key in ("L", "S", "E", "L"):
+            self.photons(key)
+            self.query("gather_photons")
+            if key == "S":
+                self.query("gather_photons", normals=True)
+
+    def twins(self):
+        """Every new family through its host twin, behind a larger device call of another family."""
+        for f in NEW_FAMILIES:
+            self.query("hit", host=False, n=257)
+            self.query(f, host=True, **({} if f in SLOW else {"n": 63}))
+
+    def queued(self):
+        """A render, a query on device tensors, then a setter of the table that query reads: no host step in between."""
+        st = self.model.state
+        for f, setter in (("march_media", lambda: self.media("B" if st.media == "A" else "A")), ("sample_phase", lambda: self.phase("Q")),
+                          ("gather_photons", lambda: self.photons("S")), ("sample_lights", lambda: self.lights("B" if st.lights == "A" else "A")),
+                          ("environment", lambda: self.environment("n16" if st.env == "n4" else "n4"))):
+            self.render(0, 3)
+            self.query(f, host=False)
+            st = self.model.state
+            setter()
+            self.query(f)
+
+
 def _settle(b, groups="A", lights="A", env=None):
+    """Words, a light table, the media table of the same name with a g vector (P for A, Q for B), and an environment map where asked."""
     b.groups(groups)
     b.lights(lights)
+    b.media(lights)
+    b.phase("P" if lights == "A" else "Q")
     if env is not None:
         b.environment(env)
 
@@ -813,9 +1160,16 @@ def _settle(b, groups="A", lights="A", env=None):
 def _same_size(b, scene):
     """Uploads that keep the object count: a scene and its edited copy, there and back."""
     other = partner(scene)
+    b.query("uniform")                                    # needs no scene
+    b.query("gather_photons")                             # refused: no map yet
+    b.query("march_media"), b.query("phase")              # refused: no scene yet
+    b.media("A"), b.phase("P")                            # refused: no scene yet
+    b.photons("L")                                        # needs no scene
+    b.query("gather_photons")
     b.upload(scene)
     b.query("sample_lights")                              # refused: no table yet
     b.query("environment")                                # refused: no map yet
+    b.query("scatter_media"), b.phase("P")                # refused: no table yet
     _settle(b, "A", "A", "n4")
     b.every_family()
     b.singles()
@@ -828,6 +1182,13 @@ def _same_size(b, scene):
     b.new_range(BLOCK_FAMILIES + MASKED)
     b.every_family()                                      # every family behind bounds rebuilt for other ranges
     b.variants()
+    b.new_media()
+    b.new_map()
+    b.media("A", bad="twice"), b.media("B", bad="negative"), b.phase("Q", wrong_count=True)   # refused: nothing changes
+    for f in MEDIA_FAMILIES:
+        b.query(f)
+    b.twins()
+    b.queued()
     b.upload(other)                                       # a cache hit: everything kept
     b.every_family()
     b.new_words()
@@ -841,13 +1202,19 @@ def _same_size(b, scene):
     b.upload(scene)                                       # back to the first scene: the accumulations go on where they stood
     b.groups(None)
     b.lights("A")                                         # set_lights after the upload: the table copies the new records
+    b.media("B")                                          # set_media after the upload: the table is packed from the new records
     b.every_family()
+    b.phase(None)
+    b.query("sample_phase")
     b.accumulate("progressive")
     b.accumulate("pixel_progressive")
     b.environment(None)
     b.query("sample_environment")                         # refused again
     b.lights(None)
     b.query("light_pdf")                                  # refused again
+    b.media(None)
+    b.query("march_media")                                # refused again
+    b.phase(None)                                         # refused: the Python layer's count of the table is 0 too
     b.query("occluded")
 
 
@@ -864,6 +1231,10 @@ def _sizes(b):
             b.every_family()
         _settle(b, GROUPS[k % 2], tuple(LIGHTS)[k % 2])
         b.query("sample_lights"), b.query("light_pdf"), b.query("emit_lights")
+        for f in MEDIA_FAMILIES:
+            b.query(f)
+        if k == 0:
+            b.new_map()
         if k in (2, 5):
             b.upload(scene)
             b.every_family()
@@ -879,6 +1250,11 @@ def _sizes(b):
             b.every_family()
         if k == 4:
             b.variants()
+            b.new_media()
+            b.twins()
+        if k == 5:
+            b.new_map()
+            b.queued()
     b.accumulate("progressive")
     b.accumulate("pixel_progressive")
 
@@ -888,6 +1264,7 @@ def _seeded(b, n_steps):
     it from a replacing one), and an accumulation's second pass only on the scene of its first."""
     rng = b.rng
     names = ("g9", "g9_e", "dense", "dense_e", "noground", "tiny")
+    b.photons("L")
     b.upload("g9")
     _settle(b, "A", "A", "n4")
     b.accumulate("progressive")
@@ -896,7 +1273,7 @@ def _seeded(b, n_steps):
         s, r = b.model.state, rng.random()
         if r < 0.06:
             scene = names[int(rng.integers(len(names)))]
-            if scene == s.scene and (s.groups is None or s.lights is None):
+            if scene == s.scene and (s.groups is None or s.lights is None or s.media is None):
                 _settle(b, GROUPS[int(rng.integers(2))], tuple(LIGHTS)[int(rng.integers(2))])
             b.upload(scene)
         elif r < 0.09:
@@ -915,6 +1292,12 @@ def _seeded(b, n_steps):
             b.new_range((f,))
         elif r < 0.36:
             b.render(int(rng.integers(2)), (0, 3)[int(rng.integers(2))])
+        elif r < 0.40:
+            b.media((None, "A", "B")[int(rng.integers(3))])
+        elif r < 0.44:
+            b.phase((None, "P", "Q")[int(rng.integers(3))])   # (refused where there is no table)
+        elif r < 0.47:
+            b.photons(("L", "S", "E")[int(rng.integers(3))])
         else:
             b.query(QUERY_FAMILIES[int(rng.integers(len(QUERY_FAMILIES)))])
     b.upload("g9")

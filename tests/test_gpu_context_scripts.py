@@ -1,23 +1,34 @@
 """One long-lived context per script on the MI355X (tests/context_scripts.py): uploads, tables, queries of every family, renders and
 two open accumulations interleaved on one stream, with no host synchronisation between the steps other than what the library and
 its Python layer force themselves: a numpy operand (the blocking _host twins), a refusal, a replacing upload (tor_scene_upload
-waits for the device before it overwrites the scene), and a block query on device tensors with time_range=None, whose range the
-Python layer reads back from the tensor's times (torch.aminmax, a download).  The test adds none: every device operand is uploaded
+waits for the device before it overwrites the scene), a block query on device tensors with time_range=None, whose range the
+Python layer reads back from the tensor's times (torch.aminmax, a download), and build_photons on device tensors, which reads the
+largest power back for its scale.  The test adds none: every device operand is uploaded
 before the first step, every device output is kept and downloaded after the last.
 
 Arbiter: every answer is compared bit for bit with the family's restatement under the MODEL's state (context_scripts.Model: which
 records, words, table and map the step must see), NaNs as the families' own tests compare them (a NaN on both sides of a float
 field is equal, every other bit counts); renders and the accumulations with oracle.render / oracle.accumulate (PORTABLE math), the
-film with deposit_restatement.  No fresh context answers for another.  What ran (res.mode / tor.last_note()) is asserted where the
-per-family tests fix it: `brute` is the brute force, and odd_objects falls back and says why.  At the end
+film with deposit_restatement; PhotonGather.irradiance alone to 2^-50 (its docstring leaves the order of four roundings open; a
+scale that is a power of two off shows at any tolerance).  No fresh context answers for another.  What ran (res.mode / tor.last_note()) is asserted where the
+per-family tests fix it: `brute` is the brute force, odd_objects falls back and says why, the media queries name the model's count
+of media ("media march: 4 media"), a build the restatement's bucket count and scale.  At the end
 ctx.scene_counters()[:2] is the model's count of uploads and cache hits.  tests/test_context_scripts.py shows on the CPU that a
 stale cache behind any of the steps would change a quarter of its rows; profiles/context_script_mutants.txt what the same_size
 script fails on when a cache key is broken.
 
-Measured wall time on an MI355X, restatements and oracle renders included: the whole module 15.2 s for 5 tests -- same_size
-(290 steps) 5.7 s, same_size_g9 (290 steps) 0.3 s, sizes (384 steps) 6.6 s, seeded_1 (123 steps) 0.4 s, seeded_2 (123 steps)
-0.1 s; nearly all of it is the restatements on the CPU (bounce, scatter and radiance loop in Python), the library's share of a
-script is tens of milliseconds."""
+test_script_on_a_stream_of_its_own runs the two cheapest scripts once more inside one torch.cuda.Stream(): the scripts above run on
+torch's default stream, the legacy one, with which every blocking hipMemcpy of a setter serialises by itself, so a setter that
+forgot to wait for the context's last query could not show there.
+
+Measured wall time on an MI355X, restatements and oracle renders included, this module and its parent commit's in one visit.  The
+parent (before the photon, media and phase steps): 15.9 s for 5 tests, 13.5 s in the tests themselves -- same_size (290 steps)
+6.0 s, same_size_g9 (290) 0.36 s, sizes (384) 6.7 s, seeded_1 (123) 0.35 s, seeded_2 (123) 0.12 s: 11.2 ms per step.  This module:
+17.1 s for 7 tests, 15.3 s in the tests -- same_size (435 steps) 6.0 s, same_size_g9 (435) 0.68 s, sizes (561) 6.8 s, seeded_1 (123)
+0.36 s, seeded_2 (123) 0.36 s, and on a stream of its own same_size_g9 0.64 s, seeded_2 0.37 s: 6.8 ms per step over 2235 steps.
+The cost per step fell: nearly all of the time is the restatements of bounce, scatter and radiance on the 724 and 1300 objects of
+same_size and sizes (they loop in Python), and the new steps' restatements see four media or a few thousand photons; the
+library's share of a script is tens of milliseconds."""
 import numpy as np
 import pytest
 import torch
@@ -123,6 +134,30 @@ def _call(tor, ctx, step, op, env):
     if f == "deposit":
         env["film"].deposit(env["dev"]["pixels"], env["dev"]["colors"])
         return {}, None
+    if f in S.MEDIA_FAMILIES:                             # the note names the table's count: the model's
+        note = f"{len(S.MEDIA[env['state'].media or 'A'][0])} media"   # (without a table the call is refused before any note)
+        if f == "march_media":
+            res = ctx.march_media(op("rays"), op("tau"))
+            assert res.mode == note, (step, res.mode)
+            return {"status": res.status, "t": res.t, "depth": res.depth, "rho": res.rho, "active": res.active}, None
+        if f == "phase":
+            res = ctx.phase(op("rays_in"), op("active"), op("rays_out"))
+            assert res.mode == note, (step, res.mode)
+            return {"value": res.value, "pdf": res.pdf}, None
+        res = (ctx.scatter_media if f == "scatter_media" else ctx.sample_phase)(op("rays"), (op("t"), op("active")), op("states"))
+        assert res.mode == note, (step, res.mode)
+        out = {"rays": res.rays, "attenuation": res.attenuation, "states": res.rng}
+        if f == "sample_phase":
+            out["pdf"] = res.pdf
+        return out, None
+    if f == "uniform":
+        res = ctx.uniform(op("states"), step["draws"])
+        assert res.mode == f"{step['draws']} draw" + ("s" if step["draws"] > 1 else ""), (step, res.mode)
+        return {"u": res.u, "states": res.rng}, None
+    if f == "gather_photons":
+        res = ctx.gather_photons(op("points"), op("normals"), op("radius"), None, step["kernel"], 1.0)
+        assert res.note == "photons gather", (step, res.note)
+        return {"sums": res.sums, "count": res.count, "irradiance": res.irradiance(S.PATHS)}, None
     cam = tor.camera(**env["x"]["camera"])
     stream = torch.cuda.current_stream().cuda_stream
     if f == "render":
@@ -137,6 +172,31 @@ def _call(tor, ctx, step, op, env):
     assert env["open"][f].samples == step["first"]
     env["open"][f].add(3)
     return {}, None
+
+
+def _set_media(ctx, step, state):
+    if state.scene is None:                               # refused before the table is looked at
+        return ctx.set_media([S.MOVED], [1.0])
+    if step["table"] is None:
+        return ctx.set_media([], [])
+    return ctx.set_media(*S.media_table(step["table"], state.scene, step.get("bad")))
+
+
+def _set_media_phase(ctx, step, state):
+    if step["g"] is None:
+        return ctx.set_media_phase(None)
+    g = S.g_vector(step["g"], len(S.MEDIA[state.media][0]) if state.media else 4)
+    return ctx.set_media_phase(g[:-1] if step.get("wrong_count") else g)
+
+
+def _build_photons(ctx, step, dev_maps):
+    """From numpy (the blocking twin) or from tensors that were uploaded before the script began; the Python layer's scale and the
+    note are the restatement's."""
+    m = S.photon_map(step["map"], step["listed"])
+    src = m if step["host"] else dev_maps[(step["map"], step["listed"])]
+    built = ctx.build_photons(src["position"], src["power"], src["direction"], radius=m["radius"], index=src["index"])
+    assert built.scale == m["scale"] and built.radius == m["radius"], (step, built.scale, m["scale"])
+    assert built.note == f"photons build: {m['stored']['n_buckets']} buckets", (step, built.note)
 
 
 def _check_what_ran(tor, step, state, ran, model_range):
@@ -164,6 +224,10 @@ def _run(tor, oracle, name):
     asks = [e.step["op"] in ("query", "render", "pass") for e in expects]
     xs = [S.inputs(oracle, e.step, e.state) if a else None for e, a in zip(expects, asks)]
     devs = [{k: _dev(v) for k, v in x.items() if isinstance(v, np.ndarray)} if x is not None else None for x in xs]
+    dev_maps = {(st["map"], st["listed"]): None for st in steps if st["op"] == "build_photons" and not st["host"]}
+    for key in dev_maps:
+        m = S.photon_map(*key)
+        dev_maps[key] = {k: None if m[k] is None else _dev(m[k]) for k in ("position", "power", "direction", "index")}
     torch.cuda.synchronize()                              # the operands are on the device; from here on nothing waits
 
     ctx = tor.Context(0)
@@ -182,9 +246,15 @@ def _run(tor, oracle, name):
                 call = lambda: ctx.set_lights(*S.light_table(step["table"])) if step["table"] else ctx.set_lights([])
             elif op == "set_environment":
                 call = lambda: ctx.set_environment(*S.env_map(step["map"])[:2]) if step["map"] else ctx.set_environment(None)
+            elif op == "set_media":
+                call = lambda: _set_media(ctx, step, e.state)
+            elif op == "set_media_phase":
+                call = lambda: _set_media_phase(ctx, step, e.state)
+            elif op == "build_photons":
+                call = lambda: _build_photons(ctx, step, dev_maps)
             else:
                 host = bool(step.get("host")) and step["family"] != "deposit" and op == "query"
-                env["x"], env["dev"] = xs[i], devs[i]
+                env["x"], env["dev"], env["state"] = xs[i], devs[i], e.state
                 operand = lambda k: (xs[i].get(k) if host else devs[i].get(k))
                 call = lambda: _call(tor, ctx, step, operand, env)
             where = f"{name}: step {i} {step} under {e.state.key()}"
@@ -219,6 +289,10 @@ def _run(tor, oracle, name):
                 last_canvas = want["pixels"]
                 continue
             got = _records_as_fields(kept[i])
+            if "irradiance" in want:                      # four roundings in an order the docstring leaves open: 2^-50, zeros exact
+                wi, gi = want.pop("irradiance"), got.pop("irradiance")
+                if not ((gi == wi) | (np.abs(gi - wi) <= 2.0 ** -50 * np.abs(wi))).all():
+                    bad.append((i, f, "the irradiance is not sums / scale x the kernel's normalisation", e.step, e.state.key()))
             rows = S.differing_rows(want, {k: got[k].reshape(np.asarray(want[k]).shape) for k in want})
             if rows.any():
                 bad.append((i, f, f"{int(rows.sum())} of {rows.size} rows", {k: v for k, v in e.step.items() if k != "op"}, e.state.key()))
@@ -244,3 +318,16 @@ def test_script_against_the_restatements(tor, oracle, name):
     t = time.perf_counter()
     _run(tor, oracle, name)
     print(f"{name}: {len(S.script(name))} steps, {time.perf_counter() - t:.2f} s")
+
+
+@pytest.mark.parametrize("name", ("same_size_g9", "seeded_2"))
+def test_script_on_a_stream_of_its_own(tor, oracle, name):
+    """The two cheapest scripts once more, the whole script inside one non-default stream (the library's rule: one stream per
+    context).  On torch's default stream -- the legacy one -- every blocking copy of a setter waits for the queued work by itself; a
+    stream made by torch.cuda.Stream() does not block against it, so a setter that forgot to wait for the context's last query would
+    overwrite a table under a running kernel here.  The expectations are the same."""
+    import time
+    t = time.perf_counter()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        _run(tor, oracle, name)
+    print(f"{name} on a stream of its own: {len(S.script(name))} steps, {time.perf_counter() - t:.2f} s")
