@@ -1035,4 +1035,9 @@ TOR_API const char* tor_version(void);
  * was not drawn -- what lets a lamp of the light table light the fog --, defined operation by operation in tor_phase.h. */
 #include "tor_phase.h"
 
+/* ---- debug entries of the reach pass in front of the plane screen's whole words -------------------------------------------------
+ * tor_debug_reach_scene, tor_debug_last_reach: which words of the sorted list a ray can be near (host mirror), and how many whole
+ * words the last launch walked; described in tor_reach.h. */
+#include "tor_reach.h"
+
 #endif /* TOR_RENDER_H */

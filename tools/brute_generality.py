@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Is the float64 brute force (the metric's kernel, `integrate_kernel<1, 2, 3, 0, 0>`) fitted to random_scene's geometry?
+"""Is the float64 brute force (the metric's kernel: `integrate_kernel<1, 3, 3, 0, 0>` on random_scene and every layout with a segment the reach pass runs on,
+`integrate_kernel<1, 2, 3, 0, 0>` on the others) fitted to random_scene's geometry?
 (the plane screen ran only on common-height segments with y-only movers.)
 
 Workloads -- the bench scene and scenes that share none of its coincidences -- x {default, TOR_PLANE=0 (second form / first form

@@ -7,7 +7,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-$R/profiles/r5_mutation_check.txt}
 D=$(mktemp -d /tmp/tor_mut_XXXX)
 FLAGS="-O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden -munsafe-fp-atomics -Wall -Wno-unused-function -pthread"
-for lvl in 1 2; do
+for lvl in 1 2 4; do
   mkdir -p $D/$lvl
   make -C $R/trace-of-radiance_amd/csrc OUT=$D/$lvl CXXFLAGS="$FLAGS -DTOR_SCREEN_MUTATE=$lvl" > $D/build$lvl.log 2>&1 || { tail -20 $D/build$lvl.log; exit 2; }
 done
@@ -43,5 +43,7 @@ for name, dc, mv in (("statics (xkind 10 / 11)", np.zeros((n, 3)), np.zeros(n, d
     keep, need = tor.selftest_screen2(o, d, c0 - dc * fm[:, None], dc, mv, fm * mv, r * r, 2)
     print(f"   {name}: {int(np.count_nonzero((need != 0) & (keep == 0)))} of {int(np.count_nonzero(need))} needed pairs dropped")
 PY
+  echo "## -DTOR_SCREEN_MUTATE=4 (the reach pass: word boxes and slab not grown by the radius, no slack, nothing rounded outward): (ray, object) pairs of random_scene whose word is not reached and that stage two keeps or the reference hits (tests/test_reach.py as a script; the product build prints 0)"
+  TOR_AB_LIB=$D/4/libtor_mi355x.so python tests/test_reach.py 2>&1 | tail -1
 } | tee $OUT
 rm -rf $D

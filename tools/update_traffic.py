@@ -11,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # key in traffic.json -> (summary file, the integrate_kernel variant <SEEDING, ARITH, WAVES_PER_SIMD, F32, BLOCKS> that mode launches:
 # strict brute force runs behind the FMA screen = ARITH 2; the exact accelerations keep ARITH 0).  A summary whose dominant
 # integrate_kernel is another variant is an ERROR (bench.py must not replay counters of a kernel it does not run).
+# (The strict brute-force summaries below were taken before the reach pass: on random_scene those launches now run ARITH 3 = ARITH 2 +
+# the pass, <1, 3, 3, 0, 0> / <0, 3, 3, 0, 0>, with fewer VALU instructions -- profiles/reach_ab.txt.  Until new summaries are committed
+# `from_profile` is the ARITH 2 kernel's record; bench.py's `executed_live` is measured in the run itself and names the kernel it ran.)
 CONFIGS = {
     "1920x1080x100:sample:strict": ("r6_c2_summary.txt", (1, 2, 3, 0, 0)),
     "1920x1080x100:pixel:strict": ("r6_c2_pixel_brute_summary.txt", (0, 2, 3, 0, 0)),

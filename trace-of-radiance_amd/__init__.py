@@ -192,6 +192,8 @@ MEDIA_REFUSED, MEDIA_ESCAPED, MEDIA_COLLIDED = -1, 0, 1   # the status of a Cont
 # the phase-function queries (include/tor_phase.h): bound in a second step of lib(), after the table _bind gives every library
 PHASE_SYMBOLS = ["tor_scene_media_phase", "tor_phase_eval_device", "tor_phase_eval_host", "tor_phase_sample_device",
                  "tor_phase_sample_host"]
+# the debug entries of the reach pass (include/tor_reach.h), bound as the phase entries are
+REACH_SYMBOLS = ["tor_debug_reach_scene", "tor_debug_last_reach"]
 PHASE_G_MAX = 0.99          # TOR_PHASE_G_MAX: the largest |g| of Context.set_media_phase
 PHASE_G_MIN = 2.0 ** -20    # TOR_PHASE_G_MIN: the smallest |g| that is not 0
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
@@ -260,6 +262,7 @@ def lib():
     L = C.CDLL(ab or LIB_PATH)
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
     _bind(L, PHASE_SYMBOLS, skip_missing=bool(ab), table=_PHASE_SIGNATURES)
+    _bind(L, REACH_SYMBOLS, skip_missing=bool(ab), table=_REACH_SIGNATURES)
     _lib = L
     return L
 
@@ -418,6 +421,18 @@ def _phase_signatures() -> dict:
 
 
 _PHASE_SIGNATURES = _phase_signatures()
+
+
+def _reach_signatures() -> dict:
+    """The entries of include/tor_reach.h, in a table of their own like the phase entries."""
+    v, i32, i64, d, P = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER
+    return {
+        "tor_debug_reach_scene": [HittableList, i64] + [P(d)] * 3 + [P(C.c_int8), P(i32), P(i32), P(d), i64, P(i64)],
+        "tor_debug_last_reach": [v, P(C.c_uint64)],
+    }
+
+
+_REACH_SIGNATURES = _reach_signatures()
 
 
 def _bind(L, names=None, skip_missing=False, table=None) -> None:
@@ -1198,6 +1213,13 @@ class Context:
         st = Stats()
         _check(lib().tor_last_stats(self._h, C.byref(st)))
         return st
+
+    def last_reach(self):
+        """(whole words of the plane screen's stage one the last strict brute-force launch walked, whole words it met): the reach
+        pass's counters (tor_debug_last_reach; statistics must be enabled).  Blocking."""
+        out = (C.c_uint64 * 2)()
+        _check(lib().tor_debug_last_reach(self._h, out))
+        return int(out[0]), int(out[1])
 
     def set_groups(self, groups):
         """The visibility groups of the uploaded scene (tor_scene_groups): one 32-bit word per object, in list order -- anything
@@ -3097,6 +3119,27 @@ def debug_plane32_scene(world: HittableList, o, d, time):
                                          keep.ctypes.data_as(C.POINTER(C.c_int8)), pad_kept.ctypes.data_as(C.POINTER(C.c_int32)),
                                          C.byref(n_pad)))
     return keep, pad_kept, int(n_pad.value)
+
+
+def debug_reach_scene(world: HittableList, o, d, time):
+    """(reach[n_rays, n_objects] int8, word[n_objects] int32, slot[n_objects] int32, boxes[n_words, 6] float64): the reach pass in
+    front of the plane screen's whole words on the host (include/tor_reach.h) -- reach 0: the ray does not reach the boxed word of
+    the object's slot, 1: it does, or the word carries no box; word: the object's word of the sorted list when it carries a box,
+    else -1; slot: its slot; boxes: {xlo, xhi, zlo, zhi, ylo, yhi} per word in absolute coordinates (-inf, +inf: no box)."""
+    dp = lambda x: np.ascontiguousarray(x, dtype=np.float64)
+    o, d, time = dp(o), dp(d), dp(time)
+    n_obj = int(world.len)
+    reach = np.zeros((len(time), n_obj), dtype=np.int8)
+    word = np.zeros(n_obj, dtype=np.int32)
+    slot = np.zeros(n_obj, dtype=np.int32)
+    max_words = (n_obj + 31) // 32 + 8 * 64   # (every segment pads by less than a word; there are few of them)
+    boxes = np.zeros((max_words, 6), dtype=np.float64)
+    n_words = C.c_int64(0)
+    P, I = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    _check(lib().tor_debug_reach_scene(world, len(time), o.ctypes.data_as(P), d.ctypes.data_as(P), time.ctypes.data_as(P),
+                                       reach.ctypes.data_as(C.POINTER(C.c_int8)), word.ctypes.data_as(I), slot.ctypes.data_as(I),
+                                       boxes.ctypes.data_as(P), max_words, C.byref(n_words)))
+    return reach, word, slot, boxes[:min(int(n_words.value), max_words)]
 
 
 def selftest_math(op: int, x: np.ndarray, y: np.ndarray | None = None, where: str = "device", device: int = -1):

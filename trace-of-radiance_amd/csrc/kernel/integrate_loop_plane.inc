@@ -107,6 +107,103 @@
                     // writes crosses a branch, where the compiler may copy it.  The running mask goes through every statement: the
                     // v_alignbit chain pins a group's objects between its two statements.  The last request of a segment reads
                     // the group behind it: the next segment's records or the table's slack (kPlaneSlackFloats), used by nobody.
+#if TOR_REACH
+                    // THE REACH PASS (tor_screen.hpp reach_ray): which of the nw words can a ray of this wave be near at all?  The
+                    // lane's piece of ray inside the segment's height slab, as a box in xz, against the words' boxes (KParams.xwb:
+                    // one 32-byte record per word through the scalar path, four float32 compares each).  reach_l: the lane's bits
+                    // (bit w <-> word w of this phase), the ONE register the word loop carries for it; reach_w: the wave's.
+                    // Words nobody reaches are not walked: no record request, no object instruction; their LDS slots are written 0
+                    // up front (the summary is rebuilt from every slot of the pass after stage two: a stale word of an earlier
+                    // query would come back as candidates), their summary bits are shifted in clear.  A walked word costs what it
+                    // cost, one word per trip: its four requests a whole group ahead of their waits, the fourth one being the first
+                    // group of the NEXT word to walk (the group behind this word when there is none, as before), `ra` landed at
+                    // both ends of a trip, so no request crosses a branch.  A lane's bits in a word it does not reach itself are
+                    // cleared before the word is stored: stage two would drop them one by one.
+                    // (kReach: the ARITH 3 builds, launched for layouts with a segment that asks for the pass; h_rpass: the host's word for
+                    // this segment -- tor_scene.cpp: a thin height slab over a wide field and enough whole words to pay for the pass;
+                    // the other segments of such a layout walk every word, one per trip; the ARITH 2 builds run the two-word trips below)
+                    if constexpr (kReach) {
+                    if (nw > 0) {
+                      typedef float __attribute__((ext_vector_type(16))) f16v;
+                      f16v ra, rb;
+                      unsigned reach_l = ~0u, reach_w = (2u << (unsigned)(nw - 1)) - 1u;
+                      if (h_rpass) {
+                        reach_l = 0; reach_w = 0;
+                        const cfptr wb = (cfptr)(uintptr_t)p.xwb + (long)kReachRecFloats * (long)((unsigned)(seg_block0 * kBlock + i) >> 5);
+                        const cdptr wy = (cdptr)(wb + 4);
+                        const ReachRay rr = reach_ray(sray, !(ps32.T < __builtin_inff()), sray.s1 + SEG_REACH + SEG_TRAVEL * __builtin_fabs(f), h_r1, h_r2, wy[0], wy[1], f);
+                        // (four records per trip: their requests go out together, one wait for the four; the last trip may read up to
+                        // three records behind the pass's words -- the next words' or the table's slack, kReachSlackWords -- whose bits
+                        // are masked off below)
+#pragma unroll 1
+                        for (int k = 0; k < nw; k += 4) {
+#pragma unroll
+                          for (int j = 0; j < 4; ++j) {
+                            const cfptr b = wb + kReachRecFloats * (k + j);
+                            const bool hit = !reach_miss(rr, b[0], b[1], b[2], b[3]);
+                            reach_l |= hit ? 1u << (unsigned)(k + j) : 0u;
+                            reach_w |= ballot64(hit) != 0 ? 1u << (unsigned)(k + j) : 0u;
+                          }
+                        }
+                        reach_w &= (2u << (unsigned)(nw - 1)) - 1u;
+                      }
+                      for (unsigned z = ~reach_w & ((2u << (unsigned)(nw - 1)) - 1u); z != 0u; z &= z - 1u)
+                        q[(unsigned)(w_count + __builtin_ctz(z)) * 64] = 0u;
+                      if (stats_on && lane == 0) {  // debug counters (tor_debug_last_reach): whole words walked, whole words met
+                        atomicAdd(p.stats + 11, (unsigned long long)__builtin_popcount(reach_w));
+                        atomicAdd(p.stats + 12, (unsigned long long)nw);
+                      }
+#define TOR_FEEDP_REQ(nxt, ptr, off) asm volatile("s_load_dwordx16 %0, %3, %4" : "=&s"(nxt), "+v"(m), "+v"(mp) : "s"(ptr), "i"(off))
+#define TOR_FEEDP_WAIT(cur) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(cur), "+v"(m), "+v"(mp))
+#define TOR_FEEDP_WAITREQ(cur, nxt, ptr, off) \
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %1, %4, %5" : "+s"(cur), "=&s"(nxt), "+v"(m), "+v"(mp) : "s"(ptr), "i"(off))
+                      auto grp = [&](const f16v& b) {
+#pragma unroll
+                        for (int j = 0; j < kBlock; ++j) m = push_bit(m, plane_word32(ps32, b[2 * j], b[2 * j + 1]));
+                      };
+                      unsigned mp = 0;
+                      unsigned left = reach_w;  // the words still to walk
+                      int cur = -1;             // the last word walked
+                      if (left != 0u) {
+                        cur = __builtin_ctz(left);
+                        left &= left - 1u;
+                        RecPtr rc = rec + PW * 4 * kBlock * cur;
+                        TOR_FEEDP_REQ(ra, rc, 0);
+                        TOR_FEEDP_WAIT(ra);
+#pragma unroll 1
+                        for (;;) {
+                          const int nxt = left != 0u ? __builtin_ctz(left) : cur + 1;
+                          const RecPtr rn = rec + PW * 4 * kBlock * nxt;
+                          m = 0;
+                          TOR_FEEDP_REQ(rb, rc, 64); grp(ra);
+                          TOR_FEEDP_WAITREQ(rb, ra, rc, 128); grp(rb);
+                          TOR_FEEDP_WAITREQ(ra, rb, rc, 192); grp(ra);
+                          TOR_FEEDP_WAITREQ(rb, ra, rn, 0); grp(rb);
+                          mp = m & (unsigned)((int)(reach_l << (unsigned)(31 - cur)) >> 31);
+                          // (a finished word is stored BEHIND the wait, not in front of it: the wait counts LDS writes too)
+                          TOR_FEEDP_WAIT(ra);
+                          q[(unsigned)(w_count + cur) * 64] = mp;
+                          nz = push_cond(nz << (unsigned)(cur - w), mp != 0u);
+                          w = cur + 1;
+                          if (left == 0u) break;
+                          left &= left - 1u;
+                          cur = nxt;
+                          rc = rn;
+                        }
+                      }
+                      nz <<= (unsigned)(nw - w);
+                      w = nw;
+                      rec += PW * 4 * kBlock * nw;
+#undef TOR_FEEDP_REQ
+#undef TOR_FEEDP_WAIT
+#undef TOR_FEEDP_WAITREQ
+                      // the first record behind the words, for the blocks that follow: in `ra` when the last word was walked
+                      if (cur == nw - 1) { n0 = ra[0]; n1 = ra[1]; }
+                      else { n0 = rec[0]; n1 = rec[1]; }
+                      m = mp;
+                    }
+                    } else
+#endif
                     if (nw > 0) {
                       typedef float __attribute__((ext_vector_type(16))) f16v;
                       f16v ra, rb;

@@ -62,12 +62,13 @@ int fail_hip(hipError_t e, const char* what) {
 hipError_t DeviceLayout::put(const HostLayout& lay, const std::vector<double>* cold_override) {
   const std::vector<double>& c = cold_override ? *cold_override : lay.cold;
   struct Part { const void* src; size_t bytes; size_t off; };
-  Part parts[11] = {{lay.stat.data(), lay.stat.size() * 8, 0}, {lay.mov.data(), lay.mov.size() * 8, 0},
+  Part parts[13] = {{lay.stat.data(), lay.stat.size() * 8, 0}, {lay.mov.data(), lay.mov.size() * 8, 0},
                    {lay.movy.data(), lay.movy.size() * 8, 0}, {lay.segs.data(), lay.segs.size() * 8, 0},
                    {c.data(), c.size() * 8, 0},               {lay.hot32.data(), lay.hot32.size() * 4, 0},
                    {lay.coop_trips.data(), lay.coop_trips.size() * 8, 0},
                    {lay.xhdr.data(), lay.xhdr.size() * 8, 0}, {lay.xrec.data(), lay.xrec.size() * 8, 0},
-                    {lay.xpl.data(), lay.xpl.size() * 8, 0}, {lay.xpl32.data(), lay.xpl32.size() * 4, 0}};
+                    {lay.xpl.data(), lay.xpl.size() * 8, 0}, {lay.xpl32.data(), lay.xpl32.size() * 4, 0},
+                    {lay.xwb.data(), lay.xwb.size() * 4, 0}, {lay.xwb_all.data(), lay.xwb_all.size() * 4, 0}};
   size_t total = 0;
   for (Part& p : parts) {
     p.off = total;
@@ -90,8 +91,16 @@ hipError_t DeviceLayout::put(const HostLayout& lay, const std::vector<double>* c
   xrec = (const double*)(b + parts[8].off);
   xpl = (const double*)(b + parts[9].off);
   xpl32 = (const float*)(b + parts[10].off);
+  xwb = (const float*)(b + parts[11].off);
+  xwb_all = (const float*)(b + parts[12].off);
   n_segs = lay.n_segs;
   n_sorted = (int)lay.n_sorted;
+  any_reach = false;  // bit 2 of a header's gate word (tor_scene.cpp)
+  for (int s = 0; s < lay.n_segs; ++s) {
+    int32_t ints[8];
+    std::memcpy(ints, &lay.xhdr[16 * (size_t)s], sizeof(ints));
+    any_reach = any_reach || (ints[7] & 4) != 0;
+  }
   n_xrec = (int)lay.xrec.size();
   has_f32 = false;
   for (int s = 0; s < lay.n_segs; ++s) has_f32 = has_f32 || lay.segs[8 * (size_t)s] >= 5.0;
@@ -360,7 +369,7 @@ int tor_context_create(int32_t device, TorContext** out) {
   if (const char* c = tor::knob("TOR_CHAIN_THETA")) ctx->chain_theta = (float)std::atof(c);
   if (const char* c = tor::knob("TOR_TAIL_LANES")) ctx->mig_tail_lanes = std::atoi(c);
   if (const char* c = tor::knob("TOR_SCREEN")) ctx->screen = std::atoi(c) != 0;
-  if (const char* c = tor::knob("TOR_PLANE")) ctx->plane_screen = std::atoi(c);  // 0 off, 1 gated (default), 2 on every segment that carries the table
+  if (const char* c = tor::knob("TOR_PLANE")) ctx->plane_screen = std::atoi(c);  // 0 off, 1 gated (default), 2 on every segment that carries the table, 3 as 1 but the reach pass culls nothing
   if (const char* c = tor::knob("TOR_TAIL_REST")) ctx->mig_tail_rest = std::atoi(c);
   if (const char* c = tor::knob("TOR_MIG_FLAGS")) ctx->mig_flags = (unsigned)std::strtoul(c, nullptr, 0);
   if (const char* b = tor::knob("TOR_BLOCKS_PER_CU"))
@@ -627,6 +636,10 @@ static void use_layout(tor::KParams& q, const tor::DeviceLayout& L, const TorCon
   q.xrec = L.xrec;
   q.xpl = ctx->plane_screen != 0 ? L.xpl : nullptr;
   q.xpl32 = ctx->plane_screen != 0 ? L.xpl32 : nullptr;
+#if TOR_REACH
+  // (null: no segment of the layout asks for the reach pass -- the launch takes the kernels without it; TOR_PLANE=2 runs it everywhere)
+  q.xwb = (ctx->plane_screen != 0 && (L.any_reach || ctx->plane_screen == 2)) ? (ctx->plane_screen == 3 ? L.xwb_all : L.xwb) : nullptr;
+#endif
   q.plane_gate2 = ctx->plane_screen == 2 ? 0.0 : 4.0 * tor::kPlaneGate * tor::kPlaneGate;
   // stage two of the plane-screened segments reads its records per lane: from LDS when the table fits beside the per-wave
   // queues -- and, with sample streams, the camera-ray reservoirs -- at this launch's workgroups per CU (random_scene: 15.9 KB + 18.7 KB
@@ -2001,6 +2014,102 @@ int tor_debug_plane32_scene(TorHittableList world, int64_t n_rays, const double*
       }
     }
   }
+  return TOR_OK;
+}
+
+// The reach pass over a whole scene on the HOST (include/tor_reach.h): the layout, the headers and the word records
+// tor_scene_upload builds; PlaneSeg32 and ReachRay from them exactly as kernel/integrate_loop_plane.inc makes them.
+int tor_debug_reach_scene(TorHittableList world, int64_t n_rays, const double* o, const double* d, const double* time, int8_t* reach,
+                          int32_t* word_out, int32_t* slot_out, double* boxes_out, int64_t max_words, int64_t* n_words_out) {
+  if (world.len < 0 || (world.len > 0 && !world.objects) || n_rays < 0 || !o || !d || !time || !reach || max_words < 0 || (max_words > 0 && !boxes_out))
+    return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_reach_scene: bad argument");
+  std::vector<int64_t> ids((size_t)world.len);
+  for (int64_t i = 0; i < world.len; ++i) ids[(size_t)i] = i;
+  tor::HostLayout lay;
+  std::string err;
+  if (!tor::build_layout(world.objects, ids, lay, err, nullptr)) return fail(TOR_ERR_INVALID_ARGUMENT, err);
+  auto orig_of = [&](size_t slot) {
+    int64_t v;
+    std::memcpy(&v, &lay.cold[16 * slot + 14], 8);
+    return v;
+  };
+  const size_t n_words = (lay.n_sorted + 31) / 32;
+  if (n_words_out) *n_words_out = (int64_t)n_words;
+  // a word's record, and whether it carries a box: (-inf, +inf) in x says it does not
+  auto rec_of = [&](size_t w) { return &lay.xwb[w * (size_t)tor::kReachRecFloats]; };
+  auto boxed = [&](size_t w) { return !(rec_of(w)[0] == -INFINITY && rec_of(w)[1] == INFINITY); };
+  for (int64_t i = 0; i < world.len; ++i) {
+    if (word_out) word_out[i] = -1;
+    if (slot_out) slot_out[i] = -1;
+  }
+  for (size_t w = 0; w < n_words && (int64_t)w < max_words; ++w) {
+    double* b = boxes_out + 6 * w;
+    b[0] = b[2] = b[4] = -INFINITY; b[1] = b[3] = b[5] = INFINITY;
+  }
+  for (int64_t r = -1; r < n_rays; ++r) {  // (r = -1: the tables that do not depend on the ray)
+    const double* oo = o + 3 * (r < 0 ? 0 : r); const double* dd = d + 3 * (r < 0 ? 0 : r);
+    tor::ScreenRay ray{};
+    tor::PlaneRay pray{};
+    if (r >= 0) {
+      const double a = dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2];  // spheres.nim:30
+      ray = tor::screen2_ray(oo[0], oo[1], oo[2], dd[0], dd[1], dd[2], a);
+      pray = tor::plane_ray(ray);
+      for (int64_t i = 0; i < world.len; ++i) reach[r * world.len + i] = 1;
+    }
+    for (int s = 0; s < lay.n_segs; ++s) {
+      const double* sg = &lay.segs[8 * (size_t)s];
+      const double* xs = &lay.xsegs[8 * (size_t)s];
+      const double* h = &lay.xhdr[16 * (size_t)s];
+      const int xkind = (int)xs[0];
+      if ((int)sg[0] > 2) continue;  // (the float32 pre-filter's segments: not part of the float64 list's screens)
+      const int count = (int)sg[2] & 0xffffff, real = count - ((int)sg[2] >> 24), block0 = (int)sg[3];
+      const size_t slot0 = (size_t)block0 * tor::kPad;
+      if (r < 0) {
+        for (int i = 0; i < real; ++i) {
+          const size_t slot = slot0 + (size_t)i, w = slot / 32;
+          const int64_t obj = orig_of(slot);
+          if (slot_out) slot_out[obj] = (int32_t)slot;
+          if (word_out && xkind >= 10 && xkind != 13 && boxed(w)) word_out[obj] = (int32_t)w;
+        }
+        for (size_t w = (slot0 + 31) / 32; xkind >= 10 && xkind != 13 && 32 * (w + 1) <= slot0 + (size_t)count; ++w) {
+          if (!boxed(w) || (int64_t)w >= max_words) continue;
+          const float* rec = rec_of(w);
+          double* b = boxes_out + 6 * w;
+          b[0] = (double)rec[0] + h[13]; b[1] = (double)rec[1] + h[13]; b[2] = (double)rec[2] + h[14]; b[3] = (double)rec[3] + h[14];
+          std::memcpy(&b[4], rec + 4, 16);
+        }
+        continue;
+      }
+      if (xkind < 10 || xkind == 13) continue;
+      const double f = xkind >= 12 ? (time[r] - sg[4]) / sg[5] : 0.0;  // moving_spheres.nim:42
+      const tor::PlaneSeg ps = tor::plane_seg(ray, pray, sg[6], sg[7], f, xs[4]);
+      float ec[2];
+      std::memcpy(ec, &h[15], 8);
+      const tor::PlaneSeg32 ps32 = tor::plane_seg32(ray, ps, h[13], h[14], (double)ec[0], (double)ec[1]);
+      // (every word of a segment carries the segment's slab; the kernel reads it from the first word of a pass)
+      for (size_t w = (slot0 + 31) / 32; 32 * (w + 1) <= slot0 + (size_t)count; ++w) {
+        const float* rec = rec_of(w);
+        double slab[2];
+        std::memcpy(slab, rec + 4, 16);
+        const tor::ReachRay rr = tor::reach_ray(ray, !(ps32.T < INFINITY), ray.s1 + sg[6] + sg[7] * std::fabs(f), h[13], h[14], slab[0], slab[1], f);
+        if (!tor::reach_miss(rr, rec[0], rec[1], rec[2], rec[3])) continue;
+        if (!boxed(w)) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_reach_scene: a word without a box was not reached (reach pass bug)");
+        for (size_t slot = 32 * w; slot < 32 * (w + 1) && slot < slot0 + (size_t)real; ++slot) reach[r * world.len + orig_of(slot)] = 0;
+      }
+    }
+  }
+  return TOR_OK;
+}
+
+int tor_debug_last_reach(TorContext* ctx, uint64_t out[2]) {
+  if (!ctx || !out) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_last_reach: NULL argument");
+  if (!ctx->collect_stats) return fail(TOR_ERR_INVALID_ARGUMENT, "tor_debug_last_reach: stats not enabled");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long h[2];
+  // words 12, 13 of the launch's counter slot (= KParams.stats + 11, + 12): kernel/integrate_loop_plane.inc
+  HIP_TRY(hipMemcpy(h, (unsigned long long*)ctx->counters.ptr + (size_t)ctx->last_slot * TorContext::kSlotWords + 12, sizeof h, hipMemcpyDeviceToHost));
+  out[0] = h[0]; out[1] = h[1];
   return TOR_OK;
 }
 

@@ -74,10 +74,12 @@ struct DeviceLayout {
   const double* coop_trips = nullptr;  // coop_pixel_kernel: 4 float64 per trip of 64 cold slots
   const double *xhdr = nullptr, *xrec = nullptr, *xpl = nullptr;  // second form of the FMA screen and its stage one (tor_scene.hpp)
   const float* xpl32 = nullptr;  // stage one in float32 (xkinds 10 / 11 / 12 / 14)
+  const float *xwb = nullptr, *xwb_all = nullptr;  // the reach pass's word records, and the table that culls nothing (tor_scene.hpp)
   int n_segs = 0;
   int n_sorted = 0;  // cold slots (padded)
   int n_xrec = 0;    // float64 in xrec
   bool has_f32 = false;
+  bool any_reach = false;  // a segment asks for the reach pass (tor_scene.hpp xwb): launches take the kernels that carry it
   hipError_t put(const HostLayout& lay, const std::vector<double>* cold_override = nullptr);
   void release() { blob.release(); }
 };
@@ -155,7 +157,7 @@ struct HitQueryState {
 struct TorContext {
   static constexpr int kRing = 64;
   // 64-bit words per ring slot: [0] work counter, [1..4] statistics, [5] probe counter, [6] split, [7] wave-kernel counter,
-  // [8..10] tile schedule, then from kMigWord0 on the chain hand-off's control lines (tor_kernels.hpp kMig*)
+  // [8..10] tile schedule, [11] block tests, [12..13] whole words walked / met by the reach pass, then from kMigWord0 on the chain hand-off's control lines (tor_kernels.hpp kMig*)
   static constexpr int kMigWord0 = 16;
   static constexpr int kSlotWords = kMigWord0 + tor::kMigWords;
   int device = 0;
@@ -192,7 +194,7 @@ struct TorContext {
   std::vector<double> probe_bnd_host[kRing];  // block bounds of the cost probe when it runs with other accel bits than the frame (host staging of an
   std::vector<float> probe_bnd32_host[kRing];  // asynchronous copy, per ring slot like bnd_host)
   bool probe_accel = true;  // the cost probe always walks the culling layout when the scene has one (it only counts queries); (round 5: the TOR_PROBE_ACCEL switch is gone)
-  int plane_screen = 1;  // TOR_PLANE: 0 = the wave-uniform test for every object (no plane screen in front), 1 = stage one where it pays (tor_screen.hpp plane_pays), 2 = on every segment with a table
+  int plane_screen = 1;  // TOR_PLANE: 0 = the wave-uniform test for every object (no plane screen in front), 1 = stage one where it pays (tor_screen.hpp plane_pays), 2 = on every segment with a table, 3 = as 1 with a reach pass in which every lane reaches every word
   bool screen = true;       // TOR_SCREEN=0: strict brute-force launches evaluate the reference's unfused discriminant for every object (no FMA screen)
   hipEvent_t ev_start[kRing] = {}, ev_stop[kRing] = {};
   int64_t launches = 0;  // timed integrator launches so far

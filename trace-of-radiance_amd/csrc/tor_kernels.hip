@@ -324,8 +324,8 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
   }
 
   // ARITH 2: the second-form records of the screen for stage two of the plane-screened segments (kernel/integrate_loop_plane.inc)
-  const bool xstaged = ARITH == 2 && p.xrec_lds_doubles > 0;
-  if (ARITH == 2 && xstaged) {
+  const bool xstaged = ARITH >= 2 && p.xrec_lds_doubles > 0;
+  if (ARITH >= 2 && xstaged) {
     for (int k = threadIdx.x; k < p.xrec_lds_doubles; k += kThreads) stage[k] = p.xrec[k];
     __syncthreads();
   }
@@ -490,7 +490,11 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
     // -- compiled into the single-level variants it cost them ~1 % (registers) -- the others always
     constexpr bool kSuper = BLOCKS == 2 || (BLOCKS == 1 && F32 == 0);
     // ARITH 2: the reference's arithmetic (as ARITH 0) behind a conservative FMA screen in the wave-uniform object loop
-    constexpr bool kScreen = ARITH == 2;
+    constexpr bool kScreen = ARITH >= 2;
+    // ARITH 3: ARITH 2 with the reach pass in front of stage one's whole words (kernel/integrate_loop_plane.inc) -- a build of its own,
+    // launched when a segment of the layout asks for the pass (KParams.xwb set): these kernels answer to every edit, and scenes
+    // without such a segment keep the kernels they had, instruction for instruction
+    constexpr bool kReach = ARITH == 3;
     {
       // ================= (B) closest hit over all objects ==============================
       // hittables_lists.nim:48-55 with t_min = 0.001, t_max = Inf (render.nim:28)
@@ -599,6 +603,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
           // for the gate of a 4-object segment, cost 2 %).  The header also carries the segment's FIRST plane record, so the loop's
           // first request (record 1 on) overlaps the per-segment set-up instead of following it.
           int seg_kind, seg_begin, seg_count_word, seg_block0, xkind = 0, h_xfirst = 0, h_plfirst = 0, h_gate = 0;
+          bool h_rpass = false;  // ARITH 3: the reach pass runs in front of this segment's whole words
           double h_t0 = 0.0, h_dt = 1.0, h_reach = 0.0, h_travel = 0.0, h_y = 0.0, h_rmax2 = 0.0, h_sx = 0.0, h_sz = 0.0;
           double h_r0 = 0.0, h_r1 = 0.0, h_r2 = 0.0, h_r3 = 0.0;
           if constexpr (kScreen) {
@@ -611,6 +616,9 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
             asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(ha), "=&s"(hb) : "s"(hp) : "memory");
             auto f64_of = [](int lo, int hi_) { return __hiloint2double(hi_, lo); };
             xkind = ha[0]; seg_kind = ha[1]; seg_count_word = ha[2]; seg_block0 = ha[3]; seg_begin = ha[4]; h_xfirst = ha[5]; h_plfirst = ha[6]; h_gate = ha[7];
+            if constexpr (kReach) {
+              h_rpass = __builtin_amdgcn_readfirstlane((int)((h_gate & 4) != 0 || p.plane_gate2 <= 0.0)) != 0; h_gate &= 3;  // (bit 2 of the gate word: the reach pass runs in front of this segment's whole words; TOR_PLANE=2: in front of every segment's)
+            }
             h_t0 = f64_of(ha[8], ha[9]); h_dt = f64_of(ha[10], ha[11]); h_reach = f64_of(ha[12], ha[13]); h_travel = f64_of(ha[14], ha[15]);
             h_y = f64_of(hb[0], hb[1]); h_rmax2 = f64_of(hb[2], hb[3]); h_sx = f64_of(hb[4], hb[5]); h_sz = f64_of(hb[6], hb[7]);
             h_r0 = f64_of(hb[8], hb[9]); h_r1 = f64_of(hb[10], hb[11]); h_r2 = f64_of(hb[12], hb[13]); h_r3 = f64_of(hb[14], hb[15]);
@@ -757,7 +765,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
       // six 21-bit fields in units of 4096 shader cycles: refill+camera, object loop, exact resolve | shade, deposit, total
       const unsigned long long total = __builtin_readcyclecounter() - prof_lds[kSecBegin];
       auto f21 = [](unsigned long long c) { c >>= 12; return c > 0x1fffffull ? 0x1fffffull : c; };
-      w[2] = (prof_lds[kStIters] & 0xffffffffffull) | (ARITH == 2 ? f21(prof_lds[kSecStage2]) << 43 : 0ull);  // bounce iterations | stage two of the plane-screened segments (part of the object loop's field)
+      w[2] = (prof_lds[kStIters] & 0xffffffffffull) | (ARITH >= 2 ? f21(prof_lds[kSecStage2]) << 43 : 0ull);  // bounce iterations | stage two of the plane-screened segments (part of the object loop's field)
       w[6] = f21(prof_lds[kSecRefill]) | (f21(prof_lds[kSecLoop]) << 21) | (f21(prof_lds[kSecResolve]) << 42);
       w[7] = f21(prof_lds[kSecShade]) | (f21(prof_lds[kSecDeposit]) << 21) | (f21(total) << 42);
 #ifdef TOR_FINE_PROBE
@@ -773,7 +781,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
       atomicAdd(p.stats + 1, prof_lds[kStCand]);
       atomicAdd(p.stats + 2, prof_lds[kStIters]);
       atomicAdd(p.stats + 3, prof_lds[kStSamples]);
-      if (ARITH != 2) atomicAdd(p.stats + 10, prof_lds[kStBlock]);
+      if (ARITH < 2) atomicAdd(p.stats + 10, prof_lds[kStBlock]);
     }
   }
 }
@@ -806,6 +814,13 @@ static IntegrateFn integrate_variant(int seeding, int arith, int w, int f32, int
   TOR_V(3, 2, 2, 0, 0) TOR_V(3, 2, 3, 0, 0)
   TOR_V(4, 2, 2, 0, 0) TOR_V(4, 2, 3, 0, 0)
   TOR_V(5, 2, 2, 0, 0) TOR_V(5, 2, 3, 0, 0) TOR_V(6, 2, 2, 0, 0) TOR_V(6, 2, 3, 0, 0) TOR_V(7, 2, 2, 0, 0) TOR_V(7, 2, 3, 0, 0)
+#if TOR_REACH
+  // arith 3: arith 2 with the reach pass (layouts with a segment that asks for it)
+  TOR_V(0, 3, 2, 0, 0) TOR_V(0, 3, 3, 0, 0) TOR_V(1, 3, 2, 0, 0) TOR_V(1, 3, 3, 0, 0) TOR_V(2, 3, 3, 0, 0)
+  TOR_V(3, 3, 2, 0, 0) TOR_V(3, 3, 3, 0, 0)
+  TOR_V(4, 3, 2, 0, 0) TOR_V(4, 3, 3, 0, 0)
+  TOR_V(5, 3, 2, 0, 0) TOR_V(5, 3, 3, 0, 0) TOR_V(6, 3, 2, 0, 0) TOR_V(6, 3, 3, 0, 0) TOR_V(7, 3, 2, 0, 0) TOR_V(7, 3, 3, 0, 0)
+#endif
   // (round 5: a 128-register build <1, 2, 4, 0, 0> for a 4th workgroup per CU now runs 2.4 x SLOWER -- 1097 against 2613 Msamples/s
   // at configs[1]: stage two's per-lane state spills inside the loops; not built)
   // (a 128-register build of <1, 2, W, 0, 0> for a 4th workgroup per CU was measured in round 4: 1951 against 1961 Msamples/s at
@@ -833,7 +848,11 @@ static size_t dynamic_lds(const KParams& p, int seeding) {
 // the kernel variant of a launch: the brute-force layouts run behind the conservative FMA screen (variant 2: the same canvas
 // bit for bit) unless the context turned it off (KParams::screen); `arith` is TOR_ARITH_STRICT (0), the only arithmetic there is
 static int arith_variant(const KParams& p, int arith) {
-  return (arith == 0 && p.screen != 0 && wants_f32(p) == 0 && wants_blocks(p) == 0) ? 2 : 0;
+  if (!(arith == 0 && p.screen != 0 && wants_f32(p) == 0 && wants_blocks(p) == 0)) return 0;
+#if TOR_REACH
+  if (p.xwb != nullptr) return 3;  // (the same arithmetic and canvas: integrate_variant_key reports it as 2)
+#endif
+  return 2;
 }
 
 hipError_t launch_probe(const KParams& p, int blocks, hipStream_t stream) {
@@ -873,7 +892,7 @@ hipError_t launch_integrate(const KParams& p, int seeding, int arith, int waves_
 }
 
 void integrate_variant_key(const KParams& p, int seeding, int arith, int waves_per_simd, int32_t out[5]) {
-  out[0] = seeding; out[1] = arith_variant(p, arith); out[2] = clamp_w(waves_per_simd); out[3] = wants_f32(p); out[4] = wants_blocks(p);
+  out[0] = seeding; out[1] = arith_variant(p, arith) >= 2 ? 2 : 0; out[2] = clamp_w(waves_per_simd); out[3] = wants_f32(p); out[4] = wants_blocks(p);
 }
 
 int integrate_blocks_per_cu(const KParams& p, int seeding, int arith, int waves_per_simd) {

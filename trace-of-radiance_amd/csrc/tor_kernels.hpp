@@ -9,6 +9,11 @@
 #include "tor_device.hpp"
 #include "tor_filter32.hpp"
 
+// (-DTOR_REACH=0: A/B builds only -- no reach pass in front of the plane screen's whole words and no table for it: tor_screen.hpp)
+#ifndef TOR_REACH
+#define TOR_REACH 1
+#endif
+
 namespace tor {
 
 constexpr int kThreads = 256;  // 4 waves per workgroup
@@ -126,6 +131,12 @@ struct KParams {
   // starts the sums at 0; > 0: it loads {rstate, out[, mom]} of the pixel.  At the end of the pixel's pass it stores the generator
   // state (4 x u64 per pixel), the RAW sequential sum to out and -- mom != null -- the sequential sum of c * c to mom; else null
   unsigned long long* rstate;
+  // the reach pass of the plane-screened segments (kernel/integrate_loop_plane.inc, tor_screen.hpp reach_ray): kReachRecFloats floats per
+  // 32-slot word of the sorted list; null when no segment of the layout asks for the pass: the launch then takes the ARITH 2
+  // kernels, which do not carry it (TOR_PLANE=3: the table in which every word is reached by everybody)
+#if TOR_REACH
+  const float* xwb;
+#endif
 };
 
 // Control words of the hand-off, one 128-byte line per access pattern (thousands of waiting servers poll their flags and,

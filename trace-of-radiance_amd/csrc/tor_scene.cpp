@@ -284,6 +284,50 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     m.material = objs[idx].u.sphere.material;
     return m;
   };
+  // Inside a plane-screened segment with float32 plane records that the reach pass will run on, the objects go by the Morton code of their ground position over the
+  // segment's ground box (16 bits per axis), so that a word of 32 consecutive slots is a patch of ground the reach pass can rule
+  // out as a whole (tor_screen.hpp).  The order is free: the closest hit does not depend on it, ties go by the original index
+  // (cold).  Stable: equal codes -- and every non-finite centre, code 0 -- keep the order of appearance.
+  // Only where the reach pass will run (seg_reach, bit 2 of the header's gate word below): a segment of enough objects for
+  // kReachMinWords whole words wherever it starts, whose height slab is thin against its ground box -- a field.  The pass costs
+  // about what four whole words cost, and in a cloud as tall as it is wide a ray's piece inside the slab is most of the ray
+  // (measured: 3 to 10 % lost with the pass everywhere; the order alone cost a 3-D cloud of statics 4 %: profiles/reach_ab.txt).
+  // Every other segment keeps the order of appearance and the kernels it had.  A performance decision only.
+  std::vector<char> seg_reach(segs64.size(), 0);
+  for (size_t si = 0; si < segs64.size(); ++si) {
+    Seg64& sg = segs64[si];
+    if (!(TOR_REACH && sg.xkind >= 10 && sg.xkind != 13 && sg.ids.size() >= 32 * (size_t)(kReachMinWords + 1))) continue;
+    double xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY, rmax = 0.0;
+    for (int64_t idx : sg.ids) {
+      const TorMovingSphere s = as_mover(idx);
+      if (std::isfinite(s.center0.x)) { xlo = std::fmin(xlo, s.center0.x); xhi = std::fmax(xhi, s.center0.x); }
+      if (std::isfinite(s.center0.z)) { zlo = std::fmin(zlo, s.center0.z); zhi = std::fmax(zhi, s.center0.z); }
+      ylo = std::fmin(ylo, std::fmin(s.center0.y, s.center1.y)); yhi = std::fmax(yhi, std::fmax(s.center0.y, s.center1.y));
+      rmax = std::fmax(rmax, std::fabs(s.radius));
+    }
+    if (!(kReachSlabRatio * ((yhi - ylo) + 2.0 * rmax) <= std::fmin(xhi - xlo, zhi - zlo))) continue;   // (a NaN anywhere: no pass)
+    seg_reach[si] = 1;
+    auto cell = [](double c, double lo, double hi) -> uint32_t {
+      if (!std::isfinite(c) || !(hi > lo)) return 0u;
+      const double t = (c - lo) / (hi - lo) * 65535.0;   // (hi - lo may overflow: t = 0 then, or NaN from inf / inf)
+      return t >= 0.0 && t <= 65535.0 ? (uint32_t)t : 0u;
+    };
+    auto spread16 = [](uint32_t v) {  // 16 bits -> every second bit
+      v = (v | (v << 8)) & 0x00ff00ffu;
+      v = (v | (v << 4)) & 0x0f0f0f0fu;
+      v = (v | (v << 2)) & 0x33333333u;
+      v = (v | (v << 1)) & 0x55555555u;
+      return v;
+    };
+    std::vector<std::pair<uint32_t, int64_t>> keyed;
+    keyed.reserve(sg.ids.size());
+    for (int64_t idx : sg.ids) {
+      const TorMovingSphere s = as_mover(idx);
+      keyed.push_back({spread16(cell(s.center0.x, xlo, xhi)) | (spread16(cell(s.center0.z, zlo, zhi)) << 1), idx});
+    }
+    std::stable_sort(keyed.begin(), keyed.end(), [](const std::pair<uint32_t, int64_t>& a, const std::pair<uint32_t, int64_t>& b) { return a.first < b.first; });
+    for (size_t k = 0; k < keyed.size(); ++k) sg.ids[k] = keyed[k].second;
+  }
   // float64 per slot of the second-stage records (xrec) and of the plane table (xpl), by xkind
   auto xs_of = [](int xkind) { return xkind == 0 ? 0 : (xkind >= 13 ? 8 : 4); };
   auto pw_of = [](int xkind) { return xkind == 0 ? 0 : (xkind == 13 ? 4 : 2); };
@@ -328,6 +372,17 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
   out.xpl32.assign(n_xpl + kPlaneSlackFloats, kPlane32PadX);  // (the same, float32: tor_screen.hpp plane_seg32; the slack: stage one's read-ahead)
   for (size_t k = 1; k < out.xpl32.size(); k += 2) out.xpl32[k] = kPlane32PadZ;
   out.xpl32seg.clear();
+  {  // the reach pass's word records: everybody reaches everything until a segment says otherwise below
+    const size_t n_words = (out.n_sorted + 31) / 32 + (size_t)kReachSlackWords;
+    out.xwb.assign(n_words * (size_t)kReachRecFloats, 0.0f);
+    const double slab[2] = {-INFINITY, INFINITY};
+    for (size_t w = 0; w < n_words; ++w) {
+      float* rec = &out.xwb[w * (size_t)kReachRecFloats];
+      rec[0] = rec[2] = -INFINITY; rec[1] = rec[3] = INFINITY;
+      std::memcpy(rec + 4, slab, 16);
+    }
+    out.xwb_all = out.xwb;
+  }
   out.hot32.assign(n32_floats + 32, 0.0f);
   out.cold.assign(16 * out.n_sorted + 16, 0.0);
   out.segs.clear();
@@ -388,6 +443,34 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
       cm32 = std::fmax(cm32, std::fmax(std::fabs((double)fx), std::fabs((double)fz)));
     }
     out.xpl32seg.insert(out.xpl32seg.end(), {orx, orz, e32, cm32});
+    // the reach pass's records of the words wholly inside this segment (tor_screen.hpp reach_ray): the box of the STORED offsets of
+    // the word's real slots, grown by R + E; the heights the segment's centres take for f in [0, 1], grown by R.  Padding slots do
+    // not widen a box (a word of padding alone is empty: nobody who has a box reaches it, and stage two would drop it anyway).
+    // A non-finite centre, radius or rounding bound anywhere in the segment leaves all its words to everybody.
+    if (pl32) {
+      const double R = std::sqrt(rmax2) * (1.0 + 0x1p-50);
+      double ylo = INFINITY, yhi = -INFINITY;
+      bool finite = std::isfinite(R) && std::isfinite(e32) && std::isfinite(orx) && std::isfinite(orz);
+      for (int64_t idx : sg.ids) {
+        const TorMovingSphere s = as_mover(idx);
+        const double y0 = s.center0.y, y1 = s.center0.y + (s.center1.y - s.center0.y);
+        finite = finite && std::isfinite(s.center0.x) && std::isfinite(s.center0.z) && std::isfinite(y0) && std::isfinite(y1) && std::isfinite(s.radius);
+        ylo = std::fmin(ylo, std::fmin(y0, y1)); yhi = std::fmax(yhi, std::fmax(y0, y1));
+      }
+      const double slab[2] = {reach_slab_lo(ylo, R), reach_slab_hi(yhi, R)};
+      const double g0 = kReachMutant ? 0.0 : R + e32;
+      for (size_t w = (sorted + 31) / 32; finite && 32 * (w + 1) <= sorted + cnt_p; ++w) {
+        double bxl = INFINITY, bxh = -INFINITY, bzl = INFINITY, bzh = -INFINITY;
+        for (size_t k = 32 * w - sorted; k < 32 * (w + 1) - sorted && k < sg.ids.size(); ++k) {
+          const double fx = (double)out.xpl32[pl_off + 2 * k], fz = (double)out.xpl32[pl_off + 2 * k + 1];
+          bxl = std::fmin(bxl, fx); bxh = std::fmax(bxh, fx); bzl = std::fmin(bzl, fz); bzh = std::fmax(bzh, fz);
+        }
+        float* rec = &out.xwb[w * (size_t)kReachRecFloats];
+        if (bxh >= bxl) { rec[0] = reach_box_lo(bxl, g0); rec[1] = reach_box_hi(bxh, g0); rec[2] = reach_box_lo(bzl, g0); rec[3] = reach_box_hi(bzh, g0); }
+        else { rec[0] = rec[2] = INFINITY; rec[1] = rec[3] = -INFINITY; }
+        std::memcpy(rec + 4, slab, 16);
+      }
+    }
     const size_t xs = (size_t)xs_of(sg.xkind), pw = (size_t)pw_of(sg.xkind);
     for (size_t k = 0; k < cnt_p && xs != 0; ++k) {  // padding: never a candidate (second form: t'' = T - 1e300 < 0, disc'' < 0; first form: r^2 = -1), except for a wild ray, which the exact test rejects
       double* x = &out.xrec[x_off + xs * k];
@@ -514,6 +597,13 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
       const double band = 2.0 * kPlaneGate * std::sqrt(xs[4]);
       const double e_min = std::fmin(xs[5], xs[6]), e_max = std::hypot(xs[5], xs[6]);
       gate = band < e_min ? 1 : (band < e_max ? 2 : 0);     // (a NaN anywhere: never)
+    }
+    // ... and whether the reach pass runs in front of the segment's whole words: bit 2 of the gate word (seg_reach above; the words
+    // must carry boxes -- no non-finite input).  TOR_PLANE=2 runs the pass on every segment that has boxes.
+    if ((size_t)s < seg_reach.size() && seg_reach[(size_t)s] != 0) {
+      const size_t w0 = ((size_t)sg[3] * kPad + 31) / 32;
+      const float* rec = &out.xwb[w0 * (size_t)kReachRecFloats];
+      if (!(rec[0] == -INFINITY && rec[1] == INFINITY)) gate |= 4;
     }
     const int32_t ints[8] = {(int32_t)xs[0], (int32_t)sg[0], (int32_t)sg[2], (int32_t)sg[3], (int32_t)sg[1], (int32_t)xs[1], (int32_t)xs[3], gate};
     std::memcpy(h, ints, sizeof(ints));

@@ -19,7 +19,7 @@ struct HostLayout {
   // {cx, cy, cz, K} | {cx, cz, K', 0} | {cx, cz, K', dcy}: 4 float64 each, padded like the first form's
   std::vector<double> xsegs, xrec;
   // what the kernel reads of segs / xsegs, one 128-byte record per segment (16 float64 slots): int32 {xkind, kind, padded count |
-  // padding << 24, first block, first hot record, first float64 in xrec, first float64 in xpl, the plane screen's gate (0 never, 1 always, 2 the wave votes)}, then float64 {time0, time1 -
+  // padding << 24, first block, first hot record, first float64 in xrec, first float64 in xpl, the plane screen's gate (0 never, 1 always, 2 the wave votes; + 4: the reach pass runs in front of the whole words)}, then float64 {time0, time1 -
   // time0, reach, travel, common c0.y, largest radius^2, extent x, extent z} and the segment's first plane record (4 slots);
   // for xkinds 10 / 11 / 12 / 14 those 4 slots are {the first float32 record {cx', cz'}, Ox, Oz, {E, Cm} as float32 rounded up}
   std::vector<double> xhdr;
@@ -31,6 +31,12 @@ struct HostLayout {
   // segments without the float32 table).  The header (xhdr) of such a segment carries them in place of the float64 first record.
   std::vector<float> xpl32;
   std::vector<double> xpl32seg;
+  // the reach pass in front of stage one's whole words (tor_screen.hpp reach_ray): kReachRecFloats floats per 32-slot WORD of the
+  // sorted list, word w = slots [32 w, 32 w + 32) -- {xlo, xhi, zlo, zhi} float32 offsets from the segment's origin, {ylo, yhi}
+  // float64 -- for the words wholly inside a segment of xkind 10 / 11 / 12 / 14; every other word (-inf, +inf): reached by everybody.
+  // The segments of those xkinds that the reach pass runs on (tor_scene.cpp: enough objects, a thin height slab) are ordered by the
+  // Morton code of their centres' ground position, so that a word is a patch of ground.  xwb_all: the same table with every word (-inf, +inf) (TOR_PLANE=3: the reach pass runs and culls nothing)
+  std::vector<float> xwb, xwb_all;
   std::vector<float> hot32;  // TOR_ACCEL_F32 segments (kinds 5/6/7): packed pair records, see tor_kernels.hpp
   int n_segs = 0;
   size_t n_sorted = 0;  // cold slots (padded)
@@ -50,7 +56,8 @@ struct F32Options {
 // against a few huge or far-away objects (the ground sphere of random_scene sits 1000 units below).
 F32Options f32_options_for(const TorHittableVariant* objs, int64_t n);
 
-// Builds the layout for objects `ids` (original indices, kept in this order inside each segment).
+// Builds the layout for objects `ids` (original indices, kept in this order inside each segment, except in the plane-screened
+// segments that are ordered by ground position: see xwb).
 // Returns false and sets err for unknown kinds.
 bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& ids, HostLayout& out, std::string& err,
                   const F32Options* f32 = nullptr);

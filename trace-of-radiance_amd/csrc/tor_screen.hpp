@@ -409,6 +409,116 @@ TOR_HD float plane32_offset(double c, double o, double& err_io) {
   return f;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// THE REACH PASS in front of stage one's whole words (xkinds 10, 11, 12, 14).  Stage one tests the whole infinite ground LINE of
+// a ray against every slot; a sphere can only be a candidate where the RAY -- t >= 0 -- is near it, in y as well.  The host sorts
+// a segment's objects by the Morton code of their ground position (tor_scene.cpp), so that a word of 32 consecutive slots is a
+// small patch of ground, and keeps one record per word of the sorted list (KParams.xwb, kReachRecFloats floats):
+//     {xlo, xhi, zlo, zhi}   float32: the box of the word's stored offsets c' (xpl32), grown by G0 = (R + E)(1 + 2^-40) and rounded
+//                            outward; R = the segment's largest |radius|, E = the table's rounding bound (plane_seg32)
+//     {ylo, yhi}             float64: the heights the SEGMENT's centres take while the time fraction f is in [0, 1], grown by R and
+//                            rounded outward (the same two values in every word of a segment)
+// A word that is not wholly inside one such segment, or whose segment holds a non-finite centre or radius, is (-inf, +inf)
+// throughout: everybody reaches it.  A lane takes the piece of its ray with t >= 0 inside the slab [ylo - S, yhi + S], the xz
+// bounding box of that piece relative to the segment's origin O, grows it by S (+ 2^-40 of each end) and rounds it outward to
+// float32 (reach_ray: float64, once per segment and pass); a word whose box does not meet it is NOT REACHED (reach_miss: four
+// float32 compares against scalar operands).  Words no lane of the wave reaches are not walked at all, and a lane's bits in a
+// walked word it does not reach are cleared before the word is stored.
+//
+// What that needs: a slot in a word the lane does not reach is dropped by the segment's own second-stage test (screen2_* for
+// xkinds 10 / 11 / 12, screen_filter for 14) -- then stage two leaves the bits it leaves today, and the candidates and the canvas
+// do not change; the reference cannot accept such a slot either, since those tests keep whatever it accepts.
+//   Notation as above: c^ the exact centre at f, oc^ = o - c^, d^ the exact unit direction, H~ = oc^ . d^, dist the distance from c^
+//   to the ray's LINE, r the radius, B the segment's bound for this ray, u = 2^-53.
+//   Second form.  It keeps only if disc'' >= 0 and (t'' >= 0 or hb'' < 0).
+//     t'' >= 0:  M~ - C + e_t >= 0 with |e_t| < 16 u B^2, so |oc^|^2 <= r^2 + 272 u B^2: the ORIGIN (t = 0) is within
+//       sqrt(r^2 + 2^-44 B^2) <= r + 2^-22 B of c^.
+//     hb'' < 0 and disc'' >= 0:  H~ < mu~ + |e_h| < 84 u B, and with m = mu~ - e_h in [44 u B, 84 u B]:
+//       0 <= (H~ - m)^2 + M~ - C + e_t, and since C = H~^2 + dist^2 - r^2:  dist^2 <= r^2 + m^2 - 2 H~ m + (256 + 16) u B^2.
+//       The foot of the perpendicular is at t_c = -H~ > -84 u B.  Centre ahead (H~ < 0, |H~| <= B): -2 H~ m <= 168 u B^2, so
+//       dist^2 <= r^2 + 441 u B^2 < r^2 + 2^-44 B^2 and the foot is ON the ray.  Centre abeam or just behind (0 <= H~ < 84 u B):
+//       dist^2 <= r^2 + 273 u B^2 and the origin is within 84 u B of the foot.
+//     Either way some point p = o + t d^, 0 <= t <= 2 B, of the ray is within  r + 2^-22 B + 2^-46 B  of c^.
+//   First form (xkind 14: screen_filter, margins mu = 2^-48 B D1, M = 2^-45 B^2 a): the same case split on its hb' and t' after
+//     dividing by |d|, |d|^2 (mu / |d| <= sqrt(3) 2^-48 B, errors 6.3 u B D1 and 48 u B^2 a as stated at the top of this file)
+//     gives dist^2 < r^2 + (256 + 48 + 2 x 6 x 1.8) u B^2 < r^2 + 2^-44 B^2 and the same conclusion.
+//   So |p.y - c^.y| and |p_xz - c^_xz| are both <= r + 2^-21.9 B.  c^.y lies between c0.y and c0.y + dcy for f in [0, 1] (a static: dcy =
+//   0), hence inside [ylo + R, yhi - R] of the record, and p.y inside [ylo - 2^-21.9 B, yhi + 2^-21.9 B].  The lane's piece:
+//     computed with d~ for d^ (3.1 u per component: p moves by <= 2 B x 3.1 u), o - O in float64 (u B), the reciprocal of d~y and two
+//     products per end (each relative 2 u of a magnitude <= |end| + B), the slab ends' own sums (u (|y| + B)) -- in all
+//     <= 2^-49 B + 2^-50 |end| per coordinate, and the piece contains p up to that.
+//     A ray flatter than |d~y| < 2^-30 is not clipped at all (its piece is the whole ray: the far end +-inf).
+//   The stored c' is within E of c^_xz - O (plane_seg32), and r <= R, so the grown box of the word holds every point within r of one
+//   of its centres' stored offsets + E; with S = 2^-21 B = 2 x 2^-22 B the lane's box, grown by S + 2^-40 |end|, holds p_xz - O with
+//   0.9 x 2^-22 B to spare.  The conversions to float32 move each end outward (a further 2^-23 of it + 2^-140, then round to nearest).
+//   Hence: second stage keeps the slot  =>  the two boxes meet  =>  the word is reached.
+// The slack is the float32 scale of the boxes (2^-21 B against offsets rounded at 2^-24): what stage two's own margin asks for --
+// M~ = 2^-45 B^2 lets it keep a small sphere 2^-22.5 B from the line -- and invisible against R unless the scene is 1e5 from the
+// origin (at 1e7 the slack is 9 units and stage two's own band 3.4).
+// Every lane reaches everything -- the box (-inf, +inf) -- when the float32 plane screen keeps everything (a wild ray, no ground
+// track, a threshold out of range: PlaneSeg32.T = +inf), when f is outside [0, 1] or not a number (the slab does not bound the
+// centres then), or when an end of the piece is not a number; every compare of reach_miss is false on a NaN.  A piece that is
+// EMPTY -- the ray never enters the slab -- reaches only the (-inf, +inf) words.
+// (TOR_SCREEN_MUTATE == 4: the mutation check of this proof -- boxes and slab not grown by the radius, no slack, nothing rounded
+// outward; tests/test_reach.py must then FAIL.  Never defined in a product build.)
+// (-DTOR_REACH=0: A/B builds only -- stage one's word loop as it was, the table unused.)
+#ifndef TOR_REACH
+#define TOR_REACH 1
+#endif
+#if defined(TOR_SCREEN_MUTATE) && TOR_SCREEN_MUTATE == 4
+constexpr bool kReachMutant = true;
+#else
+constexpr bool kReachMutant = false;
+#endif
+constexpr int kReachRecFloats = 8;  // {xlo, xhi, zlo, zhi} float32, {ylo, yhi} float64
+constexpr int kReachMinWords = 8;       // the host runs the pass on segments of enough objects for this many whole words wherever they start ...
+constexpr double kReachSlabRatio = 8.0;  // ... whose height slab, times this, fits the smaller extent of their ground box (tor_scene.cpp)
+constexpr int kReachSlackWords = 4; // records behind the table: the reach pass reads them four at a time (kernel/integrate_loop_plane.inc)
+struct ReachRay { float xlo, xhi, zlo, zhi; };  // per ray, segment and pass: the piece's box, offsets from the segment's origin
+// the largest float32 <= x / the smallest >= x by rounding to nearest a value moved out by more than half an ulp
+TOR_HD float reach_f32_down(double x) { return kReachMutant ? (float)x : (float)(fma_(-__builtin_fabs(x), 0x1p-23, x) - 0x1p-140); }
+TOR_HD float reach_f32_up(double x) { return kReachMutant ? (float)x : (float)(fma_(__builtin_fabs(x), 0x1p-23, x) + 0x1p-140); }
+// all: PlaneSeg32.T == +inf; B: the segment's bound for this ray (|o|_1 + reach + travel |f|); (orx, orz): the segment's origin O
+TOR_HD ReachRay reach_ray(const ScreenRay& r, bool all, double B, double orx, double orz, double ylo, double yhi, double f) {
+  const double inf = __builtin_inf();
+  const double S = kReachMutant ? 0.0 : B * 0x1p-21;
+  const double ox = r.ox - orx, oz = r.oz - orz;
+  const bool steep = __builtin_fabs(r.dny) >= 0x1p-30, up = r.dny > 0.0;
+  const double y0 = ylo - S, y1 = yhi + S;
+  // the piece in y: from the origin, or the face the ray enters the slab by, to the face it leaves by
+  const double ynear = up ? (r.oy > y0 ? r.oy : y0) : (r.oy < y1 ? r.oy : y1);
+  const double yfar = up ? y1 : y0;
+  const bool empty = steep && (up ? ynear > yfar : ynear < yfar);
+  const double inv = 1.0 / (steep ? r.dny : 1.0);
+  const double sa = steep ? (ynear - r.oy) * inv : 0.0, sb = (yfar - r.oy) * inv;  // t at the two ends (units of d~)
+  const double xa = fma_(sa, r.dnx, ox), za = fma_(sa, r.dnz, oz);
+  const double xb = steep ? fma_(sb, r.dnx, ox) : (r.dnx > 0.0 ? inf : (r.dnx < 0.0 ? -inf : ox));
+  const double zb = steep ? fma_(sb, r.dnz, oz) : (r.dnz > 0.0 ? inf : (r.dnz < 0.0 ? -inf : oz));
+  const double xl = xa < xb ? xa : xb, xh = xa < xb ? xb : xa, zl = za < zb ? za : zb, zh = za < zb ? zb : za;
+  // (x - x is NaN for a NaN and for an infinity: the ends must be numbers, and the near end -- the origin or a slab face -- finite)
+  const bool sane = (xa - xa) + (za - za) == 0.0 && xb == xb && zb == zb && f >= 0.0 && f <= 1.0;
+  ReachRay b;
+  if (all || !sane) {
+    b.xlo = b.zlo = -__builtin_inff(); b.xhi = b.zhi = __builtin_inff();
+  } else if (empty) {
+    b.xlo = b.zlo = __builtin_inff(); b.xhi = b.zhi = -__builtin_inff();
+  } else {
+    const double g = kReachMutant ? 0.0 : 0x1p-40;
+    b.xlo = reach_f32_down(fma_(-__builtin_fabs(xl), g, xl) - S); b.xhi = reach_f32_up(fma_(__builtin_fabs(xh), g, xh) + S);
+    b.zlo = reach_f32_down(fma_(-__builtin_fabs(zl), g, zl) - S); b.zhi = reach_f32_up(fma_(__builtin_fabs(zh), g, zh) + S);
+  }
+  return b;
+}
+// true: the lane does not reach the word {xlo, xhi, zlo, zhi} (false on every NaN)
+TOR_HD bool reach_miss(const ReachRay& b, float xlo, float xhi, float zlo, float zhi) {
+  return b.xhi < xlo || b.xlo > xhi || b.zhi < zlo || b.zlo > zhi;
+}
+// The host's side of a word record (tor_scene.cpp build_layout): grow a box end / slab end by g and round it outward
+TOR_HD float reach_box_lo(double c, double g) { return kReachMutant ? (float)c : reach_f32_down(c - g * (1.0 + 0x1p-40)); }
+TOR_HD float reach_box_hi(double c, double g) { return kReachMutant ? (float)c : reach_f32_up(c + g * (1.0 + 0x1p-40)); }
+TOR_HD double reach_slab_lo(double y, double g) { return kReachMutant ? y : fma_(-(__builtin_fabs(y) + g), 0x1p-40, y - g); }
+TOR_HD double reach_slab_hi(double y, double g) { return kReachMutant ? y : fma_(__builtin_fabs(y) + g, 0x1p-40, y + g); }
+
 // Does stage one PAY on this segment for this ray?  It leaves the objects in a band of half-width R around the ground track to a
 // per-lane stage that costs ~8 times a wave-uniform test per object, so it only pays when the band is thin against the segment:
 // a wall of spheres seen edge-on (every centre on the ray's own ground track) would send everything through both stages.  The
