@@ -1035,6 +1035,12 @@ TOR_API const char* tor_version(void);
  * was not drawn -- what lets a lamp of the light table light the fog --, defined operation by operation in tor_phase.h. */
 #include "tor_phase.h"
 
+/* ---- heterogeneous media: density grids marched cell by cell, exactly -------------------------------------------------------------------
+ * tor_scene_media_grid, tor_media_grid_info, tor_media_grid_march_device / _host, tor_media_grid_density_device / _host: a voxel grid
+ * of densities attached to one medium of the media table, the optical-depth march through it by regular tracking (a 3-D DDA, no
+ * log, no exp, no draws) and the density lookup at a point, defined operation by operation in tor_grid.h. */
+#include "tor_grid.h"
+
 /* ---- debug entries of the reach pass in front of the plane screen's whole words -------------------------------------------------
  * tor_debug_reach_scene, tor_debug_last_reach: which words of the sorted list a ray can be near (host mirror), and how many whole
  * words the last launch walked; described in tor_reach.h. */

@@ -194,6 +194,11 @@ PHASE_SYMBOLS = ["tor_scene_media_phase", "tor_phase_eval_device", "tor_phase_ev
                  "tor_phase_sample_host"]
 # the debug entries of the reach pass (include/tor_reach.h), bound as the phase entries are
 REACH_SYMBOLS = ["tor_debug_reach_scene", "tor_debug_last_reach"]
+# the density grids of heterogeneous media (include/tor_grid.h), bound as the phase entries are
+GRID_SYMBOLS = ["tor_scene_media_grid", "tor_media_grid_info", "tor_media_grid_march_device", "tor_media_grid_march_host",
+                "tor_media_grid_density_device", "tor_media_grid_density_host"]
+GRID_MAX_DIM = 1024         # TOR_GRID_MAX_DIM: the most cells of a density grid along one axis
+GRID_MAX_CELLS = 1 << 24    # TOR_GRID_MAX_CELLS: the most cells of a density grid
 PHASE_G_MAX = 0.99          # TOR_PHASE_G_MAX: the largest |g| of Context.set_media_phase
 PHASE_G_MIN = 2.0 ** -20    # TOR_PHASE_G_MIN: the smallest |g| that is not 0
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
@@ -263,6 +268,7 @@ def lib():
     _bind(L, skip_missing=bool(ab))   # (an A/B build may be older than an entry; the in-tree library has them all, or this raises)
     _bind(L, PHASE_SYMBOLS, skip_missing=bool(ab), table=_PHASE_SIGNATURES)
     _bind(L, REACH_SYMBOLS, skip_missing=bool(ab), table=_REACH_SIGNATURES)
+    _bind(L, GRID_SYMBOLS, skip_missing=bool(ab), table=_GRID_SIGNATURES)
     _lib = L
     return L
 
@@ -433,6 +439,22 @@ def _reach_signatures() -> dict:
 
 
 _REACH_SIGNATURES = _reach_signatures()
+
+
+def _grid_signatures() -> dict:
+    """The entries of include/tor_grid.h, in a table of their own like the phase entries."""
+    v, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    return {
+        "tor_scene_media_grid": [v, i32, i32, i32, i32, v, v],
+        "tor_media_grid_info": [v, i32, v, v, v],
+        "tor_media_grid_march_device": [v, i64, v, v, v, i32, v, i64, v, v, v, v, v, v, v],
+        "tor_media_grid_march_host": [v, i64, v, v, v, i32, v, i64, v, v, v, v, v, v],
+        "tor_media_grid_density_device": [v, i64, v, i32, v, i64, v, v, v],
+        "tor_media_grid_density_host": [v, i64, v, i32, v, i64, v, v],
+    }
+
+
+_GRID_SIGNATURES = _grid_signatures()
 
 
 def _bind(L, names=None, skip_missing=False, table=None) -> None:
@@ -1916,6 +1938,7 @@ class Context:
         _check(lib().tor_scene_media(self._h, int(o.size), C.c_void_p(o.ctypes.data or 16), C.c_void_p(s.ctypes.data or 16),
                                      C.c_void_p(p_albedo)))
         self._n_media = int(o.size)   # (what set_media_phase(None) passes as the table's count)
+        self._grid_media = set()      # (a new table has no density grids: media_grids() need not ask)
 
     def march_media(self, rays, tau, t_range=None, index=None, out=None) -> "MediaMarch":
         """The optical-depth march (tor_media_march_device / tor_media_march_host): per listed ray, where along it the accumulated
@@ -2081,13 +2104,115 @@ class Context:
         ops.call(ops.ptr(ops.lead), p_list, n_list, n, ops.ptr(out))
         return Uniforms(out, st, ops.note(n_list), keep=ops.keep(index))
 
+    # ---- heterogeneous media (tor_scene_media_grid, tor_media_grid_march_device, tor_media_grid_density_device) ----
+
+    def set_media_grid(self, medium, density, box=None):
+        """The density grid of medium `medium` of the table (tor_scene_media_grid, include/tor_grid.h): `density` an (nx, ny, nz)
+        array, finite and >= 0 -- the local extinction is the medium's sigma times the cell's value inside both the boundary
+        sphere and the box, 0 elsewhere --; `box` None (the sphere's bounding cube) or (lo xyz, hi xyz), six numbers, OFFSETS
+        from the sphere's centre, so the grid rides a moving boundary.  density=None removes the medium's grid.  A medium with a
+        grid takes no part in march_media: march_media_grid marches it, one medium per call.  set_media drops every grid, and so
+        does an upload that replaces the scene."""
+        if density is None:
+            _check(lib().tor_scene_media_grid(self._h, int(medium), 0, 0, 0, None, None))
+            getattr(self, "_grid_media", set()).discard(int(medium))
+            return
+        d = np.ascontiguousarray(np.asarray(density, dtype=np.float64))
+        if d.ndim != 3 or d.size == 0:
+            raise ValueError("Context.set_media_grid: density must be an (nx, ny, nz) array with at least one cell")
+        p_box = None
+        if box is not None:
+            b = np.ascontiguousarray(np.asarray(box, dtype=np.float64).reshape(-1))
+            if b.size != 6:
+                raise ValueError("Context.set_media_grid: box must be (lo xyz, hi xyz), six numbers")
+            p_box = C.c_void_p(b.ctypes.data)
+        _check(lib().tor_scene_media_grid(self._h, int(medium), int(d.shape[0]), int(d.shape[1]), int(d.shape[2]), p_box,
+                                          C.c_void_p(d.ctypes.data)))
+        self._grid_media = getattr(self, "_grid_media", set()) | {int(medium)}
+
+    def media_grid_info(self, medium):
+        """(dims (nx, ny, nz) -- zeros: no grid --, box (6,) float64 or None, the 64-bit word of the media that have a grid)
+        (tor_media_grid_info)."""
+        dims, box, word = np.zeros(3, dtype=np.int32), np.zeros(6), np.zeros(1, dtype=np.uint64)
+        _check(lib().tor_media_grid_info(self._h, int(medium), C.c_void_p(dims.ctypes.data), C.c_void_p(box.ctypes.data),
+                                         C.c_void_p(word.ctypes.data)))
+        return tuple(int(v) for v in dims), (box if dims[0] > 0 else None), int(word[0])
+
+    def media_grids(self):
+        """The media of the table that have a density grid, ascending.  A context that was given no grid since its last
+        set_media answers [] without entering the library -- so that transmittance and the media integrators enter it exactly
+        as they did before grids existed --; otherwise the library is asked (an upload that replaced the scene has dropped them,
+        and with them the table: tor_media_grid_info then refuses, and [] is the answer).  This list, and so transmittance,
+        trace_media and trace_media_direct, sees only grids set through set_media_grid of THIS object: a grid attached by calling
+        tor_scene_media_grid on the context's handle directly is marched by march_media_grid and masked out of march_media, but
+        is not in this list until set_media_grid has been called once (media_grid_info always asks the library)."""
+        if not getattr(self, "_grid_media", None):
+            return []
+        word = np.zeros(1, dtype=np.uint64)
+        dims = np.zeros(3, dtype=np.int32)
+        if lib().tor_media_grid_info(self._h, 0, C.c_void_p(dims.ctypes.data), None, C.c_void_p(word.ctypes.data)) != 0:
+            return []   # no scene or no media table any more: nothing to march
+        return [m for m in range(MEDIA_MAX) if (int(word[0]) >> m) & 1]
+
+    def march_media_grid(self, rays, tau, medium, t_range=None, index=None, out=None) -> "GridMarch":
+        """The optical-depth march through the density grid of ONE medium (tor_media_grid_march_device / _host): regular tracking,
+        an exact 3-D DDA walk through the piecewise-constant extinction sigma * density[cell] inside the medium's boundary sphere
+        and the grid's box; the definition, operation by operation in float64, is in include/tor_grid.h.  The operands of
+        march_media, and `medium`, the index of a medium that has a grid (set_media_grid).  Returns a GridMarch: a MediaMarch
+        -- at a collision active is 1 << medium and rho the local extinction, so scatter_media, sample_phase and phase take it as
+        they take march_media's -- with cell (n,) int32 (the cell of the collision, else -1) and medium.  Several sources: draw
+        one budget per source (the table, each grid medium), march each, keep the earliest collision -- independent Poisson
+        processes superpose --; the depths of a shadow segment add.  out: a GridMarch of an earlier call on as many rays."""
+        if out is not None and not isinstance(out, GridMarch):
+            raise ValueError("Context.march_media_grid: out must be a GridMarch")
+        ops = _operands(self, "media_grid_march", rays, "rays", 7)
+        n, rays = ops.n, ops.lead
+        tau = ops.rows(tau, "tau", or_number=True)
+        if tau is None:
+            ops.bad("tau", "a number or an (n,) float64 tensor or array, as the rays are")
+        t_range = ops.rows(t_range, "t_range", 2)
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            status, t, depth, active, rho = ops.new(n, dtype="int32"), ops.new(n), ops.new(n), ops.new(n, dtype="int64"), ops.new(n)
+            cell = ops.new(n, dtype="int32")
+            cell[...] = -1
+        else:
+            status, t, depth, active, rho, cell = out.status, out.t, out.depth, out.active, out.rho, out.cell
+            if not ops.fits(status, n, dtype="int32") or not ops.fits(t, n) or not ops.fits(depth, n) \
+                    or not ops.fits(active, n, dtype="int64") or not ops.fits(rho, n) or not ops.fits(cell, n, dtype="int32"):
+                ops.bad("out", "the result of a call on as many rays, on tensors or arrays as the rays are")
+        ops.call(ops.ptr(rays), ops.ptr(t_range), ops.ptr(tau), int(medium), p_list, n_list, ops.ptr(status), ops.ptr(t),
+                 ops.ptr(depth), ops.ptr(active), ops.ptr(rho), ops.ptr(cell))
+        return GridMarch(status, t, depth, active, rho, cell, int(medium), ops.note(n_list), keep=ops.keep(rays, t_range, tau, index))
+
+    def media_density(self, points, medium, index=None, out=None):
+        """The density lookup (tor_media_grid_density_device / _host): per listed point (x, y, z, time) -- (n, 4) float64, a CUDA
+        tensor or anything numpy takes -- the cell of medium `medium`'s grid that holds it and that cell's density (the grid's
+        value, not multiplied by sigma); cell -1 and density 0 outside the boundary sphere or the box.  Returns (cell (n,) int32,
+        density (n,) float64); out: such a pair of an earlier call, written again."""
+        ops = _operands(self, "media_grid_density", points, "points", 4)
+        n, points = ops.n, ops.lead
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            cell, density = ops.new(n, dtype="int32"), ops.new(n)
+            cell[...] = -1
+        else:
+            cell, density = out
+            if not ops.fits(cell, n, dtype="int32") or not ops.fits(density, n):
+                ops.bad("out", "a pair of contiguous (n,) int32 and (n,) float64 tensors or arrays, as the points are")
+        ops.call(ops.ptr(points), int(medium), p_list, n_list, ops.ptr(cell), ops.ptr(density))
+        return cell, density   # (copies made for the call are torch's, freed in stream order)
+
     def transmittance(self, p, q, time=0.0, mask=None):
         """The transmittance of the segments p -> q through the media of the table: exp(-depth) of march_media on the rays
         p -> q - p with range (0, 1) and tau = inf -- the exp is torch's or numpy's, as p is; the library computes the depth
-        alone.  mask: None, or what may stand in the way as for visible(): the result is then multiplied by visible(p, q, time,
-        mask=mask).  One value per segment, a tensor or an array as p is."""
+        alone.  With density grids (set_media_grid) the depth is march_media's plus each grid medium's march_media_grid depth at
+        tau = inf, added in ascending medium order.  mask: None, or what may stand in the way as for visible(): the result is
+        then multiplied by visible(p, q, time, mask=mask).  One value per segment, a tensor or an array as p is."""
         rays, tr = self.shadow_segments(p, q, time, 0.0)
         depth = self.march_media(rays, float("inf"), tr).depth
+        for m in self.media_grids():
+            depth = depth + self.march_media_grid(rays, float("inf"), m, tr).depth
         if _is_tensor(depth):
             import torch
             tm = torch.exp(-depth)
@@ -2377,6 +2502,17 @@ class MediaMarch:
     def __init__(self, status, t, depth, active, rho, note: str, keep=None):
         self.status, self.t, self.depth, self.active, self.rho, self._keep = status, t, depth, active, rho, keep
         self.mode = _mode_of(note, "media march: ")
+
+
+class GridMarch(MediaMarch):
+    """The answers of Context.march_media_grid (include/tor_grid.h): a MediaMarch -- at a collision active is 1 << medium and rho the
+    local extinction sigma * density[cell] -- with cell (n,) int32, the cell of the collision (-1 otherwise), and `medium`.  `mode`
+    is the library's note ("medium 3, 16x16x16")."""
+
+    def __init__(self, status, t, depth, active, rho, cell, medium: int, note: str, keep=None):
+        super().__init__(status, t, depth, active, rho, note, keep)
+        self.cell, self.medium = cell, medium
+        self.mode = _mode_of(note, "media grid march: ")
 
 
 class MediaScatter(tuple):

@@ -93,6 +93,13 @@ struct DeviceAccel {
 
 struct RcclComm;  // tor_multi.cpp
 
+// one density grid (tor_scene_media_grid, include/tor_grid.h): the box as offsets from the medium's centre, h = (hi - lo) / n
+struct MediaGrid {
+  DeviceBuffer density;             // n[0] * n[1] * n[2] float64, C order
+  int32_t n[3] = {0, 0, 0};
+  double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0}, h[3] = {0.0, 0.0, 0.0};
+};
+
 // State of the queries of a context (closest hits: tor_query.hip, radiance: tor_radiance.hip, path steps: tor_bounce.hip).
 // Separate from the render path's:
 // a query never touches the bounds ring, the counters or the per-launch ring slots.  Freed by its destructor (tor_context_destroy).
@@ -146,6 +153,13 @@ struct HitQueryState {
   // participating-media queries (tor_media.hip)
   DeviceBuffer media;               // the media table (tor_scene_media): 16 float64 per medium, packed when the table is set
   int64_t n_media = 0;              // 0: no table (the state after every upload that replaces the scene)
+  // density grids of media (tor_grid.hip): at most one per medium of the table
+  MediaGrid grids[64];              // by medium; n[0] == 0: none
+  uint64_t grid_mask = 0;           // bit m: medium m has a grid (what the homogeneous march leaves out)
+  void drop_grids() {               // every tor_scene_media call, every upload that replaces the scene, the destructor
+    for (MediaGrid& g : grids) { g.density.release(); g.n[0] = g.n[1] = g.n[2] = 0; }
+    grid_mask = 0;
+  }
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

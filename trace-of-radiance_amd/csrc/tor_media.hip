@@ -26,7 +26,9 @@
 // t_next <= t_max:  (A) s0 <= t && t < s1,  (B) s0 > t && s0 < t_next,  (C) s1 > t && s1 < t_next.  (A) implies s0 < t_max && s1 >
 // t_min; (B) implies t_min < s0 < t_max; (C) implies t_min < s1 < t_max.  touch_m = has_m && ((A') || (B') || (C')) with those
 // three implied conditions: a medium without the bit can change neither rho, A nor t_next at any step, whatever NaN or infinity
-// its roots hold, so skipping it leaves every bit of the answer as the header defines it.
+// its roots hold, so skipping it leaves every bit of the answer as the header defines it.  A medium with a density grid
+// (include/tor_grid.h; the kernel's grid_mask) never gets the bit: the march answers as if has_m were false for it, and it contributes
+// through tor_media_grid_march_device alone.  With no grid the mask is 0 and every bit of every answer is as it was.
 //
 // Float64, unfused (-ffp-contract=off), correctly rounded `/` and sqrt.  Stores are ordinary vector stores.
 #include <hip/hip_runtime.h>
@@ -102,7 +104,8 @@ __device__ __forceinline__ MdRoots medium_roots(P r, const QRay& q) {
   return x;
 }
 
-__global__ __launch_bounds__(kMediaThreads) void media_march_kernel(const MdParams P) {
+// grid_mask: bit m set: medium m has a density grid (tor_grid.hip) and takes no part here
+__global__ __launch_bounds__(kMediaThreads) void media_march_kernel(const MdParams P, const unsigned long long grid_mask) {
   const long long i = listed_ray(P.list, P.n_list, P.n_rays, (long long)blockIdx.x * kMediaThreads + threadIdx.x);
   const bool live = i >= 0;
   QRay q{};
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(kMediaThreads) void media_march_kernel(const MdPara
   unsigned long long touch = 0ull, uni = 0ull;
   for (int m = 0; m < n; ++m) {
     const MdRoots x = medium_roots(M + kMediaWords * (size_t)m, q);
-    const bool tm = !done && x.has &&
+    const bool tm = !done && x.has && ((grid_mask >> m) & 1ull) == 0ull &&
                     ((x.s0 < q.t_max && x.s1 > q.t_min) || (x.s0 > q.t_min && x.s0 < q.t_max) || (x.s1 > q.t_min && x.s1 < q.t_max));
     if (tm) touch |= 1ull << m;
     if (__ballot(tm) != 0ull) uni |= 1ull << m;
@@ -276,7 +279,7 @@ int media_launch(const char* who, TorContext* ctx, bool scatter, tor::MdParams& 
   P.n_rays = (long long)n_rays;
   const dim3 grid(media_grid(n_list)), block(tor::kMediaThreads);
   if (scatter) hipLaunchKernelGGL(tor::media_scatter_kernel, grid, block, 0, stream, P);
-  else hipLaunchKernelGGL(tor::media_march_kernel, grid, block, 0, stream, P);
+  else hipLaunchKernelGGL(tor::media_march_kernel, grid, block, 0, stream, P, (unsigned long long)ctx->hitq.grid_mask);
   const int rd = tor::query_done(ctx, stream);
   if (rd != TOR_OK) return rd;
   tor::set_last_note(std::string(scatter ? "media scatter: " : "media march: ") + std::to_string(ctx->hitq.n_media) + " media");
@@ -401,6 +404,7 @@ int tor_scene_media(TorContext* ctx, int64_t n_media, const int32_t* objects, co
     HIP_TRY(hipMemcpy(hq.media.ptr, recs.data(), recs.size() * 8, hipMemcpyHostToDevice));
   }
   hq.n_media = n_media;
+  hq.drop_grids();  // a new table: no medium has a density grid (tor_scene_media_grid), as none has a g
   return TOR_OK;
 }
 

@@ -96,6 +96,7 @@ HitQueryState::~HitQueryState() {
   absr[1].release();
   lights.release();
   media.release();
+  drop_grids();
   env.release();
   ph_cell.release();
   ph_rec.release();

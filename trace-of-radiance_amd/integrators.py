@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import BOUNCE_MISS, BOUNCE_SCATTERED, MEDIA_COLLIDED, MEDIA_ESCAPED, Camera, Photons, _Arrays, _Tensors, _is_tensor
+from . import BOUNCE_MISS, BOUNCE_SCATTERED, MEDIA_COLLIDED, MEDIA_ESCAPED, Camera, MediaMarch, Photons, _Arrays, _Tensors, _is_tensor
 
 INTEGRATORS = ("trace", "trace_direct", "trace_light", "trace_photons", "trace_photon_map", "trace_environment", "trace_media",
                "trace_media_direct")
@@ -562,7 +562,15 @@ def trace_media(ctx, rays, rng, max_depth=50, sky=None, mask=None, free_flight=N
     sky: None (Context.sky) or sky(rays, index) -> (len(index), 3), as for trace().  mask: as for hit(), or a callable
     mask(step).  free_flight: a callable on the (n,) tensor of uniforms giving tau (every entry is evaluated, the live ones
     are used).  hit() takes no list, so every iteration's closest-hit launch runs on all n rays and the hits of the rays
-    that have ended are not read; uniform, march_media and the two scatters run on the live list.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the
+    that have ended are not read; uniform, march_media and the two scatters run on the live list.
+
+    Density grids (set_media_grid): with K media that have one, ascending m_1 < .. < m_K, an iteration draws
+    1 + K uniforms per live ray in ONE uniform() call -- u[0] for the table, u[j] for grid medium m_j --, so the draw order of
+    a path is, per iteration, the table's free-flight uniform, the K grid uniforms in ascending medium order, then the draws
+    of whichever scatter it met.  tau_j = free_flight(u[j]).  First the homogeneous march up to the hit; then
+    march_media_grid of m_1 .. m_K in that order, each with t_max = the earliest collision so far (or the hit): a grid march
+    that collides replaces the candidate (independent Poisson processes superpose: the earliest collision is the path's).
+    The winner's (t, active) -- active = 1 << m for a grid medium -- feed the scatter.  K = 0: every launch as before.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the
     device and come back as numpy."""
     return _media_loop(ctx, "trace_media", rays, rng, max_depth, sky, mask, free_flight, phase, None)
 
@@ -582,9 +590,11 @@ def trace_media_direct(ctx, rays, rng, emission, lamp_mask, max_depth=50, sky=No
 
     The light draws come from _light_states of the paths' entry states, so path states and draw order are those of
     trace_media(phase=True), as trace_direct relates to trace: with an all-zero emission the colours and states are its,
-    bit for bit.  emission: (n_objects, 3) float64; strategy as for sample_lights; the rest as for trace_media.  Out of
+    bit for bit.  With density grids the draw order is trace_media's (1 + K uniforms per iteration: the table's, then one per
+    grid medium ascending), the winner's active word feeds phase(), and the shadow segment's depth is march_media's plus
+    each grid medium's march_media_grid(segment, inf, m, (0.0, 1.0)) depth, added in ascending medium order, before transmit.  emission: (n_objects, 3) float64; strategy as for sample_lights; the rest as for trace_media.  Out of
     scope: light samples at surfaces through fog, MIS between phase and light sampling, chromatic extinction, phase
-    functions other than Henyey-Greenstein."""
+    functions other than Henyey-Greenstein.  (Heterogeneous density is DESIGN 4.26: set_media_grid.)"""
     if lamp_mask is None:
         raise ValueError("Context.trace_media_direct: lamp_mask is required (the media's boundary spheres would shadow every segment)")
     return _media_loop(ctx, "trace_media_direct", rays, rng, max_depth, sky, mask, free_flight, True,
@@ -593,14 +603,22 @@ def trace_media_direct(ctx, rays, rng, emission, lamp_mask, max_depth=50, sky=No
 
 def _media_loop(ctx, who, rays, rng, max_depth, sky, mask, free_flight, phase, direct):
     """The loop of trace_media and trace_media_direct; direct: None, or (emission, lamp_mask, transmit, strategy).  Without
-    `phase` and `direct` every launch and every bit is trace_media's as it was before either existed."""
+    `phase` and `direct` every launch and every bit is trace_media's as it was before either existed, and without a density
+    grid (K = len(ctx.media_grids()) == 0) every launch and every bit is as it was before grids existed."""
     import torch
     p = _Paths.from_rays(ctx, who, rays, rng, None)
     n, dev, work, color, att = p.n, p.dev, p.work, p.color, p.att
     inf = torch.full((n,), float("inf"), dtype=torch.float64, device=dev)
     t_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
-    u = torch.zeros((n, 1), dtype=torch.float64, device=dev)
+    grids = ctx.media_grids()      # the media with a density grid (set_media_grid), ascending; none: every launch as it was
+    K = len(grids)
+    u = torch.zeros((n, 1 + K), dtype=torch.float64, device=dev)
     march, nxt = None, None
+    flight = (lambda x: -torch.log1p(-x)) if free_flight is None else \
+        (lambda x: torch.as_tensor(free_flight(x), dtype=torch.float64).to(dev).reshape(n))
+    if K:
+        grid_range = torch.zeros((n, 2), dtype=torch.float64, device=dev)
+        gm, gseg = [None] * K, [None] * K
     if direct is not None:
         emission, lamp_mask, transmit, strategy = direct
         emission = _colours(emission, dev)
@@ -615,12 +633,24 @@ def _media_loop(ctx, who, rays, rng, max_depth, sky, mask, free_flight, phase, d
     for step in p.steps(max_depth):
         live = p.live
         hit = ctx.hit(work, time_range=p.tr, mask=mask(step) if callable(mask) else mask)
-        u, p.rng = ctx.uniform(p.rng, 1, index=live, out=u)
-        tau = -torch.log1p(-u[:, 0]) if free_flight is None else \
-            torch.as_tensor(free_flight(u[:, 0]), dtype=torch.float64).to(dev).reshape(n)
+        u, p.rng = ctx.uniform(p.rng, 1 + K, index=live, out=u)
+        tau = flight(u[:, 0])
         t_range[:, 1] = torch.where(hit.object >= 0, hit.t, inf)
         march = ctx.march_media(work, tau, t_range, index=live, out=march)
         idx = live.long()
+        if K:   # one budget per grid medium; each march runs up to the earliest collision so far (or the hit) and replaces it
+            listed = torch.zeros((n,), dtype=torch.bool, device=dev)
+            listed[idx] = True
+            w_status, w_t, w_active = march.status.clone(), march.t.clone(), march.active.clone()
+            for j, m in enumerate(grids):
+                grid_range[:, 1] = torch.where(w_status == MEDIA_COLLIDED, w_t, t_range[:, 1])
+                gm[j] = ctx.march_media_grid(work, flight(u[:, 1 + j].contiguous()), m, grid_range, index=live, out=gm[j])
+                won = listed & (gm[j].status == MEDIA_COLLIDED)
+                w_status = torch.where(won, gm[j].status, w_status)
+                w_t = torch.where(won, gm[j].t, w_t)
+                w_active = torch.where(won, gm[j].active, w_active)
+            # (the winner's status, t and active -- all that is read below; depth and rho stay the HOMOGENEOUS march's, not the winner's)
+            march_h, march = march, MediaMarch(w_status, w_t, march.depth, w_active, march.rho, "")
         st, obj = march.status[idx], hit.object[idx]
         collided = live[st == MEDIA_COLLIDED]
         surface = live[(st == MEDIA_ESCAPED) & (obj >= 0)]
@@ -656,6 +686,9 @@ def _media_loop(ctx, who, rays, rng, max_depth, sky, mask, free_flight, phase, d
                     occ = ctx.occluded(ls.rays, shadow_range, collided, p.tr, "auto", out=occ, mask=lamp_mask)
                     seg = ctx.march_media(ls.rays, inf, seg_range, index=collided, out=seg)
                     depth = seg.depth[ci]
+                    for j, m in enumerate(grids):   # the depths of a shadow segment add, in ascending medium order
+                        gseg[j] = ctx.march_media_grid(ls.rays, inf, m, seg_range, index=collided, out=gseg[j])
+                        depth = depth + gseg[j].depth[ci]
                     T = torch.exp(-depth) if transmit is None else \
                         torch.as_tensor(transmit(depth), dtype=torch.float64).to(dev).reshape(-1)
                     ev = ctx.phase(work, march.active, ls.rays, collided, out=ev)
@@ -666,5 +699,7 @@ def _media_loop(ctx, who, rays, rng, max_depth, sky, mask, free_flight, phase, d
             work[ci] = nxt.rays[ci]
             att[ci] = att[ci] * nxt.attenuation[ci]
             alive[ci] = True
+        if K:
+            march = march_h   # (the homogeneous march's buffers are written again next iteration)
         p.live = torch.nonzero(alive).reshape(-1).int()
     return p.finish(color)[:2]
