@@ -1,8 +1,9 @@
 /*
  * tor_reach.h -- debug entries of the REACH PASS of libtor_mi355x.so, included by tor_render.h (which defines the types).
  *
- * The strict brute-force layout orders the objects of a plane-screened segment of xkind 10 / 11 / 12 / 14 by the Morton code of
- * their ground position and keeps one box per 32-slot word of the sorted list; in front of stage one's whole words every ray
+ * The strict brute-force layout orders the objects of a plane-screened segment of xkind 10 / 11 / 12 / 14 by an even top-down split
+ * of their ground positions, cut at the sorted list's word boundaries (TOR_REACH_ORDER=morton: by the Morton code, the order it
+ * replaced), and keeps one box per 32-slot word of the sorted list; in front of stage one's whole words every ray
  * asks which of those words it can be near at all (csrc/tor_screen.hpp reach_ray / reach_miss).  A word nobody of the wave reaches
  * is not walked; a ray's bits in a walked word it does not reach are cleared.  What must hold: the segment's own second-stage
  * test drops every slot of a word the ray does not reach (tor_debug_screen2_scene's code is never 2 there).

@@ -15,7 +15,6 @@ run anim_sah_w WRITE_SIZE 1920,1080,256,50,1,0,3,0,1,1,120 X=1
 run anim_morton_w WRITE_SIZE 1920,1080,256,50,1,0,3,0,1,1,120 TOR_ACCEL_ORDER=morton
 run anim_brute_w WRITE_SIZE 1920,1080,256,50,1,0,0,0,1,1,120 X=1
 run rand_sah_w WRITE_SIZE 1920,1080,256,50,1,0,3,0,1,1,-1 X=1
-run anim_nostage_w WRITE_SIZE 1920,1080,256,50,1,0,3,0,1,1,120 TOR_STAGE_LDS=0
 run anim_sah_tcc "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" 1920,1080,256,50,1,0,3,0,1,1,120 X=1
 run anim_sah_atom "TCC_EA0_ATOMIC_sum TCC_ATOMIC_sum" 1920,1080,256,50,1,0,3,0,1,1,120 X=1
 run anim_sah_wb "TCC_WRITEBACK_sum TCC_EA0_WRREQ_WRITE_DRAM_sum" 1920,1080,256,50,1,0,3,0,1,1,120 X=1

@@ -656,8 +656,8 @@ static void use_layout(tor::KParams& q, const tor::DeviceLayout& L, const TorCon
   q.n_segs = L.n_segs;
 }
 
-static bool fits_lds(size_t bytes, int wgs, size_t hard_cap, size_t fixed) {
-  return bytes <= hard_cap && bytes + fixed <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
+static bool fits_lds(size_t bytes, int wgs, size_t fixed) {
+  return bytes + fixed <= (size_t)(160 * 1024) / (size_t)wgs - 1024;
 }
 
 // LDS staging of the block records next to the per-wave queues (10 KB per workgroup in these variants, 160 KB per CU): the
@@ -667,19 +667,17 @@ static bool fits_lds(size_t bytes, int wgs, size_t hard_cap, size_t fixed) {
 // `full` is that count; returns the workgroups per CU the launch may run with what was staged (0: nothing staged).
 static int stage_records_in_lds(tor::KParams& q, const tor::HostAccel& hacc, size_t bnd32_stage_floats, int full, int kseed) {
   const size_t hot_bytes = q.shot32 ? hacc.hot32.size() * 4 : hacc.hot.size() * 8;
-  const char* st = tor::knob("TOR_STAGE_LDS");
-  const size_t hard_cap = st ? (size_t)std::atoll(st) : (size_t)1 << 30;
   const size_t fixed = (size_t)tor::integrate_fixed_lds_bytes(1, q.shot32 != nullptr ? 1 : 0, kseed);
   // Workgroups per CU come first: on the 1601-object animation frames 3 workgroups/CU reading the records through L2
   // render 2339 Msamples/s, 2 workgroups/CU with the records in LDS 1914.  So the launch keeps its full workgroup count
   // and stages what fits beside it: the block boxes of a two-level scene first (6.6 KB there; every lane reads 8 of
   // them per super box it expands), then the block records if there is still room; only a launch whose mode runs at 2
   // workgroups/CU anyway gets the bigger LDS share.
-  const bool stage_boxes = q.shot32 && bnd32_stage_floats > 0 && fits_lds(bnd32_stage_floats * 4, full, hard_cap, fixed);
+  const bool stage_boxes = q.shot32 && bnd32_stage_floats > 0 && fits_lds(bnd32_stage_floats * 4, full, fixed);
   const size_t box_bytes = stage_boxes ? bnd32_stage_floats * 4 : 0;
-  bool stage_hot = fits_lds(hot_bytes + box_bytes, full, hard_cap, fixed);
+  bool stage_hot = fits_lds(hot_bytes + box_bytes, full, fixed);
   int wg = (stage_hot || stage_boxes) ? full : 0;
-  if (!q.shot32 && !stage_hot && full > 2 && fits_lds(hot_bytes, full - 1, hard_cap, fixed)) {
+  if (!q.shot32 && !stage_hot && full > 2 && fits_lds(hot_bytes, full - 1, fixed)) {
     // (the float64 compact records of TOR_ACCEL_BLOCKS alone are read by every lane for every block it enters: there
     // one workgroup fewer with the records in LDS wins, 1212 against 1140 Msamples/s on the same frames)
     stage_hot = true;

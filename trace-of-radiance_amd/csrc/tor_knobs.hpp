@@ -35,9 +35,9 @@ constexpr Knob kKnobs[] = {
     {"TOR_BLOCKS_PER_CU", "3", "1..8", "context", "workgroups per CU of integrate_kernel (all modes)"},
     {"TOR_WAVES_PER_SIMD", "(from the launch shape)", "2 | 3", "context", "force the register-budget variant of integrate_kernel (256 / 168 VGPRs)"},
     {"TOR_ACCEL_ORDER", "sah", "sah | morton", "upload", "order of the objects behind TOR_ACCEL_BLOCKS' boxes: top-down surface-area build (round 6) or the Morton curve of rounds 1-5 (A/B; same canvas)"},
-    {"TOR_STAGE_LDS", "(no cap)", "bytes, 0 = off", "call", "cap of the LDS staging of block records / boxes (TOR_ACCEL_BLOCKS)"},
     {"TOR_SCREEN", "1", "0 | 1", "context", "0: strict brute-force launches evaluate the reference's unfused discriminant for every object instead of the conservative FMA screen (same canvas)"},
     {"TOR_PLANE", "1", "0 | 1 | 2 | 3", "context", "stage one of the FMA screen (the 4-instruction plane screen in front of the segment's wave-uniform test, per-lane stage two on what it keeps): 0 off, 1 on the segments where it pays (default), 2 on every segment, 3 as 1 with a reach pass in which every lane reaches every word (A/B of the word skip; same candidates, same canvas)"},
+    {"TOR_REACH_ORDER", "split", "split | morton", "upload", "order of the objects inside a segment the reach pass runs on: top-down even split of the ground positions at the sorted list's word boundaries, or the Morton curve it replaced (A/B; same candidates, same canvas)"},
     // ---- TOR_SEED_PIXEL: kernel choice, cost probe, tile schedule ----
     {"TOR_COOP_MAX_PIXELS", "114688", ">= 0", "context", "frames up to this many pixels (per device) run one WAVE per pixel when neither hand-off nor split mode applies; 0 = never"},
     {"TOR_LPT_MIN_SPP", "32", ">= 0", "context", "cost probe + chain-length-ordered tile schedule from this many spp on; 0 = never"},

@@ -284,50 +284,6 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     m.material = objs[idx].u.sphere.material;
     return m;
   };
-  // Inside a plane-screened segment with float32 plane records that the reach pass will run on, the objects go by the Morton code of their ground position over the
-  // segment's ground box (16 bits per axis), so that a word of 32 consecutive slots is a patch of ground the reach pass can rule
-  // out as a whole (tor_screen.hpp).  The order is free: the closest hit does not depend on it, ties go by the original index
-  // (cold).  Stable: equal codes -- and every non-finite centre, code 0 -- keep the order of appearance.
-  // Only where the reach pass will run (seg_reach, bit 2 of the header's gate word below): a segment of enough objects for
-  // kReachMinWords whole words wherever it starts, whose height slab is thin against its ground box -- a field.  The pass costs
-  // about what four whole words cost, and in a cloud as tall as it is wide a ray's piece inside the slab is most of the ray
-  // (measured: 3 to 10 % lost with the pass everywhere; the order alone cost a 3-D cloud of statics 4 %: profiles/reach_ab.txt).
-  // Every other segment keeps the order of appearance and the kernels it had.  A performance decision only.
-  std::vector<char> seg_reach(segs64.size(), 0);
-  for (size_t si = 0; si < segs64.size(); ++si) {
-    Seg64& sg = segs64[si];
-    if (!(TOR_REACH && sg.xkind >= 10 && sg.xkind != 13 && sg.ids.size() >= 32 * (size_t)(kReachMinWords + 1))) continue;
-    double xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY, rmax = 0.0;
-    for (int64_t idx : sg.ids) {
-      const TorMovingSphere s = as_mover(idx);
-      if (std::isfinite(s.center0.x)) { xlo = std::fmin(xlo, s.center0.x); xhi = std::fmax(xhi, s.center0.x); }
-      if (std::isfinite(s.center0.z)) { zlo = std::fmin(zlo, s.center0.z); zhi = std::fmax(zhi, s.center0.z); }
-      ylo = std::fmin(ylo, std::fmin(s.center0.y, s.center1.y)); yhi = std::fmax(yhi, std::fmax(s.center0.y, s.center1.y));
-      rmax = std::fmax(rmax, std::fabs(s.radius));
-    }
-    if (!(kReachSlabRatio * ((yhi - ylo) + 2.0 * rmax) <= std::fmin(xhi - xlo, zhi - zlo))) continue;   // (a NaN anywhere: no pass)
-    seg_reach[si] = 1;
-    auto cell = [](double c, double lo, double hi) -> uint32_t {
-      if (!std::isfinite(c) || !(hi > lo)) return 0u;
-      const double t = (c - lo) / (hi - lo) * 65535.0;   // (hi - lo may overflow: t = 0 then, or NaN from inf / inf)
-      return t >= 0.0 && t <= 65535.0 ? (uint32_t)t : 0u;
-    };
-    auto spread16 = [](uint32_t v) {  // 16 bits -> every second bit
-      v = (v | (v << 8)) & 0x00ff00ffu;
-      v = (v | (v << 4)) & 0x0f0f0f0fu;
-      v = (v | (v << 2)) & 0x33333333u;
-      v = (v | (v << 1)) & 0x55555555u;
-      return v;
-    };
-    std::vector<std::pair<uint32_t, int64_t>> keyed;
-    keyed.reserve(sg.ids.size());
-    for (int64_t idx : sg.ids) {
-      const TorMovingSphere s = as_mover(idx);
-      keyed.push_back({spread16(cell(s.center0.x, xlo, xhi)) | (spread16(cell(s.center0.z, zlo, zhi)) << 1), idx});
-    }
-    std::stable_sort(keyed.begin(), keyed.end(), [](const std::pair<uint32_t, int64_t>& a, const std::pair<uint32_t, int64_t>& b) { return a.first < b.first; });
-    for (size_t k = 0; k < keyed.size(); ++k) sg.ids[k] = keyed[k].second;
-  }
   // float64 per slot of the second-stage records (xrec) and of the plane table (xpl), by xkind
   auto xs_of = [](int xkind) { return xkind == 0 ? 0 : (xkind >= 13 ? 8 : 4); };
   auto pw_of = [](int xkind) { return xkind == 0 ? 0 : (xkind == 13 ? 4 : 2); };
@@ -345,6 +301,104 @@ bool build_layout(const TorHittableVariant* objs, const std::vector<int64_t>& id
     size_t t0 = 0, t1 = 0;
     for (const Seg64& sg : segs64) { t0 += slots_of(sg, false); t1 += slots_of(sg, true); }
     if ((t1 + 511) / 512 > (t0 + 511) / 512) pad_words = false;
+  }
+  // Inside a plane-screened segment with float32 plane records that the reach pass will run on, the objects are ordered so that
+  // a word of 32 consecutive slots is a patch of ground the reach pass can rule out as a whole (tor_screen.hpp): a top-down even
+  // split over the centres' ground positions.  A node that spans more than one word of the sorted list is cut along the longer
+  // axis of its centres' box, at the word boundary nearest its middle -- the list's OWN word boundaries: a segment need not
+  // begin on one, so the cuts are counted from its first slot mod 32, known now that the segments in front are sized -- until
+  // every node is one word (or the segment's head or tail, which share a word with a neighbour or run in the block phases and
+  // have no box).  A leaf keeps the order of appearance.  Word boxes of 6 % to 8 % of random_scene's field where the Morton
+  // curve, whose jumps a word straddles, gave 7 % to 31 % (profiles/reach_order_ab.txt); TOR_REACH_ORDER=morton keeps that
+  // order for the A/B (same candidates, same canvas).  The order is free: the closest hit does not depend on it, ties go by the
+  // original index (cold).  The keys are integers (cell: 32 bits per axis over the segment's ground box, every non-finite
+  // coordinate cell 0) with the place in the order of appearance in their low half, a strict total order whatever the centres are:
+  // the same scene gives the same bytes on every upload, and equal keys keep the order of appearance from leaf to leaf.
+  // Only where the reach pass will run (seg_reach, bit 2 of the header's gate word below): a segment of enough objects for
+  // kReachMinWords whole words wherever it starts, whose height slab is thin against its ground box -- a field.  The pass costs
+  // about what four whole words cost, and in a cloud as tall as it is wide a ray's piece inside the slab is most of the ray
+  // (measured: 3 to 10 % lost with the pass everywhere; the order alone cost a 3-D cloud of statics 4 %: profiles/reach_ab.txt).
+  // Every other segment keeps the order of appearance and the kernels it had.  A performance decision only.
+  std::vector<char> seg_reach(segs64.size(), 0);
+  const char* reach_order_knob = knob("TOR_REACH_ORDER");
+  const bool reach_morton = reach_order_knob && std::strcmp(reach_order_knob, "morton") == 0;
+  size_t seg_first = 0;   // first slot of the segment in the sorted list
+  for (size_t si = 0; si < segs64.size(); seg_first += slots_of(segs64[si], pad_words), ++si) {
+    Seg64& sg = segs64[si];
+    if (!(TOR_REACH && sg.xkind >= 10 && sg.xkind != 13 && sg.ids.size() >= 32 * (size_t)(kReachMinWords + 1))) continue;
+    double xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY, rmax = 0.0;
+    for (int64_t idx : sg.ids) {
+      const TorMovingSphere s = as_mover(idx);
+      if (std::isfinite(s.center0.x)) { xlo = std::fmin(xlo, s.center0.x); xhi = std::fmax(xhi, s.center0.x); }
+      if (std::isfinite(s.center0.z)) { zlo = std::fmin(zlo, s.center0.z); zhi = std::fmax(zhi, s.center0.z); }
+      ylo = std::fmin(ylo, std::fmin(s.center0.y, s.center1.y)); yhi = std::fmax(yhi, std::fmax(s.center0.y, s.center1.y));
+      rmax = std::fmax(rmax, std::fabs(s.radius));
+    }
+    if (!(kReachSlabRatio * ((yhi - ylo) + 2.0 * rmax) <= std::fmin(xhi - xlo, zhi - zlo))) continue;   // (a NaN anywhere: no pass)
+    seg_reach[si] = 1;
+    if (reach_morton) {  // 16 bits per axis, interleaved; stable: equal codes -- every non-finite centre is code 0 -- keep the order of appearance
+      auto cell = [](double c, double lo, double hi) -> uint32_t {
+        if (!std::isfinite(c) || !(hi > lo)) return 0u;
+        const double t = (c - lo) / (hi - lo) * 65535.0;   // (hi - lo may overflow: t = 0 then, or NaN from inf / inf)
+        return t >= 0.0 && t <= 65535.0 ? (uint32_t)t : 0u;
+      };
+      auto spread16 = [](uint32_t v) {  // 16 bits -> every second bit
+        v = (v | (v << 8)) & 0x00ff00ffu;
+        v = (v | (v << 4)) & 0x0f0f0f0fu;
+        v = (v | (v << 2)) & 0x33333333u;
+        v = (v | (v << 1)) & 0x55555555u;
+        return v;
+      };
+      std::vector<std::pair<uint32_t, int64_t>> keyed;
+      keyed.reserve(sg.ids.size());
+      for (int64_t idx : sg.ids) {
+        const TorMovingSphere s = as_mover(idx);
+        keyed.push_back({spread16(cell(s.center0.x, xlo, xhi)) | (spread16(cell(s.center0.z, zlo, zhi)) << 1), idx});
+      }
+      std::stable_sort(keyed.begin(), keyed.end(), [](const std::pair<uint32_t, int64_t>& a, const std::pair<uint32_t, int64_t>& b) { return a.first < b.first; });
+      for (size_t k = 0; k < keyed.size(); ++k) sg.ids[k] = keyed[k].second;
+      continue;
+    }
+    auto cell = [](double c, double lo, double hi) -> uint32_t {
+      if (!std::isfinite(c) || !(hi > lo)) return 0u;
+      const double t = (c - lo) / (hi - lo) * 4294967295.0;   // (hi - lo may overflow: t = 0 then, or NaN from inf / inf)
+      return t >= 0.0 && t <= 4294967295.0 ? (uint32_t)t : 0u;
+    };
+    struct Key { uint64_t k[2]; };   // per axis: cell << 32 | place in the order of appearance -- one integer comparison, no ties
+    std::vector<Key> keys(sg.ids.size());
+    for (size_t k = 0; k < keys.size(); ++k) {
+      const TorMovingSphere s = as_mover(sg.ids[k]);
+      keys[k] = {{(uint64_t)cell(s.center0.x, xlo, xhi) << 32 | k, (uint64_t)cell(s.center0.z, zlo, zhi) << 32 | k}};
+    }
+    // (a cell's size per axis, to compare a node's extents in the scene's units; an extent that overflows: its cells are all 0)
+    const double unit[2] = {std::isfinite(xhi - xlo) ? xhi - xlo : 0.0, std::isfinite(zhi - zlo) ? zhi - zlo : 0.0};
+    const size_t off = seg_first % 32;
+    std::vector<std::pair<size_t, size_t>> nodes{{0, keys.size()}};   // [a, b) of the segment's slots still to cut
+    while (!nodes.empty()) {
+      const size_t a = nodes.back().first, b = nodes.back().second;
+      nodes.pop_back();
+      const size_t next_word = a + (32 - (off + a) % 32);   // the first word boundary behind a
+      if (next_word >= b) {                                  // one word, or part of one: the order of appearance
+        std::sort(keys.begin() + (long)a, keys.begin() + (long)b, [](const Key& p, const Key& q) { return (uint32_t)p.k[0] < (uint32_t)q.k[0]; });
+        continue;
+      }
+      // the word boundary nearest the middle, inside (a, b): the largest one up to the middle or the one behind it
+      const long mid = (long)((a + b) / 2), below = mid - (long)((off + (size_t)mid) % 32), above = below + 32;   // (below < 0: the head's)
+      long at = (long)(a + b) - 2 * below <= 2 * above - (long)(a + b) ? below : above;
+      if (below <= (long)a) at = above;
+      else if (above >= (long)b) at = below;
+      const size_t cut = (size_t)at;
+      uint64_t lo[2] = {~(uint64_t)0, ~(uint64_t)0}, hi[2] = {0, 0};
+      for (size_t k = a; k < b; ++k)
+        for (int ax = 0; ax < 2; ++ax) { lo[ax] = std::min(lo[ax], keys[k].k[ax]); hi[ax] = std::max(hi[ax], keys[k].k[ax]); }
+      const int ax = (double)((hi[1] >> 32) - (lo[1] >> 32)) * unit[1] > (double)((hi[0] >> 32) - (lo[0] >> 32)) * unit[0] ? 1 : 0;
+      std::nth_element(keys.begin() + (long)a, keys.begin() + (long)cut, keys.begin() + (long)b,
+                       [ax](const Key& p, const Key& q) { return p.k[ax] < q.k[ax]; });
+      nodes.push_back({cut, b});
+      nodes.push_back({a, cut});
+    }
+    const std::vector<int64_t> appearance = sg.ids;
+    for (size_t k = 0; k < keys.size(); ++k) sg.ids[k] = appearance[(uint32_t)keys[k].k[0]];
   }
   size_t n_stat_p = 0, n_mov_p = 0, n_movy_p = 0, n_xrec = 0, n_xpl = 0;
   for (const Seg64& sg : segs64) {

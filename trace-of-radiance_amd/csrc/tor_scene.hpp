@@ -34,8 +34,8 @@ struct HostLayout {
   // the reach pass in front of stage one's whole words (tor_screen.hpp reach_ray): kReachRecFloats floats per 32-slot WORD of the
   // sorted list, word w = slots [32 w, 32 w + 32) -- {xlo, xhi, zlo, zhi} float32 offsets from the segment's origin, {ylo, yhi}
   // float64 -- for the words wholly inside a segment of xkind 10 / 11 / 12 / 14; every other word (-inf, +inf): reached by everybody.
-  // The segments of those xkinds that the reach pass runs on (tor_scene.cpp: enough objects, a thin height slab) are ordered by the
-  // Morton code of their centres' ground position, so that a word is a patch of ground.  xwb_all: the same table with every word (-inf, +inf) (TOR_PLANE=3: the reach pass runs and culls nothing)
+  // The segments of those xkinds that the reach pass runs on (tor_scene.cpp: enough objects, a thin height slab) are ordered by an
+  // even split of their centres' ground positions, so that a word is a patch of ground.  xwb_all: the same table with every word (-inf, +inf) (TOR_PLANE=3: the reach pass runs and culls nothing)
   std::vector<float> xwb, xwb_all;
   std::vector<float> hot32;  // TOR_ACCEL_F32 segments (kinds 5/6/7): packed pair records, see tor_kernels.hpp
   int n_segs = 0;

@@ -412,8 +412,8 @@ TOR_HD float plane32_offset(double c, double o, double& err_io) {
 // ---------------------------------------------------------------------------------------------------------------------
 // THE REACH PASS in front of stage one's whole words (xkinds 10, 11, 12, 14).  Stage one tests the whole infinite ground LINE of
 // a ray against every slot; a sphere can only be a candidate where the RAY -- t >= 0 -- is near it, in y as well.  The host sorts
-// a segment's objects by the Morton code of their ground position (tor_scene.cpp), so that a word of 32 consecutive slots is a
-// small patch of ground, and keeps one record per word of the sorted list (KParams.xwb, kReachRecFloats floats):
+// a segment's objects by an even top-down split of their ground positions (tor_scene.cpp), so that a word of 32 consecutive slots
+// is a small patch of ground, and keeps one record per word of the sorted list (KParams.xwb, kReachRecFloats floats):
 //     {xlo, xhi, zlo, zhi}   float32: the box of the word's stored offsets c' (xpl32), grown by G0 = (R + E)(1 + 2^-40) and rounded
 //                            outward; R = the segment's largest |radius|, E = the table's rounding bound (plane_seg32)
 //     {ylo, yhi}             float64: the heights the SEGMENT's centres take while the time fraction f is in [0, 1], grown by R and
