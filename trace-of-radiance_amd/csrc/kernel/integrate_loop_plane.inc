@@ -112,9 +112,9 @@
                     // lane's piece of ray inside the segment's height slab, as a box in xz, against the words' boxes (KParams.xwb:
                     // one 32-byte record per word through the scalar path, four float32 compares each).  reach_l: the lane's bits
                     // (bit w <-> word w of this phase), the ONE register the word loop carries for it; reach_w: the wave's.
-                    // Words nobody reaches are not walked: no record request, no object instruction; their LDS slots are written 0
-                    // up front (the summary is rebuilt from every slot of the pass after stage two: a stale word of an earlier
-                    // query would come back as candidates), their summary bits are shifted in clear.  A walked word costs what it
+                    // Words nobody reaches are not walked: no record request, no object instruction, no store; their summary bits
+                    // are shifted in clear, and reach_skip keeps them out of the summary's rebuild after stage two (a stale word
+                    // of an earlier query would come back as candidates).  A walked word costs what it
                     // cost, one word per trip: its four requests a whole group ahead of their waits, the fourth one being the first
                     // group of the NEXT word to walk (the group behind this word when there is none, as before), `ra` landed at
                     // both ends of a trip, so no request crosses a branch.  A lane's bits in a word it does not reach itself are
@@ -147,8 +147,18 @@
                         }
                         reach_w &= (2u << (unsigned)(nw - 1)) - 1u;
                       }
-                      for (unsigned z = ~reach_w & ((2u << (unsigned)(nw - 1)) - 1u); z != 0u; z &= z - 1u)
-                        q[(unsigned)(w_count + __builtin_ctz(z)) * 64] = 0u;
+                      // The words nobody reaches are NOT written: what they hold is a word of an earlier query.  Their summary bits
+                      // are shifted in clear below, and the summary's rebuild after stage two (tor_kernels.hip, `plane_ran`) leaves
+                      // them out by this mask, kept across the segments of a pass and begun afresh with every pass.  Nobody else
+                      // reads such a word: the resolve and stage two's walk go by the summary; `shared_word` / `sat_out` touch the
+                      // first word of a segment's stretch when it began in the block phase, `partial` the running word -- words
+                      // the block phases of this pass stored, never a whole word of this loop.
+                      if constexpr (kReachNoZero == 1) {
+                        reach_skip |= (~reach_w & ((2u << (unsigned)(nw - 1)) - 1u)) << (unsigned)w_count;
+                      } else if constexpr (kReachNoZero == 0) {
+                        for (unsigned z = ~reach_w & ((2u << (unsigned)(nw - 1)) - 1u); z != 0u; z &= z - 1u)
+                          q[(unsigned)(w_count + __builtin_ctz(z)) * 64] = 0u;
+                      }
                       if (stats_on && lane == 0) {  // debug counters (tor_debug_last_reach): whole words walked, whole words met
                         atomicAdd(p.stats + 11, (unsigned long long)__builtin_popcount(reach_w));
                         atomicAdd(p.stats + 12, (unsigned long long)nw);

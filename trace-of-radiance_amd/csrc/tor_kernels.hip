@@ -573,6 +573,7 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
         int w_count = 0;    // kWords: words stored in this pass (wave-uniform)
         int gb_next = 0;    // kWords: the block index behind the last block tested (wave-uniform)
         bool plane_ran = false;  // kWords: stage two of a plane-screened segment cleared bits of this pass's words (wave-uniform)
+        unsigned reach_skip = 0;  // kReach: bit k <-> word k of this pass was skipped by the reach pass and NOT written (wave-uniform)
         // (seg, i) are the same in every lane that has a live path, but they are updated under `if (active)` inside
         // this loop, which makes them divergent in the compiler's eyes -- and the object records would then come
         // through vector loads instead of the scalar data path (measured: half the speed).  readfirstlane inside
@@ -690,6 +691,9 @@ __global__ __launch_bounds__(kThreads, WAVES_PER_SIMD) void integrate_kernel(con
             unsigned all = 0;
 #pragma unroll
             for (int k2 = 0; k2 < kQCap; ++k2) all = push_cond(all, q[(unsigned)k2 * 64] != 0u);
+            // ... and so are the words the reach pass skipped: they were not written either, and what they hold is an earlier query's
+            // (reach_skip's bit k <-> slot k, `all`'s bit kQCap - 1 - k: the mask turned round)
+            if constexpr (kReach && kReachNoZero == 1) all &= ~(__builtin_bitreverse32(reach_skip) >> (unsigned)(32 - kQCap));
             nz = all >> (unsigned)(kQCap - w_count);
           }
         }

@@ -470,6 +470,14 @@ constexpr bool kReachMutant = true;
 #else
 constexpr bool kReachMutant = false;
 #endif
+// Words nobody reaches are not written at all: the pass keeps a wave-uniform mask of them and the summary's rebuild after stage two
+// leaves them out (kernel/integrate_loop_plane.inc, tor_kernels.hip `reach_skip`).  -DTOR_REACH_NOZERO=0: A/B builds only -- they are
+// written 0 up front, as they were.  (2: the MUTANT -- no zero stores and no mask; every case of tests/test_gpu_reach_feed.py must
+// then FAIL on `candidates`.  Never a product build.)
+#ifndef TOR_REACH_NOZERO
+#define TOR_REACH_NOZERO 1
+#endif
+constexpr int kReachNoZero = TOR_REACH_NOZERO;
 constexpr int kReachRecFloats = 8;  // {xlo, xhi, zlo, zhi} float32, {ylo, yhi} float64
 constexpr int kReachMinWords = 8;       // the host runs the pass on segments of enough objects for this many whole words wherever they start ...
 constexpr double kReachSlabRatio = 8.0;  // ... whose height slab, times this, fits the smaller extent of their ground box (tor_scene.cpp)
