@@ -1041,6 +1041,12 @@ TOR_API const char* tor_version(void);
  * log, no exp, no draws) and the density lookup at a point, defined operation by operation in tor_grid.h. */
 #include "tor_grid.h"
 
+/* ---- surface-texture queries: checker and octahedral image albedos --------------------------------------------------------------------
+ * tor_scene_textures, tor_texture_info, tor_texture_eval_device / _host: a table of textures bound to the objects of the uploaded
+ * list, and per hit record the colour of the surface there -- a constant, a 3-D checker, or an octahedral image looked up by the
+ * record's outward normal (nearest or bilinear, no atan2 and no acos) -- defined operation by operation in tor_texture.h. */
+#include "tor_texture.h"
+
 /* ---- debug entries of the reach pass in front of the plane screen's whole words -------------------------------------------------
  * tor_debug_reach_scene, tor_debug_last_reach: which words of the sorted list a ray can be near (host mirror), and how many whole
  * words the last launch walked; described in tor_reach.h. */

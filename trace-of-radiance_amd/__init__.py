@@ -199,6 +199,12 @@ GRID_SYMBOLS = ["tor_scene_media_grid", "tor_media_grid_info", "tor_media_grid_m
                 "tor_media_grid_density_device", "tor_media_grid_density_host"]
 GRID_MAX_DIM = 1024         # TOR_GRID_MAX_DIM: the most cells of a density grid along one axis
 GRID_MAX_CELLS = 1 << 24    # TOR_GRID_MAX_CELLS: the most cells of a density grid
+# the surface-texture queries (include/tor_texture.h), bound as the phase entries are
+TEXTURE_SYMBOLS = ["tor_scene_textures", "tor_texture_info", "tor_texture_eval_device", "tor_texture_eval_host"]
+TEXTURE_CONSTANT, TEXTURE_CHECKER, TEXTURE_IMAGE = 0, 1, 2   # TOR_TEXTURE_*: the kind of a Texture
+TEXTURE_SPACES = {"world": 0, "normal": 1}                   # TOR_TEXTURE_WORLD / _NORMAL: what a checker reads
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}              # TOR_TEXTURE_NEAREST / _BILINEAR: how an image is looked up
+TEXTURE_MAX, TEXTURE_MAX_SIDE, TEXTURE_MAX_TEXELS = 4096, 2048, 1 << 22   # TOR_TEXTURE_MAX*
 PHASE_G_MAX = 0.99          # TOR_PHASE_G_MAX: the largest |g| of Context.set_media_phase
 PHASE_G_MIN = 2.0 ** -20    # TOR_PHASE_G_MIN: the smallest |g| that is not 0
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
@@ -269,6 +275,7 @@ def lib():
     _bind(L, PHASE_SYMBOLS, skip_missing=bool(ab), table=_PHASE_SIGNATURES)
     _bind(L, REACH_SYMBOLS, skip_missing=bool(ab), table=_REACH_SIGNATURES)
     _bind(L, GRID_SYMBOLS, skip_missing=bool(ab), table=_GRID_SIGNATURES)
+    _bind(L, TEXTURE_SYMBOLS, skip_missing=bool(ab), table=_TEXTURE_SIGNATURES)
     _lib = L
     return L
 
@@ -455,6 +462,20 @@ def _grid_signatures() -> dict:
 
 
 _GRID_SIGNATURES = _grid_signatures()
+
+
+def _texture_signatures() -> dict:
+    """The entries of include/tor_texture.h, in a table of their own like the phase entries."""
+    v, i64 = C.c_void_p, C.c_int64
+    return {
+        "tor_scene_textures": [v, i64, v, i64, v, i64, v],
+        "tor_texture_info": [v, v],
+        "tor_texture_eval_device": [v, i64, v, v, i64, v, v, v],
+        "tor_texture_eval_host": [v, i64, v, v, i64, v, v],
+    }
+
+
+_TEXTURE_SIGNATURES = _texture_signatures()
 
 
 def _bind(L, names=None, skip_missing=False, table=None) -> None:
@@ -2203,6 +2224,57 @@ class Context:
         ops.call(ops.ptr(points), int(medium), p_list, n_list, ops.ptr(cell), ops.ptr(density))
         return cell, density   # (copies made for the call are torch's, freed in stream order)
 
+    # ---- surface textures (tor_scene_textures, tor_texture_eval_device): checker and octahedral image albedos ----
+
+    def set_textures(self, textures, binding):
+        """The texture table of the uploaded scene (tor_scene_textures, include/tor_texture.h): `textures` a list of Texture,
+        `binding` (n_objects,) ints, the texture of every object of the uploaded list or -1 for none (such an object answers its
+        material's albedo).  The images are packed into one atlas in list order.  An empty list clears the table, and so does
+        every upload that replaces the scene; lights, environment, media, groups and photons leave it alone.  albedo() and
+        trace(textures=True) / trace_direct(textures=True) read it; the render kernels and bounce() never do."""
+        textures = list(textures)
+        b = np.ascontiguousarray(np.asarray(binding).reshape(-1), dtype=np.int32)
+        if not textures:
+            _check(lib().tor_scene_textures(self._h, 0, None, int(b.size), None, 0, None))
+            return
+        table, atlas = pack_textures(textures)
+        _check(lib().tor_scene_textures(self._h, len(textures), C.c_void_p(C.addressof(table)), int(b.size),
+                                        C.c_void_p(b.ctypes.data) if b.size else None, int(atlas.shape[0]),
+                                        C.c_void_p(atlas.ctypes.data) if atlas.size else None))
+
+    def textures(self):
+        """(n_textures -- 0: no table --, n_texels of the atlas, the objects bound to a texture) (tor_texture_info)."""
+        out = np.zeros(3, dtype=np.int64)
+        _check(lib().tor_texture_info(self._h, C.c_void_p(out.ctypes.data)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def albedo(self, hits, index=None, out=None) -> "TextureEval":
+        """The colour of the surface at each listed hit record (tor_texture_eval_device / tor_texture_eval_host): the texture bound
+        to the record's object (set_textures) evaluated at the record -- a constant, a checker of p or of the outward normal, an
+        octahedral image looked up by the outward normal -- or, for an object without a texture, the attenuation bounce() gives a
+        ray that scattered off it; the definition, operation by operation in float64, is in include/tor_texture.h.
+
+        hits: a HitResult / BounceResult or its (n, 8) raw records, as for bsdf(): a torch CUDA tensor (zero-copy, asynchronous on
+        torch's current stream) or anything numpy takes (blocking); object, p, normal and front_face are read as given.  index as
+        for bounce().  Nothing is drawn.  Returns a TextureEval(color (n, 3) float64, texel (n,) int32: an image's nearest texel
+        row * n + col, a checker's parity, 0 for a constant, -1 where there is no texture or no usable direction); out: one of an
+        earlier call on as many records, written again (records that are not listed keep what it holds); otherwise a new one
+        (colour 0, texel -1)."""
+        if out is not None and not isinstance(out, TextureEval):
+            raise ValueError("Context.albedo: out must be a TextureEval")
+        ops = _operands(self, "texture_eval", hits.raw if hasattr(hits, "raw") else hits, "hits", 8)
+        n, raw = ops.n, ops.lead
+        index, n_list, p_list = ops.index(index)
+        if out is None:
+            color, texel = ops.new(n, 3), ops.new(n, dtype="int32", zero=False)
+            texel[...] = -1
+        else:
+            color, texel = out.color, out.texel
+            if not ops.fits(color, n, 3) or not ops.fits(texel, n, dtype="int32"):
+                ops.bad("out", "the result of a call on as many records, on tensors or arrays as the hits are")
+        ops.call(ops.ptr(raw), p_list, n_list, ops.ptr(color), ops.ptr(texel))
+        return TextureEval(color, texel, ops.note(n_list), keep=ops.keep(raw, index))
+
     def transmittance(self, p, q, time=0.0, mask=None):
         """The transmittance of the segments p -> q through the media of the table: exp(-depth) of march_media on the rays
         p -> q - p with range (0, 1) and tau = inf -- the exp is torch's or numpy's, as p is; the library computes the depth
@@ -2282,7 +2354,8 @@ def _mask_words(a: np.ndarray) -> np.ndarray:
 def environment_directions(n, a=0.5, b=0.5) -> np.ndarray:
     """The (n, n, 3) float64 unit directions of the positions (a, b) in [0, 1) inside every texel of an n x n octahedral
     environment map, [row][col] -- include/tor_env.h's decode, operation by operation in numpy; (0.5, 0.5) are the texel centres.
-    A host bakes any sky with it: set_environment(f(environment_directions(n)))."""
+    A host bakes any sky with it: set_environment(f(environment_directions(n))) -- and any surface image, whose square is the
+    same mapping of the outward normal: Texture.image(f(environment_directions(n)))."""
     n = int(n)
     if not 1 <= n <= ENV_MAX_SIDE:
         raise ValueError(f"environment_directions: need 1 <= n <= {ENV_MAX_SIDE}")
@@ -2316,6 +2389,73 @@ def groups_by_material(scene) -> np.ndarray:
     MAT_DIELECTRIC 2), for Context.set_groups.  Shadow rays that skip glass: mask = ~(1 << MAT_DIELECTRIC) & 0xFFFFFFFF."""
     recs = scene.to_records() if hasattr(scene, "to_records") else np.asarray(scene, dtype=np.float64).reshape(-1, 16)
     return (np.uint32(1) << recs[:, 10].astype(np.uint32)).astype(np.uint32)
+
+
+class TextureRecord(C.Structure):
+    """TorTexture (include/tor_texture.h), 96 bytes."""
+    _fields_ = [("kind", C.c_int32), ("option", C.c_int32), ("side", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_int64),
+                ("a", C.c_double * 3), ("b", C.c_double * 3), ("freq", C.c_double * 3)]
+
+
+assert C.sizeof(TextureRecord) == 96, "TorTexture is 96 bytes on both sides of the ABI"
+
+
+class Texture:
+    """One texture of Context.set_textures (include/tor_texture.h): Texture.constant(rgb), Texture.checker(even, odd, freq,
+    space) or Texture.image(rgb, filter).  kind, option, a, b, freq are the record's fields; rgb is an image's (n, n, 3) float64
+    texels, [row][col] of the octahedral square of the OUTWARD NORMAL -- environment_directions(n) gives the direction of every
+    texel centre, so an image is baked with one call: Texture.image(f(environment_directions(n)))."""
+    __slots__ = ("kind", "option", "a", "b", "freq", "rgb")
+
+    def __init__(self, kind, option=0, a=(0.0, 0.0, 0.0), b=(0.0, 0.0, 0.0), freq=(0.0, 0.0, 0.0), rgb=None):
+        self.kind, self.option = int(kind), int(option)
+        self.a, self.b, self.freq = (tuple(float(x) for x in np.asarray(c, dtype=np.float64).reshape(3)) for c in (a, b, freq))
+        self.rgb = rgb
+
+    @classmethod
+    def constant(cls, rgb) -> "Texture":
+        """One colour everywhere."""
+        return cls(TEXTURE_CONSTANT, a=rgb)
+
+    @classmethod
+    def checker(cls, even, odd, freq=1.0, space="world") -> "Texture":
+        """A 3-D checker: `even` where the parities of floor(x * freq) per axis sum to an even number, else `odd`; freq a number
+        or one per axis (cells per unit); space "world" (x = the record's p) or "normal" (x = the outward normal: the pattern
+        rides a moving sphere)."""
+        if space not in TEXTURE_SPACES:
+            raise ValueError('Texture.checker: space must be "world" or "normal"')
+        f = np.broadcast_to(np.asarray(freq, dtype=np.float64), (3,))
+        return cls(TEXTURE_CHECKER, TEXTURE_SPACES[space], even, odd, f)
+
+    @classmethod
+    def image(cls, rgb, filter="nearest") -> "Texture":
+        """An (n, n, 3) octahedral image, looked up by the outward normal; filter "nearest" or "bilinear"."""
+        if filter not in TEXTURE_FILTERS:
+            raise ValueError('Texture.image: filter must be "nearest" or "bilinear"')
+        c = np.ascontiguousarray(np.asarray(rgb, dtype=np.float64))
+        if c.ndim != 3 or c.shape[0] != c.shape[1] or c.shape[2] != 3 or not 1 <= c.shape[0] <= TEXTURE_MAX_SIDE:
+            raise ValueError(f"Texture.image: rgb must be (n, n, 3) with 1 <= n <= {TEXTURE_MAX_SIDE}")
+        return cls(TEXTURE_IMAGE, TEXTURE_FILTERS[filter], rgb=c)
+
+
+def pack_textures(textures):
+    """The table and the atlas of a list of Texture: (a ctypes array of TextureRecord, (n_texels, 3) float64) -- the images one
+    after the other in list order, each [row][col] from its offset."""
+    textures = list(textures)
+    table = (TextureRecord * max(1, len(textures)))()
+    parts, at = [], 0
+    for j, t in enumerate(textures):
+        if not isinstance(t, Texture):
+            raise ValueError("Context.set_textures: textures must be a list of Texture")
+        r = table[j]
+        r.kind, r.option = t.kind, t.option
+        r.a[:], r.b[:], r.freq[:] = t.a, t.b, t.freq
+        if t.kind == TEXTURE_IMAGE:
+            r.side, r.offset = int(t.rgb.shape[0]), at
+            parts.append(t.rgb.reshape(-1, 3))
+            at += int(t.rgb.shape[0]) ** 2
+    atlas = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, 3), dtype=np.float64)
+    return table, atlas
 
 
 class HitResult:
@@ -2431,6 +2571,16 @@ class BsdfEval:
 
     def __init__(self, value, pdf, kind, note: str, keep=None):
         self.value, self.pdf, self.kind, self.note, self._keep = value, pdf, kind, note, keep
+
+
+class TextureEval:
+    """Answers of Context.albedo, one per record (include/tor_texture.h): color (n, 3) float64 the surface's colour, texel (n,)
+    int32 (an image's nearest texel row * n + col, a checker's parity, 0 for a constant, -1: no texture, no object or no usable
+    direction), and `mode` ("texture eval")."""
+    __slots__ = ("color", "texel", "mode", "_keep")
+
+    def __init__(self, color, texel, note: str, keep=None):
+        self.color, self.texel, self.mode, self._keep = color, texel, note, keep
 
 
 class PhotonMap:
@@ -2715,7 +2865,8 @@ class Film:
     def add_pass(self, cam: Camera, k: int, tracer=None, chunk_pixels=None) -> "Film":
         """Samples [samples, samples + k) of every pixel: over ranges of at most chunk_pixels pixels the library's camera rays
         (Context.camera_rays, SEED_SAMPLE), colors = tracer(rays, rng) -- default Context.radiance at max_depth; a tracer may return
-        a tuple whose first item is the colours -- and their deposit into pixel chunk[entry // k]."""
+        a tuple whose first item is the colours -- and their deposit into pixel chunk[entry // k].  A textured frame:
+        tracer=functools.partial(ctx.trace, max_depth=..., textures=True)."""
         import torch
         k = int(k)
         if k < 1:

@@ -498,6 +498,7 @@ int tor_scene_upload(TorContext* ctx, TorHittableList world) {
   ctx->hitq.n_lights = 0;    // ... and no light table (tor_scene_lights)
   ctx->hitq.n_media = 0;     // ... and no media table (tor_scene_media)
   ctx->hitq.drop_grids();    // ... so no density grids (tor_scene_media_grid); the device is idle (above)
+  ctx->hitq.n_textures = 0;  // ... and no texture table (tor_scene_textures)
   ctx->scene_ready = true;
   return TOR_OK;
 }

@@ -160,6 +160,12 @@ struct HitQueryState {
     for (MediaGrid& g : grids) { g.density.release(); g.n[0] = g.n[1] = g.n[2] = 0; }
     grid_mask = 0;
   }
+  // surface-texture queries (tor_texture.hip): the library's copies of the table, the binding and the atlas
+  DeviceBuffer tex_table;           // n_textures TorTexture records
+  DeviceBuffer tex_binding;         // one int32 per object in the ORIGINAL numbering: its texture, or -1
+  DeviceBuffer tex_atlas;           // 4 float64 per texel (R, G, B, 0): a texel is two 16-byte loads
+  int64_t n_textures = 0;           // 0: no table (the state after every upload that replaces the scene)
+  int64_t n_texels = 0, tex_bound = 0;  // the atlas's texels, and the objects whose binding is not -1
   hipEvent_t ev_done = nullptr;     // recorded after the last query launch
   bool launched = false;
   void* stream = nullptr;           // stream of the last query launch

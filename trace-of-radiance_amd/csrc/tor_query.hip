@@ -102,6 +102,9 @@ HitQueryState::~HitQueryState() {
   ph_rec.release();
   ph_start.release();
   ph_tmp.release();
+  tex_table.release();
+  tex_binding.release();
+  tex_atlas.release();
   if (ev_done) (void)hipEventDestroy(ev_done);
 }
 

@@ -132,16 +132,17 @@ class _Paths:
         idx = self.live.long()
         return idx, res.status[idx], res
 
-    def advance(self, stop=None):
+    def advance(self, stop=None, albedo=None):
         """The tail of a step: the paths that scattered stay live, in order (bounce_select) -- but for those that hit an object
-        flagged in `stop` (one bool per object), which end here -- and att *= attenuation for them (render.nim:35).  Returns the
-        new live list as int64."""
+        flagged in `stop` (one bool per object), which end here -- and att *= attenuation for them (render.nim:35); with
+        `albedo` ((n, 3), Context.albedo's colours of the step's records) att *= albedo instead.  Returns the new live list as
+        int64."""
         live = self.ctx.bounce_select(self.res.status, self.live)
         if stop is not None:
             live = live[~stop[self.res.object[live.long()].long().clamp(min=0)]]
         self.live = live
         scat = live.long()
-        self.att[scat] = self.att[scat] * self.res.attenuation[scat]
+        self.att[scat] = self.att[scat] * (self.res.attenuation if albedo is None else albedo)[scat]
         return scat
 
     def sky_on_miss(self, sky, idx, st):
@@ -216,7 +217,14 @@ class _LambertianNee:
         color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
 
 
-def trace(ctx, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None, mask=None):
+def _need_textures(ctx, who):
+    """textures=True asks for a texture table (set_textures): refused before the first launch."""
+    if ctx.textures()[0] == 0:
+        raise ValueError(f"Context.{who}: textures=True needs a texture table (set_textures)")
+
+
+def trace(ctx, rays, rng, max_depth=50, sky=None, emission=None, time_range=None, mode="auto", on_bounce=None, textures=False,
+          mask=None):
     """A wavefront path tracer on top of bounce(): radiance()'s loop (render.nim:21-47) one step per launch, open where the
     reference is closed.  att = 1; per step: bounce the live rays; a miss ends with sky * att; with `emission` every hit adds
     att * emission[object] (before the attenuation is updated); att *= attenuation for the rays that scattered, which stay
@@ -230,9 +238,22 @@ def trace(ctx, rays, rng, max_depth=50, sky=None, emission=None, time_range=None
     rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through the device and come
     back as numpy.  One time range for all steps: time_range, or the rays' finite times (the library adds 0).
     mask: as for bounce(), for every step; or a callable mask(step) -> int | per-ray words, so that step 0 (the camera's rays)
-    sees other objects than the later steps."""
+    sees other objects than the later steps.
+    textures: False -- every launch and every bit as above; True -- the surfaces take their colour from the texture table
+    (set_textures; a ValueError without one): after each step albedo(result, the stepped list) runs, and att *= its colour
+    replaces att *= attenuation for the rays that scattered.  An object without a texture answers its attenuation, so with no
+    object bound the colours and states are those of textures=False, bit for bit.  `mask` stays the trailing parameter; a call
+    from before `textures` existed that passes its mask by POSITION lands in `textures`, which is a bool (Python's or numpy's)
+    and nothing else: any other value there is taken as that mask, so every such call keeps its meaning -- unless `mask` is given
+    too, which no such call could do: that is a ValueError."""
+    if not isinstance(textures, (bool, np.bool_)):
+        if mask is not None:
+            raise ValueError("Context.trace: textures must be a bool (a mask goes into mask=)")
+        mask, textures = textures, False
+    if textures:
+        _need_textures(ctx, "trace")
     p = _Paths.from_rays(ctx, "trace", rays, rng, time_range)
-    color, att = p.color, p.att
+    color, att, tex = p.color, p.att, None
     if emission is not None:
         emission = _colours(emission, p.dev)
     for step in p.steps(max_depth):
@@ -243,12 +264,16 @@ def trace(ctx, rays, rng, max_depth=50, sky=None, emission=None, time_range=None
             color[hit] = color[hit] + att[hit] * emission[res.object[hit].long()]
         if on_bounce is not None:
             on_bounce(step, p.live, res)
-        p.advance()
+        if textures:
+            tex = ctx.albedo(res, p.live, out=tex)
+            p.advance(albedo=tex.color)
+        else:
+            p.advance()
     return p.finish(color)
 
 
 def trace_direct(ctx, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=False, lamp_mask=None, time_range=None,
-                 mode="auto", strategy="solid_angle", glossy=None):
+                 mode="auto", strategy="solid_angle", glossy=None, textures=False):
     """trace()'s loop with next-event estimation: after each bounce, the rays that hit a diffuse object sample one light of
     the table (sample_lights), ask occluded() whether the segment to the sampled surface point is free, and add
         att * albedo / pi * emission[light] * max(0, n . unit(dir)) / pdf
@@ -272,8 +297,16 @@ def trace_direct(ctx, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=
     The light draws come from a second state per path, derived from the path's entry state (splitmix64 finalisers over its
     words), not from the path state itself: the bounces see exactly the states trace() gives them.  So with an all-zero
     emission the colours are trace()'s, bit for bit, and the returned states are the path states, as trace() returns
-    them."""
+    them.
+
+    textures: False -- every launch and every bit as above; True -- as for trace(): albedo(result, the stepped list) after each
+    step, att *= its colour for the rays that scattered (on the default path the throughput carries the albedo into the light
+    sample, so nothing else changes), and on the `glossy=` path the light sample's value is colour * p_b in place of bsdf()'s
+    albedo * p_b.  A ValueError without a texture table."""
     import torch
+    if textures:
+        _need_textures(ctx, "trace_direct")
+    tex = None
     p = _Paths.from_rays(ctx, "trace_direct", rays, rng, time_range)
     n, dev, f64 = p.n, p.dev, torch.float64
     work, color, att, tr = p.work, p.color, p.att, p.tr
@@ -304,7 +337,11 @@ def trace_direct(ctx, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=
         if nee_ok is not None:   # (before the attenuation moves on: the light sample is weighted by att * value)
             nee = hit[nee_ok[obj]]
             att_nee = att[nee]
-        scat = p.advance()
+        if textures:
+            tex = ctx.albedo(res, p.live, out=tex)
+            scat = p.advance(albedo=tex.color)
+        else:
+            scat = p.advance()
         if nee_ok is not None:
             # next-event estimation at every diffuse or glossy vertex, through bsdf(): also where Metal absorbed the
             # scattered ray -- the vertex reflects the lamp whatever became of the one direction the scatter drew
@@ -319,7 +356,8 @@ def trace_direct(ctx, rays, rng, emission, diffuse, max_depth=50, sky=None, mis=
             p_b, pdf, lamp = ev.pdf[nee], ls.pdf[nee], ls.light[nee].long()
             ok = (~occ.occluded[nee]) & (lamp >= 0) & (pdf > 0) & torch.isfinite(pdf) & (p_b > 0) & torch.isfinite(p_b)
             share = pdf / (pdf + p_b) if mis else torch.ones_like(pdf)
-            add = att_nee * ev.value[nee] * emission[lamp.clamp(min=0)] * (share / pdf)[:, None]
+            value = tex.color[nee] * ev.pdf[nee][:, None] if textures else ev.value[nee]
+            add = att_nee * value * emission[lamp.clamp(min=0)] * (share / pdf)[:, None]
             color[nee] = color[nee] + torch.where(ok[:, None], add, torch.zeros_like(add))
             if mis:   # the density of the direction the path actually left in (0 for an absorbed ray: it found nothing)
                 ev2 = ctx.bsdf(win, res, work, lst, out=ev2)
