@@ -1047,6 +1047,13 @@ TOR_API const char* tor_version(void);
  * record's outward normal (nearest or bilinear, no atan2 and no acos) -- defined operation by operation in tor_texture.h. */
 #include "tor_texture.h"
 
+/* ---- planar patch queries: quads and triangles for host integrators -------------------------------------------------------------------
+ * tor_scene_patches, tor_patch_info, tor_patch_hit_device / _host, tor_patch_occluded_device / _host: a context-owned table of
+ * static parallelograms and triangles, the closest patch per ray (alone, or merged into the records tor_hit_device wrote) and the
+ * any-hit bit (alone, or OR-ed into tor_occluded_device's) -- Moeller-Trumbore in float64, defined operation by operation in
+ * tor_patches.h. */
+#include "tor_patches.h"
+
 /* ---- debug entries of the reach pass in front of the plane screen's whole words -------------------------------------------------
  * tor_debug_reach_scene, tor_debug_last_reach: which words of the sorted list a ray can be near (host mirror), and how many whole
  * words the last launch walked; described in tor_reach.h. */

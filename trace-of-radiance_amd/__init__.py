@@ -205,6 +205,11 @@ TEXTURE_CONSTANT, TEXTURE_CHECKER, TEXTURE_IMAGE = 0, 1, 2   # TOR_TEXTURE_*: th
 TEXTURE_SPACES = {"world": 0, "normal": 1}                   # TOR_TEXTURE_WORLD / _NORMAL: what a checker reads
 TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}              # TOR_TEXTURE_NEAREST / _BILINEAR: how an image is looked up
 TEXTURE_MAX, TEXTURE_MAX_SIDE, TEXTURE_MAX_TEXELS = 4096, 2048, 1 << 22   # TOR_TEXTURE_MAX*
+# the planar patch queries (include/tor_patches.h), bound as the texture entries are
+PATCH_SYMBOLS = ["tor_scene_patches", "tor_patch_info", "tor_patch_hit_device", "tor_patch_hit_host", "tor_patch_occluded_device",
+                 "tor_patch_occluded_host"]
+PATCH_QUAD, PATCH_TRIANGLE = 0, 1   # TOR_PATCH_*: the kind of a Patch
+PATCH_MAX = 16384                   # TOR_PATCH_MAX: the most patches of a table
 PHASE_G_MAX = 0.99          # TOR_PHASE_G_MAX: the largest |g| of Context.set_media_phase
 PHASE_G_MIN = 2.0 ** -20    # TOR_PHASE_G_MIN: the smallest |g| that is not 0
 HIT_AUTO, HIT_BRUTE, HIT_BLOCKS = 0, 1, 2
@@ -276,6 +281,7 @@ def lib():
     _bind(L, REACH_SYMBOLS, skip_missing=bool(ab), table=_REACH_SIGNATURES)
     _bind(L, GRID_SYMBOLS, skip_missing=bool(ab), table=_GRID_SIGNATURES)
     _bind(L, TEXTURE_SYMBOLS, skip_missing=bool(ab), table=_TEXTURE_SIGNATURES)
+    _bind(L, PATCH_SYMBOLS, skip_missing=bool(ab), table=_PATCH_SIGNATURES)
     _lib = L
     return L
 
@@ -476,6 +482,22 @@ def _texture_signatures() -> dict:
 
 
 _TEXTURE_SIGNATURES = _texture_signatures()
+
+
+def _patch_signatures() -> dict:
+    """The entries of include/tor_patches.h, in a table of their own like the texture entries."""
+    v, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
+    return {
+        "tor_scene_patches": [v, i64, v],
+        "tor_patch_info": [v, v],
+        "tor_patch_hit_device": [v, i64, v, v, v, i64, i32, v, v, v, v, v, u32],
+        "tor_patch_hit_host": [v, i64, v, v, v, i64, i32, v, v, v, v, u32],
+        "tor_patch_occluded_device": [v, i64, v, v, v, i64, i32, v, v, v, u32],
+        "tor_patch_occluded_host": [v, i64, v, v, v, i64, i32, v, v, u32],
+    }
+
+
+_PATCH_SIGNATURES = _patch_signatures()
 
 
 def _bind(L, names=None, skip_missing=False, table=None) -> None:
@@ -856,11 +878,12 @@ class _Operands:
         """tor_last_note of a listed query; one with no row to answer never reaches the code that writes it."""
         return last_note() if self.n and n_list else f"{self.who}: nothing to do"
 
-    def call(self, *args, masked=None):
+    def call(self, *args, masked=None, after=()):
         """tor_<who>_device(ctx, n, *args, stream) or tor_<who>_host(ctx, n, *args); with masked = mask()'s pair the
-        _masked_ twin, which takes the pair last."""
+        _masked_ twin, which takes the pair last.  after: what an entry without a twin takes behind the stream (the patch
+        queries' mask pair)."""
         name = f"tor_{self.who}{'' if masked is None else '_masked'}{self.suffix}"
-        _check(getattr(lib(), name)(self.h, self.n, *args, *self.tail, *(masked or ())))
+        _check(getattr(lib(), name)(self.h, self.n, *args, *self.tail, *(masked or ()), *after))
 
 
 class _Tensors(_Operands):
@@ -2275,6 +2298,88 @@ class Context:
         ops.call(ops.ptr(raw), p_list, n_list, ops.ptr(color), ops.ptr(texel))
         return TextureEval(color, texel, ops.note(n_list), keep=ops.keep(raw, index))
 
+    # ---- planar patches (tor_scene_patches, tor_patch_hit_device, tor_patch_occluded_device): quads and triangles ----
+
+    def set_patches(self, patches):
+        """The patch table of the uploaded scene (tor_scene_patches, include/tor_patches.h): a list of Patch (Patch.quad,
+        Patch.triangle, box_patches) -- static, two-sided parallelograms and triangles, each wearing the material of a scene
+        object (or none) and a visibility word.  An empty list clears the table, and so does every upload that replaces the
+        scene; lights, environment, media, textures, groups and photons leave it alone.  hit_patches(), occluded_patches() and
+        trace_patches() read it; the render kernels, hit(), bounce() and every other query never do."""
+        patches = list(patches)
+        if not patches:
+            _check(lib().tor_scene_patches(self._h, 0, None))
+            return
+        table = pack_patches(patches)
+        _check(lib().tor_scene_patches(self._h, len(patches), C.c_void_p(C.addressof(table))))
+
+    def patches(self):
+        """(n_patches -- 0: no table --, the patches that wear a material) (tor_patch_info)."""
+        out = np.zeros(2, dtype=np.int64)
+        _check(lib().tor_patch_info(self._h, C.c_void_p(out.ctypes.data)))
+        return int(out[0]), int(out[1])
+
+    def _patch_operands(self, who, rays, t_range, index, mask):
+        """What the two patch queries share: the rays, the ranges, the list and the mask pair (None: every group)."""
+        ops = _operands(self, who, rays, "rays", 7)
+        t_range = ops.rows(t_range, "t_range", 2)
+        index, n_list, p_list = ops.index(index)
+        mk, pair = (None, (0, 0xFFFFFFFF)) if mask is None else ops.mask(mask)
+        return ops, t_range, index, n_list, p_list, mk, pair
+
+    def hit_patches(self, rays, t_range=None, index=None, mask=None, merge=None, out=None) -> "PatchHits":
+        """The closest patch of the table per listed ray (tor_patch_hit_device / tor_patch_hit_host): Moeller-Trumbore in float64,
+        operation by operation as include/tor_patches.h defines it; the smallest accepted t wins, ties go to the lower index.
+
+        rays: (n, 7) float64 -- a torch CUDA tensor (zero-copy, asynchronous on torch's current stream) or anything numpy takes
+        (blocking); the time is not read.  t_range, index and mask as for occluded(): a patch takes part for ray i iff its
+        groups & mask_i != 0.  merge: None -- the records are the patches' alone, a ray without a patch gets hit()'s miss record;
+        or a HitResult / BounceResult or its (n, 8) raw records: the answer starts from a copy of them (in place with out=), a
+        patch replaces a record only where it is strictly nearer than the record's t (a tie stays with the sphere), and a ray
+        without such a patch keeps its record.  Returns PatchHits: a HitResult's fields -- `object` the patch's material -- plus
+        patch (n,) int32 (-1: no patch) and uv (n, 2) float64, the patch's coordinates (a, b) of the point.  out: a PatchHits of
+        an earlier call on as many rays, written again (rays that are not listed keep what it holds; with merge given too, out
+        is merged into and merge itself only says so)."""
+        if out is not None and not isinstance(out, PatchHits):
+            raise ValueError("Context.hit_patches: out must be a PatchHits")
+        ops, t_range, index, n_list, p_list, mk, pair = self._patch_operands("patch_hit", rays, t_range, index, mask)
+        n, rays = ops.n, ops.lead
+        if out is not None:
+            raw, patch, uv = out.raw, out.patch, out.uv
+            if not ops.fits(raw, n, 8) or not ops.fits(patch, n, dtype="int32") or not ops.fits(uv, n, 2):
+                ops.bad("out", "the result of a call on as many rays, on tensors or arrays as the rays are")
+        else:
+            if merge is None:
+                raw = ops.new(n, 8, unused=14)
+            else:
+                raw = ops.rows(merge.raw if hasattr(merge, "raw") else merge, "merge", 8)
+                raw = raw.clone() if _is_tensor(raw) else raw.copy()
+            patch, uv = ops.new(n, dtype="int32", zero=False), ops.new(n, 2)
+            patch[...] = -1
+        ops.call(ops.ptr(rays), ops.ptr(t_range), p_list, n_list, 0 if merge is None else 1, ops.ptr(raw), ops.ptr(patch),
+                 ops.ptr(uv), after=pair)
+        return PatchHits(raw, ops.words(raw), patch, uv, ops.note(n_list), keep=ops.keep(rays, t_range, index, mk))
+
+    def occluded_patches(self, rays, t_range=None, index=None, mask=None, merge=None, out=None) -> "OccludedResult":
+        """Any-hit query against the patch table (tor_patch_occluded_device / tor_patch_occluded_host): per listed ray ONE bit,
+        whether some patch is accepted in (t_min, t_max).  rays, t_range, index, mask as for hit_patches().  merge: None -- the
+        bit is written, 0 or 1; or an OccludedResult of occluded() (or its raw int32 array): the answer starts from a copy of it
+        (in place with out=) and the query only ever writes 1, so the result is "a sphere or a patch occludes".  out: an
+        OccludedResult of an earlier call on as many rays, or its raw int32 array, written again."""
+        ops, t_range, index, n_list, p_list, mk, pair = self._patch_operands("patch_occluded", rays, t_range, index, mask)
+        n, rays = ops.n, ops.lead
+        raw = out.raw if hasattr(out, "raw") else out
+        if raw is None:
+            if merge is None:
+                raw = ops.new(n, dtype="int32")
+            else:
+                raw = ops.rows(merge.raw if hasattr(merge, "raw") else merge, "merge", dtype="int32")
+                raw = raw.clone() if _is_tensor(raw) else raw.copy()
+        elif not ops.fits(raw, n, dtype="int32"):
+            ops.bad("out", "a contiguous (n,) int32 tensor or array, as the rays are")
+        ops.call(ops.ptr(rays), ops.ptr(t_range), p_list, n_list, 0 if merge is None else 1, ops.ptr(raw), after=pair)
+        return OccludedResult(raw, ops.as_bool(raw), ops.note(n_list), keep=ops.keep(rays, t_range, index, mk))
+
     def transmittance(self, p, q, time=0.0, mask=None):
         """The transmittance of the segments p -> q through the media of the table: exp(-depth) of march_media on the rays
         p -> q - p with range (0, 1) and tau = inf -- the exp is torch's or numpy's, as p is; the library computes the depth
@@ -2458,6 +2563,62 @@ def pack_textures(textures):
     return table, atlas
 
 
+class PatchRecord(C.Structure):
+    """TorPatch (include/tor_patches.h), 88 bytes."""
+    _fields_ = [("kind", C.c_int32), ("material", C.c_int32), ("groups", C.c_uint32), ("reserved", C.c_int32),
+                ("q", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3)]
+
+
+assert C.sizeof(PatchRecord) == 88, "TorPatch is 88 bytes on both sides of the ABI"
+
+
+class Patch:
+    """One patch of Context.set_patches (include/tor_patches.h): the surface q + a * u + b * v, a parallelogram (Patch.quad:
+    0 <= a, b <= 1) or a triangle (Patch.triangle: a, b >= 0, a + b <= 1), two-sided and static.  material: the index of the
+    scene object whose material it wears (what a hit's `object` says), or -1 for none; groups: its visibility word."""
+    __slots__ = ("kind", "material", "groups", "q", "u", "v")
+
+    def __init__(self, kind, q, u, v, material=-1, groups=0xFFFFFFFF):
+        self.kind, self.material, self.groups = int(kind), int(material), int(groups) & 0xFFFFFFFF
+        self.q, self.u, self.v = (tuple(float(x) for x in np.asarray(c, dtype=np.float64).reshape(3)) for c in (q, u, v))
+
+    @classmethod
+    def quad(cls, q, u, v, material=-1, groups=0xFFFFFFFF) -> "Patch":
+        """The parallelogram with the corner q and the edges u and v from it."""
+        return cls(PATCH_QUAD, q, u, v, material, groups)
+
+    @classmethod
+    def triangle(cls, a, b, c, material=-1, groups=0xFFFFFFFF) -> "Patch":
+        """The triangle with the corners a, b, c: q = a, u = b - a, v = c - a."""
+        a, b, c = (np.asarray(x, dtype=np.float64).reshape(3) for x in (a, b, c))
+        return cls(PATCH_TRIANGLE, a, b - a, c - a, material, groups)
+
+
+def box_patches(lo, hi, material=-1, groups=0xFFFFFFFF) -> list:
+    """The six quads of the axis-aligned box lo .. hi, cross(u, v) of each pointing outwards: -x, +x, -y, +y, -z, +z."""
+    lo, hi = (np.asarray(x, dtype=np.float64).reshape(3) for x in (lo, hi))
+    e = np.diag(hi - lo)
+    out = []
+    for k in range(3):
+        a, b = e[(k + 1) % 3], e[(k + 2) % 3]   # cross(a, b) points along +k
+        out.append(Patch.quad(lo, b, a, material, groups))
+        out.append(Patch.quad(lo + e[k], a, b, material, groups))
+    return out
+
+
+def pack_patches(patches):
+    """The table of a list of Patch: a ctypes array of PatchRecord."""
+    patches = list(patches)
+    table = (PatchRecord * max(1, len(patches)))()
+    for j, p in enumerate(patches):
+        if not isinstance(p, Patch):
+            raise ValueError("Context.set_patches: patches must be a list of Patch")
+        r = table[j]
+        r.kind, r.material, r.groups = p.kind, p.material, p.groups
+        r.q[:], r.u[:], r.v[:] = p.q, p.u, p.v
+    return table
+
+
 class HitResult:
     """Closest hits of Context.hit, one TorHit per ray (include/tor_render.h): t, p (n, 3), normal (n, 3), object (int32, -1 = miss)
     and front_face (int32) are views of `raw` ((n, 8) float64, the records as the library wrote them) -- torch tensors or numpy
@@ -2479,6 +2640,15 @@ class BounceResult(HitResult):
         super().__init__(raw, words, note, keep=keep)
         self.attenuation, self.status, self.rays, self.rng = attenuation, status, rays, rng
         self.mode = _mode_of(note, "bounce: ")
+
+
+class PatchHits(HitResult):
+    """Closest patches of Context.hit_patches, one per ray (include/tor_patches.h): HitResult's fields (object: the patch's
+    material, or what the merged record held), patch (n,) int32 the table index (-1: no patch), uv (n, 2) float64 the patch's
+    coordinates of the point, and `mode` ("patch hit")."""
+    def __init__(self, raw, words, patch, uv, note: str, keep=None):
+        super().__init__(raw, words, note, keep)
+        self.patch, self.uv = patch, uv
 
 
 class OccludedResult:

@@ -20,6 +20,7 @@
 
 #include "tor_context.hpp"
 #include "tor_knobs.hpp"
+#include "tor_patches.hpp"
 #include "tor_screen.hpp"
 
 // ---- layout guards: the structs must match what Nim's C backend emits --------
@@ -393,6 +394,7 @@ int tor_context_destroy(TorContext* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
   (void)tor_comm_destroy(ctx);
+  tor::patches_context_destroyed(ctx);  // the patch table (tor_patches.hip) lives outside the context
   for (int v = 0; v < 2; ++v) {
     ctx->flat[v].release();
     ctx->d_accel[v].release();
@@ -499,6 +501,7 @@ int tor_scene_upload(TorContext* ctx, TorHittableList world) {
   ctx->hitq.n_media = 0;     // ... and no media table (tor_scene_media)
   ctx->hitq.drop_grids();    // ... so no density grids (tor_scene_media_grid); the device is idle (above)
   ctx->hitq.n_textures = 0;  // ... and no texture table (tor_scene_textures)
+  tor::patches_scene_replaced(ctx);  // ... and no patch table (tor_scene_patches)
   ctx->scene_ready = true;
   return TOR_OK;
 }

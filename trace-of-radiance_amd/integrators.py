@@ -11,7 +11,7 @@ import numpy as np
 from . import BOUNCE_MISS, BOUNCE_SCATTERED, MEDIA_COLLIDED, MEDIA_ESCAPED, Camera, MediaMarch, Photons, _Arrays, _Tensors, _is_tensor
 
 INTEGRATORS = ("trace", "trace_direct", "trace_light", "trace_photons", "trace_photon_map", "trace_environment", "trace_media",
-               "trace_media_direct")
+               "trace_media_direct", "trace_patches")
 
 
 def _flags(x, dev):
@@ -269,6 +269,60 @@ def trace(ctx, rays, rng, max_depth=50, sky=None, emission=None, time_range=None
             p.advance(albedo=tex.color)
         else:
             p.advance()
+    return p.finish(color)
+
+
+def trace_patches(ctx, rays, rng, max_depth=50, sky=None, emission=None, patch_emission=None, time_range=None, mode="auto",
+                  mask=None):
+    """trace()'s loop over the spheres AND the patch table (set_patches; a ValueError without one): a floor, walls, a lamp
+    panel, boxes.  att = 1; per step, for the live rays: hit() (with `mask`, if given), then hit_patches(merge=) of the same
+    rays with the same mask -- the closest of spheres and patches, a tie staying with the sphere --; a ray with neither an
+    object nor a patch ends with sky * att; every record with object >= 0 adds att * emission[object], every patch hit adds
+    att * patch_emission[patch]; a patch without a material (-1) ends its path there, with no sky; the rest go through
+    scatter(), att *= attenuation for the rays that scattered, which stay live, in order.  Returns (color, rng, the mode hit()
+    ran).
+
+    With a table that no ray reaches, colours and states are trace()'s with the same arguments, bit for bit (bounce() equals
+    hit() followed by scatter()), and Context.radiance's when sky, emission and patch_emission are None.
+    sky, emission, time_range, mode as for trace(); patch_emission: (n_patches, 3) float64; mask: None, an int or per-ray
+    words, for every step.  rays are not modified; a contiguous CUDA rng tensor is updated in place; numpy operands go through
+    the device and come back as numpy."""
+    import torch
+    if ctx.patches()[0] == 0:
+        raise ValueError("Context.trace_patches: needs a patch table (set_patches)")
+    p = _Paths.from_rays(ctx, "trace_patches", rays, rng, time_range)
+    color, att, work, states = p.color, p.att, p.work, p.entry()
+    if emission is not None:
+        emission = _colours(emission, p.dev)
+    if patch_emission is not None:
+        patch_emission = _colours(patch_emission, p.dev)
+    if mask is not None and not isinstance(mask, (int, np.integer)):
+        mask = torch.as_tensor(np.asarray(mask.cpu() if _is_tensor(mask) else mask).astype(np.int64) & 0xFFFFFFFF).to(p.dev)
+    for step in p.steps(max_depth):
+        idx = p.live.long()
+        r, s = work[idx], states[idx]   # the live rays and their states, compacted: every query of the step answers all of them
+        m = mask if mask is None or isinstance(mask, (int, np.integer)) else mask[idx].to(torch.int32)
+        spheres = ctx.hit(r, None, p.tr, mode, mask=m)
+        p.ran = p.ran or spheres.mode
+        rec = ctx.hit_patches(r, mask=m, merge=spheres)
+        obj, patch = rec.object.long(), rec.patch.long()
+        on_patch, has_obj = patch >= 0, obj >= 0
+        miss = ~on_patch & ~has_obj
+        if sky is None:
+            color[idx] = torch.where(miss[:, None], ctx.sky(r) * att[idx], color[idx])
+        else:
+            p.caller_sky(sky, idx[miss])
+        if emission is not None:
+            color[idx] = color[idx] + torch.where(has_obj[:, None], att[idx] * emission[obj.clamp(min=0)], torch.zeros_like(r[:, 0:3]))
+        if patch_emission is not None:
+            color[idx] = color[idx] + torch.where(on_patch[:, None], att[idx] * patch_emission[patch.clamp(min=0)],
+                                                  torch.zeros_like(r[:, 0:3]))
+        res = ctx.scatter(r, rec, s)   # (a record without an object is scatter()'s miss: nothing drawn, ray and state kept)
+        work[idx], states[idx] = res.rays, res.rng
+        scat = res.status == BOUNCE_SCATTERED
+        on = idx[scat]
+        att[on] = att[on] * res.attenuation[scat]
+        p.live = on.int()
     return p.finish(color)
 
 
