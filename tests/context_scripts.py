@@ -2,11 +2,12 @@
 tests/test_gpu_context_scripts.py on the MI355X).
 
 A script is a list of steps -- setters (upload, set_groups, set_lights, set_environment, set_media, set_media_phase,
-build_photons), queries of every family, renders and the passes of two open accumulations -- as a host that keeps one context alive for a whole animation issues them.  script(name) returns
+build_photons, set_media_grid, set_textures, set_patches), queries of every family, renders and the passes of two open accumulations -- as a host that keeps one context alive for a whole animation issues them.  script(name) returns
 the steps; Model replays them and says, per step, EITHER the state the answer depends on (records, group words or none, light table
-or none, environment map or none, media table with its g or none, photon map or none) OR that the step must be refused (code, a
-word of the message).  The model restates include/tor_render.h, tor_lights.h, tor_env.h, tor_media.h, tor_phase.h, tor_photons.h
-and the Python docstrings (what an upload resets and what it keeps); inputs() draws a
+or none, environment map or none, media table with its g or none, photon map or none, the density grids by medium, texture
+table or none, patch table or none) OR that the step must be refused (code, a
+word of the message).  The model restates include/tor_render.h, tor_lights.h, tor_env.h, tor_media.h, tor_phase.h, tor_photons.h,
+tor_grid.h, tor_texture.h, tor_patches.h and the Python docstrings (what an upload resets and what it keeps); inputs() draws a
 step's operands and answer() hands them to the family's restatement under a given state.  Nothing here judges an answer.
 
 The inputs are shaped so that a stale cache shows: the edited copy of a scene changes the ground sphere's radius and material and
@@ -14,7 +15,21 @@ the centre of object 3, so `probe` rows (segments that end between the two groun
 items on the ground, lamps that include object 3) answer differently under the old records; `movers` rows are aimed at movers at
 times at the far end of the new time range; media rows are aimed at the boundary objects of the media tables, object 3 first
 among them; gather points come from the point sets of the current photon map and of the one before it.  numpy only (the restatements of bounce, scatter, radiance and the samplers draw
-through the oracle's exported generator, which the caller hands in)."""
+through the oracle's exported generator, which the caller hands in).
+
+The grids, the textures and the patches: a grid march's rays are aimed at the boundary object of its medium and a lookup's points
+lie in and around it (MOVED's grid rides a centre that the edit moves); albedo's records are the hit restatement's on ground
+probes, rows aimed at MOVED, back faces and misses (the ground is unbound under texture key A: its material is what the edit
+changes); the patch families' probe rows end on the floor the patch tables lie on, between the original's ground and the edited
+copy's.  hit_patches_merged is ctx.hit_patches(rays, merge=ctx.hit(rays)) issued as ONE step, occluded_patches merges into
+occluded()'s bits where the step says so.  Exempt from the stale-sensitivity rule, with alternatives()'s reasons: hit_patches and
+the unmerged occluded_patches behind an upload (they read no scene record); the merged occluded_patches behind another patch
+table (the original's ground occludes every probe row; the unmerged steps hold the table); albedo behind set_textures behind a
+replacing upload under key B (the ground is bound: key A holds the untextured path); a grid family there when the list before
+holds the medium's boundary unchanged (the mover's); media_density never depends on sigma (a stale sigma cannot show in it: the
+march holds it); `time` and `words` at all of them.  The host integrators (trace_patches, trace_media, trace_media_direct, trace
+with textures, transmittance) stay out of the scripts: they are Python loops over these queries, and their own tests hold them.
+"""
 import copy
 
 import numpy as np
@@ -29,6 +44,8 @@ import deposit_inputs as DI
 import deposit_restatement as D
 import env_inputs as EI
 import env_restatement as ER
+import grid_inputs as GI
+import grid_restatement as GR
 import hit_restatement as H
 import light_inputs as LI
 import light_restatement as LR
@@ -37,12 +54,15 @@ import media_inputs as MI
 import media_restatement as MR
 import nearest_inputs as NI
 import nearest_restatement as N
+import patch_restatement as PT
 import phase_restatement as PR
 import photon_inputs as PI
 import photon_restatement as PH
 import query_regimes as Q
 import radiance_restatement as RR
 import render_regimes as R
+import texture_inputs as TI
+import texture_restatement as TR
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------------------
 # name: (the regime of tests/query_regimes.py it is cut from, how many of its records, edited copy?)
@@ -226,6 +246,142 @@ def photon_map(key, listed=False):
     return _maps[(key, listed)]
 
 
+# ---- density grids, texture tables, patch tables -------------------------------------------------------------------------------------------
+# A grid is attached to a ROLE of the media table, resolved to a medium index under the table that is set: "moved" is the entry
+# that is object MOVED (index 0 of table A, 1 of B), "mover" the entry that is boundaries()[1] (1 of A, 2 of B) -- a medium index
+# kept across set_media names another object --; an int is taken as it is (7: outside every table).
+# name: (dims, the box as multiples of the boundary's |radius| or None for the sphere's bounding cube, every which cell is 0).
+# Every dimension is distinct (a transposed stride shows); G2 has fewer cells than G1 (a smaller grid replaces a larger one); G3 has
+# G1's cell count in another shape (strides kept from the grid before would show).
+GRIDS = {"G1": ((5, 4, 3), (-0.9, -0.5, -0.7, 0.6, 0.8, 0.75), 7), "G2": ((2, 3, 7), None, 5), "G3": ((3, 5, 4), None, 6)}
+BAD_GRIDS = {"dims": "TOR_GRID_MAX_DIM", "nan": "finite and >= 0", "negative": "finite and >= 0"}   # refused grids (no such key is stored)
+ROLES = {"moved": 0, "mover": 1}                         # role: which of boundaries()
+TEXTURES = ("A", "B")
+PATCHES = {"A": 65, "B": 9}                              # one past a wave's worth, and a smaller table behind it
+PATCH_MASK = 0x16                                        # the scalar mask of every third patch step: bits 1, 2 and 4
+_densities, _textures, _patch_tables = {}, {}, {}
+
+
+def medium_of(table, who):
+    """The medium index `who` names under media table `table`: a role's index in the table (None where it lists no such object), or
+    the int itself."""
+    if not isinstance(who, str):
+        return int(who)
+    which = MEDIA[table][0]
+    return which.index(ROLES[who]) if ROLES[who] in which else None
+
+
+def grid_density(key):
+    """(nx, ny, nz) densities of a named grid: distinct per cell, with exact zeros; or a refused one: 1025 x 1 x 1 cells, a NaN, a
+    negative value."""
+    if key not in _densities:
+        if key == "dims":
+            d = np.ones((GR.GRID_MAX_DIM + 1, 1, 1))
+        else:
+            dims, _, zero = GRIDS["G1" if key in BAD_GRIDS else key]
+            d = GI._distinct(dims, sum(dims)).copy()
+            d.reshape(-1)[::zero] = 0.0
+            if key in BAD_GRIDS:
+                d[1, 1, 1] = np.nan if key == "nan" else -0.5
+        d.setflags(write=False)
+        _densities[key] = d
+    return _densities[key]
+
+
+def grid_box(key, name, obj):
+    """The box of a named grid on object `obj` of the named scene: offsets from the centre, six numbers, or None."""
+    box = GRIDS["G1" if key in BAD_GRIDS else key][1]
+    return None if box is None else np.array(box, dtype=np.float64) * abs(records(name)[obj, 9])
+
+
+def _grid(state, medium):
+    """grid_restatement's grid of `medium` under `state` (it rides the centre the table was packed with: state.packed's)."""
+    objects = media_table(state.media, state.scene)[0]
+    key = state.grids[medium]
+    return GR.make_grid(records(state.packed or state.scene), objects, medium, grid_density(key), grid_box(key, state.scene, int(objects[medium])))
+
+
+def texture_table(key, name, bad=None):
+    """(textures as texture_restatement's dicts, binding (n_objects,) int32) of the named table on the named scene.  A: a constant,
+    a world-space checker (cells in units of the scene's scale), a normal-space checker, an 8 x 8 bilinear image and a 4 x 4 nearest
+    image behind it in the atlas; the ground unbound.  B: a constant and a 2 x 2 bilinear image: a smaller table with a smaller
+    atlas; the ground bound.  MOVED wears an image in both.  bad: "long" (one binding too many), "outside" (a binding past the table)."""
+    if (key, name) not in _textures:
+        s, n = scale(name), len(records(name))
+        j = np.arange(n)
+        if key == "A":
+            tex = [TR.constant((0.8, 0.4, 0.1)), TR.checker((0.9, 0.9, 0.2), (0.1, 0.2, 0.7), (1.3 / s, 0.7 / s, 2.1 / s), TR.WORLD),
+                   TR.checker((0.2, 0.7, 0.3), (0.6, 0.1, 0.5), (3.0, 2.0, 5.0), TR.NORMAL), TR.image(TI.ramp(8), TR.BILINEAR),
+                   TR.image(TI.ramp(4, 100.0), TR.NEAREST)]
+            binding = np.array([-1, 0, 1, 3, 2, 4, -1], dtype=np.int32)[j % 7]
+            binding[0], binding[MOVED] = -1, 3
+        else:
+            tex = [TR.constant((0.3, 0.6, 0.9)), TR.image(TI.ramp(2, 7.0), TR.BILINEAR)]
+            binding = np.array([-1, 0, 1], dtype=np.int32)[j % 3]
+            binding[0], binding[MOVED] = 0, 1
+        binding.setflags(write=False)
+        _textures[(key, name)] = (tex, binding)
+    tex, binding = _textures[(key, name)]
+    if bad == "long":
+        binding = np.concatenate([binding, [-1]]).astype(np.int32)
+    if bad == "outside":
+        binding = binding.copy()
+        binding[1] = len(tex)
+    return tex, binding
+
+
+def floor_height(name, x, z):
+    """The surface the patch tables lie on and the patch families' probe rows end at: the sphere half way between the ground and
+    the edited copy's (the same from either scene); without a ground, the plane one scale below the objects."""
+    recs = records(name)
+    x, z = np.asarray(x, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    if ground(recs) == 0:
+        return _ground_height(name, recs, x, z, _probe_radius(name, recs))
+    return np.full(np.broadcast(x, z).shape, _others_box(records(name[:-2] if name.endswith("_e") else name))[0][1] - scale(name))
+
+
+def patch_region(name):
+    """(x0, x1, z0, z1) the probe rows are drawn over: the box of the ORIGINAL scene's objects (the same from a scene and its copy)."""
+    lo, hi = _others_box(records(name[:-2] if name.endswith("_e") else name))
+    return float(lo[0]), float(hi[0]), float(lo[2]), float(hi[2])
+
+
+def patch_table(key, name, bad=None, of=None):
+    """The named patch table on the named scene, as patch_restatement's patches: A tiles the lower 60 % of the region's x extent
+    8 x 8 (and one more patch across its middle), B the upper 60 % 3 x 3 -- they share no patch --; every patch fills 90 % of its
+    tile, every third is a triangle (half of that).  A patch lies along the floor (floor_height at three of its corners), 0.05
+    scales above it where the index is 2 of 3 -- between the two grounds: the original's ground wins a merge, in the edited copy
+    the patch does -- and 0.3 above it otherwise -- above both grounds: the patch wins in either scene.  Materials by
+    turns -1, 0 (the ground), MOVED; visibility words one bit of five, every 7th every group, every 11th none.  bad = "material":
+    patch 1 wears the last object of scene `of`, or (of None) one past this scene's last."""
+    if (key, name) not in _patch_tables:
+        s = scale(name)
+        x0, x1, z0, z1 = patch_region(name)
+        w = x1 - x0
+        (xa, xb), k = ((x0, x0 + 0.6 * w), 8) if key == "A" else ((x0 + 0.4 * w, x1), 3)
+        dx, dz = (xb - xa) / k, (z1 - z0) / k
+        tiles = [(xa + a * dx, z0 + b * dz, dx, dz) for a in range(k) for b in range(k)]
+        if key == "A":
+            tiles.append((xa + 0.25 * (xb - xa), z0 + 0.25 * (z1 - z0), 0.5 * (xb - xa), 0.5 * (z1 - z0)))
+        table = []
+        for j, (tx, tz, ex, ez) in enumerate(tiles):
+            up = (0.05 if j % 3 == 2 else 0.3) * s + (0.1 * s if j == 64 else 0.0)
+            cx, cz = (tx + 0.05 * ex, tx + 0.95 * ex), (tz + 0.05 * ez, tz + 0.95 * ez)
+            q = np.array([cx[0], float(floor_height(name, cx[0], cz[0])) + up, cz[0]])
+            pu = np.array([cx[1], float(floor_height(name, cx[1], cz[0])) + up, cz[0]])
+            pv = np.array([cx[0], float(floor_height(name, cx[0], cz[1])) + up, cz[1]])
+            groups = Q.ALL if j % 7 == 0 else 0 if j % 11 == 5 else 1 << (j % 5)
+            material = (-1, 0, MOVED)[(j // 3) % 3]
+            table.append(PT.triangle(q, pu, pv, material, groups) if j % 3 == 1 else PT.quad(q, pu - q, pv - q, material, groups))
+        assert len(table) == PATCHES[key]
+        _patch_tables[(key, name)] = table
+    table = _patch_tables[(key, name)]
+    if bad == "material":
+        table = list(table)
+        table[1] = dict(table[1], material=len(records(of)) - 1 if of else len(records(name)))
+    return table
+
+
 # ---- families ---------------------------------------------------------------------------------------------------------------------------
 RAY_FAMILIES = ("hit", "occluded", "crossings", "bounce", "radiance")
 BLOCK_FAMILIES = RAY_FAMILIES + ("nearest",)            # they take a mode and a time range: `bnd` and what hangs on it
@@ -234,12 +390,15 @@ LIGHT_FAMILIES = ("sample_lights", "light_pdf", "emit_lights")
 ENV_FAMILIES = ("environment", "sample_environment")
 MEDIA_FAMILIES = ("march_media", "scatter_media", "sample_phase", "phase")   # they read the media table
 PHASE_FAMILIES = ("sample_phase", "phase")              # ... and word 15 of it
-NEW_FAMILIES = ("gather_photons",) + MEDIA_FAMILIES + ("uniform",)
+GRID_FAMILIES = ("march_media_grid", "media_density")    # they read ONE medium's density grid (and the media table under it)
+PATCH_FAMILIES = ("hit_patches", "hit_patches_merged", "occluded_patches")
+TABLE_FAMILIES = GRID_FAMILIES + ("albedo",) + PATCH_FAMILIES   # the grids, the texture table, the patch table
+NEW_FAMILIES = ("gather_photons",) + MEDIA_FAMILIES + ("uniform",) + TABLE_FAMILIES
 SCENE_FREE = ENV_FAMILIES + ("connect_camera", "deposit", "gather_photons", "uniform")   # they read no scene: no upload can change their answer
 QUERY_FAMILIES = BLOCK_FAMILIES + ("scatter", "bsdf") + MASKED + LIGHT_FAMILIES + ENV_FAMILIES + ("connect_camera", "deposit") + NEW_FAMILIES
 FAMILIES = QUERY_FAMILIES + ("render",)
 ACCUMULATIONS = ("progressive", "pixel_progressive")
-SLOW = ("bounce", "bounce_m", "scatter", "radiance", "sample_phase")    # their restatements loop in Python: 64 rays
+SLOW = ("bounce", "bounce_m", "scatter", "radiance", "sample_phase", "march_media_grid")    # their restatements loop in Python: 64 rays
 BATCHES = (1, 63, 64, 65, 257)
 MODES = ("auto", "brute", "blocks")
 TIME_RANGES = ((0.0, 1.0), (0.5, 0.5), (-3.0, 0.5), None)
@@ -259,7 +418,9 @@ EVENTS = UPLOAD_EVENTS + ("time", "words")
 # which setter writes the table a family reads (the `setter` / `behind_queued_work` pair)
 SETTER_OF = dict([(f, ("set_lights",)) for f in LIGHT_FAMILIES] + [(f, ("set_environment",)) for f in ENV_FAMILIES]
                  + [(f, ("set_media", "set_media_phase") if f in PHASE_FAMILIES else ("set_media",)) for f in MEDIA_FAMILIES]
-                 + [("gather_photons", ("build_photons",))])
+                 + [("gather_photons", ("build_photons",))] + [(f, ("set_media_grid",)) for f in GRID_FAMILIES]
+                 + [("albedo", ("set_textures",))] + [(f, ("set_patches",)) for f in PATCH_FAMILIES])
+TABLE_SETTERS = ("set_media_grid", "set_textures", "set_patches")
 
 
 def transition_table():
@@ -276,6 +437,18 @@ def transition_table():
     t += [(f, "media_table") for f in MEDIA_FAMILIES] + [(f, "phase_g") for f in PHASE_FAMILIES] + [("gather_photons", "photon_map")]
     t += [(f, "media_after_upload") for f in MEDIA_FAMILIES] + [("gather_photons", "map_kept")]
     t += [("new_host_twin", "smaller_after_device"), ("setter", "behind_queued_work")]
+    # the density grids, the texture table and the patch table (the five events of every family come with FAMILIES above).
+    # grid: another grid on the medium since the family last ran; grid_removed: the medium's grid removed (refused); grids_dropped:
+    # a set_media since (the grid march refused, the homogeneous march counts the medium again); grids_kept: behind set_media_phase,
+    # set_lights or a cache-hit upload; grid_after_upload: set_media and set_media_grid after a replacing upload (the grid rides the
+    # new centre); (march_media, grid): the homogeneous march behind a grid set and behind one removed.  texture_table /
+    # patch_table: the other key; *_after_upload: the table set again behind a replacing upload; *_kept: behind another setter or a
+    # cache-hit upload.  A host twin of these families behind a larger device call; each of the three setters behind queued work.
+    t += [(f, e) for f in GRID_FAMILIES for e in ("grid", "grid_removed", "grids_dropped", "grids_kept", "grid_after_upload")]
+    t += [("march_media", "grid"), ("march_media", "grid_removed"), ("march_media", "grids_dropped")]
+    t += [("albedo", e) for e in ("texture_table", "textures_after_upload", "textures_kept")]
+    t += [(f, e) for f in PATCH_FAMILIES for e in ("patch_table", "patches_after_upload", "patches_kept")]
+    t += [("table_host_twin", "smaller_after_device")] + [(op, "behind_queued_work") for op in TABLE_SETTERS]
     return t
 
 
@@ -283,9 +456,12 @@ def transition_table():
 class State:
     """What an answer can depend on: names and keys, resolved by records(), words(), light_table(), env_map()."""
 
-    def __init__(self, scene=None, groups=None, lights=None, env=None, media=None, phase=None, photons=None):
+    def __init__(self, scene=None, groups=None, lights=None, env=None, media=None, phase=None, photons=None, grids=None, textures=None,
+                 patches=None):
         self.scene, self.groups, self.lights, self.env = scene, groups, lights, env
         self.media, self.phase, self.photons = media, phase, photons   # a key of MEDIA, a key of G, (a key of PHOTON_MAPS, listed?)
+        self.grids = dict(grids or {})                    # medium index: a key of GRIDS (never changed in place: but() replaces it)
+        self.textures, self.patches = textures, patches   # a key of TEXTURES, a key of PATCHES
         self.packed = None                                # alternatives() alone: the scene whose records a stale table was packed from
 
     def but(self, **kw):
@@ -295,10 +471,29 @@ class State:
         return s
 
     def key(self):
-        return (self.scene, self.groups, self.lights, self.env, self.media, self.phase, self.photons)
+        return (self.scene, self.groups, self.lights, self.env, self.media, self.phase, self.photons, tuple(sorted(self.grids.items())),
+                self.textures, self.patches)
 
 
 REFUSED = "refused"
+
+
+def table_refusal(step, s):
+    """The refusal of a query of TABLE_FAMILIES under state s, in the headers' order, or None: no scene; then (grids) no media
+    table, a medium outside it, a medium without a grid; (albedo) no texture table; (patches) no patch table."""
+    f = step["family"]
+    if s.scene is None:
+        return (-1, "no scene")
+    if f in GRID_FAMILIES:
+        if s.media is None:
+            return (-1, "media table")
+        m = medium_of(s.media, step["who"])
+        if m is None or not 0 <= m < len(MEDIA[s.media][0]):
+            return (-1, "outside the media table")
+        return None if m in s.grids else (-1, "has no density grid")
+    if f == "albedo":
+        return None if s.textures is not None else (-1, "no texture table")
+    return None if s.patches is not None else (-1, "no patch table")
 
 
 class Expect:
@@ -325,7 +520,21 @@ class Model:
     before the first upload ("no scene") and without a table ("media table").  tor_photons_build_device (tor_photons.h): the map
     belongs to the context and survives every upload, a build replaces it and needs no scene; a gather before any build is refused
     ("no photon map"), one with normals on a map built without directions too ("without directions"; a build of no photons holds
-    nothing that normals could miss).  tor_rng_uniform_device needs nothing."""
+    nothing that normals could miss).  tor_rng_uniform_device needs nothing.
+
+    tor_scene_media_grid (include/tor_grid.h): refused with no scene, an empty media table ("media table"), a medium outside the table
+    ("outside the media table"), bad dimensions ("TOR_GRID_MAX_DIM"), a density that is NaN or negative ("finite and >= 0"), in
+    that order; (0, 0, 0) removes that medium's grid only, a second grid on a medium replaces the first.  EVERY accepted
+    tor_scene_media call -- the empty table included -- drops every grid, and so does a replacing upload; a refused table, a
+    cache-hit and a refused upload, tor_scene_media_phase, the lights, the environment, the words, the photon map, the textures
+    and the patches keep them.  The grid march and the density lookup are refused with no scene, no media table, a medium outside
+    it and a medium without a grid ("has no density grid"); a medium with a grid takes no part in the homogeneous march.
+    tor_scene_textures (tor_texture.h): refused with no scene, a binding whose length is not the scene's count ("n_objects must
+    be"), a binding outside the table ("is outside"); an empty table clears it, as a replacing upload does; every other setter
+    leaves it alone.  The query is refused with no scene, then with no table ("no texture table").  tor_scene_patches
+    (tor_patches.h): refused with no scene and with a material outside [-1, n_objects) ("material outside"); an empty table clears
+    it, as a replacing upload does; every other setter leaves it alone.  The two queries are refused with no scene, then with no
+    table ("no patch table")."""
 
     def __init__(self):
         self.state = State()
@@ -339,6 +548,11 @@ class Model:
     def _note(self, event, value, families=FAMILIES + ACCUMULATIONS):
         for f in families:
             self.since.setdefault(f, {})[event] = value
+
+    def _kept(self, op, families=TABLE_FAMILIES):
+        """An accepted setter that must leave the tables of `families` alone: the family's next step could tell."""
+        for f in families:
+            self.since.setdefault(f, {}).setdefault("kept", set()).add(op)
 
     def effective_range(self, step, times):
         """The (lo, hi) the library builds block bounds for: the step's range, or the finite min / max of the operand's times."""
@@ -365,6 +579,7 @@ class Model:
             for ev in self.since.values():               # (what an earlier upload left pending is superseded)
                 ev.pop("cache_hit", None), ev.pop("refused", None)
             self._note("replace", s.scene)
+            self._note("before", s, TABLE_FAMILIES)      # (what the upload cleared: the grids, the textures, the patches)
             self.state = State(step["scene"], None, None, s.env, None, None, s.photons)
             return Expect(step, self.state, None, {})
         if op == "set_media":
@@ -374,7 +589,51 @@ class Model:
                 return Expect(step, s, (-1, BAD_MEDIA[step["bad"]]), {})
             self._note("media_table", s.media, MEDIA_FAMILIES)
             self._note("phase_g", s.phase, PHASE_FAMILIES)   # (every table starts isotropic)
-            self.state = s.but(media=step["table"], phase=None)
+            if s.grids:                                  # ... and without a grid (the first drop since a family ran is the one that counts)
+                for f in GRID_FAMILIES + ("march_media",):
+                    self.since.setdefault(f, {}).setdefault("grids_dropped", (s.media, dict(s.grids)))
+            self._kept(op, ("albedo",) + PATCH_FAMILIES)
+            self.state = s.but(media=step["table"], phase=None, grids={})
+            return Expect(step, self.state, None, {})
+        if op == "set_media_grid":
+            if s.scene is None:
+                return Expect(step, s, (-1, "no scene"), {})
+            if s.media is None:
+                return Expect(step, s, (-1, "media table"), {})
+            m = medium_of(s.media, step["who"])
+            if m is None or not 0 <= m < len(MEDIA[s.media][0]):
+                return Expect(step, s, (-1, "outside the media table"), {})
+            if step["grid"] in BAD_GRIDS:
+                return Expect(step, s, (-1, BAD_GRIDS[step["grid"]]), {})
+            for f in GRID_FAMILIES + ("march_media",):   # (the key the family last saw on that medium)
+                self.since.setdefault(f, {}).setdefault("grid", {}).setdefault(m, s.grids.get(m))
+            self._kept(op, ("albedo",) + PATCH_FAMILIES)
+            grids = {k: v for k, v in s.grids.items() if k != m}
+            if step["grid"] is not None:
+                grids[m] = step["grid"]
+            self.state = s.but(grids=grids)
+            return Expect(step, self.state, None, {})
+        if op == "set_textures":
+            if s.scene is None:
+                return Expect(step, s, (-1, "no scene"), {})
+            n = len(records(s.scene))
+            if step.get("bad") == "long" or (step.get("count_of") and len(records(step["count_of"])) != n):
+                return Expect(step, s, (-1, "n_objects must be"), {})
+            if step.get("bad") == "outside":
+                return Expect(step, s, (-1, "is outside"), {})
+            self._note("texture_table", s.textures, ("albedo",))
+            self._kept(op, GRID_FAMILIES + PATCH_FAMILIES)
+            self.state = s.but(textures=step["table"])
+            return Expect(step, self.state, None, {})
+        if op == "set_patches":
+            if s.scene is None:
+                return Expect(step, s, (-1, "no scene"), {})
+            n = len(records(s.scene))
+            if step.get("bad") == "material" and (len(records(step["of"])) - 1 if step.get("of") else n) >= n:
+                return Expect(step, s, (-1, "material outside"), {})
+            self._note("patch_table", s.patches, PATCH_FAMILIES)
+            self._kept(op, GRID_FAMILIES + ("albedo",))
+            self.state = s.but(patches=step["table"])
             return Expect(step, self.state, None, {})
         if op == "set_media_phase":
             if s.scene is None:
@@ -384,21 +643,26 @@ class Model:
             if step.get("wrong_count"):
                 return Expect(step, s, (-1, "n_media"), {})
             self._note("phase_g", s.phase, PHASE_FAMILIES)
+            self._kept(op)
             self.state = s.but(phase=step["g"])
             return Expect(step, self.state, None, {})
         if op == "build_photons":
             self._note("photon_map", s.photons, ("gather_photons",))
+            self._kept(op)
             self.state = s.but(photons=(step["map"], bool(step["listed"])))
             return Expect(step, self.state, None, {})
         if op == "set_groups":
+            self._kept(op)
             self.state = s.but(groups=step["words"])
             return Expect(step, self.state, None, {})
         if op == "set_lights":
             self._note("table", s.lights, LIGHT_FAMILIES)
+            self._kept(op)
             self.state = s.but(lights=step["table"])
             return Expect(step, self.state, None, {})
         if op == "set_environment":
             self._note("map", s.env, ENV_FAMILIES)
+            self._kept(op)
             self.state = s.but(env=step["map"])
             return Expect(step, self.state, None, {})
         family = step["family"]
@@ -420,6 +684,8 @@ class Model:
             return Expect(step, s, (-1, "no photon map"), events)
         if family == "gather_photons" and step.get("normals") and not photon_map(*s.photons)["has_dir"]:
             return Expect(step, s, (-1, "without directions"), events)
+        if family in TABLE_FAMILIES and table_refusal(step, s) is not None:
+            return Expect(step, s, table_refusal(step, s), events)
         if takes_mode(family) and step["mode"] != "brute":
             now = self.effective_range(step, times)
             if self.block_range is not None and now != self.block_range:
@@ -447,6 +713,83 @@ def _times(oracle, step, state):
     return x["points"][:, 3] if base(step["family"]) == "nearest" else x["rays"][:, 6]
 
 
+def _table_alternative(e, event, old):
+    """(the stale state | REFUSED | None, why) of one event at a family of TABLE_FAMILIES, or of a grid event at march_media.
+
+    replace, the table gone: the state the upload found -- its grids, textures, patches would still answer.  replace, the table
+    set again since: the grid families under a grid that rides the PREVIOUS records' centre (state.packed); albedo under the
+    previous records (the untextured path's cold records; under key B the ground is bound and no row reads a record the edit
+    changes: key A holds that path); the merged patch queries under the previous records (the sphere records a merge starts from).
+    cache_hit / refused / kept: the table cleared, had the upload or the other setter been taken for one that clears it.  grid:
+    the keys the family last saw on the media set since.  grids_dropped: the grids before the set_media, at their medium INDICES
+    (a stale grid_mask names whatever object the new table lists there).  texture_table / patch_table: the previous key.
+    Exempt: hit_patches and the unmerged occluded_patches at `replace` (they read no scene record); the merged occluded_patches at
+    patch_table (in a scene with its original ground the ground occludes every probe row whatever the table; unmerged steps hold
+    it); `time` and `words` (these families read neither)."""
+    f, s, st = e.step["family"], e.state, e.step
+    merged = f == "hit_patches_merged" or (f == "occluded_patches" and bool(st.get("merge")))
+    if event in ("time", "words"):
+        return None, "reads neither the block bounds nor the words"
+    if f == "march_media":                               # a grid event at the homogeneous march: which media it leaves out
+        if s.media is None or e.refuse is not None:
+            return None, "no table either way"
+        n = len(MEDIA[s.media][0])
+        then = {**s.grids, **old} if event == "grid" else {m: k for m, k in old[1].items() if m < n}
+        then = {m: k for m, k in then.items() if k is not None}
+        return (None, "the same media have grids") if set(then) == set(s.grids) else (s.but(grids=then), "")
+    if event == "replace":
+        before = e.events.get("before")
+        if e.refuse is not None:
+            if before is None or before.scene is None:
+                return None, "there was no scene before"
+            stale = s.but(media=before.media, grids=before.grids, textures=before.textures, patches=before.patches)
+        elif old is None:
+            return None, "there was no scene before"
+        elif f in GRID_FAMILIES:
+            obj = int(media_table(s.media, s.scene)[0][medium_of(s.media, st["who"])])
+            if len(records(old)) <= int(media_table(s.media, s.scene)[0].max()):
+                return None, "the previous list does not hold these objects"
+            if (records(old)[obj] == records(s.scene)[obj]).all():
+                return None, "the previous list holds this boundary as it is"
+            stale = s.but(packed=old)
+        elif f == "albedo" and (s.textures != "A" or ground(records(s.scene)) != 0):
+            return None, "under key B (or without a ground) no row reads a record that the edit changes"
+        elif f in PATCH_FAMILIES and not merged:
+            return None, "reads no scene record"
+        else:
+            stale = s.but(packed=old)
+    elif event in ("cache_hit", "refused", "kept"):
+        stale = s.but(grids={}) if f in GRID_FAMILIES else s.but(textures=None) if f == "albedo" else s.but(patches=None)
+    elif event == "grid":
+        then = {m: k for m, k in {**s.grids, **old}.items() if k is not None}
+        m = medium_of(s.media, st["who"]) if s.media else None
+        if then.get(m) == s.grids.get(m):
+            return None, "this medium's grid is set again to what it was"
+        stale = s.but(grids=then)
+    elif event == "grids_dropped":
+        n = len(MEDIA[s.media][0]) if s.media else 0
+        stale = s.but(grids={m: k for m, k in old[1].items() if m < n})
+        m = medium_of(s.media, st["who"]) if s.media else None
+        if stale.grids.get(m) == s.grids.get(m):
+            return None, "this medium's grid is back"
+    elif event == "texture_table":
+        if old == s.textures:
+            return None, "set again to what it was"
+        stale = s.but(textures=old)
+    elif event == "patch_table":
+        if old == s.patches:
+            return None, "set again to what it was"
+        if f == "occluded_patches" and merged:
+            return None, "merged into the spheres' bits: the unmerged steps hold the table"
+        stale = s.but(patches=old)
+    else:
+        return None, "not an event of this family"
+    then = table_refusal(st, stale)
+    if then is not None:
+        return (None, "refused either way") if e.refuse is not None else (REFUSED, "")
+    return stale, ""
+
+
 def alternatives(e):
     """[(event, the state whose answer the step's must differ from | REFUSED | None with the reason it is exempt)] of an Expect.
 
@@ -461,10 +804,16 @@ def alternatives(e):
     the table set again -- the march under a table packed from the PREVIOUS records (the scatter, the sampler and the evaluation
     read sigma, albedo and g alone); cache_hit / refused -- REFUSED, had the upload cleared the table; media_table / phase_g /
     photon_map -- the previous table, g, map (REFUSED where there was none, or where the previous map would refuse the normals).
-    `uniform` reads nothing and is exempt from everything; `gather_photons` reads no scene and is exempt from the upload events."""
+    `uniform` reads nothing and is exempt from everything; `gather_photons` reads no scene and is exempt from the upload events.
+
+    The grid, texture and patch families, and the grid events at march_media: _table_alternative()."""
     f, s, out = e.step["family"], e.state, []
     for event, old in e.events.items():
-        if event in UPLOAD_EVENTS and f in SCENE_FREE:
+        if event == "before":                            # (the state a replacing upload found: `replace` reads it)
+            continue
+        if f in TABLE_FAMILIES or event in ("grid", "grids_dropped"):
+            out.append((event,) + _table_alternative(e, event, old))
+        elif event in UPLOAD_EVENTS and f in SCENE_FREE:
             out.append((event, None, "reads no scene"))
         elif f == "uniform":
             out.append((event, None, "reads nothing"))
@@ -747,6 +1096,89 @@ def _gather_inputs(step, x):
         x["radius"] = rng.uniform(0.1, 0.375, n)          # (0.4 .. 1.5 of the larger R: some are clamped to the map's)
 
 
+def _aim(rng, recs, chosen, t, inside):
+    """Origins and directions of rows aimed at the objects `chosen` (indices) at times t: two to three radii out (inside: within
+    0.8 radii), towards a point within 0.3 radii of the centre, of any length."""
+    n = len(t)
+    rec = recs[chosen]
+    c, r = _centres(rec, t), np.abs(rec[:, 9])
+    o = c + _unit(rng, n) * (r * np.where(inside, rng.uniform(0.0, 0.8, n), rng.uniform(2.0, 3.0, n)))[:, None]
+    d = (c + _unit(rng, n) * (0.3 * r)[:, None]) - o
+    return o, d / np.linalg.norm(d, axis=1, keepdims=True) * (r * rng.uniform(0.3, 3.0, n))[:, None]
+
+
+def _grid_inputs(step, state, x):
+    """The grid march: rays aimed at the boundary object of the step's medium, every fourth origin inside it, tau finite and (one
+    in five) infinite.  The lookup: points within 0.55 (every other row), 1.0 and 1.3 radii of the boundary's centre at the point's
+    time, on every axis -- inside and outside the sphere and the box.  Without a scene, a table or such a medium: aimed at MOVED (the call is refused)."""
+    n, seed, rng = int(step["n"]), int(step["seed"]), _rng(step, 6)
+    if state.scene is None:
+        rays = np.ascontiguousarray(MI._rays(seed, n))
+        x.update({"rays": rays, "tau": MI._taus(seed, n)} if step["family"] == "march_media_grid" else {"points": np.ascontiguousarray(rays[:, [0, 1, 2, 6]])})
+        return
+    recs = records(state.scene)
+    m = medium_of(state.media, step["who"]) if state.media is not None else None
+    obj = int(media_table(state.media, state.scene)[0][m]) if m is not None and 0 <= m < len(MEDIA[state.media][0]) else MOVED
+    t = rng.uniform(0.0, 1.0, n)
+    if step["family"] == "march_media_grid":
+        o, d = _aim(rng, recs, np.full(n, obj), t, np.arange(n) % 4 == 2)
+        x["rays"], x["tau"] = np.ascontiguousarray(np.concatenate([o, d, t[:, None]], axis=1)), MI._taus(seed, n) * 2.0
+    else:
+        c = _centres(recs[np.full(n, obj)], t)
+        reach = np.array([0.55, 1.3, 0.55, 1.0])[np.arange(n) % 4] * abs(recs[obj, 9])   # (0.55: every such point lies inside the sphere)
+        x["points"] = np.ascontiguousarray(np.concatenate([c + rng.uniform(-1.0, 1.0, (n, 3)) * reach[:, None], t[:, None]], axis=1))
+
+
+def _albedo_inputs(step, name, x):
+    """Hit records of the hit restatement on rows that, of every eight, probe the ground three times (0, 2, 4: vertical rays from
+    above it; without a ground they aim at objects), aim at MOVED twice (1, 5), start inside an object once (3: a back face), aim at
+    an object once (6) and point away from the scene once (7: a record with no such object)."""
+    n, rng = int(step["n"]), _rng(step, 7)
+    recs = records(name)
+    i = np.arange(n)
+    pool = np.flatnonzero(placeable(recs))
+    chosen = np.where(np.isin(i % 8, (1, 5)), MOVED, pool[rng.integers(0, len(pool), n)])
+    t = rng.uniform(0.0, 1.0, n)
+    o, d = _aim(rng, recs, chosen, t, i % 8 == 3)
+    away = i % 8 == 7
+    d[away] = -d[away]
+    if ground(recs) == 0:
+        probe = np.flatnonzero(np.isin(i % 8, (0, 2, 4)))
+        lo, hi = _others_box(recs)
+        px, pz = rng.uniform(lo[0], hi[0], probe.size), rng.uniform(lo[2], hi[2], probe.size)
+        h = rng.uniform(0.5, 2.0, probe.size) * scale(name)
+        o[probe] = np.stack([px, _ground_height(name, recs, px, pz, abs(recs[0, 9])) + h, pz], axis=1)
+        d[probe] = np.stack([np.zeros(probe.size), -h, np.zeros(probe.size)], axis=1)
+    ok = np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1)
+    o[~ok], d[~ok] = 0.0, 1.0
+    x["hits"] = np.ascontiguousarray(H.world_hit(recs, np.concatenate([o, d, t[:, None]], axis=1)))
+
+
+def _patch_inputs(step, name, x):
+    """rays and t_range: of every eight rows seven probe the floor the patch tables lie on (vertical segments from 0.5 to 2 scales
+    above floor_height down to it, range (0.001, 1): a patch, the original's ground or nothing stops them) and one is
+    query_regimes' ray; the mask by the step: none, PATCH_MASK, or one word of query_regimes.ray_masks per ray."""
+    n, rng = int(step["n"]), _rng(step, 8)
+    recs = records(name)
+    rays, tr = Q.rays(recs, max(n, 8), int(step["seed"]))
+    rays, tr = np.array(rays[:n]), np.array(tr[:n])
+    probe = np.flatnonzero(np.arange(n) % 8 != 7)
+    x0, x1, z0, z1 = patch_region(name)
+    px, pz = rng.uniform(x0, x1, probe.size), rng.uniform(z0, z1, probe.size)
+    h = rng.uniform(0.5, 2.0, probe.size) * scale(name)
+    rays[probe, 0], rays[probe, 1], rays[probe, 2] = px, floor_height(name, px, pz) + h, pz
+    rays[probe, 3], rays[probe, 4], rays[probe, 5] = 0.0, -h, 0.0
+    tr[probe] = (0.001, 1.0)
+    x["rays"], x["t_range"] = np.ascontiguousarray(rays), np.ascontiguousarray(tr)
+    if step.get("masks") == "rays":
+        x["masks"] = Q.ray_masks(n, int(step["seed"])).copy()
+
+
+def patch_mask(step, x):
+    """The mask operand of a patch step: None, the scalar, or the per-ray words."""
+    return {None: None, "scalar": PATCH_MASK, "rays": x.get("masks")}[step.get("masks")]
+
+
 def inputs(oracle, step, state):
     """The operands of a query, render or pass step under `state`, as numpy arrays: drawn from the step's seed, the scene's
     records and (scatter, bsdf) the restatement's own hits."""
@@ -796,6 +1228,15 @@ def inputs(oracle, step, state):
         _gather_inputs(step, x)
     elif f == "uniform":
         x["states"] = _states(n, seed)
+    elif f in GRID_FAMILIES:
+        _grid_inputs(step, state, x)
+    elif f in TABLE_FAMILIES and name is None:           # (refused: no scene)
+        x["rays"], x["t_range"] = np.ascontiguousarray(MI._rays(seed, n)), np.tile([0.001, 1.0], (n, 1))
+        x["hits"] = TR.make_hits(np.zeros((n, 3)), np.zeros((n, 3)), -1, 0)
+    elif f == "albedo":
+        _albedo_inputs(step, name, x)
+    elif f in PATCH_FAMILIES:
+        _patch_inputs(step, name, x)
     elif f in ("render",) + ACCUMULATIONS:
         recs = records(name)                            # (the camera looks at the objects: a ground sphere does not stretch its box)
         x["camera"] = R.camera(regime(name), "outside", recs[1:] if ground(recs) == 0 else recs)
@@ -871,8 +1312,9 @@ def answer(oracle, step, x, state):
         return {q: w[q] for q in ("sums", "moments", "counts")}
     if f in MEDIA_FAMILIES:
         mrecs, objects, sigma, albedo, gs = _media_of(state)
-        if f == "march_media":
-            w = MR.march(mrecs, objects, sigma, x["rays"], x["tau"])
+        if f == "march_media":                          # (a medium with a grid takes no part: grid_restatement's sub-table)
+            w = GR.march_with_grids(mrecs, objects, sigma, sorted(state.grids), x["rays"], x["tau"]) if state.grids else \
+                MR.march(mrecs, objects, sigma, x["rays"], x["tau"])
             return {q: w[q] for q in ("status", "t", "depth", "rho", "active")}
         if f == "scatter_media":
             w = MR.scatter(oracle, sigma, albedo, x["rays"], x["t"], x["active"], x["states"])
@@ -884,6 +1326,27 @@ def answer(oracle, step, x, state):
     if f == "uniform":
         u, st = MR.uniforms(oracle, x["states"], int(step["draws"]))
         return {"u": u, "states": st}
+    if f in GRID_FAMILIES:
+        mrecs, objects, sigma, _, _ = _media_of(state)
+        grid = _grid(state, medium_of(state.media, step["who"]))
+        if f == "march_media_grid":
+            w = GR.march(mrecs, objects, sigma, grid, x["rays"], x["tau"])
+            return {q: w[q] for q in ("status", "t", "depth", "rho", "active", "cell")}
+        cell, value = GR.density(mrecs, objects, grid, x["points"])
+        return {"cell": cell, "density": value}
+    if f == "albedo":
+        tex, binding = texture_table(state.textures, state.scene)
+        return TR.evaluate(records(state.packed or state.scene), tex, binding, x["hits"])
+    if f in PATCH_FAMILIES:
+        table, mask = patch_table(state.patches, state.scene), patch_mask(step, x)
+        srecs = records(state.packed or state.scene)
+        if f == "occluded_patches":
+            start = (H.fields(H.world_hit(srecs, x["rays"], x["t_range"]))["object"] >= 0).astype(np.int32) if step.get("merge") else None
+            return {"occluded": PT.occluded(table, x["rays"], x["t_range"], mask, merge=start)}
+        w = PT.merge(srecs, table, x["rays"], x["t_range"], mask) if f == "hit_patches_merged" else PT.hit(table, x["rays"], x["t_range"], mask)
+        out = _hit_fields(w["raw"])
+        out.update(patch=w["patch"], uv=w["uv"])
+        return out
     if f == "gather_photons":
         m = photon_map(*state.photons)
         w = PH.gather(m["stored"], x["points"], x.get("normals"), x.get("radius"), step["kernel"], 1.0)
@@ -988,6 +1451,18 @@ class _Builder:
         t = self.turns["build_photons"] = self.turns.get("build_photons", 0) + 1
         self.add(op="build_photons", map=key, host=bool(t % 2), listed=bool((t // 2) % 2))
 
+    def grid(self, who, key):
+        """set_media_grid: a named grid (or one of BAD_GRIDS) on the medium a role names, or on the int itself; None removes it."""
+        self.add(op="set_media_grid", who=who, grid=key)
+
+    def textures(self, key, bad=None, count_of=None):
+        """set_textures: a named table or None (the empty one); bad: "long", "outside"; count_of: the binding built for that scene."""
+        self.add(op="set_textures", table=key, bad=bad, count_of=count_of)
+
+    def patches(self, key, bad=None, of=None):
+        """set_patches: a named table or None (the empty one); bad = "material" (of: a material valid for that scene)."""
+        self.add(op="set_patches", table=key, bad=bad, of=of)
+
     def _draw(self, values):
         return values[int(self.rng.integers(len(values)))]
 
@@ -1029,6 +1504,19 @@ class _Builder:
             relisted = cur is not None and old is not None and cur[0] == old[0]   # (the same photons through a list: half are gone)
             step["normals"] = bool((t // 2) % 2) and (has_dir or not pending) and not relisted   # (a refusal settles nothing pending)
             step["radius"], step["kernel"] = t % 3 == 0, ("constant", "epanechnikov")[(t // 4) % 2]
+        if family in GRID_FAMILIES:                      # by turns the roles whose medium has a grid; one set or dropped since first
+            st, t = m.state, self.turns[family]
+            has = [w for w in ROLES if st.media and medium_of(st.media, w) in st.grids]
+            was = {**pending.get("grids_dropped", (None, {}))[1], **pending.get("grid", {})}
+            first = [w for w in ROLES if st.media and medium_of(st.media, w) in was and was[medium_of(st.media, w)] != st.grids.get(medium_of(st.media, w))]
+            if "replace" in pending and "moved" in has:  # (the edit moves MOVED's centre, not the mover's)
+                first = ["moved"]
+            step["who"] = (first or has or ["moved"])[t % len(first or has or ["moved"])]
+        if family in PATCH_FAMILIES:                     # by turns: every group, one scalar mask, a word per ray
+            t = self.turns[family]
+            step["masks"] = None if {"patch_table", "replace", "refused"} & set(pending) else (None, "scalar", "rays")[t % 3]   # (no words between the row and what it must tell)
+            if family == "occluded_patches":             # merged where a scene event is pending, unmerged where a table is, else by turns
+                step["merge"] = bool({"replace", "refused"} & set(pending)) or ("patch_table" not in pending and bool((t // 3) % 2))
         step.update(kw)
         if base(family) == "crossings":
             step["records"] = step["k"] == 4
@@ -1128,6 +1616,71 @@ class _Builder:
             if key == "S":
                 self.query("gather_photons", normals=True)
 
+    def new_grids(self):
+        """The grid families and the homogeneous march behind every change of the grids: none yet (refused), G1 on MOVED's medium and
+        G2 on the mover's, G3 (G1's cell count in another shape) and G2 (fewer cells) in G1's place, kept behind set_media_phase and
+        set_lights, MOVED's removed (the mover's stays), the refused setters (each behind a step that could tell), and the other
+        media table: every grid dropped, and a medium index names another object.  Leaves G1 and G2 on the other table."""
+        other = lambda: "B" if self.model.state.media == "A" else "A"
+        both = lambda: [self.query(f, who=w) for f in GRID_FAMILIES for w in ROLES]
+        self.media(other())
+        both()                                            # refused: no grid yet
+        self.grid("moved", "G1"), self.grid("mover", "G2")
+        both(), self.query("march_media")
+        self.query("media_density", who="moved", n=1)
+        for key in ("G3", "G2"):
+            self.grid("moved", key)
+            for f in GRID_FAMILIES:
+                self.query(f, who="moved")
+        self.phase("Q" if self.model.state.phase == "P" else "P"), self.lights("B" if self.model.state.lights == "A" else "A")
+        both()                                            # kept
+        self.grid("moved", None)
+        both(), self.query("march_media")                 # MOVED's is refused, the mover's answers, the march counts MOVED again
+        self.grid("moved", "G1")
+        for f in GRID_FAMILIES:
+            self.query(f, who="moved")
+        self.grid(7, "G1"), self.grid("moved", "dims"), self.grid("moved", "nan"), self.grid("mover", "negative")   # refused
+        both()
+        self.media(other())                               # every grid dropped; MOVED's index is the mover's old one
+        both(), self.query("march_media")
+        self.grid("moved", "G1"), self.grid("mover", "G2")
+        both(), self.query("march_media")
+
+    def new_textures(self):
+        """albedo behind every change of the table: the other key and back, the refused tables, the empty one (refused), a key again."""
+        other = lambda: "B" if self.model.state.textures == "A" else "A"
+        for _ in range(2):
+            self.textures(other())
+            self.query("albedo")
+        self.textures(other(), bad="long"), self.textures(other(), bad="outside")   # refused: nothing changes
+        self.query("albedo")
+        self.textures(None)
+        self.query("albedo")                              # refused
+        self.textures("B")
+        self.query("albedo")
+        self.textures("A")
+        self.query("albedo")
+
+    def new_patches(self):
+        """The patch families behind every change of the table: the other key and back, a refused table, the empty one, a key again."""
+        other = lambda: "B" if self.model.state.patches == "A" else "A"
+        for _ in range(2):
+            self.patches(other())
+            for f in PATCH_FAMILIES:
+                self.query(f)
+        self.patches(other(), bad="material")             # refused: nothing changes
+        for f in PATCH_FAMILIES:
+            self.query(f)
+        self.patches(None)
+        for f in PATCH_FAMILIES:
+            self.query(f)                                 # refused
+        self.patches("B")                                 # the smaller table first: then the larger behind it
+        for f in PATCH_FAMILIES:
+            self.query(f)
+        self.patches("A")
+        for f in PATCH_FAMILIES:
+            self.query(f)
+
     def twins(self):
         """Every new family through its host twin, behind a larger device call of another family."""
         for f in NEW_FAMILIES:
@@ -1135,24 +1688,37 @@ class _Builder:
             self.query(f, host=True, **({} if f in SLOW else {"n": 63}))
 
     def queued(self):
-        """A render, a query on device tensors, then a setter of the table that query reads: no host step in between."""
+        """A render, a query on device tensors, then a setter of the table that query reads: no host step in between.  The grid,
+        texture and patch setters too: each replaces a device buffer the query in front of it reads."""
         st = self.model.state
         for f, setter in (("march_media", lambda: self.media("B" if st.media == "A" else "A")), ("sample_phase", lambda: self.phase("Q")),
                           ("gather_photons", lambda: self.photons("S")), ("sample_lights", lambda: self.lights("B" if st.lights == "A" else "A")),
-                          ("environment", lambda: self.environment("n16" if st.env == "n4" else "n4"))):
+                          ("environment", lambda: self.environment("n16" if st.env == "n4" else "n4")),
+                          ("march_media_grid", lambda: self.grid("moved", "G2" if st.grids.get(medium_of(st.media, "moved")) == "G1" else "G1")),
+                          ("media_density", lambda: self.grid("mover", "G3" if st.grids.get(medium_of(st.media, "mover")) == "G2" else "G2")),
+                          ("albedo", lambda: self.textures("B" if st.textures == "A" else "A")),
+                          ("hit_patches", lambda: self.patches("B" if st.patches == "A" else "A")),
+                          ("occluded_patches", lambda: self.patches("B" if st.patches == "A" else "A"))):
+            if f in GRID_FAMILIES and not self.model.state.grids:   # (the media setter above dropped them)
+                self.grid("moved", "G1"), self.grid("mover", "G2")
+            kw = {"who": "moved" if f == "march_media_grid" else "mover"} if f in GRID_FAMILIES else {}   # (the medium the setter writes)
             self.render(0, 3)
-            self.query(f, host=False)
+            self.query(f, host=False, **kw)
             st = self.model.state
             setter()
-            self.query(f)
+            self.query(f, **kw)
 
 
 def _settle(b, groups="A", lights="A", env=None):
-    """Words, a light table, the media table of the same name with a g vector (P for A, Q for B), and an environment map where asked."""
+    """Words, a light table, the media table of the same name with a g vector (P for A, Q for B), the texture and the patch table of
+    that name, and an environment map where asked.  No grids: a medium with a grid leaves the homogeneous march, whose rows are
+    aimed at MOVED; new_grids() and the steps around the uploads set them."""
     b.groups(groups)
     b.lights(lights)
     b.media(lights)
     b.phase("P" if lights == "A" else "Q")
+    b.textures(lights)
+    b.patches(lights)
     if env is not None:
         b.environment(env)
 
@@ -1164,32 +1730,48 @@ def _same_size(b, scene):
     b.query("gather_photons")                             # refused: no map yet
     b.query("march_media"), b.query("phase")              # refused: no scene yet
     b.media("A"), b.phase("P")                            # refused: no scene yet
+    b.grid("moved", "G1"), b.textures("A"), b.patches("A")   # refused: no scene yet
+    b.query("march_media_grid"), b.query("albedo"), b.query("hit_patches")   # refused: no scene yet
     b.photons("L")                                        # needs no scene
     b.query("gather_photons")
     b.upload(scene)
     b.query("sample_lights")                              # refused: no table yet
     b.query("environment")                                # refused: no map yet
     b.query("scatter_media"), b.phase("P")                # refused: no table yet
+    b.grid("moved", "G1"), b.query("media_density")       # refused: no media table yet
+    b.query("albedo"), b.query("occluded_patches"), b.query("hit_patches_merged")   # refused: no table yet
     _settle(b, "A", "A", "n4")
     b.every_family()
     b.singles()
     b.accumulate("progressive")
     b.accumulate("pixel_progressive")
-    b.upload(other)                                       # replacing: words and table gone, the map kept
+    b.grid("moved", "G1"), b.grid("mover", "G2")
+    for f in GRID_FAMILIES:
+        b.query(f)
+    b.upload(other)                                       # replacing: words, tables and grids gone, the map kept
     b.every_family()                                      # (the light queries are refused; the masked ones see every object)
     _settle(b, "B", "B")
+    b.query("march_media")                                # (its rows are aimed at MOVED: before a grid takes MOVED out of it)
+    b.grid("moved", "G2"), b.grid("mover", "G1")          # behind the replacing upload: they ride the new centres
+    for f in TABLE_FAMILIES:
+        b.query(f)
+    b.query("march_media")
+    b.media("B")                                          # dropped again: the steps below aim the homogeneous march at MOVED
     b.query("sample_lights"), b.query("light_pdf"), b.query("emit_lights")
     b.new_range(BLOCK_FAMILIES + MASKED)
     b.every_family()                                      # every family behind bounds rebuilt for other ranges
     b.variants()
     b.new_media()
+    b.new_grids()
+    b.new_textures()
+    b.new_patches()
     b.new_map()
     b.media("A", bad="twice"), b.media("B", bad="negative"), b.phase("Q", wrong_count=True)   # refused: nothing changes
     for f in MEDIA_FAMILIES:
         b.query(f)
     b.twins()
     b.queued()
-    b.upload(other)                                       # a cache hit: everything kept
+    b.upload(other)                                       # a cache hit: everything kept, the grids queued() left too
     b.every_family()
     b.new_words()
     b.every_family()                                      # every family behind words rebuilt
@@ -1203,6 +1785,10 @@ def _same_size(b, scene):
     b.groups(None)
     b.lights("A")                                         # set_lights after the upload: the table copies the new records
     b.media("B")                                          # set_media after the upload: the table is packed from the new records
+    b.textures("A"), b.patches("A")                       # ... the binding is in the new list's numbering, the materials name its objects
+    b.query("albedo")                                     # (the first reader of the by-object records behind the upload: the ground is unbound)
+    b.query("march_media")                                # (before a grid takes MOVED out of it)
+    b.grid("moved", "G1"), b.grid("mover", "G2")          # ... and the grids ride the new centres
     b.every_family()
     b.phase(None)
     b.query("sample_phase")
@@ -1212,9 +1798,12 @@ def _same_size(b, scene):
     b.query("sample_environment")                         # refused again
     b.lights(None)
     b.query("light_pdf")                                  # refused again
-    b.media(None)
+    b.media(None)                                         # the empty table drops the grids too
     b.query("march_media")                                # refused again
+    b.query("march_media_grid")                           # refused again: no media table
     b.phase(None)                                         # refused: the Python layer's count of the table is 0 too
+    b.textures(None), b.patches(None)
+    b.query("albedo"), b.query("hit_patches")             # refused again
     b.query("occluded")
 
 
@@ -1229,10 +1818,19 @@ def _sizes(b):
             b.accumulate("pixel_progressive")
         if k in (1, 4):                                   # straight after a replacing upload
             b.every_family()
+        if k in (1, 2, 6):                                # a binding of the previous list's count, a material of its last object
+            b.textures("A", count_of=order[k - 1]), b.patches("A", bad="material", of=order[k - 1])
+            b.query("albedo"), b.query("hit_patches")    # (refused where the setter was: the upload cleared the tables)
         _settle(b, GROUPS[k % 2], tuple(LIGHTS)[k % 2])
         b.query("sample_lights"), b.query("light_pdf"), b.query("emit_lights")
         for f in MEDIA_FAMILIES:
             b.query(f)
+        b.grid("moved", "G1"), b.grid("mover", "G2")      # behind the replacing upload
+        for f in TABLE_FAMILIES:
+            b.query(f)
+        b.query("march_media")
+        if k not in (2, 5):                               # (dense2 and dense keep them through the cache-hit upload below)
+            b.media(tuple(LIGHTS)[k % 2])
         if k == 0:
             b.new_map()
         if k in (2, 5):
@@ -1251,6 +1849,9 @@ def _sizes(b):
         if k == 4:
             b.variants()
             b.new_media()
+            b.new_grids()
+            b.new_textures()
+            b.new_patches()
             b.twins()
         if k == 5:
             b.new_map()
@@ -1298,6 +1899,12 @@ def _seeded(b, n_steps):
             b.phase((None, "P", "Q")[int(rng.integers(3))])   # (refused where there is no table)
         elif r < 0.47:
             b.photons(("L", "S", "E")[int(rng.integers(3))])
+        elif r < 0.51:                                    # (refused where there is no table; a grid on either role, or none)
+            b.grid(("moved", "mover")[int(rng.integers(2))], (None, "G1", "G2", "G3")[int(rng.integers(4))])
+        elif r < 0.54:
+            b.textures((None, "A", "B")[int(rng.integers(3))])
+        elif r < 0.57:
+            b.patches((None, "A", "B")[int(rng.integers(3))])
         else:
             b.query(QUERY_FAMILIES[int(rng.integers(len(QUERY_FAMILIES)))])
     b.upload("g9")
@@ -1319,6 +1926,6 @@ def script(name):
         elif name == "sizes":
             _sizes(b)
         else:
-            _seeded(b, 120)
+            _seeded(b, 150)
         _scripts[name] = b.steps
     return _scripts[name]

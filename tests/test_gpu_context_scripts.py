@@ -12,8 +12,10 @@ field is equal, every other bit counts); renders and the accumulations with orac
 film with deposit_restatement; PhotonGather.irradiance alone to 2^-50 (its docstring leaves the order of four roundings open; a
 scale that is a power of two off shows at any tolerance).  No fresh context answers for another.  What ran (res.mode / tor.last_note()) is asserted where the
 per-family tests fix it: `brute` is the brute force, odd_objects falls back and says why, the media queries name the model's count
-of media ("media march: 4 media"), a build the restatement's bucket count and scale.  At the end
-ctx.scene_counters()[:2] is the model's count of uploads and cache hits.  tests/test_context_scripts.py shows on the CPU that a
+of media ("media march: 4 media"), a build the restatement's bucket count and scale, a grid march the model's medium and its
+grid's dimensions ("media grid march: medium 1, 2x3x7"), the patch steps "patch hit" / "patch occluded", a texture step "texture
+eval".  At the end ctx.scene_counters()[:2] is the model's count of uploads and cache hits, and ctx.patches(), ctx.textures() and
+ctx.media_grids() say what the model's final state says.  tests/test_context_scripts.py shows on the CPU that a
 stale cache behind any of the steps would change a quarter of its rows; profiles/context_script_mutants.txt what the same_size
 script fails on when a cache key is broken.
 
@@ -28,14 +30,26 @@ parent (before the photon, media and phase steps): 15.9 s for 5 tests, 13.5 s in
 0.36 s, seeded_2 (123) 0.36 s, and on a stream of its own same_size_g9 0.64 s, seeded_2 0.37 s: 6.8 ms per step over 2235 steps.
 The cost per step fell: nearly all of the time is the restatements of bounce, scatter and radiance on the 724 and 1300 objects of
 same_size and sizes (they loop in Python), and the new steps' restatements see four media or a few thousand photons; the
-library's share of a script is tens of milliseconds."""
+library's share of a script is tens of milliseconds.
+
+With the grid, texture and patch steps, again this module and its parent commit's in one visit.  The parent: 17.2 s for 7 tests,
+15.1 s in the tests -- same_size (435 steps) 5.74 s, same_size_g9 (435) 0.67 s, sizes (561) 6.98 s, seeded_1 (123) 0.37 s, seeded_2
+(123) 0.36 s, on a stream of its own same_size_g9 0.64 s, seeded_2 0.36 s: 6.8 ms per step over 2235 steps.  This module: 21.4 s
+for 7 tests, 19.3 s in the tests -- same_size (654 steps) 7.32 s, same_size_g9 (654) 0.83 s, sizes (842) 8.00 s, seeded_1 (153)
+0.49 s, seeded_2 (153) 0.91 s, on a stream of its own same_size_g9 0.83 s, seeded_2 0.90 s: 5.9 ms per step over 3263 steps (one
+step was added to the same_size scripts afterwards: 655 steps, 7.32 s and 0.82 s in a later visit).  The new steps cost their
+Python restatements -- the grid march and lookup loop per ray at 64 rows and at most 257 points on grids of at most 7 cells per
+axis, albedo loops per record, the patch restatement walks 65 patches over all rays at once --; the library's share stays
+milliseconds."""
 import numpy as np
 import pytest
 import torch
 
 import context_scripts as S
 import deposit_restatement as D
+import patch_restatement as PT
 import render_regimes as R
+import texture_restatement as TR
 
 pytestmark = pytest.mark.gpu
 _scenes = {}
@@ -158,6 +172,32 @@ def _call(tor, ctx, step, op, env):
         res = ctx.gather_photons(op("points"), op("normals"), op("radius"), None, step["kernel"], 1.0)
         assert res.note == "photons gather", (step, res.note)
         return {"sums": res.sums, "count": res.count, "irradiance": res.irradiance(S.PATHS)}, None
+    if f in S.GRID_FAMILIES:                              # the note names the model's medium and its grid's dimensions
+        state = env["state"]
+        m = S.medium_of(state.media, step["who"]) if state.media else 0
+        dims = "x".join(str(v) for v in S.GRIDS[state.grids[m]][0]) if m in state.grids else None   # (else the call is refused)
+        if f == "march_media_grid":
+            res = ctx.march_media_grid(op("rays"), op("tau"), m)
+            assert res.mode == f"medium {m}, {dims}" and tor.last_note() == f"media grid march: medium {m}, {dims}", (step, res.mode, tor.last_note())
+            return {"status": res.status, "t": res.t, "depth": res.depth, "rho": res.rho, "active": res.active, "cell": res.cell}, None
+        cell, value = ctx.media_density(op("points"), m)
+        assert tor.last_note() == f"media grid density: medium {m}, {dims}", (step, tor.last_note())
+        return {"cell": cell, "density": value}, None
+    if f == "albedo":
+        ev = ctx.albedo(op("hits"))
+        assert tor.last_note() == "texture eval", (step, tor.last_note())
+        return {"color": ev.color, "texel": ev.texel}, None
+    if f in S.PATCH_FAMILIES:
+        mask = S.patch_mask(step, {"masks": op("masks")})
+        if f == "occluded_patches":                       # merged: into occluded()'s bits (the brute force: it keys no bounds)
+            start = ctx.occluded(op("rays"), op("t_range"), None, (0.0, 1.0), "brute") if step.get("merge") else None
+            res = ctx.occluded_patches(op("rays"), op("t_range"), mask=mask, merge=start)
+            assert tor.last_note() == "patch occluded", (step, tor.last_note())
+            return {"occluded": res.raw}, None
+        start = ctx.hit(op("rays"), op("t_range"), (0.0, 1.0), "brute") if f == "hit_patches_merged" else None
+        res = ctx.hit_patches(op("rays"), op("t_range"), mask=mask, merge=start)
+        assert tor.last_note() == "patch hit", (step, tor.last_note())
+        return {"raw": res.raw, "patch": res.patch, "uv": res.uv}, None
     cam = tor.camera(**env["x"]["camera"])
     stream = torch.cuda.current_stream().cuda_stream
     if f == "render":
@@ -187,6 +227,49 @@ def _set_media_phase(ctx, step, state):
         return ctx.set_media_phase(None)
     g = S.g_vector(step["g"], len(S.MEDIA[state.media][0]) if state.media else 4)
     return ctx.set_media_phase(g[:-1] if step.get("wrong_count") else g)
+
+
+def _set_media_grid(ctx, step, state):
+    """The medium the step's role names under the model's table (0 where the call is refused before the medium is looked at)."""
+    m = S.medium_of(state.media, step["who"]) if state.media else 0
+    if step["grid"] is None:
+        return ctx.set_media_grid(m, None)
+    objects = S.media_table(state.media, state.scene)[0] if state.media else None
+    inside = objects is not None and 0 <= m < len(objects)
+    box = S.grid_box(step["grid"], state.scene, int(objects[m])) if inside else None
+    return ctx.set_media_grid(m, S.grid_density(step["grid"]), box)
+
+
+def _textures(tor, textures):
+    out = []
+    for t in textures:
+        if t["kind"] == TR.CONSTANT:
+            out.append(tor.Texture.constant(t["a"]))
+        elif t["kind"] == TR.CHECKER:
+            out.append(tor.Texture.checker(t["a"], t["b"], t["freq"], "world" if t["option"] == TR.WORLD else "normal"))
+        else:
+            out.append(tor.Texture.image(t["rgb"], "nearest" if t["option"] == TR.NEAREST else "bilinear"))
+    return out
+
+
+def _set_textures(tor, ctx, step, state):
+    if state.scene is None:                               # refused before the table is looked at
+        return ctx.set_textures([tor.Texture.constant((0.5, 0.5, 0.5))], [0])
+    if step["table"] is None:
+        return ctx.set_textures([], np.zeros(len(S.records(state.scene))))
+    tex, binding = S.texture_table(step["table"], state.scene, step.get("bad"))
+    if step.get("count_of"):                              # the binding built for another list
+        binding = S.texture_table(step["table"], step["count_of"])[1]
+    return ctx.set_textures(_textures(tor, tex), binding)
+
+
+def _set_patches(tor, ctx, step, state):
+    if state.scene is None:                               # refused before the table is looked at
+        return ctx.set_patches([tor.Patch.quad((0, 0, 0), (1, 0, 0), (0, 1, 0))])
+    if step["table"] is None:
+        return ctx.set_patches([])
+    table = S.patch_table(step["table"], state.scene, step.get("bad"), step.get("of"))
+    return ctx.set_patches([tor.Patch(p["kind"], p["q"], p["u"], p["v"], p["material"], p["groups"]) for p in table])
 
 
 def _build_photons(ctx, step, dev_maps):
@@ -252,6 +335,12 @@ def _run(tor, oracle, name):
                 call = lambda: _set_media_phase(ctx, step, e.state)
             elif op == "build_photons":
                 call = lambda: _build_photons(ctx, step, dev_maps)
+            elif op == "set_media_grid":
+                call = lambda: _set_media_grid(ctx, step, e.state)
+            elif op == "set_textures":
+                call = lambda: _set_textures(tor, ctx, step, e.state)
+            elif op == "set_patches":
+                call = lambda: _set_patches(tor, ctx, step, e.state)
             else:
                 host = bool(step.get("host")) and step["family"] != "deposit" and op == "query"
                 env["x"], env["dev"], env["state"] = xs[i], devs[i], e.state
@@ -270,6 +359,13 @@ def _run(tor, oracle, name):
                 times = xs[i].get("points", xs[i].get("rays"))[:, -1] if S.takes_mode(step["family"]) else None
                 _check_what_ran(tor, step, e.state, got[1], S.Model().effective_range(step, times) if times is not None else None)
         assert tuple(ctx.scene_counters()[:2]) == (model.n_uploads, model.n_cache_hits)
+        last = model.state                                # the three tables say what the model's final state says
+        table = S.patch_table(last.patches, last.scene) if last.patches else []
+        assert ctx.patches() == (len(table), sum(p["material"] >= 0 for p in table)), (name, ctx.patches(), last.key())
+        tex, binding = S.texture_table(last.textures, last.scene) if last.textures else ([], np.zeros(0))
+        texels = sum(t["rgb"].shape[0] ** 2 for t in tex if t["rgb"] is not None)
+        assert ctx.textures() == (len(tex), texels, int((binding >= 0).sum())), (name, ctx.textures(), last.key())
+        assert ctx.media_grids() == sorted(last.grids), (name, ctx.media_grids(), last.key())
         torch.cuda.synchronize()
 
         bad = []
